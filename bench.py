@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: descriptor pairs/sec, brute-force Hamming knn=2 at 64k x 64k.
 
-    python bench.py --gpus N --steps K --warmup W [--workload 64k|loop-closure]
+    python bench.py --gpus N --steps K --warmup W [--workload 64k|loop-closure] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch: all 65536 query descriptors matched
 (knn=2) against 65536 train descriptors, inputs resident in HBM before the timed region.
@@ -21,14 +21,21 @@ step), the query keyframes sharded over the ranks (64 per rank at 8 GPUs), the 3
 the fabric with slam_comm_broadcast when RCCL is up, by per-rank upload otherwise), the per-shard top-2 rows all-gathered
 and decoded on the device to OpenCV's multi-image form (imgIdx, trainIdx, distance).  The default workload stays 64k x 64k.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run sets up, warms up, times the K steps and prints ONE JSON line from rank 0: the contract fields (`ms_per_step`
+is the wall time of one timed step in milliseconds) and
   roofline      — the dominant kernel (bf_top2_kernel) against the HBM roofline on ALGORITHMIC
-                  bytes, as the contract asks, plus the VALU-integer figures that actually bound it;
+                  bytes, as the contract asks, plus the VALU-integer figures that actually bound it
+                  (from the timed steps and the committed PMC summary: no run of its own).
+--dump-outputs DIR writes the tables the last timed step computed, as a caller receives them, to DIR/<name>.npy in
+float32 (row indices and distances are integers below 2^24: exact): train_idx and distance [n_query, 2], and img_idx for
+the loop-closure workload (24 MiB in all there).  The inputs come from fixed seeds, so two builds compare output for output.
+--full adds, after the timed region, everything else the benchmark measures or checks:
+  parity_spot_check — 256 sampled rows of the last timed step against the CPU oracle (null in a plain run);
   cpu_baseline  — the CPU oracle (oracle/bf_hamming_oracle.c, a port: cv2 is not installable
-                  here) timed on the host cores over the same arrays (N = 1 only);
+                  here) timed on the host cores over the same arrays (N = 1 only; --no-cpu-baseline skips it);
   pipelined     — with --pipelined: the same searches issued alternately on two contexts (N = 1 only; reported, not `value`);
   reproj        — the second hot path (residual/Jacobian build, 200 poses x 50k points dense)
-                  with its own HBM roofline (only at the default N=1 run);
+                  with its own HBM roofline (N = 1, default workload only; --no-reproj skips it);
   next_rows     — the rows SURVEY.md 8f marks "next", as the calls a frame loop makes: one pose-only refinement (200 edges)
                   and one window bundle adjustment at the reference's window, each beside the same loop in plain C on
                   one host core and checked against it (N = 1 only; reported, not `value`; --no-next-rows skips it).
@@ -96,6 +103,24 @@ def profiled_traffic(kernel: str):
 
 def make_descriptors(n: int, seed: int) -> np.ndarray:
     return np.random.default_rng(seed).integers(0, 256, (n, 32), dtype=np.uint8)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as <out_dir>/<name>.npy in float32; refuses values float32 cannot hold exactly and more
+    than DUMP_LIMIT_BYTES in all."""
+    conv = {name: np.ascontiguousarray(a, dtype=np.float32) for name, a in arrays.items()}
+    for name, a in conv.items():
+        if not np.array_equal(a.astype(arrays[name].dtype), arrays[name]):
+            raise ValueError(f"--dump-outputs: {name} does not convert to float32 exactly")
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes, the limit is {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def launch_plan(ctx, n: int, m: int) -> dict:
@@ -395,14 +420,23 @@ def main() -> int:
     ap.add_argument("--workload", choices=("64k", "loop-closure"), default="64k",
                     help="64k: 65536 x 65536 (BASELINE configs[2], the headline); loop-closure: 512 keyframes x 2048 rows "
                          "all-to-all (BASELINE configs[3])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the tables of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the oracle spot check, the CPU baselines, the residual kernel and the "
+                         "'next' rows (the options below trim this)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-reproj", action="store_true")
     ap.add_argument("--no-next-rows", action="store_true", help="skip the pose-refinement / window-BA calls (SURVEY 8f rows f3, f4)")
     ap.add_argument("--pipelined", action="store_true",
-                    help="also time the searches alternating between two contexts (extra object `pipelined`; off by default "
-                         "so that a rocprofv3 summary of the default command only holds back-to-back launches)")
+                    help="with --full: also time the searches alternating between two contexts (extra object `pipelined`; "
+                         "off by default so that a rocprofv3 summary of the default command only holds back-to-back launches)")
     ap.add_argument("--no-pipelined", action="store_true", help=argparse.SUPPRESS)   # accepted for older command lines
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.pipelined and not args.full:
+        ap.error("--pipelined is a leg of --full")
 
     from slamhip.launch import Rendezvous, from_env, spawn_ranks
 
@@ -569,13 +603,19 @@ def main() -> int:
     wall_ms, dev_ms = max(t[0] for t in times), max(t[1] for t in times)
     rank_kernel_ms = [t[2] for t in times]
 
-    # correctness of what was timed: full table on every rank, spot-checked against the oracle on rank 0
-    if loop_closure:
-        img, local, dist_tab = sm.result_images()
-    else:
-        idx, dist_tab = sm.result()
-    ok = True
-    if rank == 0:
+    # what the last timed step computed: the full table on every rank; dumped by rank 0, spot-checked against the oracle there
+    # with --full (parity_spot_check stays null in a plain run)
+    if args.full or args.dump_outputs:
+        if loop_closure:
+            img, local, dist_tab = sm.result_images()
+            outputs = {"img_idx": img, "train_idx": local, "distance": dist_tab}
+        else:
+            idx, dist_tab = sm.result()
+            outputs = {"train_idx": idx, "distance": dist_tab}
+        if rank == 0 and args.dump_outputs:
+            write_outputs(args.dump_outputs, outputs)
+    ok = None
+    if rank == 0 and args.full:
         from oracle import oracle
 
         sel = np.random.default_rng(1).choice(n_query, 256, replace=False)
@@ -598,17 +638,18 @@ def main() -> int:
                          collective=collective, fallback_reason=fallback_reason,
                          rccl_version=None if rccl_version is None else rccl_version.value,
                          plan=launch_plan(ctx, max(sm.n_local, 1), n_train), ok=ok, train_replication=sm.train_replication)
-        if world > 1:
+        if args.full and world > 1:
             out["cpu_baseline"] = None
             out["cpu_baseline_note"] = "the CPU leg is timed at N=1 only (same arrays; see the N=1 line)"
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(query, train)
     sm.free(barrier)                   # unmap peers -> barrier -> free the exported buffers (HIP IPC teardown order)
-    if rank == 0 and world == 1 and args.pipelined and not loop_closure:
+    full_n1 = rank == 0 and world == 1 and args.full and not loop_closure
+    if full_n1 and args.pipelined:
         out["pipelined"] = pipelined_leg(query, train, max(args.steps, 20))
-    if rank == 0 and world == 1 and not args.no_reproj and not loop_closure:
+    if full_n1 and not args.no_reproj:
         out["reproj"] = reproj_bench(ctx, max(3, min(args.steps, 20)), args.warmup, cpu=not args.no_cpu_baseline)
-    if rank == 0 and world == 1 and not args.no_next_rows and not loop_closure:
+    if full_n1 and not args.no_next_rows:
         try:
             out["next_rows"] = next_rows_leg(ctx, cpu=not args.no_cpu_baseline)
         except Exception as exc:   # noqa: BLE001 - an extra leg must never cost the line
@@ -623,7 +664,7 @@ def main() -> int:
         raise SystemExit("slam_comm_destroy failed")
     if rank == 0:
         print(json.dumps(out), flush=True)
-    rc = 0 if ok or rank != 0 else 1
+    rc = 0 if ok is not False or rank != 0 else 1
     if abandoned:
         # a helper thread is still inside a native call that never returned: a normal interpreter exit would wait for
         # the runtime's teardown behind it

@@ -1,9 +1,12 @@
 """CPU suite: the schema and the invariants of bench.py's JSON line, built from made-up measurements (no GPU): the contract
 fields of the driver, the roofline / valu_int objects (every fraction at most 1: VERDICT r02 item 2), the N > 1 diagnostics
- and the traffic stamp check (item 6)."""
+(VERDICT r02 item 5), the traffic stamp check (item 6) and the --dump-outputs writer."""
 import importlib.util
 import json
 import os
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -77,3 +80,18 @@ def test_traffic_is_withheld_when_a_kernel_source_changed(tmp_path, monkeypatch)
     assert b.profiled_traffic("reproj_rj_kernel")[0] == 456.0                  # its own source is unchanged
     f.write_text("{}")
     assert b.profiled_traffic("bf_top2_kernel")[0] is None
+
+
+def test_dumped_outputs_are_exact_float32_and_bounded(tmp_path, monkeypatch):
+    b = _bench()
+    idx = np.array([[0, 65535], [-1, (1 << 20) - 1]], np.int32)
+    b.write_outputs(str(tmp_path / "d"), {"train_idx": idx, "distance": np.array([[0, 256], [-1, 3]], np.int32)})
+    got = np.load(tmp_path / "d" / "train_idx.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, idx)
+    assert sorted(os.listdir(tmp_path / "d")) == ["distance.npy", "train_idx.npy"]
+    with pytest.raises(ValueError, match="exactly"):
+        b.write_outputs(str(tmp_path / "e"), {"x": np.array([(1 << 24) + 1], np.int64)})
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 15)
+    with pytest.raises(ValueError, match="limit"):
+        b.write_outputs(str(tmp_path / "f"), {"train_idx": idx})
+    assert not (tmp_path / "e").exists() and not (tmp_path / "f").exists()

@@ -58,7 +58,7 @@ def test_bench_under_the_driver_launcher_one_rank(built):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
-           "--warmup", "1", "--no-cpu-baseline", "--no-reproj", "--no-pipelined"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-reproj", "--no-pipelined"]
     rec = _bench_line(subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT))
     assert rec["n_gpus"] == 1 and rec["parity_spot_check"] is True and rec["value"] > 1e11
     assert rec["roofline"]["kernel_ms"] > 0 and rec["unit"] == "pairs/s"
@@ -74,7 +74,7 @@ def test_self_contained_launch_two_ranks_on_one_gpu(built, force, expect):
     env = dict(os.environ, SLAM_BENCH_SINGLE_DEVICE="1", SLAM_BENCH_COLLECTIVE=force)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SLAM_RDZV"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     rec = _bench_line(out)
     assert rec["n_gpus"] == 2 and rec["parity_spot_check"] is True
@@ -108,7 +108,7 @@ def test_a_communicator_set_up_that_never_returns_becomes_a_labelled_fallback(bu
     env = dict(os.environ, SLAM_BENCH_SINGLE_DEVICE="1", SLAM_BENCH_FAKE_HANG="init", SLAM_BENCH_DEADLINE="6")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SLAM_RDZV", "SLAM_BENCH_COLLECTIVE"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     t0 = time.monotonic()
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert time.monotonic() - t0 < 300, "the run must not wait for the stuck calls"
@@ -128,7 +128,7 @@ def test_loop_closure_workload(built, ranks, force):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SLAM_RDZV"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--workload", "loop-closure", "--steps", "2",
-           "--warmup", "0", "--no-cpu-baseline"]
+           "--warmup", "0", "--full", "--no-cpu-baseline"]
     rec = _bench_line(subprocess.run(cmd, capture_output=True, text=True, timeout=1100, env=env, cwd=ROOT))
     assert rec["n_gpus"] == ranks and rec["parity_spot_check"] is True
     assert rec["config"]["n_query"] == rec["config"]["n_train"] == 512 * 2048 and "loop closure" in rec["config"]["workload"]
@@ -139,12 +139,11 @@ def test_loop_closure_workload(built, ranks, force):
         assert rec["value"] > 2.5e12          # round 2 measured 2.91e12 pairs/s here
 
 
-def test_driver_launch_line_two_ranks_needs_no_torch_in_the_ranks(built):
+def test_driver_launch_line_two_ranks_needs_no_torch_in_the_ranks(built, tmp_path):
     """The driver's N > 1 line (`python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2`): the ranks read
     RANK / WORLD_SIZE / MASTER_PORT from the environment and rendezvous through slamhip.launch; torch stays the
     launcher's business (a sitecustomize hook makes `import torch` inside a rank fail the run)."""
-    hook = os.path.join(ROOT, "gpurun_out", "_no_torch_hook")
-    os.makedirs(hook, exist_ok=True)
+    hook = str(tmp_path)
     with open(os.path.join(hook, "sitecustomize.py"), "w") as f:
         f.write("import os, sys\n"
                 "if os.environ.get('RANK') is not None and sys.argv and sys.argv[0].endswith('bench.py'):\n"
@@ -157,7 +156,8 @@ def test_driver_launch_line_two_ranks_needs_no_torch_in_the_ranks(built):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", SLAM_BENCH_SINGLE_DEVICE="1",
                PYTHONPATH=hook + os.pathsep + os.environ.get("PYTHONPATH", ""))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", "29637", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+           "127.0.0.1", "--master-port", "29637", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--full"]
     rec = _bench_line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT))
     assert rec["n_gpus"] == 2 and rec["parity_spot_check"] is True
 

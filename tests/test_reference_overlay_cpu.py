@@ -2,7 +2,9 @@
 
 ``tests/overlay_probe.py`` runs in a child process with ``slam-experiments_amd/`` ahead of ``/root/reference`` on
 ``sys.path`` and name-only stubs for the three wheels the image lacks (cv2, g2o, jaxlie); this file asserts on what it
-observed.  Skipped wherever the reference is absent (the GPU box): nothing of the reference is copied or shipped.
+observed.  Those tests are skipped wherever the reference is absent: nothing of the reference is copied or shipped.  The
+stand-in check at the end reads the reference's class member names from tests/golden/reference_classes.json and runs
+everywhere.
 The stubs compute nothing, so this pins NAMES and CONTRACTS (imports, argument order, attributes, ``__slots__``,
 write-back), not arithmetic: parity of the hot path stays "unpinned" (DESIGN.md)."""
 import json
@@ -16,8 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "slam-experiments_amd")
 REFERENCE = os.environ.get("SLAM_REFERENCE_DIR", "/root/reference")
 
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REFERENCE, "slam.py")),
-                                reason="the reference checkout is only present in the build container")
+needs_reference = pytest.mark.skipif(not os.path.isfile(os.path.join(REFERENCE, "slam.py")),
+                                     reason="the reference checkout is only present in the build container")
 
 
 @pytest.fixture(scope="module")
@@ -31,6 +33,7 @@ def probe(built):
     return json.loads(line[-1][len("OVERLAY_PROBE "):])
 
 
+@needs_reference
 def test_reference_imports_resolve_to_the_overlay(probe):
     """slam.py:9-13 and frontend.py:14-17 (`from backend import Backend, Map`, `from feature_matchers import ...`) work
     unchanged: matcher and Backend come from the overlay, Map (class attributes NUM_ACTIVE_KEYFRAMES / MIN_DIST_THRESHOLD,
@@ -45,6 +48,7 @@ def test_reference_imports_resolve_to_the_overlay(probe):
     assert probe["map_slots"] == ["_landmarks", "_keyframes", "_active_landmarks", "_active_keyframes", "_current_frame"]
 
 
+@needs_reference
 def test_reference_frontend_runs_on_the_overlay_matcher(probe):
     """OrbSLAM.__init__ (slam.py:22-28) builds the overlay's matcher with cv2.NORM_HAMMING and hands it to the reference's
     Frontend; _match_features / _track_current_frame (frontend.py:156-187) consume what match() returns."""
@@ -58,6 +62,7 @@ def test_reference_frontend_runs_on_the_overlay_matcher(probe):
     assert probe["empty_desc"] == ["float64", [0]] and probe["empty_matches"] == 0           # primitives.py:200-205 with n = 0
 
 
+@needs_reference
 def test_consecutive_frames_reuse_the_resident_rows(probe):
     """frontend.py:181-187 with real Frame.get_descriptors copies: frame k's query rows are frame k+1's source rows and
     are not sent again."""
@@ -68,6 +73,7 @@ def test_consecutive_frames_reuse_the_resident_rows(probe):
     assert probe["cache_hits"] == 1
 
 
+@needs_reference
 def test_backend_glue_on_the_reference_containers(probe):
     """Backend.optimize_map / correct_frame_pose on real Frame / Feature / MapPoint / Map objects
     (primitives.py:92-205, backend.py:10-53): what is read (Feature.position int32 pixels, MapPoint.position,
@@ -120,14 +126,20 @@ def _class_members(tree):
 def test_hand_made_stand_ins_match_the_reference_classes():
     """The duck-typed Frame / MapPoint / Feature / Map stand-ins that the GPU tests and the host tests declare by hand
     (they must run where the reference is absent) may only use names the reference's classes really have
-    (primitives.py:92-205, backend.py:10-53).  Compared on the syntax trees; nothing is imported."""
+    (primitives.py:92-205, backend.py:10-53), as tests/golden/make_reference_classes.py stored them; where the reference is
+    present, the stored names must still be its names.  Compared on the syntax trees; nothing is imported."""
     import ast
 
-    real = {}
-    for fname in ("primitives.py", "backend.py"):
-        with open(os.path.join(REFERENCE, fname)) as f:
-            for k, v in _class_members(ast.parse(f.read())).items():
-                real.setdefault(k, set()).update(v)
+    with open(os.path.join(ROOT, "tests", "golden", "reference_classes.json")) as f:
+        stored = json.load(f)
+    real = {cls: set(names) for cls, names in stored.items()}
+    if os.path.isfile(os.path.join(REFERENCE, "slam.py")):
+        found = {}
+        for fname in ("primitives.py", "backend.py"):
+            with open(os.path.join(REFERENCE, fname)) as f:
+                for k, v in _class_members(ast.parse(f.read())).items():
+                    found.setdefault(k, set()).update(v)
+        assert {k: found.get(k) for k in real} == real, "tests/golden/reference_classes.json no longer matches the reference"
     checked = 0
     for fname in ("test_optimize_gpu.py", "test_abi_and_host_cpu.py", "test_frontend_pattern_gpu.py"):
         with open(os.path.join(ROOT, "tests", fname)) as f:

@@ -48,7 +48,9 @@ def _worker(rank, world, port, n, m, out):
 
 @pytest.mark.parametrize("n,m", [(1000, 777), (7, 50), (1, 3)])
 def test_query_sharded_gather_equals_monolithic(n, m):
-    import torch.multiprocessing as mp
+    # the standard library's spawn: torch (which bundles its own ROCm runtime libraries) stays out of the pytest process,
+    # where the GPU tests have libslamhip's HIP runtime initialised; only the spawned workers import it
+    import multiprocessing as mp
 
     ctx = mp.get_context("spawn")
     out = ctx.Queue()

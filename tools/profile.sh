@@ -13,26 +13,26 @@ OUT=gpurun_out/$ROUND
 mkdir -p $OUT
 export TMPDIR=/tmp
 PY=python3
-B="bench.py --steps 5 --warmup 1 --no-cpu-baseline"
+B="bench.py --full --steps 5 --warmup 1 --no-cpu-baseline"
 
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o fetch -- $PY $B > /dev/null 2> $OUT/pmc_fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o write -- $PY $B > /dev/null 2> $OUT/pmc_write.err
 $PY tools/pmc_summary.py $OUT/pmc_fetch $OUT/pmc_write > $OUT/hbm_counters.json && cp $OUT/hbm_counters.json profiles/hbm_counters.json
 echo "hbm counters done: $(grep -c traffic_bytes $OUT/hbm_counters.json) kernels"
 
-$PY bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+$PY bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 echo "bench done: $(cut -c1-200 $OUT/bench_n1.json)"
 # PROFILE_ONLY=hbm: the counters and the line that reads them only (after an edit that touched a kernel source's text)
 if [ "${PROFILE_ONLY:-}" = "hbm" ]; then
-    rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_default -o stats -- $PY bench.py > $OUT/bench_default_under_rocprof.json 2> $OUT/stats_default.err
+    rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_default -o stats -- $PY bench.py --full > $OUT/bench_default_under_rocprof.json 2> $OUT/stats_default.err
     exit 0
 fi
-$PY bench.py --workload loop-closure --steps 10 --warmup 1 > $OUT/bench_loop_closure_n1.json 2> $OUT/bench_loop_closure_n1.err
+$PY bench.py --full --workload loop-closure --steps 10 --warmup 1 > $OUT/bench_loop_closure_n1.json 2> $OUT/bench_loop_closure_n1.err
 echo "loop closure done: $(cut -c1-160 $OUT/bench_loop_closure_n1.json)"
-SLAM_BENCH_SINGLE_DEVICE=1 SLAM_BENCH_COLLECTIVE=p2p $PY bench.py --gpus 2 --workload loop-closure --steps 3 --warmup 0 > $OUT/bench_loop_closure_2ranks_one_gpu.json 2> $OUT/bench_loop_closure_2ranks_one_gpu.err
-SLAM_BENCH_SINGLE_DEVICE=1 SLAM_BENCH_COLLECTIVE=p2p $PY bench.py --gpus 2 --steps 10 --warmup 2 > $OUT/bench_2ranks_one_gpu.json 2> $OUT/bench_2ranks_one_gpu.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_default -o stats -- $PY bench.py > $OUT/bench_default_under_rocprof.json 2> $OUT/stats_default.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_long -o stats -- $PY bench.py --steps 400 --warmup 20 --no-reproj --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats_long.err
+SLAM_BENCH_SINGLE_DEVICE=1 SLAM_BENCH_COLLECTIVE=p2p $PY bench.py --full --gpus 2 --workload loop-closure --steps 3 --warmup 0 > $OUT/bench_loop_closure_2ranks_one_gpu.json 2> $OUT/bench_loop_closure_2ranks_one_gpu.err
+SLAM_BENCH_SINGLE_DEVICE=1 SLAM_BENCH_COLLECTIVE=p2p $PY bench.py --full --gpus 2 --steps 10 --warmup 2 > $OUT/bench_2ranks_one_gpu.json 2> $OUT/bench_2ranks_one_gpu.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_default -o stats -- $PY bench.py --full > $OUT/bench_default_under_rocprof.json 2> $OUT/stats_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_long -o stats -- $PY bench.py --full --steps 400 --warmup 20 --no-reproj --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats_long.err
 # BASELINE configs[1] (4096 x 4096) and the 1/8 shard of the headline grid under the same profiler
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_4096 -o stats -- $PY tools/run_search.py 4096x4096 400 > /dev/null 2> $OUT/stats_4096.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_shard -o stats -- $PY tools/run_search.py 8192x65536 200 > /dev/null 2> $OUT/stats_shard.err
@@ -55,7 +55,7 @@ $PY tools/latency.py > $OUT/latency_small_calls.log 2>&1
 $PY tools/fire_probe.py > $OUT/update_path_share.log 2>&1
 $PY tools/ba_time.py > $OUT/ba_timing.log 2>&1
 $PY tools/pose_lm_probe.py > $OUT/pose_lm_probe.log 2>&1
-$PY bench.py --pipelined --no-reproj --no-cpu-baseline > $OUT/bench_pipelined.json 2> $OUT/bench_pipelined.err
+$PY bench.py --full --pipelined --no-reproj --no-cpu-baseline > $OUT/bench_pipelined.json 2> $OUT/bench_pipelined.err
 find $OUT -name "*kernel_stats.csv" | head
 # the trace databases are large; keep the csv summaries only
 find $OUT -name "*.db" -delete 2>/dev/null
