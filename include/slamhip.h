@@ -137,6 +137,27 @@ SLAM_API int slam_bf_knn2_u256_host(slam_ctx* ctx, const uint8_t* h_query, int64
                            const uint8_t* h_train, int64_t M,
                            int32_t* h_idx, int32_t* h_dist);
 
+/* Top-k search, k in [1, SLAM_BF_KNN_MAX]: cv2.BFMatcher(NORM_HAMMING).knnMatch(query, train, k) for any k up to 32
+ * (keyframe voting against a KeyframeDatabase wants more candidates per descriptor than the top-2 search gives).
+ * d_idx/d_dist are int32 [N,K], each row ordered by (distance asc, train index asc); missing neighbours (M < K) are
+ * (-1, INT32_MAX); train_base is added to every reported index; train sets beyond 2^23 rows run in passes that are
+ * merged.  Argument checks and empty inputs as slam_bf_knn2_u256; K outside [1, 32] is SLAM_ERR_INVALID and launches
+ * nothing.  Asynchronous on the ctx stream.  K = 1 and K = 2 run this search too (bit-identical to slam_bf_knn2_u256). */
+#define SLAM_BF_KNN_MAX 32
+SLAM_API int slam_bf_knn_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M,
+                              int64_t train_base, int K, int32_t* d_idx, int32_t* d_dist);
+/* cv2.BFMatcher.knnMatch(k) on host buffers: uploads, searches, downloads, one stream synchronisation. */
+SLAM_API int slam_bf_knn_u256_host(slam_ctx* ctx, const uint8_t* h_query, int64_t N, const uint8_t* h_train, int64_t M,
+                                   int K, int32_t* h_idx, int32_t* h_dist);
+/* cv2.BFMatcher.knnMatch(k) over a train set split in G parts: merge G partial top-k tables ([G][N][K] idx and dist,
+ * already holding global indices, each row sorted) into one [N,K] table by (dist, idx). */
+SLAM_API int slam_bf_merge_topk(slam_ctx* ctx, const int32_t* d_idx_parts, const int32_t* d_dist_parts, int64_t G,
+                                int64_t N, int K, int32_t* d_idx, int32_t* d_dist);
+/* The launch plan of slam_bf_knn_u256 (cv2.BFMatcher.knnMatch(k)) for N x M on a device with num_cu CUs, WITHOUT a
+ * device.  h_plan int32 [8] = {K of the kernel instantiation (4, 8, 16 or 32), query blocks, chunks (grid.y of a full
+ * pass), rows per chunk, blocks per CU counted on, passes, bytes of partial tables, 1 when a merge kernel follows}. */
+SLAM_API int slam_bf_topk_plan_describe(int num_cu, int64_t N, int64_t M, int K, int32_t* h_plan);
+
 /* Tuning overrides for experiments, per context.  h_knobs is an int32 array of up to SLAM_BF_KNOBS entries (missing
  * entries and a NULL array mean 0 = the shipped choice):
  *   [0] R             queries per lane: 1, 2, 4 or 8 (shipped: 1)

@@ -147,8 +147,12 @@ class BruteForceFeatureMatcher(FeatureMatcher):
         return _m.knn_match_arrays(query_descriptors, train_descriptors, k)
 
     def knn_match(self, query_descriptors, train_descriptors, k: int = 2) -> list:
-        """``bf.knnMatch(query, train, k)``: one list of up to k DMatch per query."""
-        idx, dist = _m.knn_match_arrays(query_descriptors, train_descriptors, k)
+        """``bf.knnMatch(query, train, k)``: one list of up to k DMatch per query, k in [1, 32] (k >= 3 runs the top-k
+        search, k = 1 and 2 the top-2 search)."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 3:
+            idx, dist = _m.knn_match_arrays(query_descriptors, train_descriptors, k)
+        else:
+            idx, dist = _m.topk_match_arrays(query_descriptors, train_descriptors, k)
         return [[_make_dmatch(q, t, d) for t, d in zip(irow, drow) if t >= 0]
                 for q, (irow, drow) in enumerate(zip(idx.tolist(), dist.tolist()))]
 

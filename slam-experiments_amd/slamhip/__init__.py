@@ -9,6 +9,7 @@ from .matching import (  # noqa: F401
     ResidentMatcher,
     Top2Table,
     as_descriptors,
+    check_topk_k,
     cross_check_arrays,
     knn2_device,
     knn2_device_batch,
@@ -16,8 +17,12 @@ from .matching import (  # noqa: F401
     knn_match_arrays,
     knn_match_arrays_batch,
     knn_match_collection,
+    knn_topk_device,
     match_arrays,
+    plan_describe_topk,
     ratio_test_arrays,
     split_image_index,
+    topk_match_arrays,
+    topk_match_collection,
 )
 from .reproj import PoseOnlyProblem, ReprojProblem, build_linearization, poses_to_rt12  # noqa: F401

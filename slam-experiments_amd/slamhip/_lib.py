@@ -62,6 +62,10 @@ SIGNATURES = {
                                          c_void_p, POINTER(c_int64)]),
     "slam_bf_merge_top2": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "slam_bf_knn2_u256_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "slam_bf_knn_u256": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "slam_bf_knn_u256_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "slam_bf_merge_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "slam_bf_topk_plan_describe": (c_int, [c_int, c_int64, c_int64, c_int, POINTER(c_int32)]),
     "slam_bf_set_tuning": (c_int, [c_void_p, POINTER(c_int32), c_int]),
     "slam_bf_plan_info": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_int32)]),
     "slam_bf_plan_describe": (c_int, [c_int, POINTER(c_int32), c_int, c_int64, c_int64, c_int64, c_int, POINTER(c_int32),
@@ -127,6 +131,7 @@ class BfSearch(ctypes.Structure):
 
 
 BF_BATCH_MAX = 32
+BF_KNN_MAX = 32             # SLAM_BF_KNN_MAX: the largest k of the top-k search
 _lib = None
 
 

@@ -13,7 +13,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import DESC_BYTES, NO_MATCH_DIST, NO_MATCH_IDX, addr, check
+from ._lib import BF_KNN_MAX, DESC_BYTES, NO_MATCH_DIST, NO_MATCH_IDX, addr, check, load
 from .device import Context, DeviceBuffer, default_context
 
 NORM_HAMMING = 6           # cv2.NORM_HAMMING, the only norm the reference constructs (slam.py:24)
@@ -95,6 +95,65 @@ def knn_match_arrays(query, train, k: int = 2, ctx: Optional[Context] = None) ->
     if n:
         check(ctx.lib.slam_bf_knn2_u256_host(ctx.handle, addr(q), n, addr(t) if m else None, m, addr(idx), addr(dist)))
     return np.ascontiguousarray(idx[:, :k]), np.ascontiguousarray(dist[:, :k])
+
+
+def check_topk_k(k) -> int:
+    """``k`` of the top-k search as an int in [1, 32]; ``ValueError`` otherwise (raised before any context exists or any
+    library call is made)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"k must be an integer in [1, {BF_KNN_MAX}], got {k!r}")
+    if not 1 <= int(k) <= BF_KNN_MAX:
+        raise ValueError(f"k must be in [1, {BF_KNN_MAX}], got {k}")
+    return int(k)
+
+
+def knn_topk_device(ctx: Context, d_query: DeviceBuffer, n: int, d_train: DeviceBuffer, m: int, k: int, d_idx: DeviceBuffer,
+                    d_dist: DeviceBuffer, train_base: int = 0) -> None:
+    """Launch the top-k search (k in [1, 32]) on device-resident rows (``slam_bf_knn_u256``; asynchronous on the ctx
+    stream): ``d_idx`` / ``d_dist`` int32 [n, k], rows ordered by (distance, train index), missing neighbours (-1, INT32_MAX)."""
+    k = check_topk_k(k)
+    check(ctx.lib.slam_bf_knn_u256(ctx.handle, d_query.ptr if n else None, n, d_train.ptr if m else None, m, train_base, k,
+                                   d_idx.ptr, d_dist.ptr))
+
+
+def topk_match_arrays(query, train, k: int, ctx: Optional[Context] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """``knnMatch(query, train, k)`` for any k in [1, 32] as arrays: (idx, dist) int32 [N, k], each row ordered by
+    (distance asc, train index asc); missing neighbours (M < k) are (-1, INT32_MAX).  One library call: upload, search,
+    download (``slam_bf_knn_u256_host``)."""
+    k = check_topk_k(k)
+    q, t = as_descriptors(query), as_descriptors(train)
+    ctx = ctx or default_context()
+    n, m = q.shape[0], t.shape[0]
+    idx = np.empty((n, k), np.int32)
+    dist = np.empty((n, k), np.int32)
+    if n:
+        check(ctx.lib.slam_bf_knn_u256_host(ctx.handle, addr(q), n, addr(t) if m else None, m, k, addr(idx), addr(dist)))
+    return idx, dist
+
+
+def topk_match_collection(query, train_images: Sequence[np.ndarray], k: int, ctx: Optional[Context] = None):
+    """``topk_match_arrays`` against a collection of train images (``BFMatcher.add`` + ``knnMatch(k)``).
+
+    Returns (imgIdx, trainIdx, dist) int32 [N, k] in OpenCV's order (dist, imgIdx, trainIdx)."""
+    k = check_topk_k(k)
+    imgs = [as_descriptors(t) for t in train_images]
+    rows = [t.shape[0] for t in imgs]
+    if any(r >= (1 << IMGIDX_SHIFT) for r in rows):
+        raise ValueError("each train image must have fewer than 2^18 rows (OpenCV IMGIDX_ONE)")
+    cat = np.concatenate(imgs, 0) if imgs else np.zeros((0, DESC_BYTES), np.uint8)
+    idx, dist = topk_match_arrays(query, cat, k, ctx)
+    img, local = split_image_index(idx, rows)
+    return img, local, dist
+
+
+def plan_describe_topk(n: int, m: int, k: int, num_cu: int = 256) -> dict:
+    """The launch plan of the top-k search for n x m on a device with ``num_cu`` CUs, WITHOUT a device
+    (``slam_bf_topk_plan_describe``)."""
+    k = check_topk_k(k)
+    plan = (ctypes.c_int32 * 8)()
+    check(load().slam_bf_topk_plan_describe(num_cu, n, m, k, plan))
+    names = ("K", "qblocks", "chunks", "chunk", "resident", "passes", "workspace_bytes", "merge")
+    return dict(zip(names, plan))
 
 
 class _MatchOutputs:
@@ -413,6 +472,29 @@ class KeyframeDatabase:
         idx, dist = d_idx.download(np.int32, (n, 2)), d_dist.download(np.int32, (n, 2))
         img, local = split_image_index(idx, self.rows)
         return (np.ascontiguousarray(img[:, :k]), np.ascontiguousarray(local[:, :k]), np.ascontiguousarray(dist[:, :k]))
+
+    def query_topk(self, descriptors, k: int):
+        """(imgIdx, trainIdx, dist) int32 [N, k], k in [1, 32], of the query rows against every keyframe added so far (the
+        top-k search on the resident rows: only the query rows go up and the [N, k] tables come down)."""
+        k = check_topk_k(k)
+        q = as_descriptors(descriptors)
+        n = q.shape[0]
+        if n == 0:
+            z = np.zeros((0, k), np.int32)
+            return z, z.copy(), z.copy()
+        need = n * (DESC_BYTES + 8 * k)
+        if n > self._qcap or self._qcap * (DESC_BYTES + 16) < need:   # the buffer of query(), grown to hold [n, k] tables
+            if self._qbuf is not None:
+                self._qbuf.free()
+            self._qcap = max(2 * n, 1024, -(-need // (DESC_BYTES + 16)))
+            self._qbuf = self.ctx.malloc(self._qcap * (DESC_BYTES + 16))
+        dq = self._qbuf.view(0, n * DESC_BYTES).upload(q)
+        d_idx = self._qbuf.view(n * DESC_BYTES, n * 4 * k)
+        d_dist = self._qbuf.view(n * (DESC_BYTES + 4 * k), n * 4 * k)
+        knn_topk_device(self.ctx, dq, n, self._buf, self.total, k, d_idx, d_dist)
+        idx, dist = d_idx.download(np.int32, (n, k)), d_dist.download(np.int32, (n, k))
+        img, local = split_image_index(idx, self.rows)
+        return img, local, dist
 
     def free(self) -> None:
         self._buf.free()
