@@ -203,6 +203,19 @@ SLAM_API int slam_bf_plan_info(slam_ctx* ctx, int64_t N, int64_t M, int32_t* h_p
  * searches that share the launch (slam_bf_knn2_batch_u256), 0 for a search that has the grid to itself. */
 SLAM_API int slam_bf_plan_describe(int num_cu, const int32_t* h_knobs, int count, int64_t N, int64_t M, int64_t qb_all,
                                    int rows_on_host, int32_t* h_plan, int32_t* h_tbl, int64_t tbl_cap, int64_t* tbl_len);
+/* Which engine runs the top-2 search (slam_bf_knn2_u256 and the calls built on it) on this context: 0 = auto (the shipped
+ * choice), 1 = the VALU popcount kernel always, 2 = the matrix-core kernel (a +-1 FP4 dot product on the MFMA units, same
+ * results bit for bit) wherever it is eligible.  Eligible: one pass of at most 2^23 train rows in device memory with every
+ * slam_bf_set_tuning knob at its shipped value (a forced knob describes a VALU plan); auto runs it on the shapes where it
+ * measured faster (slam_bf_mx_plan_describe h_plan[7]).  The batch call, pinned-host frame-sized calls and
+ * slam_bf_knn_u256 stay on the VALU kernels. */
+SLAM_API int slam_bf_set_engine(slam_ctx* ctx, int engine);
+/* The matrix-core plan for N x M on a device with num_cu CUs, WITHOUT a device: h_plan int32 [8] = {query blocks, worker
+ * blocks per query block, uniform chunk rows, chunks, shrinking chunks at the end of the queue, train rows per LDS stage,
+ * blocks per CU counted on, 1 when engine 0 runs this shape on the matrix cores}.  The chunk boundary table (chunks + 1
+ * ascending row indices from 0 to M) goes to h_tbl (up to tbl_cap entries; may be NULL) and its length to *tbl_len. */
+SLAM_API int slam_bf_mx_plan_describe(int num_cu, int64_t N, int64_t M, int32_t* h_plan, int32_t* h_tbl, int64_t tbl_cap,
+                                      int64_t* tbl_len);
 /* Restore the matcher's per-context merge state to its idle values.  Every search leaves it clean by itself;
  * call this after a search failed part-way (the library does so on a failed launch).  Stream-ordered. */
 SLAM_API int slam_bf_reset_state(slam_ctx* ctx);

@@ -2,6 +2,7 @@
 // (bf_hamming.hip) and the top-k search (bf_topk.hip).  Not part of the C ABI.
 #pragma once
 #include "internal.h"
+#include <vector>
 
 typedef uint32_t u32;
 
@@ -13,6 +14,7 @@ typedef uint32_t u32;
 #define SLAM_KEY_NONE 0xFFFFFFFFu
 #define SLAM_ACC_BIAS 0x80000000u
 #define SLAM_BOUND_IDLE 0x7F7F7F7Fu  // bound[] between launches (one byte pattern: restored by memset as well)
+#define SLAM_CURSOR_STRIDE 32       // u32 words between the cursors of two query waves (one 128-byte line each)
 
 // D = popcount(x) + acc in ONE instruction.  Written as asm because hipcc
 // re-associates __builtin_popcount(x)+acc chains into bcnt(x,0)+v_add3 (20
@@ -148,3 +150,169 @@ struct bf_state {
 
 // the context's merge state for up to N queries (bf_hamming.hip; allocated on first use, idle between searches)
 int bf_state_get(slam_ctx* ctx, int64_t N, bf_state* out);
+
+// Selection fused into the decode (round 4): the last arriver of a query block has (k1, k2) of its queries
+// in hand, so the selections that need NO reduction over the queries - "has a neighbour" (bf.match, feature_matchers.py:39,44)
+// and the Lowe ratio test - are made there: one flag per query, and how many each wave kept (a plain store per wave: nothing
+// to zero beforehand, the host adds them up).  A search + ratio test on resident rows is ONE launch instead of two.
+struct bf_select {
+    uint8_t* keep;        // [N] 1 = kept; null = no selection
+    int* wave_kept;       // [ceil(N / 64)] rows kept in each group of 64 consecutive queries (device or pinned host memory)
+    double param;         // mode 2: the ratio
+    int mode;             // 0 = keep every query that has a neighbour, 2 = Lowe ratio: dist0 < param * dist1 (needs two neighbours)
+    unsigned epoch;       // what the last arriver of query block x stores into done[x] once its results are visible to the host
+    unsigned* done;       // pinned host memory, or null: the caller synchronises the stream instead of polling (slam_wait_done)
+};
+
+// ---- epilogue of the top-2 searches (bf_top2_kernel, bf_top2_mx_kernel): merge, then the last arriver of this query block decodes
+// Lane `lane` of wave (tid >> 6) holds the top-2 (b1, b2) of the queries qbase + r * 64 (r < R); gk / pend: what the exchanges
+// left (share_bound / share_union); S_e: blocks that arrive for each query block; s_last: a __shared__ word of the caller.
+// (The arguments N_e ... od_e arrive in vector registers where the caller parked them in front of its scan.)
+template <int R, bool QUEUE>
+__device__ __forceinline__ void bf_top2_epilogue(const bf_state st, const int bx, const int tid, const int lane, const int qbase,
+                                                 const bool merging, const bool leader, const u32 (&b1)[R], const u32 (&b2)[R],
+                                                 const u32 (&gk)[R], const u32 (&pend)[R], const int N_e, const int S_e,
+                                                 const int base_e, int2* const oi_e, int2* const od_e, const bf_select sel,
+                                                 u32& s_last) {
+    __builtin_amdgcn_s_setprio(0);   // the scan raised it (row_acc); merges and tickets run at the default priority
+    // Merge into best[q] = (1st key << 32 | 2nd key) with TWO 32-bit atomic minima instead of a 64-bit CAS loop: the 1st
+    // key goes into the high half with a returning atomicMin; whichever of (what was there, mine) lost, or my 2nd key if
+    // that is smaller, goes into the low half.  Every key is distinct, so: the high half ends as the smallest key m; m is
+    // never pushed into the low half (its holder pushes min(loser, own 2nd), both > m; everybody else pushes keys > m);
+    // and the second smallest key s always is (if s is somebody's 1st key it either loses against m directly or is
+    // displaced by m later, and the displacing thread pushes it; if it is the 2nd key of m's holder, that thread pushes
+    // it).  One round trip, no retries when the 16-64 chunk blocks of a query finish together - the CAS loop paid a
+    // load plus one round trip per lost race (epilogue of a 4096 x 4096 block: 6.6 us mean, profiles/r02_block_timeline.log).
+    // gk >= the final 2nd-best distance (share_bound): a block whose best row is farther than that cannot contribute and
+    // skips the atomics without looking (rows AT that distance may still win the tie on index).
+    if (merging) {
+    // (merge form of the exchange: a lane whose pair has not changed since its last fold has nothing left to merge)
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int qi = qbase + r * 64;
+        if (qi < N_e && b1[r] != SLAM_KEY_NONE && (b1[r] >> SLAM_KEY_IDX_BITS) <= gk[r] &&
+            (b2[r] != pend[r] || b2[r] == SLAM_KEY_NONE)) {       // (a lone row: b2 is none, and so was it at the last fold)
+            u32* half = (u32*)&st.best[qi];
+            const u32 o1 = atomicMin(half + 1, b1[r]);
+            const u32 loser = o1 == b1[r] ? SLAM_KEY_NONE : max(o1, b1[r]);
+            const u32 push = min(loser, b2[r]);
+            if (push != SLAM_KEY_NONE) {
+                // returning form on purpose: "the value is back" means the minimum has been taken at the memory side, which is
+                // what the arrival ticket below relies on (a no-return atomic is only known to have been sent)
+                const u32 o2 = atomicMin(half, push);
+                asm volatile("" ::"v"(o2));
+            }
+        }
+    }
+    } else {
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int qi = qbase + r * 64;
+        if (qi < N_e && b1[r] != SLAM_KEY_NONE && (b1[r] >> SLAM_KEY_IDX_BITS) <= gk[r]) {
+            u32* half = (u32*)&st.best[qi];                       // little endian: [0] = 2nd key, [1] = 1st key
+            const u32 o1 = atomicMin(half + 1, b1[r]);
+            const u32 push = min(max(o1, b1[r]), b2[r]);
+            if (leader) {
+                // leaders leave the 2nd key of everything merged so far as the bound (an upper bound of the final one:
+                // the low half only ever holds keys other than the smallest)
+                const u32 k2 = min(atomicMin(half, push), push);
+                if ((k2 >> SLAM_KEY_IDX_BITS) < gk[r]) {           // returning form, like every write to bound[] (share_bound)
+                    const u32 ob = atomicMin(&st.bound[qi], k2 >> SLAM_KEY_IDX_BITS);
+                    asm volatile("" ::"v"(ob));
+                }
+            } else if (push != SLAM_KEY_NONE) {
+                // returning form on purpose: "the value is back" means the minimum has been taken at the memory side, which is
+                // what the arrival ticket below relies on (a no-return atomic is only known to have been sent)
+                const u32 o2 = atomicMin(half, push);
+                asm volatile("" ::"v"(o2));
+            }
+        }
+    }
+    }
+    // Arrival ticket.  Everything a block contributes travels in agent-scope INTEGER atomics in the RETURNING form
+    // (global_atomic_umin ... sc0: the merges above, every write to bound[] in share_bound / share_union), and what is relied
+    // on is this, no more:
+    //   (1) a returned value means the read-modify-write has been performed at the point all XCDs share - an agent-scope
+    //       atomic is never satisfied from an XCD's own L2 (the guide measures that for float atomics, "Global float atomics";
+    //       for the integer minima used here it is what 140 000 + 46 000 fuzzed searches and the state soaks of rounds 3 / 4
+    //       show, and what makes cross-XCD merges come out right at all), and nothing of it stays dirty in an L2;
+    //   (2) every wave waits for all its returns (s_waitcnt vmcnt(0): vector-memory operations return in issue order), then
+    //       the block barrier, then ONE lane's relaxed agent-scope ticket - the guide's hand-off table, first row: "an
+    //       agent-scope atomic add ... after every storing wave's vmcnt(0) wait ... the workgroup whose add came last, told by
+    //       the value its add returned";
+    //   (3) the block that draws the last ticket passes a barrier and TAKES the slots with returning 8-byte atomic exchanges
+    //       (which also put them back to idle): agent-scope atomics on BOTH sides of the hand-off - the guide's "{8-B agent
+    //       atomics both sides}" form - so no load is involved that an L1 or an XCD's L2 could serve, and no acquire fence is
+    //       needed (round 3 read the slots with sc1 loads behind a buffer_inv sc1: 4096 x 4096 16.2 -> 15.6 us without it, other
+    //       sizes equal; profiles/r04_ab_queue.log "swap").
+    // The G16 counter recipe has an agent-scope RELEASE fence (buffer_wbl2 sc1) in front of the ticket; it writes back dirty L2
+    // lines, of which this hand-off has none, and cost 1.7 us on the critical path of every block: 4096 x 4096 18.4 -> 16.7 us,
+    // 2000 x 2000 10.7 -> 9.4 us, the 1/8 shard 159.9 -> 154.8 us without it (profiles/r03_ab_cold_start.log).
+    // tests/test_isa_handoff_cpu.py holds every build to (1)-(3) on the disassembly (return forms, wait and barrier in front
+    // of the ticket, returning exchanges behind it; profiles/r04_isa_handoff_excerpt.txt), and every search leaves the
+    // whole state idle, which the GPU tests assert on the state itself (slam_bf_state_dirty).  Placement-independent: nothing
+    // relies on which XCD a block runs on.
+    if (!merging) {
+#pragma unroll
+        for (int r = 0; r < R; r++) asm volatile("" ::"v"(pend[r]));   // the parked returns of share_bound
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        const u32 ticket = __hip_atomic_fetch_add(&st.arrivals[bx], 1u, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+        s_last = ticket == (u32)S_e - 1 ? 1u : 0u;
+        asm volatile("" ::"s"(ticket));                 // (the ticket is back: its value was just used)
+    }
+    __syncthreads();
+    if (!s_last) return;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int qi = qbase + r * 64;
+        int kept = 0;
+        if (qi < N_e) {
+            // every contribution was made by an agent-scope atomic; it is taken - and the slot put back to idle for the next
+            // launch - by one more (all other blocks are done with these queries)
+            const unsigned long long v = __hip_atomic_exchange(&st.best[qi], ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const u32 k1 = (u32)(v >> 32), k2 = (u32)v;
+            int2 oi, od;
+            oi.x = k1 == SLAM_KEY_NONE ? SLAM_NO_MATCH_IDX : (int)(k1 & SLAM_KEY_IDX_MASK) + base_e;
+            od.x = k1 == SLAM_KEY_NONE ? SLAM_NO_MATCH_DIST : (int)(k1 >> SLAM_KEY_IDX_BITS);
+            oi.y = k2 == SLAM_KEY_NONE ? SLAM_NO_MATCH_IDX : (int)(k2 & SLAM_KEY_IDX_MASK) + base_e;
+            od.y = k2 == SLAM_KEY_NONE ? SLAM_NO_MATCH_DIST : (int)(k2 >> SLAM_KEY_IDX_BITS);
+            oi_e[qi] = oi;
+            od_e[qi] = od;
+            if (sel.keep) {
+                // (double) comparisons of integers <= 256: exact, and the same arithmetic as filter_keep_kernel
+                const bool k = oi.x >= 0 && (sel.mode == 0 || (oi.y >= 0 && (double)od.x < sel.param * (double)od.y));
+                sel.keep[qi] = k ? 1 : 0;
+                kept = k ? 1 : 0;
+            }
+            if (!merging) __hip_atomic_store(&st.bound[qi], SLAM_BOUND_IDLE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (sel.keep && qi - lane < N_e) {                   // (wave-uniform: the group's first query exists)
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) kept += __shfl_xor(kept, off, 64);
+            if (lane == 0) sel.wave_kept[qi >> 6] = kept;
+        }
+    }
+    if (tid == 0) __hip_atomic_store(&st.arrivals[bx], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (QUEUE && tid < 4)   // every worker of this query block has arrived, so nobody draws a ticket any more
+        __hip_atomic_store(&st.cursor[(size_t)(4 * bx + tid) * SLAM_CURSOR_STRIDE], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (__builtin_expect(sel.done != nullptr, 0)) {   // (laid out behind the common path: tests/test_isa_handoff_cpu.py reads the text in order)
+        // A host thread polls done[bx] instead of synchronising the stream (frame-sized calls: 4 us less per call,
+        // tools/ubench/sync_vs_poll.hip).  Every thread makes its own result stores visible at system scope, the block meets,
+        // one lane releases the flag.  The state restores above need no such care: the next launch is ordered behind this
+        // one by the stream.
+        __threadfence_system();
+        __syncthreads();
+        if (tid == 0) __hip_atomic_store(&sel.done[bx], sel.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// the chunk boundary table on the device (bf_hamming.hip: a ring of recent tables, uploaded only when it changes)
+int bf_table_get(slam_ctx* ctx, const std::vector<int>& tbl, const int** d_tbl);
+// the matrix-core search of one pass (bf_mx.hip): whether N x M runs there (engine, knobs, where the rows lie), and the launch
+bool bf_mx_route(slam_ctx* ctx, int64_t N, int64_t M, bool rows_on_host);
+int bf_mx_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, int64_t train_base, int32_t* d_idx,
+               int32_t* d_dist, void* d_keep, const bf_select& sel, int* qblocks_out);

@@ -7,7 +7,8 @@
 //     (8*R VGPRs), so the per-query top-2 lives in registers and never needs a
 //     cross-lane reduction.
 //   * inner op per 32-bit word: v_xor_b32 + accumulating v_bcnt_u32_b32 =
-//     16 VALU ops per 256-bit pair, the floor for this ISA without MFMA.  A
+//     16 VALU ops per 256-bit pair, the floor on the VALU.  (Large searches run on
+//     the matrix cores instead - bf_mx.hip, a +-1 FP4 dot product; bf_pass routes them.)  A
 //     gfx950 SIMD runs two wave64 VALU instructions at once when they come from
 //     different waves and at most one of them is a v_bcnt, so the floor is
 //     16 x 4 / 2 = 32 cycles per wave-row; the wave raises its priority for its
@@ -63,7 +64,6 @@
 #include "bf_common.h"
 
 #define SLAM_L2_RESIDENT_ROWS 65536 // train sets up to this many rows (2 MiB) stay in every XCD's 4 MiB L2 once touched
-#define SLAM_CURSOR_STRIDE 32       // u32 words between the cursors of two query waves (one 128-byte line each)
 #define SLAM_BF_RESIDENT 6          // blocks of bf_top2_kernel<1, true, true> a CU holds at once (106 SGPRs: 6 waves per SIMD); queue plans
 
 // Filter + update for U consecutive train rows.  "Some pair of this lane improved" <=> the AND of
@@ -152,18 +152,6 @@ __device__ __forceinline__ void share_union(unsigned long long* __restrict__ bes
     }
 }
 
-// Selection fused into the decode (round 4): the last arriver of a query block has (k1, k2) of its queries
-// in hand, so the selections that need NO reduction over the queries - "has a neighbour" (bf.match, feature_matchers.py:39,44)
-// and the Lowe ratio test - are made there: one flag per query, and how many each wave kept (a plain store per wave: nothing
-// to zero beforehand, the host adds them up).  A search + ratio test on resident rows is ONE launch instead of two.
-struct bf_select {
-    uint8_t* keep;        // [N] 1 = kept; null = no selection
-    int* wave_kept;       // [ceil(N / 64)] rows kept in each group of 64 consecutive queries (device or pinned host memory)
-    double param;         // mode 2: the ratio
-    int mode;             // 0 = keep every query that has a neighbour, 2 = Lowe ratio: dist0 < param * dist1 (needs two neighbours)
-    unsigned epoch;       // what the last arriver of query block x stores into done[x] once its results are visible to the host
-    unsigned* done;       // pinned host memory, or null: the caller synchronises the stream instead of polling (slam_wait_done)
-};
 
 // grid.x = query blocks of 256*R rows, grid.y = train chunks: block (x, y) scans rows [tbl[y], tbl[y+1]).  Every block
 // merges its top-2 into st.best; the last block to arrive for a query block decodes (idx + train_base, dist) and
@@ -466,141 +454,8 @@ __device__ __forceinline__ void bf_top2_block(const uint4* __restrict__ q, int N
         }
     }
 
-    // ---- epilogue: merge, then the last arriver of this query block decodes ----------------------
-    __builtin_amdgcn_s_setprio(0);   // the scan raised it (row_acc); merges and tickets run at the default priority
-    // Merge into best[q] = (1st key << 32 | 2nd key) with TWO 32-bit atomic minima instead of a 64-bit CAS loop: the 1st
-    // key goes into the high half with a returning atomicMin; whichever of (what was there, mine) lost, or my 2nd key if
-    // that is smaller, goes into the low half.  Every key is distinct, so: the high half ends as the smallest key m; m is
-    // never pushed into the low half (its holder pushes min(loser, own 2nd), both > m; everybody else pushes keys > m);
-    // and the second smallest key s always is (if s is somebody's 1st key it either loses against m directly or is
-    // displaced by m later, and the displacing thread pushes it; if it is the 2nd key of m's holder, that thread pushes
-    // it).  One round trip, no retries when the 16-64 chunk blocks of a query finish together - the CAS loop paid a
-    // load plus one round trip per lost race (epilogue of a 4096 x 4096 block: 6.6 us mean, profiles/r02_block_timeline.log).
-    // gk >= the final 2nd-best distance (share_bound): a block whose best row is farther than that cannot contribute and
-    // skips the atomics without looking (rows AT that distance may still win the tie on index).
-    if (merging) {
-    // (merge form of the exchange: a lane whose pair has not changed since its last fold has nothing left to merge)
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int qi = qbase + r * 64;
-        if (qi < N_e && b1[r] != SLAM_KEY_NONE && (b1[r] >> SLAM_KEY_IDX_BITS) <= gk[r] &&
-            (b2[r] != pend[r] || b2[r] == SLAM_KEY_NONE)) {       // (a lone row: b2 is none, and so was it at the last fold)
-            u32* half = (u32*)&st.best[qi];
-            const u32 o1 = atomicMin(half + 1, b1[r]);
-            const u32 loser = o1 == b1[r] ? SLAM_KEY_NONE : max(o1, b1[r]);
-            const u32 push = min(loser, b2[r]);
-            if (push != SLAM_KEY_NONE) {
-                // returning form on purpose: "the value is back" means the minimum has been taken at the memory side, which is
-                // what the arrival ticket below relies on (a no-return atomic is only known to have been sent)
-                const u32 o2 = atomicMin(half, push);
-                asm volatile("" ::"v"(o2));
-            }
-        }
-    }
-    } else {
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int qi = qbase + r * 64;
-        if (qi < N_e && b1[r] != SLAM_KEY_NONE && (b1[r] >> SLAM_KEY_IDX_BITS) <= gk[r]) {
-            u32* half = (u32*)&st.best[qi];                       // little endian: [0] = 2nd key, [1] = 1st key
-            const u32 o1 = atomicMin(half + 1, b1[r]);
-            const u32 push = min(max(o1, b1[r]), b2[r]);
-            if (leader) {
-                // leaders leave the 2nd key of everything merged so far as the bound (an upper bound of the final one:
-                // the low half only ever holds keys other than the smallest)
-                const u32 k2 = min(atomicMin(half, push), push);
-                if ((k2 >> SLAM_KEY_IDX_BITS) < gk[r]) {           // returning form, like every write to bound[] (share_bound)
-                    const u32 ob = atomicMin(&st.bound[qi], k2 >> SLAM_KEY_IDX_BITS);
-                    asm volatile("" ::"v"(ob));
-                }
-            } else if (push != SLAM_KEY_NONE) {
-                // returning form on purpose: "the value is back" means the minimum has been taken at the memory side, which is
-                // what the arrival ticket below relies on (a no-return atomic is only known to have been sent)
-                const u32 o2 = atomicMin(half, push);
-                asm volatile("" ::"v"(o2));
-            }
-        }
-    }
-    }
-    // Arrival ticket.  Everything a block contributes travels in agent-scope INTEGER atomics in the RETURNING form
-    // (global_atomic_umin ... sc0: the merges above, every write to bound[] in share_bound / share_union), and what is relied
-    // on is this, no more:
-    //   (1) a returned value means the read-modify-write has been performed at the point all XCDs share - an agent-scope
-    //       atomic is never satisfied from an XCD's own L2 (the guide measures that for float atomics, "Global float atomics";
-    //       for the integer minima used here it is what 140 000 + 46 000 fuzzed searches and the state soaks of rounds 3 / 4
-    //       show, and what makes cross-XCD merges come out right at all), and nothing of it stays dirty in an L2;
-    //   (2) every wave waits for all its returns (s_waitcnt vmcnt(0): vector-memory operations return in issue order), then
-    //       the block barrier, then ONE lane's relaxed agent-scope ticket - the guide's hand-off table, first row: "an
-    //       agent-scope atomic add ... after every storing wave's vmcnt(0) wait ... the workgroup whose add came last, told by
-    //       the value its add returned";
-    //   (3) the block that draws the last ticket passes a barrier and TAKES the slots with returning 8-byte atomic exchanges
-    //       (which also put them back to idle): agent-scope atomics on BOTH sides of the hand-off - the guide's "{8-B agent
-    //       atomics both sides}" form - so no load is involved that an L1 or an XCD's L2 could serve, and no acquire fence is
-    //       needed (round 3 read the slots with sc1 loads behind a buffer_inv sc1: 4096 x 4096 16.2 -> 15.6 us without it, other
-    //       sizes equal; profiles/r04_ab_queue.log "swap").
-    // The G16 counter recipe has an agent-scope RELEASE fence (buffer_wbl2 sc1) in front of the ticket; it writes back dirty L2
-    // lines, of which this hand-off has none, and cost 1.7 us on the critical path of every block: 4096 x 4096 18.4 -> 16.7 us,
-    // 2000 x 2000 10.7 -> 9.4 us, the 1/8 shard 159.9 -> 154.8 us without it (profiles/r03_ab_cold_start.log).
-    // tests/test_isa_handoff_cpu.py holds every build to (1)-(3) on the disassembly (return forms, wait and barrier in front
-    // of the ticket, returning exchanges behind it; profiles/r04_isa_handoff_excerpt.txt), and every search leaves the
-    // whole state idle, which the GPU tests assert on the state itself (slam_bf_state_dirty).  Placement-independent: nothing
-    // relies on which XCD a block runs on.
-    if (!merging) {
-#pragma unroll
-        for (int r = 0; r < R; r++) asm volatile("" ::"v"(pend[r]));   // the parked returns of share_bound
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const u32 ticket = __hip_atomic_fetch_add(&st.arrivals[bx], 1u, __ATOMIC_RELAXED,
-                                                  __HIP_MEMORY_SCOPE_AGENT);
-        s_last = ticket == (u32)S_e - 1 ? 1u : 0u;
-        asm volatile("" ::"s"(ticket));                 // (the ticket is back: its value was just used)
-    }
-    __syncthreads();
-    if (!s_last) return;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int qi = qbase + r * 64;
-        int kept = 0;
-        if (qi < N_e) {
-            // every contribution was made by an agent-scope atomic; it is taken - and the slot put back to idle for the next
-            // launch - by one more (all other blocks are done with these queries)
-            const unsigned long long v = __hip_atomic_exchange(&st.best[qi], ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const u32 k1 = (u32)(v >> 32), k2 = (u32)v;
-            int2 oi, od;
-            oi.x = k1 == SLAM_KEY_NONE ? SLAM_NO_MATCH_IDX : (int)(k1 & SLAM_KEY_IDX_MASK) + base_e;
-            od.x = k1 == SLAM_KEY_NONE ? SLAM_NO_MATCH_DIST : (int)(k1 >> SLAM_KEY_IDX_BITS);
-            oi.y = k2 == SLAM_KEY_NONE ? SLAM_NO_MATCH_IDX : (int)(k2 & SLAM_KEY_IDX_MASK) + base_e;
-            od.y = k2 == SLAM_KEY_NONE ? SLAM_NO_MATCH_DIST : (int)(k2 >> SLAM_KEY_IDX_BITS);
-            oi_e[qi] = oi;
-            od_e[qi] = od;
-            if (sel.keep) {
-                // (double) comparisons of integers <= 256: exact, and the same arithmetic as filter_keep_kernel
-                const bool k = oi.x >= 0 && (sel.mode == 0 || (oi.y >= 0 && (double)od.x < sel.param * (double)od.y));
-                sel.keep[qi] = k ? 1 : 0;
-                kept = k ? 1 : 0;
-            }
-            if (!merging) __hip_atomic_store(&st.bound[qi], SLAM_BOUND_IDLE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (sel.keep && qi - lane < N_e) {                   // (wave-uniform: the group's first query exists)
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) kept += __shfl_xor(kept, off, 64);
-            if (lane == 0) sel.wave_kept[qi >> 6] = kept;
-        }
-    }
-    if (tid == 0) __hip_atomic_store(&st.arrivals[bx], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (QUEUE && tid < 4)   // every worker of this query block has arrived, so nobody draws a ticket any more
-        __hip_atomic_store(&st.cursor[(size_t)(4 * bx + tid) * SLAM_CURSOR_STRIDE], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (__builtin_expect(sel.done != nullptr, 0)) {   // (laid out behind the common path: tests/test_isa_handoff_cpu.py reads the text in order)
-        // A host thread polls done[bx] instead of synchronising the stream (frame-sized calls: 4 us less per call,
-        // tools/ubench/sync_vs_poll.hip).  Every thread makes its own result stores visible at system scope, the block meets,
-        // one lane releases the flag.  The state restores above need no such care: the next launch is ordered behind this
-        // one by the stream.
-        __threadfence_system();
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(&sel.done[bx], sel.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    // ---- epilogue: merge, then the last arriver of this query block decodes (bf_common.h)
+    bf_top2_epilogue<R, QUEUE>(st, bx, tid, lane, qbase, merging, leader, b1, b2, gk, pend, N_e, S_e, base_e, oi_e, od_e, sel, s_last);
 }
 
 template <int R, bool SFEED, bool QUEUE>
@@ -1057,7 +912,7 @@ int bf_state_get(slam_ctx* ctx, int64_t N, bf_state* out) {
 // SLAM_BF_TBL_RING changes of shape later (it has long fired).
 // Tables with more than SLAM_BF_TBL_SLOT entries (train sets cut into > 4095 chunks) take the one big slot, which
 // is rewritten behind a stream synchronisation.
-static int bf_table_get(slam_ctx* ctx, const std::vector<int>& tbl, const int** d_tbl) {
+int bf_table_get(slam_ctx* ctx, const std::vector<int>& tbl, const int** d_tbl) {
     std::lock_guard<std::mutex> g(ctx->mu);
     const size_t n = tbl.size();
     SLAM_REQUIRE(n <= SLAM_BF_TBL_MAX, "train set needs %zu chunks, more than one launch can index", n - 1);
@@ -1205,8 +1060,11 @@ int slam_wait_done(slam_ctx* ctx, const unsigned* flags, int count, unsigned epo
 static int bf_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M,
                    int64_t train_base, int32_t* d_idx, int32_t* d_dist, void* d_keep, const bf_select sel = bf_select{},
                    int* qblocks_out = nullptr) {
+    const bool rows_on_host = bf_rows_on_host(ctx, d_train);
+    if (bf_mx_route(ctx, N, M, rows_on_host))   // the matrix-core search (bf_mx.hip): same results, shapes where it is faster
+        return bf_mx_pass(ctx, d_query, N, d_train, M, train_base, d_idx, d_dist, d_keep, sel, qblocks_out);
     std::vector<int> tbl;
-    const bf_plan p = make_plan(ctx, N, M, &tbl, 0, bf_rows_on_host(ctx, d_train));
+    const bf_plan p = make_plan(ctx, N, M, &tbl, 0, rows_on_host);
     bf_state st;
     if (int rc = bf_state_get(ctx, N, &st)) return rc;
     const int* d_tbl = nullptr;

@@ -84,6 +84,11 @@ class Context:
         knobs = (ctypes.c_int32 * 10)(R, blocks_per_cu, lead_rows, lead_chunk, tail, feed, cold, chunk, queue, merge)
         check(self.lib.slam_bf_set_tuning(self.handle, knobs, 10))
 
+    def set_engine(self, engine: int = 0) -> None:
+        """Which engine runs the top-2 search on this context (``slam_bf_set_engine``): 0 = auto (shipped), 1 = the VALU
+        popcount kernel, 2 = the matrix-core kernel wherever it is eligible."""
+        check(self.lib.slam_bf_set_engine(self.handle, int(engine)))
+
     def state_dirty(self) -> int:
         """Words of the search's merge state that are not idle once the stream has drained (``slam_bf_state_dirty``):
         0 after every completed search."""
@@ -132,6 +137,19 @@ def default_context() -> Context:
 
 
 PLAN_KNOBS = ("R", "blocks_per_cu", "lead_rows", "lead_chunk", "tail", "feed", "cold", "chunk", "queue", "merge")
+
+
+def mx_plan_describe(n: int, m: int, num_cu: int = 256):
+    """The matrix-core plan of the top-2 search for n x m on a device with ``num_cu`` CUs, WITHOUT a device
+    (``slam_bf_mx_plan_describe``): (plan dict, chunk boundary table)."""
+    lib = _lib.load()
+    plan = (ctypes.c_int32 * 8)()
+    cap = 1 << 16
+    tbl = (ctypes.c_int32 * cap)()
+    length = ctypes.c_int64(0)
+    check(lib.slam_bf_mx_plan_describe(num_cu, n, m, plan, tbl, cap, ctypes.byref(length)))
+    names = ("qblocks", "workers", "chunk", "chunks", "tail_chunks", "stage_rows", "resident", "auto")
+    return dict(zip(names, plan)), list(tbl[:min(length.value, cap)])
 
 
 def plan_describe(n: int, m: int, num_cu: int = 256, qb_all: int = 0, rows_on_host: bool = False, **knobs):

@@ -3,7 +3,8 @@
 
     python tools/ab_time.py LIB[:k=v...][,LIB...] [NxM ...] [--rounds R] [--reps K] [--check]
 
-A library may carry tuning knobs of slam_bf_set_tuning, e.g. path/libslamhip.so:R=2:bpc=16 (R, bpc, lead, leadchunk, tail, feed, cold, chunk, queue).
+A library may carry tuning knobs of slam_bf_set_tuning, e.g. path/libslamhip.so:R=2:bpc=16 (R, bpc, lead, leadchunk, tail, feed, cold, chunk, queue),
+and the engine of slam_bf_set_engine, e.g. path/libslamhip.so:engine=1 (0 = auto, 1 = VALU, 2 = matrix cores where eligible).
 
 Each library is dlopen'ed privately (RTLD_LOCAL; the builds export the same symbols), gets its own context and its
 own copy of the inputs.  Per round and library: K back-to-back searches between two HIP events.  --check compares
@@ -41,6 +42,7 @@ class Lib:
     def __init__(self, spec):
         path, *kv = spec.split(":")
         knobs = dict((k, int(v)) for k, v in (x.split("=") for x in kv))
+        engine = knobs.pop("engine", None)
         self.name = (os.path.basename(path).replace("libslamhip", "").replace(".so", "") or "shipped") + "".join(":" + x for x in kv)
         self.lib = ctypes.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL | os.RTLD_NOW)
         for n, (res, args) in SIGNATURES.items():
@@ -54,6 +56,8 @@ class Lib:
             nk = 10 if "merge" in knobs else 9 if "queue" in knobs else (8 if ("cold" in knobs or "chunk" in knobs) else 6)      # older builds know six / eight knobs
             k = (ctypes.c_int32 * nk)(*(knobs.get(n, 0) for n in names[:nk]))
             assert self.lib.slam_bf_set_tuning(self.ctx, k, nk) == 0, self.lib.slam_last_error()
+        if engine is not None:
+            assert self.lib.slam_bf_set_engine(self.ctx, engine) == 0, self.lib.slam_last_error()
 
     def malloc(self, nbytes):
         p = ctypes.c_void_p()
