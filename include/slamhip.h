@@ -158,6 +158,32 @@ SLAM_API int slam_bf_merge_topk(slam_ctx* ctx, const int32_t* d_idx_parts, const
  * pass), rows per chunk, blocks per CU counted on, passes, bytes of partial tables, 1 when a merge kernel follows}. */
 SLAM_API int slam_bf_topk_plan_describe(int num_cu, int64_t N, int64_t M, int K, int32_t* h_plan);
 
+/* Radius search: cv2.BFMatcher(NORM_HAMMING).radiusMatch(query, train, maxDistance) - for each query EVERY train row with
+ * distance <= max_distance (compared as a float, as OpenCV's CPU matcher does: d <= floor(max_distance); NaN and negative
+ * radii keep nothing, 256 and beyond keep every row; slam_bf_radius_threshold).  The result is compressed-row: d_offsets
+ * int64 [N+1], query q's matches are d_idx / d_dist int32 [d_offsets[q], d_offsets[q+1]), ordered by (distance asc,
+ * train index asc); train_base is added to every index.  The call counts, scans and reads the total back into *h_total
+ * (synchronous).  If the total fits in capacity it also writes the matches (asynchronous behind the read-back: synchronise
+ * the stream before reading them); otherwise d_offsets is still valid, nothing else is written and the call returns 0 with
+ * *h_total > capacity, so that the caller can grow its buffers and call again.  No state is kept between calls.  Null
+ * pointers (d_idx / d_dist may be null when capacity is 0), negative sizes or train_base + M beyond int32 are
+ * SLAM_ERR_INVALID and launch nothing.  N = 0 writes d_offsets = {0}; M = 0 gives N empty lists.  No 2^23 limit on M. */
+SLAM_API int slam_bf_radius_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M,
+                                 float max_distance, int64_t train_base, int64_t* d_offsets, int64_t capacity,
+                                 int32_t* d_idx, int32_t* d_dist, int64_t* h_total);
+/* cv2.BFMatcher.radiusMatch on host buffers (the frame-sized drop-in path): uploads, searches, downloads, one stream
+ * synchronisation; the same contract as slam_bf_radius_u256 with h_* host arrays.  Returns when the results are in place. */
+SLAM_API int slam_bf_radius_u256_host(slam_ctx* ctx, const uint8_t* h_query, int64_t N, const uint8_t* h_train, int64_t M,
+                                      float max_distance, int64_t* h_offsets, int64_t capacity, int32_t* h_idx,
+                                      int32_t* h_dist, int64_t* h_total);
+/* The threshold th of a radius: a row is kept when distance < th; th = floor(max_distance) + 1 clamped to [0, 257]. */
+SLAM_API int slam_bf_radius_threshold(float max_distance);
+/* The launch plan of slam_bf_radius_u256 for N x M on a device with num_cu CUs, WITHOUT a device.  h_plan int32 [8] =
+ * {query blocks, chunks (grid.y of the count and emit kernels), rows per chunk, blocks per CU counted on, passes (always
+ * 1: row indices are not packed into keys), bytes of the chunk count table, entries up to which a list is sorted by one
+ * wave (longer ones take the tiled path, in tiles of as many entries), distance bins of the sort}. */
+SLAM_API int slam_bf_radius_plan_describe(int num_cu, int64_t N, int64_t M, int32_t* h_plan);
+
 /* Tuning overrides for experiments, per context.  h_knobs is an int32 array of up to SLAM_BF_KNOBS entries (missing
  * entries and a NULL array mean 0 = the shipped choice):
  *   [0] R             queries per lane: 1, 2, 4 or 8 (shipped: 1)

@@ -72,6 +72,7 @@ extern "C" int slam_ctx_destroy(slam_ctx* ctx) {
     slam_second_stream_destroy(ctx);
     for (auto& kv : ctx->allocs) (void)hipFree(kv.first);
     if (ctx->workspace) (void)hipFree(ctx->workspace);
+    if (ctx->radius_mem) (void)hipFree(ctx->radius_mem);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->io_dev) (void)hipFree(ctx->io_dev);
     if (ctx->io_host) (void)hipHostFree(ctx->io_host);

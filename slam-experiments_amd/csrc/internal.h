@@ -20,6 +20,8 @@ struct slam_ctx {
     std::unordered_map<void*, uint64_t> allocs;     // device pointers handed out by slam_malloc
     void* workspace = nullptr;                      // partial top-2 tables etc.
     uint64_t workspace_bytes = 0;
+    void* radius_mem = nullptr;                     // radius search: chunk count table + scan arrays (grow-only, bf_radius.hip)
+    uint64_t radius_mem_bytes = 0;
     int num_cu = 0;
     void* bf_state_mem = nullptr;                   // matcher merge state (best/bound/arrivals), clean between launches
     int64_t bf_state_rows = 0;

@@ -156,6 +156,20 @@ class BruteForceFeatureMatcher(FeatureMatcher):
         return [[_make_dmatch(q, t, d) for t, d in zip(irow, drow) if t >= 0]
                 for q, (irow, drow) in enumerate(zip(idx.tolist(), dist.tolist()))]
 
+    def radius_match(self, query_descriptors, train_descriptors, max_distance: float, compact_result: bool = False) -> list:
+        """``bf.radiusMatch(query, train, maxDistance, compactResult=compact_result)``: per query the list of DMatch of every
+        train row with distance <= max_distance, ordered by (distance, train index); ``compact_result`` drops the queries
+        that have none."""
+        offsets, idx, dist = _m.radius_match_arrays(query_descriptors, train_descriptors, max_distance)
+        off, il, dl = offsets.tolist(), idx.tolist(), dist.tolist()
+        out = []
+        for q in range(len(off) - 1):
+            a, b = off[q], off[q + 1]
+            if a == b and compact_result:
+                continue
+            out.append([_make_dmatch(q, il[i], dl[i]) for i in range(a, b)])
+        return out
+
     def ratio_test(self, query_descriptors, train_descriptors, ratio: float = 0.75) -> list:
         return _to_dmatches(*_m.ratio_test_arrays(query_descriptors, train_descriptors, ratio))
 

@@ -19,7 +19,12 @@ from .matching import (  # noqa: F401
     knn_match_collection,
     knn_topk_device,
     match_arrays,
+    plan_describe_radius,
     plan_describe_topk,
+    radius_device,
+    radius_match_arrays,
+    radius_match_collection,
+    radius_threshold,
     ratio_test_arrays,
     split_image_index,
     topk_match_arrays,

@@ -9,6 +9,8 @@ Semantics are those of ``cv2.BFMatcher(NORM_HAMMING)`` as the reference uses it
 from __future__ import annotations
 
 import ctypes
+import math
+import threading
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -153,6 +155,108 @@ def plan_describe_topk(n: int, m: int, k: int, num_cu: int = 256) -> dict:
     plan = (ctypes.c_int32 * 8)()
     check(load().slam_bf_topk_plan_describe(num_cu, n, m, k, plan))
     names = ("K", "qblocks", "chunks", "chunk", "resident", "passes", "workspace_bytes", "merge")
+    return dict(zip(names, plan))
+
+
+def radius_threshold(max_distance) -> int:
+    """The threshold th of ``radiusMatch(maxDistance)``: a row is kept when its distance is < th (``slam_bf_radius_threshold``).
+
+    The radius is a float32, as cv2's ``maxDistance`` and the C ABI take it, and rows are kept when distance <= radius
+    (OpenCV's CPU matcher): th = floor(radius) + 1 clamped to [0, 257]; NaN and negative radii keep
+    nothing, 256 and beyond (+inf included) keep every row.  ``TypeError`` / ``ValueError`` for what is not a number."""
+    if isinstance(max_distance, (str, bytes)) or max_distance is None:
+        raise TypeError(f"max_distance must be a real number, got {max_distance!r}")
+    with np.errstate(over="ignore"):
+        r = float(np.float32(float(max_distance)))
+    if not r >= 0.0:
+        return 0
+    if r >= 256.0:
+        return 257
+    return int(math.floor(r)) + 1
+
+
+def _radius_arg(max_distance) -> float:
+    radius_threshold(max_distance)                       # (the type check, before any context or library call)
+    return float(max_distance)
+
+
+def radius_device(ctx: Context, d_query: DeviceBuffer, n: int, d_train: DeviceBuffer, m: int, max_distance: float,
+                  d_offsets: DeviceBuffer, capacity: int, d_idx: Optional[DeviceBuffer], d_dist: Optional[DeviceBuffer],
+                  train_base: int = 0) -> int:
+    """The radius search on device-resident rows (``slam_bf_radius_u256``): counts, writes ``d_offsets`` int64 [n + 1] and
+    returns the total (synchronous).  If it is at most ``capacity`` the matches follow in ``d_idx`` / ``d_dist`` int32
+    [total], each query's list ordered by (distance, train index), asynchronously on the ctx stream; otherwise nothing more
+    is written and the caller grows its buffers to the total and calls again."""
+    total = ctypes.c_int64(0)
+    check(ctx.lib.slam_bf_radius_u256(ctx.handle, d_query.ptr if n else None, n, d_train.ptr if m else None, m,
+                                      _radius_arg(max_distance), train_base, d_offsets.ptr, int(capacity),
+                                      d_idx.ptr if d_idx is not None else None, d_dist.ptr if d_dist is not None else None,
+                                      ctypes.byref(total)))
+    return total.value
+
+
+class _RadiusOutputs:
+    """Host result arrays of ``radius_match_arrays``, kept per context and grown only: the steady state is one library call."""
+
+    def __init__(self):
+        self.lock = threading.Lock()
+        self.cap = 0
+        self.reserve(4096)
+
+    def reserve(self, n: int) -> None:
+        if n > self.cap:
+            self.cap = max(4096, n + (n >> 2))
+            self.idx, self.dist = np.empty(self.cap, np.int32), np.empty(self.cap, np.int32)
+            self.p_idx, self.p_dist = addr(self.idx), addr(self.dist)
+
+
+def radius_match_arrays(query, train, max_distance: float, ctx: Optional[Context] = None):
+    """``radiusMatch(query, train, maxDistance)`` as compressed rows: (offsets int64 [N + 1], idx int32 [T], dist int32 [T]);
+    query q's matches are ``idx[offsets[q]:offsets[q + 1]]``, every train row with distance <= max_distance, ordered by
+    (distance asc, train index asc).  One library call (``slam_bf_radius_u256_host``) while the total fits the output
+    capacity kept from earlier calls; a larger total grows it and runs once more."""
+    r = _radius_arg(max_distance)
+    q, t = as_descriptors(query), as_descriptors(train)
+    ctx = ctx or default_context()
+    n, m = q.shape[0], t.shape[0]
+    out = getattr(ctx, "_radius_out", None)
+    if out is None:
+        out = ctx._radius_out = _RadiusOutputs()
+    offsets = np.empty(n + 1, np.int64)
+    total = ctypes.c_int64(0)
+    with out.lock:
+        while True:
+            check(ctx.lib.slam_bf_radius_u256_host(ctx.handle, addr(q) if n else None, n, addr(t) if m else None, m, r, addr(offsets),
+                                                   out.cap, out.p_idx, out.p_dist, ctypes.byref(total)))
+            if total.value <= out.cap:
+                break
+            out.reserve(total.value)
+        c = total.value
+        return offsets, out.idx[:c].copy(), out.dist[:c].copy()
+
+
+def radius_match_collection(query, train_images: Sequence[np.ndarray], max_distance: float, ctx: Optional[Context] = None):
+    """``radius_match_arrays`` against a collection of train images (``BFMatcher.add`` + ``radiusMatch``).
+
+    Returns (offsets int64 [N + 1], imgIdx, trainIdx, dist int32 [T]); each query's list in OpenCV's order (dist, imgIdx,
+    trainIdx), which is the order of the concatenated rows."""
+    r = _radius_arg(max_distance)
+    imgs = [as_descriptors(t) for t in train_images]
+    rows = [t.shape[0] for t in imgs]
+    if any(n >= (1 << IMGIDX_SHIFT) for n in rows):
+        raise ValueError("each train image must have fewer than 2^18 rows (OpenCV IMGIDX_ONE)")
+    cat = np.concatenate(imgs, 0) if imgs else np.zeros((0, DESC_BYTES), np.uint8)
+    offsets, idx, dist = radius_match_arrays(query, cat, r, ctx)
+    img, local = split_image_index(idx, rows)
+    return offsets, img, local, dist
+
+
+def plan_describe_radius(n: int, m: int, num_cu: int = 256) -> dict:
+    """The launch plan of the radius search for n x m on a device with ``num_cu`` CUs, WITHOUT a device
+    (``slam_bf_radius_plan_describe``)."""
+    plan = (ctypes.c_int32 * 8)()
+    check(load().slam_bf_radius_plan_describe(num_cu, n, m, plan))
+    names = ("qblocks", "chunks", "chunk", "resident", "passes", "workspace_bytes", "short_max", "bins")
     return dict(zip(names, plan))
 
 
@@ -429,6 +533,9 @@ class KeyframeDatabase:
         self.total = 0
         self._qbuf: Optional[DeviceBuffer] = None   # query rows + result tables, reused from query to query
         self._qcap = 0
+        self._rq: Optional[DeviceBuffer] = None     # query_radius: query rows + offsets, and the CSR results (grow-only)
+        self._rres: Optional[DeviceBuffer] = None
+        self._rcap = 0
 
     def add(self, descriptors) -> int:
         """Append one keyframe's descriptors; returns its index (the ``imgIdx`` later results refer to)."""
@@ -496,9 +603,50 @@ class KeyframeDatabase:
         img, local = split_image_index(idx, self.rows)
         return img, local, dist
 
+    def query_radius(self, descriptors, max_distance: float):
+        """``radiusMatch`` of the query rows against every keyframe added so far: (offsets int64 [N + 1], imgIdx, trainIdx,
+        dist int32 [T]), each query's list ordered by (dist, imgIdx, trainIdx).  Only the query rows go up and the
+        compressed rows come down; the result buffers are kept and grown from call to call."""
+        r = _radius_arg(max_distance)
+        q = as_descriptors(descriptors)
+        n = q.shape[0]
+        if n == 0:
+            z = np.zeros(0, np.int32)
+            return np.zeros(1, np.int64), z, z.copy(), z.copy()
+        need = n * (DESC_BYTES + 8) + 8
+        if self._rq is None or self._rq.nbytes < need:
+            if self._rq is not None:
+                self._rq.free()
+            self._rq = self.ctx.malloc(max(2 * need, 1024 * (DESC_BYTES + 8)))
+        dq = self._rq.view(0, n * DESC_BYTES).upload(q)
+        d_off = self._rq.view(n * DESC_BYTES, (n + 1) * 8)
+        while True:
+            res = self._rres
+            total = radius_device(self.ctx, dq, n, self._buf, self.total, r, d_off, self._rcap,
+                                  res.view(0, self._rcap * 4) if res is not None else None,
+                                  res.view(self._rcap * 4, self._rcap * 4) if res is not None else None)
+            if total <= self._rcap:
+                break
+            if self._rres is not None:
+                self._rres.free()
+            self._rcap = max(4096, total + (total >> 2))
+            self._rres = self.ctx.malloc(self._rcap * 8)
+        offsets = d_off.download(np.int64, (n + 1,))
+        if total:
+            idx = self._rres.view(0, total * 4).download(np.int32, (total,))
+            dist = self._rres.view(self._rcap * 4, total * 4).download(np.int32, (total,))
+        else:
+            idx, dist = np.zeros(0, np.int32), np.zeros(0, np.int32)
+        img, local = split_image_index(idx, self.rows)
+        return offsets, img, local, dist
+
     def free(self) -> None:
         self._buf.free()
         if self._qbuf is not None:
             self._qbuf.free()
             self._qbuf, self._qcap = None, 0
+        for b in (self._rq, self._rres):
+            if b is not None:
+                b.free()
+        self._rq, self._rres, self._rcap = None, None, 0
         self.rows, self.total = [], 0
