@@ -105,6 +105,13 @@ def test_mx_auto_shapes(built):
         assert describe(n, m)[0]["auto"] == 0, (n, m)
     for n, m in ((500, 1000000), (1000, 65536), (3000, 40000), (8192, 16384), (262144, 1000000)):
         assert describe(n, m)[0]["auto"] == 1, (n, m)
+    # one step inside and one outside each clause of bf_mx_auto (tests/test_mx_edges_gpu.py runs these shapes)
+    for n, m in ((8191, 16384), (8192, 16383), (2999, 40000), (3000, 39999), (999, 65536), (1000, 65535), (499, 200000),
+                 (500, 199999), (499, 1 << 23), (130, 1 << 23), (640, 777), (65536, 16383)):
+        assert describe(n, m)[0]["auto"] == 0, (n, m)
+    for n, m in ((8192, 16384), (3000, 40000), (1000, 65536), (500, 200000), (640, 1 << 23), (8229, 16384), (65537, 30001),
+                 ((1 << 18) + 3, 16384), (1000, 150001)):
+        assert describe(n, m)[0]["auto"] == 1, (n, m)
 
 
 def test_describe_refuses_bad_sizes(built):

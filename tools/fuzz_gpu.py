@@ -2,9 +2,11 @@
 
     python tools/fuzz_gpu.py [iterations] [seed]
 
-Every iteration draws a shape, a launch plan (queries per lane, blocks per CU, leader rows / chunk, tail length), and a
-data distribution (uniform bytes, low-entropy rows with mass ties, planted duplicates across chunk boundaries), runs
-slam_bf_knn2_u256 on device-resident rows and compares both tables bit for bit with oracle.bf_knn_c."""
+Every iteration draws a shape, an engine (0 auto, 1 VALU, 2 matrix cores: slam_bf_set_engine), a launch plan (queries per
+lane, blocks per CU, leader rows / chunk, tail length; three quarters of the engine-2 searches keep the shipped plan, since
+a tuning knob sends a search to the VALU kernel), and a data distribution (uniform bytes, low-entropy rows with mass ties,
+planted duplicates across chunk boundaries), runs slam_bf_knn2_u256 on device-resident rows and compares both tables bit
+for bit with oracle.bf_knn_c."""
 import os
 import sys
 import time
@@ -23,6 +25,7 @@ rng = np.random.default_rng(seed)
 ctx = slamhip.default_context()
 t_start = time.time()
 worst = None
+on_mx = 0
 for it in range(iters):
     n = int(rng.choice([rng.integers(1, 70), rng.integers(1, 700), rng.integers(1, 6000)]))
     m = int(rng.choice([rng.integers(1, 70), rng.integers(1, 3000), rng.integers(1, 50000)]))
@@ -48,17 +51,23 @@ for it in range(iters):
     # queue plans (resident workers drawing chunks by ticket): forced on a third of the searches that may take one
     knobs["queue"] = int(rng.choice([0, 1, -1])) if knobs["R"] in (0, 1) and knobs["feed"] != -1 else int(rng.choice([0, -1]))
     knobs["merge"] = int(rng.choice([0, 1, -1]))          # how the workers of a queue plan exchange what they know
+    eng = int(rng.integers(0, 3))
+    if eng == 2 and rng.integers(0, 4):
+        knobs = {}
     ctx.set_tuning(**knobs)
+    ctx.set_engine(eng)
+    on_mx += not any(knobs.values()) and (eng == 2 or (eng == 0 and slamhip.mx_plan_describe(n, m)[0]["auto"] == 1))
     dq, dt = slamhip.DeviceDescriptors(ctx, q), slamhip.DeviceDescriptors(ctx, t)
     tab = slamhip.Top2Table(ctx, n)
     slamhip.knn2_device(ctx, dq.buf, n, dt.buf, m, tab.idx, tab.dist)
     gi, gd = tab.download()
+    ctx.set_engine(0)
     ei, ed = oracle.bf_knn_c(q, t, 2, threads=8)
     ok = np.array_equal(gi, ei) and np.array_equal(gd, ed) and ctx.state_dirty() == 0
     for o in (tab, dq, dt):
         o.free()
     if not ok:
-        print(f"MISMATCH at iteration {it}: n={n} m={m} kind={kind} knobs={knobs} plan={ctx.plan_info(n, m)}", flush=True)
+        print(f"MISMATCH at iteration {it}: n={n} m={m} kind={kind} engine={eng} knobs={knobs} plan={ctx.plan_info(n, m)}", flush=True)
         bad = np.flatnonzero((gi != ei).any(1) | (gd != ed).any(1))[:5]
         for b in bad:
             print("  query", b, "got", gi[b], gd[b], "expected", ei[b], ed[b])
@@ -67,7 +76,7 @@ for it in range(iters):
     if it % 200 == 199:
         print(f"{it + 1} iterations ok ({time.time() - t_start:.0f} s)", flush=True)
 ctx.set_tuning()
-print(f"fuzz ok: {iters} iterations, seed {seed}, {time.time() - t_start:.0f} s")
+print(f"fuzz ok: {iters} iterations ({on_mx} on the matrix cores), seed {seed}, {time.time() - t_start:.0f} s")
 
 # ---- the per-frame host-buffer calls: match (with and without the frame cache), ratio, crossCheck ---------------------
 t_start = time.time()
