@@ -442,6 +442,10 @@ SLAM_API int slam_ba_backsub_f64(slam_ctx* ctx, int64_t L, const int32_t* d_pt_p
 #define SLAM_BA_LM_MAX_FREE 16
 #define SLAM_BA_LM_MAX_OBS (1 << 17)
 SLAM_API int slam_ba_optimize_workspace(int64_t K, int64_t L, int64_t O, uint64_t* bytes);
+/* The launch shape slam_ba_optimize_f64 takes for a window of K poses, O observations and n_free moving poses, WITHOUT a
+ * device: *blocks workgroups, and every pose or pair task cut into *slices parts.  SLAM_ERR_INVALID for the sizes
+ * slam_ba_optimize_f64 refuses. */
+SLAM_API int slam_ba_optimize_shape(int64_t K, int64_t O, int64_t n_free, int32_t* blocks, int32_t* slices);
 SLAM_API int slam_ba_optimize_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, const int32_t* d_obs_pose,
                                   const int32_t* d_obs_point, const double* d_meas, const int32_t* d_pt_ptr,
                                   const int32_t* d_pt_obs, const int32_t* d_ps_ptr, const int32_t* d_ps_obs,

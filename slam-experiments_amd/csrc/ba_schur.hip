@@ -1264,6 +1264,18 @@ extern "C" int slam_ba_optimize_workspace(int64_t K, int64_t L, int64_t O, uint6
     return SLAM_OK;
 }
 
+extern "C" int slam_ba_optimize_shape(int64_t K, int64_t O, int64_t n_free, int32_t* blocks, int32_t* slices) {
+    SLAM_REQUIRE(blocks && slices, "slam_ba_optimize_shape: null pointer");
+    SLAM_REQUIRE(K >= 1 && K <= 64 && O >= 0 && O <= SLAM_BA_LM_MAX_OBS, "bad sizes (K=%lld, O=%lld)", (long long)K, (long long)O);
+    SLAM_REQUIRE(n_free >= 0 && n_free <= SLAM_BA_LM_MAX_FREE && n_free <= K, "n_free=%lld: at most %d free poses", (long long)n_free,
+                 SLAM_BA_LM_MAX_FREE);
+    int b = 0, s = 0;
+    bg_shape(K, O, n_free, &b, &s);
+    *blocks = b;
+    *slices = s;
+    return SLAM_OK;
+}
+
 extern "C" int slam_ba_optimize_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, const int32_t* d_obs_pose,
                                     const int32_t* d_obs_point, const double* d_meas, const int32_t* d_pt_ptr,
                                     const int32_t* d_pt_obs, const int32_t* d_ps_ptr, const int32_t* d_ps_obs,

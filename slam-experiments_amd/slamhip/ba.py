@@ -10,12 +10,13 @@ and finite differences only.
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import SLAM_ERR_INVALID, SlamHipBusy, SlamHipError, addr, check
+from ._lib import SLAM_ERR_INVALID, SlamHipBusy, SlamHipError, addr, check, load
 from .device import Context, default_context
 from .pose_opt import se3_exp
 from .reproj import ReprojProblem, poses_to_rt12
@@ -247,6 +248,20 @@ class SchurProblem:
 # 64 poses and 131072 observations; measured (tools/ba_time.py) it is ahead of the multi-launch form at K = 7 (1.0 vs 2.9 ms
 # for five steps) and at K = 16 / 48 k observations (3.3 vs 5.4 ms)
 ONE_LAUNCH_MAX_FREE, ONE_LAUNCH_MAX_OBS = 16, 131072
+
+
+def one_launch_shape(K: int, O: int, n_free: int) -> tuple:
+    """The launch shape of the one-launch form for K poses, O observations and n_free moving poses, WITHOUT a device
+    (``slam_ba_optimize_shape``, the rule the launch itself uses): (workgroups, slices per pose or pair task).  Raises
+    ``ValueError`` for a window the form refuses."""
+    blocks, slices = ctypes.c_int32(0), ctypes.c_int32(0)
+    try:
+        check(load().slam_ba_optimize_shape(int(K), int(O), int(n_free), ctypes.byref(blocks), ctypes.byref(slices)))
+    except SlamHipError as exc:
+        if exc.code == SLAM_ERR_INVALID:
+            raise ValueError(str(exc)) from None
+        raise
+    return blocks.value, slices.value
 
 
 def bundle_adjust_one_launch(poses, points, obs_pose_idx, obs_point_idx, meas, intrinsics, iterations: int = 10,
