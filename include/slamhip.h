@@ -184,6 +184,36 @@ SLAM_API int slam_bf_radius_threshold(float max_distance);
  * wave (longer ones take the tiled path, in tiles of as many entries), distance bins of the sort}. */
 SLAM_API int slam_bf_radius_plan_describe(int num_cu, int64_t N, int64_t M, int32_t* h_plan);
 
+/* Window-constrained top-2: cv2.BFMatcher(NORM_HAMMING).knnMatch(query, train, k, mask=W) for the geometric mask the
+ * reference draws around each last-frame feature (get_featured_detection_mask, utils.py:58-73, built by
+ * Frontend._detect_features, frontend.py:231-251), applied to the per-frame match of Frontend._match_features
+ * (frontend.py:181-187): ORB-SLAM's search by projection.  Train row j is a candidate for query i iff
+ * fabsf(qx_i - tx_j) <= r_j && fabsf(qy_i - ty_j) <= r_j, in float32, inclusive (the square of cv2.rectangle(pt - r,
+ * pt + r, FILLED)); NaN coordinates or radii and negative radii match nothing, r = +inf puts every row in window (the
+ * result then equals slam_bf_knn2_u256's).  d_query_xy float32 [N,2] (the current keypoints), d_train_xy float32 [M,2]
+ * (window centres: last positions or predicted projections), d_radius float32 [M] per train row, or NULL and the scalar
+ * radius.  d_idx / d_dist int32 [N,k], k in {1,2}: the k nearest in-window train rows ordered by (distance asc, train
+ * index asc), missing ones (-1, INT32_MAX); bit-identical whatever the grid, the chunking or the order of the atomics.
+ * cells caps the cell grid (0 = the shipped rule: about one cell per train row, at most 1024 x 1024; 1 = one cell, a dense
+ * scan).  No N x M work or memory: a cell grid over the train centres, its bins, and the candidate rows of each query's
+ * neighbourhood; the workspace is the context's (grow-only, slam_bf_window_plan_describe).  Asynchronous on the ctx stream.
+ * M >= 2^23 (the 23-bit row field of the selection keys), N > 2^28, k not in {1,2} and null pointers are SLAM_ERR_INVALID
+ * and launch nothing.  N = 0 does nothing; M = 0 gives N rows of (-1, INT32_MAX). */
+SLAM_API int slam_bf_window_knn_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M,
+                                     const float* d_query_xy, const float* d_train_xy, const float* d_radius, float radius,
+                                     int k, int64_t cells, int32_t* d_idx, int32_t* d_dist);
+/* The same on host buffers (the frame-sized drop-in of frontend.py:181-187 with windows): uploads, searches, downloads,
+ * one stream synchronisation.  h_radius is float32 [M] or NULL (the scalar radius).  Returns when the results are in place. */
+SLAM_API int slam_bf_window_knn_u256_host(slam_ctx* ctx, const uint8_t* h_query, int64_t N, const uint8_t* h_train, int64_t M,
+                                          const float* h_query_xy, const float* h_train_xy, const float* h_radius,
+                                          float radius, int k, int64_t cells, int32_t* h_idx, int32_t* h_dist);
+/* The launch plan of slam_bf_window_knn_u256 for N x M under the cell cap `cells` (0 = shipped rule) on a device with
+ * num_cu CUs, WITHOUT a device.  h_plan int64 [10] = {cells per axis at most, cells at most, query tiles at most,
+ * queries per work item, candidate rows per work item, blocks of the search kernel (4 waves each), parts of the histogram
+ * scan (0: one block), parts of the item scan (0: one block), workspace bytes, cells per query tile side at most}.
+ * M >= 2^23 and N > 2^28 are SLAM_ERR_INVALID, as in the search. */
+SLAM_API int slam_bf_window_plan_describe(int num_cu, int64_t N, int64_t M, int64_t cells, int64_t* h_plan);
+
 /* Tuning overrides for experiments, per context.  h_knobs is an int32 array of up to SLAM_BF_KNOBS entries (missing
  * entries and a NULL array mean 0 = the shipped choice):
  *   [0] R             queries per lane: 1, 2, 4 or 8 (shipped: 1)

@@ -156,6 +156,17 @@ class BruteForceFeatureMatcher(FeatureMatcher):
         return [[_make_dmatch(q, t, d) for t, d in zip(irow, drow) if t >= 0]
                 for q, (irow, drow) in enumerate(zip(idx.tolist(), dist.tolist()))]
 
+    def match_in_windows(self, source_descriptors, query_descriptors, source_xy, query_xy, radius,
+                         dist_threshold: Optional[float] = None) -> Sequence[DMatch]:
+        """``match(source, query, dist_threshold)`` where query row i may only pair with source rows whose window holds
+        it: ``|query_xy[i] - source_xy[j]| <= radius`` in both axes (float32, inclusive) - the squares the reference draws
+        around the last frame's features (``utils.py:58-73``, ``frontend.py:231-251``), used for the match of
+        ``frontend.py:181-187`` instead of a search over the whole image.  ``radius`` is a number or one per source row;
+        ``source_xy`` are the last positions or the predicted projections.  Same post-filter and result type as ``match``;
+        query rows with no source row in reach are not in the result."""
+        return MatchList(*_m.window_match_filtered(source_descriptors, query_descriptors, source_xy, query_xy, radius,
+                                                   dist_threshold))
+
     def radius_match(self, query_descriptors, train_descriptors, max_distance: float, compact_result: bool = False) -> list:
         """``bf.radiusMatch(query, train, maxDistance, compactResult=compact_result)``: per query the list of DMatch of every
         train row with distance <= max_distance, ordered by (distance, train index); ``compact_result`` drops the queries

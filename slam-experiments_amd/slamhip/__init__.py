@@ -21,6 +21,7 @@ from .matching import (  # noqa: F401
     match_arrays,
     plan_describe_radius,
     plan_describe_topk,
+    plan_describe_window,
     radius_device,
     radius_match_arrays,
     radius_match_collection,
@@ -29,5 +30,8 @@ from .matching import (  # noqa: F401
     split_image_index,
     topk_match_arrays,
     topk_match_collection,
+    window_knn_device,
+    window_match_arrays,
+    window_match_filtered,
 )
 from .reproj import PoseOnlyProblem, ReprojProblem, build_linearization, poses_to_rt12  # noqa: F401

@@ -72,6 +72,11 @@ SIGNATURES = {
                                          c_void_p, POINTER(c_int64)]),
     "slam_bf_radius_threshold": (c_int, [c_float]),
     "slam_bf_radius_plan_describe": (c_int, [c_int, c_int64, c_int64, POINTER(c_int32)]),
+    "slam_bf_window_knn_u256": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float,
+                                        c_int, c_int64, c_void_p, c_void_p]),
+    "slam_bf_window_knn_u256_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                             c_float, c_int, c_int64, c_void_p, c_void_p]),
+    "slam_bf_window_plan_describe": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_int64)]),
     "slam_bf_set_tuning": (c_int, [c_void_p, POINTER(c_int32), c_int]),
     "slam_bf_plan_info": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_int32)]),
     "slam_bf_plan_describe": (c_int, [c_int, POINTER(c_int32), c_int, c_int64, c_int64, c_int64, c_int, POINTER(c_int32),

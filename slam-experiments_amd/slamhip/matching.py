@@ -260,6 +260,141 @@ def plan_describe_radius(n: int, m: int, num_cu: int = 256) -> dict:
     return dict(zip(names, plan))
 
 
+WINDOW_M_MAX = (1 << 23) - 1     # train rows of one window search: the selection keys hold the row in 23 bits
+
+
+def _window_k(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) not in (1, 2):
+        raise ValueError(f"k must be 1 or 2, got {k!r}")
+    return int(k)
+
+
+def _window_xy(xy, n: int, what: str) -> np.ndarray:
+    """Positions as C-contiguous float32 [n, 2]: any real dtype (keypoints often come as integers); ``TypeError`` for
+    others, ``ValueError`` for a shape that is not (n, 2).  An empty array stands for n == 0 whatever its shape."""
+    a = np.asarray(xy)
+    if a.dtype.kind not in "fiu":
+        raise TypeError(f"{what} must hold real numbers, got dtype {a.dtype}")
+    if n == 0 and a.size == 0:
+        return np.zeros((0, 2), np.float32)
+    if a.shape != (n, 2):
+        raise ValueError(f"{what} must have shape ({n}, 2), got {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _window_radius(radius, m: int):
+    """(scalar float32 or None, per-row float32 [m] or None): a real scalar, or one value per train row."""
+    if radius is None or isinstance(radius, (str, bytes)):
+        raise TypeError(f"radius must be a real number or an array of {m} of them, got {radius!r}")
+    a = np.asarray(radius)
+    if a.dtype.kind not in "fiu":
+        raise TypeError(f"radius must hold real numbers, got dtype {a.dtype}")
+    if a.ndim == 0:
+        with np.errstate(over="ignore"):
+            return float(np.float32(a)), None
+    if a.shape != (m,):
+        raise ValueError(f"a per-row radius must have shape ({m},), got {a.shape}")
+    return 0.0, np.ascontiguousarray(a, dtype=np.float32)
+
+
+def window_knn_device(ctx: Context, d_query: DeviceBuffer, n: int, d_train: DeviceBuffer, m: int, d_query_xy: DeviceBuffer,
+                      d_train_xy: DeviceBuffer, radius, k: int, d_idx: DeviceBuffer, d_dist: DeviceBuffer, cells: int = 0) -> None:
+    """The window-constrained top-k (k in {1, 2}) on device-resident rows (``slam_bf_window_knn_u256``; asynchronous on the
+    ctx stream): ``d_query_xy`` / ``d_train_xy`` float32 [n, 2] / [m, 2], ``radius`` a number or a ``DeviceBuffer`` of
+    float32 [m] (one per train row); ``d_idx`` / ``d_dist`` int32 [n, k] as ``knn_match_arrays`` lays them out."""
+    k = _window_k(k)
+    if isinstance(radius, DeviceBuffer):
+        d_rad, r = radius.ptr, 0.0
+    else:
+        r, rows = _window_radius(radius, m)
+        if rows is not None:
+            raise TypeError("a per-row radius must be a DeviceBuffer here (float32 [m])")
+        d_rad = None
+    check(ctx.lib.slam_bf_window_knn_u256(ctx.handle, d_query.ptr if n else None, n, d_train.ptr if m else None, m,
+                                          d_query_xy.ptr if n else None, d_train_xy.ptr if m else None, d_rad, r, k, int(cells),
+                                          d_idx.ptr if n else None, d_dist.ptr if n else None))
+
+
+def window_match_arrays(query, train, query_xy, train_xy, radius, k: int = 2, ctx: Optional[Context] = None,
+                        cells: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """``knnMatch(query, train, k, mask=W)`` for the geometric window W: train row j is a candidate for query i iff
+    ``|qx_i - tx_j| <= r_j`` and ``|qy_i - ty_j| <= r_j`` in float32 (inclusive; NaN and negative radii match nothing,
+    ``+inf`` everything).  ``query_xy`` [N, 2] are the current keypoints, ``train_xy`` [M, 2] the window centres, ``radius``
+    a number or one per train row [M].  Returns (idx, dist) int32 [N, k], k in {1, 2}, ordered by (distance, train index);
+    missing neighbours (-1, INT32_MAX), rows with an empty window included.  ``cells`` caps the cell grid (0 = the
+    shipped rule; the result does not depend on it).  One library call (``slam_bf_window_knn_u256_host``)."""
+    k = _window_k(k)
+    q, t = as_descriptors(query), as_descriptors(train)
+    n, m = q.shape[0], t.shape[0]
+    if m > WINDOW_M_MAX:
+        raise ValueError(f"the window search takes fewer than 2^23 train rows, got {m}")
+    qxy, txy = _window_xy(query_xy, n, "query_xy"), _window_xy(train_xy, m, "train_xy")
+    r, rows = _window_radius(radius, m)
+    ctx = ctx or default_context()
+    idx = np.empty((n, k), np.int32)
+    dist = np.empty((n, k), np.int32)
+    check(ctx.lib.slam_bf_window_knn_u256_host(ctx.handle, addr(q) if n else None, n, addr(t) if m else None, m,
+                                               addr(qxy) if n else None, addr(txy) if m else None,
+                                               addr(rows) if rows is not None and m else None, r, k, int(cells),
+                                               addr(idx) if n else None, addr(dist) if n else None))
+    return idx, dist
+
+
+def window_match_filtered(source, query, source_xy, query_xy, radius, dist_threshold: Optional[float] = None,
+                          ctx: Optional[Context] = None):
+    """``BruteForceFeatureMatcher.match`` restricted to windows around the source (last-frame) positions: the windowed
+    nearest neighbour of every query row, then ``match``'s post-filter (``distance < max(2*min_dist, dist_threshold)``
+    when a threshold is given; rows without an in-window neighbour are dropped).  The search's device tables go straight
+    into ``slam_bf_match_filter``.  Returns (queryIdx, trainIdx int32, distance float32) in ascending queryIdx."""
+    q, t = as_descriptors(query), as_descriptors(source)
+    n, m = q.shape[0], t.shape[0]
+    if m > WINDOW_M_MAX:
+        raise ValueError(f"the window search takes fewer than 2^23 train rows, got {m}")
+    qxy, txy = _window_xy(query_xy, n, "query_xy"), _window_xy(source_xy, m, "source_xy")
+    r, rows = _window_radius(radius, m)
+    mode = MODE_MIN_DIST if dist_threshold else MODE_ALL     # `if dist_threshold and ...` (feature_matchers.py:41)
+    param = float(dist_threshold or 0.0)
+    ctx = ctx or default_context()
+    if n == 0:
+        z = np.zeros(0, np.int32)
+        return z, z.copy(), np.zeros(0, np.float32)
+    # one device block: query rows | train rows | query xy | train xy | radii | idx [n,2] | dist [n,2] | keep [n]
+    sizes = [n * DESC_BYTES, m * DESC_BYTES, n * 8, m * 8, (m * 4 if rows is not None else 0), n * 8, n * 8, n]
+    offs = np.cumsum([0] + [(b + 255) // 256 * 256 for b in sizes]).tolist()
+    buf = ctx.malloc(max(offs[-1], 256))
+    try:
+        views = [buf.view(offs[i], sizes[i]) for i in range(len(sizes))]
+        views[0].upload(q)
+        views[2].upload(qxy)
+        if m:
+            views[1].upload(t)
+            views[3].upload(txy)
+            if rows is not None:
+                views[4].upload(rows)
+        window_knn_device(ctx, views[0], n, views[1], m, views[2], views[3], views[4] if rows is not None else r, 2,
+                          views[5], views[6])
+        cnt, mind = ctypes.c_int64(0), ctypes.c_int32(0)
+        check(ctx.lib.slam_bf_match_filter(ctx.handle, views[5].ptr, views[6].ptr, n, mode, param, views[7].ptr,
+                                           ctypes.byref(cnt), ctypes.byref(mind)))
+        keep = views[7].download(np.uint8, (n,))
+        idx = views[5].download(np.int32, (n, 2))
+        dist = views[6].download(np.int32, (n, 2))
+    finally:
+        buf.free()
+    qi = np.flatnonzero(keep).astype(np.int32)
+    return qi, np.ascontiguousarray(idx[qi, 0]), dist[qi, 0].astype(np.float32)
+
+
+def plan_describe_window(n: int, m: int, cells: int = 0, num_cu: int = 256) -> dict:
+    """The launch plan of the window search for n x m under the cell cap ``cells`` (0 = the shipped rule) on a device with
+    ``num_cu`` CUs, WITHOUT a device (``slam_bf_window_plan_describe``)."""
+    plan = (ctypes.c_int64 * 10)()
+    check(load().slam_bf_window_plan_describe(num_cu, n, m, cells, plan))
+    names = ("side", "cells", "tiles", "queries_per_item", "chunk", "blocks", "scan_parts_cells", "scan_parts_items",
+             "workspace_bytes", "tile_max")
+    return dict(zip(names, plan))
+
+
 class _MatchOutputs:
     """Result buffers of ``slam_bf_match_host`` kept between calls (grown on demand) with their addresses: a frame loop
     allocates nothing per call and looks no pointer up twice."""
