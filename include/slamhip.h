@@ -29,11 +29,15 @@
  *     same context; pointers named h_* are host pointers owned by the caller
  *     and only read/written during the call.
  *   - a slam_ctx owns one HIP device + one HIP stream; calls on one ctx are
- *     stream-ordered, different ctxs are independent (one per thread / GPU).
- *     The host-buffer entry points (*_host) may be called from several threads
- *     on one ctx (they serialise on its staging block); the device-pointer
- *     entry points share the ctx's workspace and merge state and expect ONE
- *     calling thread per ctx at a time.
+ *     stream-ordered, different ctxs are independent.  Any number of threads
+ *     may call any entry point on one ctx, host-buffer (*_host) and
+ *     device-pointer ones alike.  Calls that use a block the ctx owns (its
+ *     workspace, merge state, chunk tables, pinned completion / count block,
+ *     filter scratch, staging arena) serialise on the ctx's call lock, held
+ *     from taking the block through the last launch and, for calls that
+ *     wait, through the read-back of their counts.  Device buffers the caller
+ *     owns (d_* arguments) remain the caller's business: two threads that
+ *     hand one ctx the same output buffer race on it.
  *   - empty inputs are not errors: N == 0 is a no-op; M == 0 yields idx = -1,
  *     dist = INT32_MAX (OpenCV's "no neighbour").
  */
@@ -78,6 +82,9 @@ SLAM_API int slam_ctx_create(int device, slam_ctx** out);
 SLAM_API int slam_ctx_destroy(slam_ctx* ctx);
 SLAM_API int slam_ctx_device(slam_ctx* ctx, int* device);
 SLAM_API int slam_sync(slam_ctx* ctx);
+/* current sizes of the ctx's grow-only blocks (for tests): h_bytes[0..count), count <= 6, of {workspace, merge state,
+ * pinned completion / count block, staging arena (device), staging arena (pinned host), radius tables}; 0 = not yet taken */
+SLAM_API int slam_ctx_block_bytes(slam_ctx* ctx, int64_t* h_bytes, int count);
 
 /* ---- device memory (caller keeps the pointer, library tracks it) ------- */
 SLAM_API int slam_malloc(slam_ctx* ctx, uint64_t bytes, void** d_ptr);

@@ -126,9 +126,9 @@ int slam_filter_launch(slam_ctx* ctx, const int32_t* d_idx, const int32_t* d_dis
     return SLAM_OK;
 }
 
-extern "C" int slam_bf_match_filter(slam_ctx* ctx, const int32_t* d_idx, const int32_t* d_dist, int64_t N,
-                                    int mode, double param, uint8_t* d_keep, int64_t* h_count,
-                                    int32_t* h_min_dist) {
+// the count and minimum come back through ctx->scratch: the caller holds ctx->call_mu from the launch through the read-back
+int slam_filter_count(slam_ctx* ctx, const int32_t* d_idx, const int32_t* d_dist, int64_t N, int mode, double param,
+                      uint8_t* d_keep, int64_t* h_count, int32_t* h_min_dist) {
     SLAM_REQUIRE(ctx, "slam_bf_match_filter: null ctx");
     SLAM_REQUIRE(mode >= 0 && mode <= 2, "mode %d not in {0,1,2}", mode);
     SLAM_REQUIRE(N >= 0 && N <= (1ll << 30), "bad N=%lld", (long long)N);
@@ -144,6 +144,14 @@ extern "C" int slam_bf_match_filter(slam_ctx* ctx, const int32_t* d_idx, const i
     if (h_count) *h_count = (int64_t)h.count;
     if (h_min_dist) *h_min_dist = h.min_dist;
     return SLAM_OK;
+}
+
+extern "C" int slam_bf_match_filter(slam_ctx* ctx, const int32_t* d_idx, const int32_t* d_dist, int64_t N,
+                                    int mode, double param, uint8_t* d_keep, int64_t* h_count,
+                                    int32_t* h_min_dist) {
+    SLAM_REQUIRE(ctx, "slam_bf_match_filter: null ctx");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    return slam_filter_count(ctx, d_idx, d_dist, N, mode, param, d_keep, h_count, h_min_dist);
 }
 
 // ---- crossCheck ------------------------------------------------------------
@@ -186,6 +194,7 @@ extern "C" int slam_bf_cross_check(slam_ctx* ctx, const int32_t* d_fwd_idx, cons
                                    const int32_t* d_rev_idx, int64_t M, int32_t* d_out_idx, int32_t* d_out_dist,
                                    int64_t* h_count) {
     SLAM_REQUIRE(ctx, "slam_bf_cross_check: null ctx");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);         // the count comes back through ctx->scratch
     SLAM_REQUIRE(N >= 0 && M >= 0 && N <= (1ll << 30) && M <= (1ll << 30), "bad sizes");
     if (h_count) *h_count = 0;
     if (N == 0) return SLAM_OK;

@@ -868,7 +868,7 @@ extern "C" int slam_bf_plan_info(slam_ctx* ctx, int64_t N, int64_t M, int32_t* h
 // merge state for up to N queries, kept clean between launches (see bf_state), followed by the chunk boundary table
 #define SLAM_BF_TBL_MAX 65536   // entries; grid.y <= 65535
 // (SLAM_BF_TBL_RING slots of SLAM_BF_TBL_SLOT entries + one slot of SLAM_BF_TBL_MAX: internal.h)
-static size_t bf_state_bytes(size_t rows) {      // best u64 [rows] + bound u32 [rows] + arrivals u32 [blocks] + padded cursors + alignment slack
+size_t bf_state_bytes(size_t rows) {      // best u64 [rows] + bound u32 [rows] + arrivals u32 [blocks] + padded cursors + alignment slack
     const size_t blocks = (rows + 255) / 256;   // query blocks at R = 1, the finest split
     return rows * 12 + blocks * 4 + blocks * 16 * SLAM_CURSOR_STRIDE + 128;
 }
@@ -882,8 +882,8 @@ static int bf_state_fill(slam_ctx* ctx) {
     return SLAM_OK;
 }
 
+// (callers hold ctx->call_mu, as for the chunk table slots and the pinned block below)
 int bf_state_get(slam_ctx* ctx, int64_t N, bf_state* out) {
-    std::lock_guard<std::mutex> g(ctx->mu);
     if (N > ctx->bf_state_rows) {
         SLAM_HIP(hipStreamSynchronize(ctx->stream));
         if (ctx->bf_state_mem) SLAM_HIP(hipFree(ctx->bf_state_mem));
@@ -913,7 +913,6 @@ int bf_state_get(slam_ctx* ctx, int64_t N, bf_state* out) {
 // Tables with more than SLAM_BF_TBL_SLOT entries (train sets cut into > 4095 chunks) take the one big slot, which
 // is rewritten behind a stream synchronisation.
 int bf_table_get(slam_ctx* ctx, const std::vector<int>& tbl, const int** d_tbl) {
-    std::lock_guard<std::mutex> g(ctx->mu);
     const size_t n = tbl.size();
     SLAM_REQUIRE(n <= SLAM_BF_TBL_MAX, "train set needs %zu chunks, more than one launch can index", n - 1);
     if (!ctx->bf_tbl_ready) {
@@ -980,12 +979,16 @@ int bf_table_get(slam_ctx* ctx, const std::vector<int>& tbl, const int** d_tbl) 
 // Put the merge state back to its idle values (best = none, bound = loose, arrivals = 0).  The kernel restores
 // it itself at the end of every search; this is for the case where one did not finish (a failed launch, a device
 // error reported by a later call): stream-ordered, so it may be issued right behind whatever is still queued.
+int bf_state_reset(slam_ctx* ctx) {
+    if (!ctx->bf_state_mem) return SLAM_OK;
+    return bf_state_fill(ctx);
+}
+
 extern "C" int slam_bf_reset_state(slam_ctx* ctx) {
     SLAM_REQUIRE(ctx, "slam_bf_reset_state: null ctx");
     SLAM_HIP(hipSetDevice(ctx->device));
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->bf_state_mem) return SLAM_OK;
-    return bf_state_fill(ctx);
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    return bf_state_reset(ctx);
 }
 
 // How many 32-bit words of the merge state are NOT at their idle value (best = ~0, bound = 0x7F7F7F7F, arrivals = 0,
@@ -994,11 +997,12 @@ extern "C" int slam_bf_reset_state(slam_ctx* ctx) {
 extern "C" int slam_bf_state_dirty(slam_ctx* ctx, int64_t* h_words) {
     SLAM_REQUIRE(ctx && h_words, "slam_bf_state_dirty: null argument");
     SLAM_HIP(hipSetDevice(ctx->device));
-    SLAM_HIP(hipStreamSynchronize(ctx->stream));
     std::vector<u32> host;
     size_t rows;
     {
-        std::lock_guard<std::mutex> g(ctx->mu);
+        // under the call lock: no other thread's search is queued between the drain and the copy
+        std::lock_guard<std::mutex> lk(ctx->call_mu);
+        SLAM_HIP(hipStreamSynchronize(ctx->stream));
         rows = (size_t)ctx->bf_state_rows;
         *h_words = 0;
         if (!ctx->bf_state_mem) return SLAM_OK;
@@ -1020,16 +1024,16 @@ extern "C" int slam_bf_state_dirty(slam_ctx* ctx, int64_t* h_words) {
 // after 2 ms of spinning - a long one, or a launch that failed - is waited for the ordinary way, which also surfaces errors;
 // and every 256th polled call synchronises anyway, so the runtime retires its completion signals at a bounded distance.
 // The context's pinned block: SLAM_BF_DONE_FLAGS completion words, then `extra` bytes (the fused selection's per-wave counts).
+// Grow-only, and an outgrown block is not freed before slam_ctx_destroy: a search queued without a count may still write it.
+// The caller holds ctx->call_mu from here through the read-back of the words and counts its kernel writes.
 int slam_done_block(slam_ctx* ctx, uint64_t extra) {
-    std::lock_guard<std::mutex> g(ctx->mu);
     if (SLAM_BF_DONE_BYTES + extra > ctx->sel_host_bytes) {
-        SLAM_HIP(hipStreamSynchronize(ctx->stream));          // a queued search may still write the old block
-        if (ctx->sel_host) SLAM_HIP(hipHostFree(ctx->sel_host));
-        ctx->sel_host = nullptr;
-        ctx->sel_host_bytes = 0;
         const uint64_t bytes = (SLAM_BF_DONE_BYTES + extra + 4095) / 4096 * 4096 * 2;
-        SLAM_HIP(hipHostMalloc(&ctx->sel_host, bytes, hipHostMallocDefault));
-        memset(ctx->sel_host, 0, bytes);
+        void* p = nullptr;
+        SLAM_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+        memset(p, 0, bytes);
+        if (ctx->sel_host) ctx->sel_host_old.push_back(ctx->sel_host);
+        ctx->sel_host = p;
         ctx->sel_host_bytes = bytes;
     }
     return SLAM_OK;
@@ -1044,8 +1048,8 @@ int slam_wait_done(slam_ctx* ctx, const unsigned* flags, int count, unsigned epo
     bool done = false;
     for (unsigned spins = 1; !done; spins++) {
         int i = 0;
-        // (== and not "this epoch or a later one": two threads on one context may draw their epochs and launch in different
-        // orders; a word overwritten by the other thread's call is then simply never seen, and the wait falls back to the stream)
+        // (== and not "this epoch or a later one": a word of the block is only this call's while it holds ctx->call_mu; a search
+        // queued earlier without a count may still store an older epoch, which is then simply not this one)
         while (i < count && __atomic_load_n(&flags[i], __ATOMIC_ACQUIRE) == epoch) i++;
         done = i == count;
         if (done) break;
@@ -1111,7 +1115,7 @@ static int bf_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_
     if (int rc = slam_prof_end(ctx)) return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        (void)slam_bf_reset_state(ctx);
+        (void)bf_state_reset(ctx);
         return slam_set_error(SLAM_ERR_HIP, "top-2 kernel launch failed: %s", hipGetErrorString(e));
     }
     return SLAM_OK;
@@ -1119,6 +1123,8 @@ static int bf_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_
 
 extern "C" int slam_bf_knn2_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train,
                                  int64_t M, int64_t train_base, int32_t* d_idx, int32_t* d_dist) {
+    SLAM_REQUIRE(ctx, "slam_bf_knn2_u256: null ctx");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     return slam_bf_knn2_keep(ctx, d_query, N, d_train, M, train_base, d_idx, d_dist, nullptr);
 }
 
@@ -1180,7 +1186,7 @@ int slam_bf_knn2_select(slam_ctx* ctx, const void* d_query, int64_t N, const voi
     if (!fused) {
         if (int rc = slam_bf_knn2_keep(ctx, d_query, N, d_train, M, train_base, d_idx, d_dist, d_query_keep)) return rc;
         if (!h_count) return slam_filter_launch(ctx, d_idx, d_dist, N, mode, param, d_sel_keep);
-        return slam_bf_match_filter(ctx, d_idx, d_dist, N, mode, param, d_sel_keep, h_count, nullptr);
+        return slam_filter_count(ctx, d_idx, d_dist, N, mode, param, d_sel_keep, h_count, nullptr);
     }
     SLAM_REQUIRE(M >= 0 && d_query && d_train && d_idx && d_dist, "slam_bf_knn2_select_u256: null device pointer");
     SLAM_REQUIRE(((uintptr_t)d_query & 15) == 0 && ((uintptr_t)d_train & 15) == 0 && ((uintptr_t)d_query_keep & 15) == 0,
@@ -1217,6 +1223,8 @@ int slam_bf_knn2_select(slam_ctx* ctx, const void* d_query, int64_t N, const voi
 extern "C" int slam_bf_knn2_select_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M,
                                         int64_t train_base, int32_t* d_idx, int32_t* d_dist, int mode, double param,
                                         uint8_t* d_keep, int64_t* h_count) {
+    SLAM_REQUIRE(ctx, "slam_bf_knn2_select_u256: null ctx");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     return slam_bf_knn2_select(ctx, d_query, N, d_train, M, train_base, d_idx, d_dist, nullptr, mode, param, d_keep, h_count);
 }
 
@@ -1301,7 +1309,7 @@ int slam_bf_knn2_batch_keep(slam_ctx* ctx, int64_t B, const slam_bf_search* h_se
     if (int rc = slam_prof_end(ctx)) return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        (void)slam_bf_reset_state(ctx);
+        (void)bf_state_reset(ctx);
         return slam_set_error(SLAM_ERR_HIP, "batched top-2 kernel launch failed: %s", hipGetErrorString(e));
     }
     if (poll) return slam_wait_done(ctx, batch.done, done_words, batch.epoch);
@@ -1310,6 +1318,8 @@ int slam_bf_knn2_batch_keep(slam_ctx* ctx, int64_t B, const slam_bf_search* h_se
 }
 
 extern "C" int slam_bf_knn2_batch_u256(slam_ctx* ctx, int64_t B, const slam_bf_search* h_searches) {
+    SLAM_REQUIRE(ctx, "slam_bf_knn2_batch_u256: null ctx");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     return slam_bf_knn2_batch_keep(ctx, B, h_searches, nullptr, false);
 }
 

@@ -338,7 +338,7 @@ int bf_mx_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_trai
     if (int rc = slam_prof_end(ctx)) return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        (void)slam_bf_reset_state(ctx);
+        (void)bf_state_reset(ctx);
         return slam_set_error(SLAM_ERR_HIP, "top-2 MX kernel launch failed: %s", hipGetErrorString(e));
     }
     return SLAM_OK;

@@ -473,8 +473,7 @@ static inline uint64_t radius_align(uint64_t v) { return (v + 255) / 256 * 256; 
 
 // the context's grow-only block for the count table and the scan's arrays (kept apart from slam_workspace, which the
 // staging area of the emit step grows once the total is known)
-static int radius_tables(slam_ctx* ctx, uint64_t bytes, void** out) {
-    std::lock_guard<std::mutex> g(ctx->mu);
+static int radius_tables(slam_ctx* ctx, uint64_t bytes, void** out) {    // (under ctx->call_mu)
     if (bytes > ctx->radius_mem_bytes) {
         SLAM_HIP(hipStreamSynchronize(ctx->stream));
         if (ctx->radius_mem) SLAM_HIP(hipFree(ctx->radius_mem));
@@ -494,9 +493,10 @@ static int radius_launch_check(const char* what) {
     return SLAM_OK;
 }
 
-extern "C" int slam_bf_radius_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, float max_distance,
-                                   int64_t train_base, int64_t* d_offsets, int64_t capacity, int32_t* d_idx, int32_t* d_dist,
-                                   int64_t* h_total) {
+// slam_bf_radius_u256 without the call lock
+static int radius_search(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, float max_distance,
+                         int64_t train_base, int64_t* d_offsets, int64_t capacity, int32_t* d_idx, int32_t* d_dist,
+                         int64_t* h_total) {
     SLAM_REQUIRE(ctx, "slam_bf_radius_u256: null ctx");
     SLAM_REQUIRE(N >= 0 && M >= 0 && capacity >= 0, "negative size (N=%lld, M=%lld, capacity=%lld)", (long long)N, (long long)M,
                  (long long)capacity);
@@ -580,6 +580,14 @@ extern "C" int slam_bf_radius_u256(slam_ctx* ctx, const void* d_query, int64_t N
     return radius_launch_check("emit / sort");
 }
 
+extern "C" int slam_bf_radius_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, float max_distance,
+                                   int64_t train_base, int64_t* d_offsets, int64_t capacity, int32_t* d_idx, int32_t* d_dist,
+                                   int64_t* h_total) {
+    SLAM_REQUIRE(ctx, "slam_bf_radius_u256: null ctx");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    return radius_search(ctx, d_query, N, d_train, M, max_distance, train_base, d_offsets, capacity, d_idx, d_dist, h_total);
+}
+
 // upload, search, download, one stream synchronisation (through the context's host-buffer arena)
 extern "C" int slam_bf_radius_u256_host(slam_ctx* ctx, const uint8_t* h_query, int64_t N, const uint8_t* h_train, int64_t M,
                                         float max_distance, int64_t* h_offsets, int64_t capacity, int32_t* h_idx, int32_t* h_dist,
@@ -589,7 +597,7 @@ extern "C" int slam_bf_radius_u256_host(slam_ctx* ctx, const uint8_t* h_query, i
                  (long long)N, (long long)M, (long long)capacity);
     SLAM_REQUIRE(h_offsets && h_total && (h_query || N == 0) && (h_train || M == 0) && (capacity == 0 || (h_idx && h_dist)),
                  "slam_bf_radius_u256_host: null host pointer");
-    std::lock_guard<std::mutex> lk(ctx->io_mu);
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     SLAM_HIP(hipSetDevice(ctx->device));
     const int64_t cap = capacity < N * M ? capacity : N * M;         // (no list holds more than M entries)
     const uint64_t qbytes = (uint64_t)N * SLAM_DESC_BYTES, tbytes = (uint64_t)M * SLAM_DESC_BYTES, obytes = (uint64_t)(N + 1) * 8,
@@ -604,7 +612,7 @@ extern "C" int slam_bf_radius_u256_host(slam_ctx* ctx, const uint8_t* h_query, i
     if (tbytes) memcpy(hb + off_t, h_train, tbytes);
     ctx->io_h2d_bytes += qbytes + tbytes;
     if (qbytes + tbytes) SLAM_HIP(hipMemcpyAsync(db, hb, off_t + tbytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = slam_bf_radius_u256(ctx, db, N, db + off_t, M, max_distance, 0, (int64_t*)(db + off_o), cap, (int32_t*)(db + off_i),
+    if (int rc = radius_search(ctx, db, N, db + off_t, M, max_distance, 0, (int64_t*)(db + off_o), cap, (int32_t*)(db + off_i),
                                      (int32_t*)(db + off_d), h_total))
         return rc;
     const int64_t T = *h_total <= cap ? *h_total : 0;                // (beyond the capacity only the offsets come back)

@@ -402,7 +402,7 @@ static int topk_pass(slam_ctx* ctx, const topk_plan& p, const void* d_query, int
     if (int rc = slam_prof_end(ctx)) return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        (void)slam_bf_reset_state(ctx);
+        (void)bf_state_reset(ctx);
         return slam_set_error(SLAM_ERR_HIP, "top-k kernel launch failed: %s", hipGetErrorString(e));
     }
     return SLAM_OK;
@@ -421,8 +421,9 @@ static int topk_merge_launch(slam_ctx* ctx, const int32_t* d_idx_parts, const in
     return SLAM_OK;
 }
 
-extern "C" int slam_bf_knn_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, int64_t train_base,
-                                int K, int32_t* d_idx, int32_t* d_dist) {
+// slam_bf_knn_u256 without the call lock
+static int topk_search(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, int64_t train_base,
+                       int K, int32_t* d_idx, int32_t* d_dist) {
     SLAM_REQUIRE(ctx, "slam_bf_knn_u256: null ctx");
     SLAM_REQUIRE(K >= 1 && K <= SLAM_BF_KNN_MAX, "K=%d outside [1, %d]", K, SLAM_BF_KNN_MAX);
     SLAM_REQUIRE(N >= 0 && M >= 0, "negative size (N=%lld, M=%lld)", (long long)N, (long long)M);
@@ -466,6 +467,13 @@ extern "C" int slam_bf_knn_u256(slam_ctx* ctx, const void* d_query, int64_t N, c
     return topk_merge_launch(ctx, idx_parts, dist_parts, p.passes, N, K, d_idx, d_dist);
 }
 
+extern "C" int slam_bf_knn_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, int64_t train_base,
+                                int K, int32_t* d_idx, int32_t* d_dist) {
+    SLAM_REQUIRE(ctx, "slam_bf_knn_u256: null ctx");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    return topk_search(ctx, d_query, N, d_train, M, train_base, K, d_idx, d_dist);
+}
+
 extern "C" int slam_bf_merge_topk(slam_ctx* ctx, const int32_t* d_idx_parts, const int32_t* d_dist_parts, int64_t G, int64_t N, int K,
                                   int32_t* d_idx, int32_t* d_dist) {
     SLAM_REQUIRE(ctx, "slam_bf_merge_topk: null ctx");
@@ -489,7 +497,7 @@ extern "C" int slam_bf_knn_u256_host(slam_ctx* ctx, const uint8_t* h_query, int6
     SLAM_REQUIRE(N >= 0 && M >= 0 && N <= (1ll << 28) && M <= (1ll << 28), "bad sizes N=%lld M=%lld", (long long)N, (long long)M);
     if (N == 0) return SLAM_OK;
     SLAM_REQUIRE(h_query && h_idx && h_dist && (h_train || M == 0), "slam_bf_knn_u256_host: null host pointer");
-    std::lock_guard<std::mutex> lk(ctx->io_mu);
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     SLAM_HIP(hipSetDevice(ctx->device));
     const uint64_t qbytes = (uint64_t)N * SLAM_DESC_BYTES, tbytes = (uint64_t)M * SLAM_DESC_BYTES, table = (uint64_t)N * K * 4;
     const uint64_t off_t = topk_align(qbytes), off_i = off_t + topk_align(tbytes), off_d = off_i + topk_align(table);
@@ -503,7 +511,7 @@ extern "C" int slam_bf_knn_u256_host(slam_ctx* ctx, const uint8_t* h_query, int6
     ctx->io_h2d_bytes += qbytes + tbytes;
     ctx->io_d2h_bytes += 2 * table;
     SLAM_HIP(hipMemcpyAsync(db, hb, off_t + tbytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = slam_bf_knn_u256(ctx, db, N, db + off_t, M, 0, K, (int32_t*)(db + off_i), (int32_t*)(db + off_d))) return rc;
+    if (int rc = topk_search(ctx, db, N, db + off_t, M, 0, K, (int32_t*)(db + off_i), (int32_t*)(db + off_d))) return rc;
     SLAM_HIP(hipMemcpyAsync(hb + off_i, db + off_i, off_d - off_i + table, hipMemcpyDeviceToHost, ctx->stream));
     SLAM_HIP(hipStreamSynchronize(ctx->stream));
     memcpy(h_idx, hb + off_i, table);

@@ -544,9 +544,10 @@ static int win_check_args(slam_ctx* ctx, int64_t N, int64_t M, int k, int64_t ce
     return SLAM_OK;
 }
 
-extern "C" int slam_bf_window_knn_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M,
-                                       const float* d_query_xy, const float* d_train_xy, const float* d_radius, float radius,
-                                       int k, int64_t cells, int32_t* d_idx, int32_t* d_dist) {
+// slam_bf_window_knn_u256 without the call lock
+static int window_search(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M,
+                         const float* d_query_xy, const float* d_train_xy, const float* d_radius, float radius,
+                         int k, int64_t cells, int32_t* d_idx, int32_t* d_dist) {
     if (int rc = win_check_args(ctx, N, M, k, cells, "slam_bf_window_knn_u256")) return rc;
     SLAM_REQUIRE(N == 0 || (d_query && d_query_xy && d_idx && d_dist), "slam_bf_window_knn_u256: null query or result pointer");
     SLAM_REQUIRE(N == 0 || M == 0 || (d_train && d_train_xy), "slam_bf_window_knn_u256: null train pointer");
@@ -600,6 +601,14 @@ extern "C" int slam_bf_window_knn_u256(slam_ctx* ctx, const void* d_query, int64
     return win_launch_check("search");
 }
 
+extern "C" int slam_bf_window_knn_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M,
+                                       const float* d_query_xy, const float* d_train_xy, const float* d_radius, float radius,
+                                       int k, int64_t cells, int32_t* d_idx, int32_t* d_dist) {
+    if (int rc = win_check_args(ctx, N, M, k, cells, "slam_bf_window_knn_u256")) return rc;   // (before the context is touched)
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    return window_search(ctx, d_query, N, d_train, M, d_query_xy, d_train_xy, d_radius, radius, k, cells, d_idx, d_dist);
+}
+
 // upload, search, download, one stream synchronisation (through the context's host-buffer arena)
 extern "C" int slam_bf_window_knn_u256_host(slam_ctx* ctx, const uint8_t* h_query, int64_t N, const uint8_t* h_train, int64_t M,
                                             const float* h_query_xy, const float* h_train_xy, const float* h_radius, float radius,
@@ -608,7 +617,7 @@ extern "C" int slam_bf_window_knn_u256_host(slam_ctx* ctx, const uint8_t* h_quer
     SLAM_REQUIRE(N == 0 || (h_query && h_query_xy && h_idx && h_dist), "slam_bf_window_knn_u256_host: null query or result pointer");
     SLAM_REQUIRE(M == 0 || (h_train && h_train_xy), "slam_bf_window_knn_u256_host: null train pointer");
     if (N == 0) return SLAM_OK;
-    std::lock_guard<std::mutex> lk(ctx->io_mu);
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     SLAM_HIP(hipSetDevice(ctx->device));
     const uint64_t qb = (uint64_t)N * SLAM_DESC_BYTES, tb = (uint64_t)M * SLAM_DESC_BYTES, qxb = (uint64_t)N * 8,
                    txb = (uint64_t)M * 8, rb = h_radius ? (uint64_t)M * 4 : 0, ob = (uint64_t)N * k * 4;
@@ -625,7 +634,7 @@ extern "C" int slam_bf_window_knn_u256_host(slam_ctx* ctx, const uint8_t* h_quer
     if (rb) memcpy(hb + o_r, h_radius, rb);
     ctx->io_h2d_bytes += qb + tb + qxb + txb + rb;
     SLAM_HIP(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = slam_bf_window_knn_u256(ctx, db, N, M ? db + o_t : nullptr, M, (const float*)(db + o_qx),
+    if (int rc = window_search(ctx, db, N, M ? db + o_t : nullptr, M, (const float*)(db + o_qx),
                                          M ? (const float*)(db + o_tx) : nullptr, rb ? (const float*)(db + o_r) : nullptr, radius,
                                          k, cells, (int32_t*)(db + o_i), (int32_t*)(db + o_d)))
         return rc;

@@ -77,6 +77,7 @@ extern "C" int slam_ctx_destroy(slam_ctx* ctx) {
     if (ctx->io_dev) (void)hipFree(ctx->io_dev);
     if (ctx->io_host) (void)hipHostFree(ctx->io_host);
     if (ctx->sel_host) (void)hipHostFree(ctx->sel_host);
+    for (void* old : ctx->sel_host_old) (void)hipHostFree(old);
     if (ctx->bf_state_mem) (void)hipFree(ctx->bf_state_mem);
     if (ctx->bf_tbl_ready) {
         (void)hipFree(ctx->bf_tbl_dev);
@@ -170,8 +171,8 @@ extern "C" int slam_download(slam_ctx* ctx, void* h_dst, const void* d_src, uint
     return SLAM_OK;
 }
 
+// (callers hold ctx->call_mu: the block stays theirs until their last launch is queued; a later grow synchronises first)
 int slam_workspace(slam_ctx* ctx, uint64_t bytes, void** out) {
-    std::lock_guard<std::mutex> g(ctx->mu);
     if (bytes > ctx->workspace_bytes) {
         SLAM_HIP(hipStreamSynchronize(ctx->stream));
         if (ctx->workspace) SLAM_HIP(hipFree(ctx->workspace));
@@ -186,7 +187,6 @@ int slam_workspace(slam_ctx* ctx, uint64_t bytes, void** out) {
 }
 
 int slam_io_arena(slam_ctx* ctx, uint64_t dev_bytes, uint64_t host_bytes, void** dev, void** host) {
-    std::lock_guard<std::mutex> g(ctx->mu);
     if (dev_bytes > ctx->io_dev_bytes || host_bytes > ctx->io_host_bytes) SLAM_HIP(hipStreamSynchronize(ctx->stream));
     if (dev_bytes > ctx->io_dev_bytes) {
         if (ctx->io_dev) SLAM_HIP(hipFree(ctx->io_dev));
@@ -222,9 +222,21 @@ extern "C" int slam_index_errors(slam_ctx* ctx, int64_t* count) {
 
 extern "C" int slam_io_counters(slam_ctx* ctx, uint64_t* h2d_bytes, uint64_t* d2h_bytes) {
     SLAM_REQUIRE(ctx, "slam_io_counters: null ctx");
-    std::lock_guard<std::mutex> lk(ctx->io_mu);
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     if (h2d_bytes) *h2d_bytes = ctx->io_h2d_bytes;
     if (d2h_bytes) *d2h_bytes = ctx->io_d2h_bytes;
+    return SLAM_OK;
+}
+
+// Current sizes of the context's grow-only blocks, for tests that make them grow: h_bytes[0..count) of {workspace, merge
+// state, pinned completion / count block, io device arena, io pinned staging, radius tables}.
+extern "C" int slam_ctx_block_bytes(slam_ctx* ctx, int64_t* h_bytes, int count) {
+    SLAM_REQUIRE(ctx && (h_bytes || count == 0) && count >= 0 && count <= 6, "slam_ctx_block_bytes: bad argument");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    const int64_t b[6] = {(int64_t)ctx->workspace_bytes, ctx->bf_state_mem ? (int64_t)bf_state_bytes((size_t)ctx->bf_state_rows) : 0,
+                          (int64_t)ctx->sel_host_bytes, (int64_t)ctx->io_dev_bytes, (int64_t)ctx->io_host_bytes,
+                          (int64_t)ctx->radius_mem_bytes};
+    for (int i = 0; i < count; i++) h_bytes[i] = b[i];
     return SLAM_OK;
 }
 

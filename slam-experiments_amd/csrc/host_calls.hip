@@ -5,8 +5,8 @@
 // Each function here packs its inputs into one pinned staging block, does ONE host-to-device copy,
 // launches everything on the context stream, does ONE device-to-host copy and synchronises once - or, frame-sized, does no
 // copy at all (the kernels read and write the pinned block) and waits for the last kernel's completion word (slam_wait_done).
-// The staging block belongs to the context, so these calls serialise per context (ctypes drops the GIL:
-// the reference's tracking thread and a backend thread may both be in here).
+// The staging block belongs to the context, so these calls hold its call lock (ctypes drops the GIL: the reference's tracking
+// thread and a backend thread may both be in here); inside it they reach the other entry points' bodies, never the entry points.
 //   slam_bf_knn2_u256_host       cv2.BFMatcher.knnMatch(k=2) (the search behind feature_matchers.py:39)
 //   slam_bf_match_host           BruteForceFeatureMatcher.match (feature_matchers.py:36-44)
 //   slam_pose_optimize_host_f64  Frontend._correct_current_pose (frontend.py:298-393)
@@ -27,7 +27,7 @@ extern "C" int slam_bf_knn2_u256_host(slam_ctx* ctx, const uint8_t* h_query, int
     SLAM_REQUIRE(N >= 0 && M >= 0 && N <= (1ll << 28) && M <= (1ll << 28), "bad sizes N=%lld M=%lld", (long long)N, (long long)M);
     if (N == 0) return SLAM_OK;
     SLAM_REQUIRE(h_query && h_idx && h_dist && (h_train || M == 0), "slam_bf_knn2_u256_host: null host pointer");
-    std::lock_guard<std::mutex> lk(ctx->io_mu);
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     SLAM_HIP(hipSetDevice(ctx->device));
     const uint64_t qbytes = (uint64_t)N * SLAM_DESC_BYTES, tbytes = (uint64_t)M * SLAM_DESC_BYTES;
     const uint64_t off_t = align_up(qbytes, 256), off_i = off_t + align_up(tbytes, 256);
@@ -48,11 +48,11 @@ extern "C" int slam_bf_knn2_u256_host(slam_ctx* ctx, const uint8_t* h_query, int
         if (int rc = slam_bf_knn2_select(ctx, hb, N, hb + off_t, M, 0, (int32_t*)(hb + off_i), (int32_t*)(hb + off_d), nullptr, 0, 0.0,
                                          hb + off_k, &with_neighbour)) return rc;
     } else if (zero_copy(N, M)) {
-        if (int rc = slam_bf_knn2_u256(ctx, hb, N, hb + off_t, M, 0, (int32_t*)(hb + off_i), (int32_t*)(hb + off_d))) return rc;
+        if (int rc = slam_bf_knn2_keep(ctx, hb, N, hb + off_t, M, 0, (int32_t*)(hb + off_i), (int32_t*)(hb + off_d), nullptr)) return rc;
         SLAM_HIP(hipStreamSynchronize(ctx->stream));
     } else {
         SLAM_HIP(hipMemcpyAsync(db, hb, off_t + tbytes, hipMemcpyHostToDevice, ctx->stream));
-        if (int rc = slam_bf_knn2_u256(ctx, db, N, db + off_t, M, 0, (int32_t*)(db + off_i), (int32_t*)(db + off_d))) return rc;
+        if (int rc = slam_bf_knn2_keep(ctx, db, N, db + off_t, M, 0, (int32_t*)(db + off_i), (int32_t*)(db + off_d), nullptr)) return rc;
         SLAM_HIP(hipMemcpyAsync(hb + off_i, db + off_i, (uint64_t)N * 16, hipMemcpyDeviceToHost, ctx->stream));
         SLAM_HIP(hipStreamSynchronize(ctx->stream));
     }
@@ -73,7 +73,7 @@ extern "C" int slam_bf_match_host(slam_ctx* ctx, const uint8_t* h_query, int64_t
     SLAM_REQUIRE(N == 0 || h_query, "slam_bf_match_host: null h_query");
     SLAM_REQUIRE(N == 0 || (h_query_idx && h_train_idx && h_distance), "slam_bf_match_host: null output pointer");
     SLAM_REQUIRE(M == 0 || h_train || d_train, "slam_bf_match_host: no train descriptors");
-    std::lock_guard<std::mutex> lk(ctx->io_mu);
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     SLAM_HIP(hipSetDevice(ctx->device));
     const uint64_t qbytes = (uint64_t)N * SLAM_DESC_BYTES, tbytes = h_train ? (uint64_t)M * SLAM_DESC_BYTES : 0;
     if (N == 0 || M == 0) {
@@ -137,7 +137,7 @@ extern "C" int slam_bf_match_host(slam_ctx* ctx, const uint8_t* h_query, int64_t
             if (int rc = slam_bf_knn2_batch_keep(ctx, 2, both, keeps, zc)) return rc;    // frame-sized: waits by polling
         } else {
             if (int rc = slam_bf_knn2_keep(ctx, dq, N, dt, M, 0, fwd_idx, fwd_dist, keep_in_kernel)) return rc;
-            if (int rc = slam_bf_knn2_u256(ctx, dt, M, dq, N, 0, rev_idx, rev_dist)) return rc;
+            if (int rc = slam_bf_knn2_keep(ctx, dt, M, dq, N, 0, rev_idx, rev_dist, nullptr)) return rc;
         }
         int64_t c = 0;
         if (zc) {
@@ -225,7 +225,7 @@ extern "C" int slam_pose_optimize_host_f64(slam_ctx* ctx, const double* h_pose_i
     SLAM_REQUIRE(O >= 0 && O <= (1 << 24), "O=%lld out of range [0, 2^24]", (long long)O);
     SLAM_REQUIRE(h_pose_in && h_pose_out && h_stats && (O == 0 || (h_points && h_meas && h_inlier && h_chi2)),
                  "slam_pose_optimize_host_f64: null host pointer");
-    std::lock_guard<std::mutex> lk(ctx->io_mu);
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     SLAM_HIP(hipSetDevice(ctx->device));
     // in: [pose 12 | points 3O | pad | meas 2O]   out: [pose 12 | chi2 O | stats (2 x int32) | inlier u8[O]]
     const uint64_t o = (uint64_t)O;
@@ -297,7 +297,7 @@ extern "C" int slam_ba_optimize_host_f64(slam_ctx* ctx, int64_t K, int64_t L, in
     for (int64_t o = 0; o < O; o++)
         SLAM_REQUIRE(h_obs_pose[o] >= 0 && h_obs_pose[o] < K && h_obs_point[o] >= 0 && h_obs_point[o] < L,
                      "observation %lld: index out of range (pose %d, point %d)", (long long)o, h_obs_pose[o], h_obs_point[o]);
-    std::lock_guard<std::mutex> lk(ctx->io_mu);
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
     SLAM_HIP(hipSetDevice(ctx->device));
     // staging layout (16-byte aligned pieces): obs_pose | obs_point | meas | pt_ptr | pt_obs | ps_ptr | ps_obs | free | poses2 | points2 | stats
     const uint64_t o4 = align_up((uint64_t)(O ? O : 1) * 4, 16);

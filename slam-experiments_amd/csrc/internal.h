@@ -7,6 +7,7 @@
 #include <unordered_map>
 #include <atomic>
 #include <mutex>
+#include <vector>
 #include "slamhip.h"
 
 #define SLAM_BF_TBL_RING 8
@@ -16,7 +17,12 @@ struct slam_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    std::mutex mu;                                  // guards allocs / workspace growth
+    // The call lock: every extern "C" entry point that uses one of the blocks below (workspace, radius tables, merge state,
+    // chunk table slots, the pinned completion / count block, the filter scratch, the io arena) holds it from taking the block
+    // through its last launch, and through the read-back of what it waits for.  Only entry points take it (it is not
+    // recursive): the bodies they share with each other are internal functions that expect it held.
+    std::mutex call_mu;
+    std::mutex mu;                                  // guards the allocation bookkeeping (allocs) and the tuning knobs
     std::unordered_map<void*, uint64_t> allocs;     // device pointers handed out by slam_malloc
     void* workspace = nullptr;                      // partial top-2 tables etc.
     uint64_t workspace_bytes = 0;
@@ -38,13 +44,13 @@ struct slam_ctx {
     void* scratch = nullptr;                        // 4 KiB device scratch (filter counters, reductions)
     void* sel_host = nullptr;                       // pinned host block the search's fused selection writes its per-wave counts to
     uint64_t sel_host_bytes = 0;
+    std::vector<void*> sel_host_old;                // blocks sel_host outgrew: kept until slam_ctx_destroy (a queued kernel may write one)
     std::atomic<unsigned> done_epoch{0}, polled_calls{0};   // searches waited for by polling the block's completion words (bf_wait_done)
     void* io_dev = nullptr;                         // device arena of the host-buffer entry points (grow-only)
     uint64_t io_dev_bytes = 0;
     void* io_host = nullptr;                        // pinned host staging for the same (grow-only)
     uint64_t io_host_bytes = 0;
-    std::mutex io_mu;                               // one host-buffer call at a time per context (they share the arena)
-    uint64_t io_h2d_bytes = 0, io_d2h_bytes = 0;    // bytes the host-buffer entry points moved over PCIe (copies and zero-copy), under io_mu
+    uint64_t io_h2d_bytes = 0, io_d2h_bytes = 0;    // bytes the host-buffer entry points moved over PCIe (copies and zero-copy), under call_mu
     // profiling of the dominant kernel
     int prof_on = 0;
     static const int PROF_MAX = 4096;
@@ -100,6 +106,13 @@ int slam_pose_optimize_polled(slam_ctx* ctx, const double* d_pose_in, const doub
                               double fx, double fy, double cx, double cy, int rounds, int iterations, double chi2_threshold,
                               double huber_delta, double* d_pose_out, uint8_t* d_inlier, double* d_chi2, int32_t* d_stats,
                               unsigned* done, unsigned epoch);
+// slam_bf_match_filter without the call lock (for entry points that already hold it)
+int slam_filter_count(slam_ctx* ctx, const int32_t* d_idx, const int32_t* d_dist, int64_t N, int mode, double param,
+                      uint8_t* d_keep, int64_t* h_count, int32_t* h_min_dist);
+// bytes of the merge state block for `rows` query rows (bf_hamming.hip)
+size_t bf_state_bytes(size_t rows);
+// slam_bf_reset_state without the call lock
+int bf_state_reset(slam_ctx* ctx);
 // the filter kernels of slam_bf_match_filter without the read-back (asynchronous on the ctx stream)
 int slam_filter_launch(slam_ctx* ctx, const int32_t* d_idx, const int32_t* d_dist, int64_t N, int mode, double param,
                        uint8_t* d_keep, unsigned* done = nullptr, unsigned epoch = 0, bool* polled = nullptr);

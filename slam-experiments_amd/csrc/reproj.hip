@@ -242,6 +242,7 @@ extern "C" int slam_pose_normal_eq_f64(slam_ctx* ctx, const double* d_pose, cons
                                        double fy, double cx, double cy, double huber_delta, double* d_H,
                                        double* d_b, double* d_chi2) {
     SLAM_REQUIRE(ctx, "slam_pose_normal_eq_f64: null ctx");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);         // the partial sums live in the context's workspace
     SLAM_REQUIRE(O >= 0, "negative size");
     SLAM_REQUIRE(d_pose && d_H && d_b && (O == 0 || (d_points && d_meas && d_chi2)),
                  "slam_pose_normal_eq_f64: null device pointer");

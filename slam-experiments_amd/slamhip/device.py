@@ -96,6 +96,14 @@ class Context:
         check(self.lib.slam_bf_state_dirty(self.handle, ctypes.byref(n)))
         return n.value
 
+    BLOCKS = ("workspace", "merge_state", "pinned_block", "io_dev", "io_host", "radius_tables")
+
+    def block_bytes(self) -> dict:
+        """Current sizes of the context's grow-only blocks (``slam_ctx_block_bytes``), 0 for a block not yet taken."""
+        b = (ctypes.c_int64 * len(self.BLOCKS))()
+        check(self.lib.slam_ctx_block_bytes(self.handle, b, len(self.BLOCKS)))
+        return dict(zip(self.BLOCKS, b))
+
     def plan_info(self, n: int, m: int) -> dict:
         """The launch plan the top-2 search would use for n x m (``slam_bf_plan_info``)."""
         p = (ctypes.c_int32 * 10)()
