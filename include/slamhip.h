@@ -18,6 +18,8 @@
  *   slam_pose_normal_eq_f64 / slam_pose_optimize_f64
  *                          the g2o graph + LM loop of Frontend._correct_current_pose
  *                          (frontend.py:298-393)
+ *   slam_tv_*              cv2.findEssentialMat / recoverPose / triangulatePoints behind
+ *                          pose_estimation_2d2d and triangulation (utils.py:10-55)
  *   slam_comm_*            no reference counterpart (the reference is single
  *                          process); RCCL all-gather of per-shard top-2 rows
  *
@@ -388,6 +390,70 @@ SLAM_API int slam_pose_optimize_batch_f64(slam_ctx* ctx, int64_t B, const double
                                           double fy, double cx, double cy, int rounds, int iterations,
                                           double chi2_threshold, double huber_delta, double* d_pose_out,
                                           uint8_t* d_inlier, double* d_chi2, int32_t* d_stats);
+
+/* ---- two-view geometry (f64): utils.py:10-28 (pose_estimation_2d2d) and utils.py:32-55 (triangulation), batched ------------
+ * Conventions: points 1 are the reference's source_pts (last frame, trainIdx), points 2 its query_pts (current frame,
+ * queryIdx); normalised coordinates x = ((u - cx) / fx, (v - cy) / fy, 1); x2^T E x1 = 0 with E [9] row-major; the
+ * recovered pose maps frame 1 to frame 2, X2 = R X1 + t, |t| = 1, as [12] row-major 3x4 like d_pose above.  PARITY
+ * UNPINNED against OpenCV (absent here): restated from the algorithms' definitions; OpenCV's own RANSAC draws, its
+ * early termination and the sign its SVD gives t are not reproduced.  All calls are asynchronous on the ctx stream. */
+
+/* The five-point minimal solver on its own (what cv2.findEssentialMat runs per RANSAC sample, utils.py:24): for each of
+ * S samples all real essential matrices through five correspondences d_x1 / d_x2 [S,5,2] (normalised).  d_E [S,10,9]:
+ * each with Frobenius norm 1, in ascending order of the root variable (the coefficient of the third null-space vector
+ * in the solver's own basis), unused slots zero; d_nroots int32 [S] (0..10). */
+SLAM_API int slam_tv_fivepoint_f64(slam_ctx* ctx, int64_t S, const double* d_x1, const double* d_x2, double* d_E,
+                                   int32_t* d_nroots);
+
+/* cv2.findEssentialMat(source_pts, query_pts, cameraMatrix=K) (utils.py:24) for B frame pairs in one call.  Pair b owns
+ * the matches [d_offsets[b], d_offsets[b+1]) of d_px1 / d_px2 [M,2] (pixels; 16-byte aligned); d_offsets int32 [B+1]
+ * under the contract of slam_pose_optimize_batch_f64 (a table that is not ascending or leaves [0, M] never causes an
+ * access outside the arrays: the pair shrinks to the part inside and slam_index_errors counts it).  B <= 65535.
+ * Per pair: H hypotheses (1 <= H <= 2^20), no early termination.  Hypothesis h draws five DISTINCT match indices of the
+ * pair's n matches from a counter-based generator, all arithmetic in uint64 (wrapping):
+ *     splitmix(x):  x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *                   x = (x ^ (x >> 27)) * 0x94D049BB133111EB; return x ^ (x >> 31)
+ *     word(seed, h, d) = splitmix(splitmix(seed ^ (h * 0xD1B54A32D192ED03)) ^ (d * 0x8CB92BA72F3D8DD7))
+ *     index(d) = ((word(seed, h, d) >> 32) * n) >> 32
+ *   with the draw number d = 0, 1, 2, ...: an index already drawn is skipped and the next d is taken, until there are
+ *   five, in that order.  The pair index b is NOT mixed in: a pair's draws, and so its result, are the same wherever
+ *   in whatever batch it stands.
+ * Every root of every hypothesis is scored on all n matches by the squared Sampson distance in normalised coordinates,
+ * evaluated without fused multiply-adds in exactly this order (x1 = (a, b), x2 = (c, d), E row-major e0..e8):
+ *     l0 = e0*a + e1*b + e2;  l1 = e3*a + e4*b + e5;  l2 = e6*a + e7*b + e8;      (E x1)
+ *     m0 = e0*c + e3*d + e6;  m1 = e1*c + e4*d + e7;                               (E^T x2)
+ *     r = c*l0 + d*l1 + l2;   d2 = r*r / (l0*l0 + l1*l1 + m0*m0 + m1*m1)
+ *   inlier iff d2 < (threshold_px / ((fx + fy) / 2))^2 (OpenCV's rule).  Winner: most inliers, ties to the lower
+ *   hypothesis index, then the lower root index - found with packed integer keys, so the result is bit-identical for
+ *   given (matches, intrinsics, H, threshold, seed) whatever B and whatever order the workgroups finish in.
+ * Outputs: d_E [B,9] the winner (Frobenius norm 1), d_inlier uint8 [M] its mask (entries outside every pair: 0),
+ * d_stats int32 [B,4] = {inlier count, winning hypothesis, winning root, number of (hypothesis, root) models scored}.
+ * A pair of fewer than 5 matches (frontend.py:116) yields E = 0, mask 0, stats {0, -1, -1, 0} and is not an error. */
+SLAM_API int slam_tv_essential_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_px1,
+                                          const double* d_px2, int64_t M, double fx, double fy, double cx, double cy,
+                                          int H, double threshold_px, uint64_t seed, double* d_E, uint8_t* d_inlier,
+                                          int32_t* d_stats);
+
+/* cv2.recoverPose(E, source_pts, query_pts, cameraMatrix=K) (utils.py:25) for B pairs (offsets as above).  SVD of
+ * d_E [B,9] as E = U diag(s1, s2, s3) V^T, s3 the smallest, with det U = det V = +1 (the third columns take the sign
+ * that makes it so); R1 = U W V^T, R2 = U W^T V^T, W = [0 1 0; -1 0 0; 0 0 1] (which of the two an SVD calls R1 depends
+ * on how it orders the two equal singular vectors, here as in OpenCV); t = the unit left null vector of E with its largest
+ * component (first of equals) positive; the matches with d_inlier_in != 0 (null: all) are triangulated (as
+ * slam_tv_triangulate_f64, P1 = [I|0], P2 = [R|t]) under the candidates (R1,t), (R2,t), (R1,-t), (R2,-t); a point is
+ * good if its depth is in (0, distance_thresh) in both cameras (OpenCV: 50); most good points win, ties to the lower
+ * candidate.  d_pose [B,12], d_inlier_out uint8 [M] (good under the winner; outside every pair: 0), d_stats int32 [B,2]
+ * = {good count, candidate}.  E = 0 (no model) gives the identity pose, mask 0, stats {0, -1}. */
+SLAM_API int slam_tv_recover_pose_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_px1,
+                                      const double* d_px2, int64_t M, double fx, double fy, double cx, double cy,
+                                      const double* d_E, const uint8_t* d_inlier_in, double distance_thresh,
+                                      double* d_pose, uint8_t* d_inlier_out, int32_t* d_stats);
+
+/* cv2.triangulatePoints as utils.py:49-53 uses it: per point the 4x4 DLT matrix (x P[2] - P[0], y P[2] - P[1] for both
+ * views; d_P1 / d_P2 [12] row-major 3x4, d_x1 / d_x2 [N,2] in the coordinates the projections expect, 16-byte aligned),
+ * v = its right singular vector of the smallest singular value (eigenvector of A^T A by cyclic Jacobi), |v| = 1,
+ * v[3] >= 0; d_X [N,3] = v[:3] / v[3] (utils.py:52-53) and d_w [N] = v[3], so a caller can see points at infinity. */
+SLAM_API int slam_tv_triangulate_f64(slam_ctx* ctx, int64_t N, const double* d_P1, const double* d_P2,
+                                     const double* d_x1, const double* d_x2, double* d_X, double* d_w);
 
 /* ---- per-frame calls on caller-owned host buffers: one upload, one download, one wait (frame-sized: zero-copy, polled) ---- */
 /* BruteForceFeatureMatcher.match (feature_matchers.py:36-44; cv2.BFMatcher.match + the min-distance filter) in

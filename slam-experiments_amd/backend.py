@@ -24,6 +24,7 @@ import numpy as np
 from slamhip import ba as _ba
 from slamhip import pose_opt as _po
 from slamhip import reproj as _r
+from slamhip import two_view as _tv
 from slamhip.device import Context, default_context
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -120,6 +121,46 @@ class Backend:
         """Residuals and Jacobians of every observation: (e [O,2], J_pose [O,2,6], J_point [O,2,3])."""
         return _r.build_linearization(poses, points, obs_pose_idx, obs_point_idx, meas, fx, fy, cx, cy,
                                       with_point, self.ctx)
+
+    def estimate_two_view(self, px1, px2, fx, fy, cx, cy, hypotheses: int = _tv.DEFAULT_HYPOTHESES,
+                          threshold: float = _tv.DEFAULT_THRESHOLD, seed: int = 0):
+        """``pose_estimation_2d2d`` (``utils.py:10-28``: ``cv2.findEssentialMat`` + ``cv2.recoverPose``) on arrays:
+        ``px1`` [N,2] the last frame's pixels (``trainIdx``), ``px2`` [N,2] the current frame's (``queryIdx``) ->
+        (R [3,3], t [3], RANSAC inlier mask [N]) with ``X2 = R X1 + t``, ``|t| = 1`` - what the reference wraps into an
+        ``SE3`` as the relative motion (``frontend.py:119-120``)."""
+        return _tv.estimate_two_view(px1, px2, (fx, fy, cx, cy), hypotheses, threshold, seed, ctx=self._ctx)
+
+    def verify_pairs(self, pairs, fx, fy, cx, cy, hypotheses: int = _tv.DEFAULT_HYPOTHESES,
+                     threshold: float = _tv.DEFAULT_THRESHOLD, seed: int = 0):
+        """Geometric verification of many candidate frame pairs in one call (loop-closure or relocalisation candidates
+        from ``KeyframeDatabase``): ``pairs`` = list of ``(px1 [N_b,2], px2 [N_b,2])`` -> (poses [B,4,4] mapping frame 1 to
+        frame 2, inlier counts [B], list of inlier masks).  A pair of fewer than five matches (``frontend.py:116``) comes
+        back with the identity and a count of 0."""
+        R, t, masks, counts = _tv.verify_pairs(pairs, (fx, fy, cx, cy), hypotheses, threshold, seed, ctx=self._ctx)
+        poses = np.tile(np.eye(4), (len(R), 1, 1))
+        poses[:, :3, :3] = R
+        poses[:, :3, 3] = t
+        return poses, counts, masks
+
+    def triangulate(self, pose1, pose2, px1, px2, fx, fy, cx, cy, reference_projection: bool = False):
+        """``triangulation`` (``utils.py:32-55``) on arrays: the poses (4x4 or 3x4 Tcw) of the source and the query frame
+        and their matched pixels -> (points [N,3], px1_normalised [N,2]), the reference's return pair.  The pixels are
+        normalised (``Camera.pixel_to_camera``) and triangulated against the projections ``pose[:3]``.  The reference
+        hands ``cv2.triangulatePoints`` the projections ``K @ pose[:3]`` (``primitives.py:31-32``) together with
+        NORMALISED points, i.e. applies the intrinsics twice; ``reference_projection=True`` reproduces that."""
+        K = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+        P = [np.asarray(p, np.float64).reshape(-1, 4)[:3, :4] for p in (pose1, pose2)]
+        if reference_projection:
+            P = [K @ p for p in P]
+        px1, px2 = _tv._points(px1, "px1"), _tv._points(px2, "px2")
+        x1 = np.stack([(px1[:, 0] - cx) / fx, (px1[:, 1] - cy) / fy], 1)
+        x2 = np.stack([(px2[:, 0] - cx) / fx, (px2[:, 1] - cy) / fy], 1)
+        X, _ = _tv.triangulate_arrays(P[0], P[1], x1, x2, ctx=self._ctx)
+        return X, x1
+
+    def mean_reprojection_error(self, points, px, pose, fx, fy, cx, cy) -> float:
+        """``Frontend._get_reprojection_error`` (``frontend.py:216-222``) from the residual kernel."""
+        return _tv.mean_reprojection_error(points, px, pose, (fx, fy, cx, cy), ctx=self._ctx)
 
     def optimize_pose(self, pose, points, meas, fx, fy, cx, cy, rounds: int = 4, iterations: int = 10,
                       on_device: bool = True):
