@@ -567,6 +567,80 @@ SLAM_API int slam_ba_optimize_host_f64(slam_ctx* ctx, int64_t K, int64_t L, int6
                                        double cy, double huber_delta, int iterations, double* h_poses_out,
                                        double* h_points_out, double* h_stats);
 
+/* ---- SE(3) pose-graph optimisation (pose_graph.hip) -----------------------------------------------------------------
+ * What pose_graph_sphere_example.py does with g2o: a graph of VertexSE3 / EdgeSE3 (:24-28, :45-52), vertex 0 fixed
+ * (:29-30), Levenberg-Marquardt (:7) for 15 iterations (:57).  The block solver with a sparse direct factorisation
+ * (BlockSolverSE3(LinearSolverEigenSE3()), :7) is replaced by conjugate gradients with a block-Jacobi preconditioner.
+ *
+ * Conventions.  Poses T = [R|t], [12] row-major 3x4, X_cam = R X_world + t; tangent vectors [w, v], rotation first; the
+ * update is T <- Exp(d) T (as slam_pose_optimize_f64).
+ *   measurement   edge (i, j) carries Z_ij [12], a measured value of T_j T_i^-1 (what recover_pose gives: X2 = R X1 + t)
+ *   residual      r_ij = Log(T_j T_i^-1 Z_ij^-1) in R^6, the full SE(3) logarithm
+ *   cost          F = sum rho(r^T Omega r), no factor 1/2 (g2o's chi2); Omega [36] symmetric, [w, v] order; rho = identity,
+ *                 or Huber with huber_delta > 0 applied as slam_pose_optimize_f64 applies it (weight delta / sqrt(chi2))
+ *   Jacobians     dr/dd_j = Jl^-1(r), dr/dd_i = -Jl^-1(r) Ad(T_j T_i^-1), Ad([R|t]) = [[R, 0], [t^ R, R]], Jl^-1 the exact
+ *                 inverse left Jacobian of SE(3)
+ *   system        H = sum w J^T Omega J, b = sum w J^T Omega r (no factor 2), solved as (H + lambda I) d = -b
+ *   fixed         uint8 [V]; fixed poses come back bit for bit, their rows and columns leave the system; a graph without
+ *                 a fixed vertex is SLAM_ERR_INVALID
+ *   LM            g2o's schedule as slam_pose_optimize_f64 restates it: lambda_0 = 1e-5 * largest diagonal entry, the
+ *                 gain-ratio update, ten trials per iteration before giving up
+ * Relation to g2o (PARITY UNPINNED: g2o is absent): with X = T^-1 and Z_g = Z^-1, EdgeSE3's Z_g^-1 X_i^-1 X_j is the
+ * inverse of T_j T_i^-1 Z^-1, so r is minus g2o's error taken as a logarithm and the information matrix carries over;
+ * EdgeSE3 orders its error [translation, quaternion vector part], so a g2o file's 6x6 is permuted to rotation first and
+ * scaled for q ~ w/2 (Omega_ww = Omega_qq / 4, Omega_wv = Omega_qv / 2) - slamhip.read_g2o does it.
+ *
+ * Vertex lists (device form): d_vtx_ptr [V+1], d_vtx_adj [2E]; the slots [ptr[v], ptr[v+1]) of vertex v hold 2 e + side
+ * for every edge e that has v as its i (side 0) or j (side 1), in the order the sums are to be taken (the host form uses
+ * ascending edge index).  Limits: V <= 2^24, E <= 2^25 (int32 indices).  Edge indices outside [0, V), self-edges and lists
+ * that do not match the edges are found on the device before any kernel follows them: SLAM_ERR_INVALID, outputs untouched.
+ * All arithmetic is f64 without contraction and without floating-point atomics: results are pure functions of the inputs.
+ * Workspace: the context's grow-only block; the calls serialise on the context's call lock.  Angles of r beyond 3.1 rad
+ * are outside the contract and reported (SLAM_PG_STATUS_ANGLE) instead of producing NaN. */
+#define SLAM_PG_MAX_VERTICES (1 << 24)
+#define SLAM_PG_MAX_EDGES (1 << 25)
+#define SLAM_PG_STATUS_INDEX 1      /* bad edge index / vertex list (the call returns SLAM_ERR_INVALID) */
+#define SLAM_PG_STATUS_ANGLE 2      /* a residual's rotation angle is beyond 3.1 rad: that edge was given weight 0 */
+#define SLAM_PG_STATUS_PRECOND 4    /* a diagonal block H_vv + lambda I was not positive definite (identity used) */
+#define SLAM_PG_STATUS_BREAKDOWN 8  /* CG met p.Ap <= 0 and stopped */
+#define SLAM_PG_STATUS_NONFINITE 16 /* a non-finite cost or CG scalar */
+/* bytes of context workspace a graph of V vertices and E edges takes; needs no device */
+SLAM_API int slam_pg_workspace(int64_t V, int64_t E, uint64_t* bytes);
+/* the launch plan, without a device: plan[8] = {blocks of the product's main path (= partial sums per dot product),
+ * extra blocks for hub vertices, vertices per block (six lanes each), slots above which a vertex is a hub, blocks of the
+ * edge kernel, CG iterations between two reads of the done flag, launches per CG iteration, 0} */
+SLAM_API int slam_pg_plan(int64_t V, int64_t E, int32_t* plan);
+/* Linearisation at d_poses: *d_cost = F, d_grad [V,6] = b, d_Hdiag [V,36] = the diagonal blocks H_vv, d_W [E,36] = the
+ * off-diagonal blocks w J_i^T Omega J_j (row block i, column block j).  *h_status = SLAM_PG_STATUS_* bits (the call waits). */
+SLAM_API int slam_pg_linearize_f64(slam_ctx* ctx, int64_t V, int64_t E, const double* d_poses, const int32_t* d_edges,
+                                   const double* d_meas, const double* d_info, const int32_t* d_vtx_ptr,
+                                   const int32_t* d_vtx_adj, double huber_delta, double* d_cost, double* d_grad,
+                                   double* d_Hdiag, double* d_W, int32_t* h_status);
+/* d_y [V,6] = (H + lambda I) d_x restricted to the free vertices (rows of fixed vertices 0, their columns ignored), H given
+ * by d_Hdiag and d_W as slam_pg_linearize_f64 leaves them.  d_Hdiag and d_x 16-byte aligned. */
+SLAM_API int slam_pg_hmul_f64(slam_ctx* ctx, int64_t V, int64_t E, const int32_t* d_edges, const int32_t* d_vtx_ptr,
+                              const int32_t* d_vtx_adj, const uint8_t* d_fixed, const double* d_Hdiag, const double* d_W,
+                              double lambda, const double* d_x, double* d_y);
+/* Preconditioned CG on (H + lambda I) x = -d_b over the free vertices, stopping at |r| <= tol |b| or max_iter; alpha, beta
+ * and the stop decision stay on the device.  h_stats[4] = {iterations, converged, |r| / |b| of the recurrence, status}. */
+SLAM_API int slam_pg_pcg_f64(slam_ctx* ctx, int64_t V, int64_t E, const int32_t* d_edges, const int32_t* d_vtx_ptr,
+                             const int32_t* d_vtx_adj, const uint8_t* d_fixed, const double* d_Hdiag, const double* d_W,
+                             const double* d_b, double lambda, double tol, int max_iter, double* d_x, double* h_stats);
+/* optimizer.optimize(15) of pose_graph_sphere_example.py:56-57 on device buffers.  n_fixed: how many entries of d_fixed are
+ * non-zero (>= 1, checked against the mask on the device).  h_stats[8] = {initial chi2, final chi2, accepted LM
+ * iterations, LM trials, CG iterations in total, final lambda, status bits, 0}.  V = 0 or E = 0 is not an error (E = 0:
+ * the poses are copied).  One host read-back per LM trial and one per 32 CG iterations. */
+SLAM_API int slam_pg_optimize_f64(slam_ctx* ctx, int64_t V, int64_t E, const double* d_poses, const int32_t* d_edges,
+                                  const double* d_meas, const double* d_info, const uint8_t* d_fixed, int64_t n_fixed,
+                                  const int32_t* d_vtx_ptr, const int32_t* d_vtx_adj, int iterations, double huber_delta,
+                                  double pcg_tol, int pcg_max_iter, double* d_poses_out, double* h_stats);
+/* the same on HOST buffers (the loop of pose_graph_sphere_example.py:24-57 after the file is read): the vertex lists are
+ * built inside, one upload, one download.  On SLAM_ERR_INVALID h_poses_out is not written. */
+SLAM_API int slam_pg_optimize_host_f64(slam_ctx* ctx, int64_t V, int64_t E, const double* h_poses, const int32_t* h_edges,
+                                       const double* h_meas, const double* h_info, const uint8_t* h_fixed, int iterations,
+                                       double huber_delta, double pcg_tol, int pcg_max_iter, double* h_poses_out,
+                                       double* h_stats);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

@@ -22,6 +22,7 @@ from typing import Optional
 import numpy as np
 
 from slamhip import ba as _ba
+from slamhip import pose_graph as _pg
 from slamhip import pose_opt as _po
 from slamhip import reproj as _r
 from slamhip import two_view as _tv
@@ -199,6 +200,23 @@ class Backend:
             fn = _ba.bundle_adjust_auto if one_launch else _ba.bundle_adjust_device
         return fn(poses, points, obs_pose_idx, obs_point_idx, meas, (fx, fy, cx, cy), iterations, fixed_poses,
                   huber_delta, ctx=self.ctx)
+
+    def optimize_pose_graph(self, poses, edges, meas, info, fixed=(0,), iterations: int = _pg.DEFAULT_ITERATIONS,
+                            huber_delta: float = 0.0, pcg_tol: float = _pg.DEFAULT_PCG_TOL,
+                            pcg_max_iter: int = _pg.DEFAULT_PCG_MAX_ITER):
+        """Pose-graph optimisation over keyframe poses (``pose_graph_sphere_example.py:24-57``: ``VertexSE3`` /
+        ``EdgeSE3``, vertex 0 fixed, 15 LM iterations): ``poses`` [V,4,4] / [V,3,4] Tcw, ``edges`` [E,2], ``meas`` the
+        measured ``T_j T_i^-1`` per edge (``Frontend._relative_motion``, ``verify_pairs``), ``info`` [E,6,6] in
+        ``[w, v]`` order, ``fixed`` the vertex indices (or a bool mask of length V) that hold the gauge.
+        Returns (poses in the input's format, stats dict) from ``slamhip.optimize_pose_graph``."""
+        V = len(poses)
+        fx = np.asarray(fixed)
+        if fx.dtype == bool:
+            mask = fx.astype(np.uint8)
+        else:
+            mask = np.zeros(V, np.uint8)
+            mask[np.asarray(fixed, np.int64).reshape(-1)] = 1
+        return _pg.optimize_pose_graph(poses, edges, meas, info, mask, iterations, huber_delta, pcg_tol, pcg_max_iter, ctx=self.ctx)
 
     def optimize_map(self, map_, fx, fy, cx, cy, iterations: int = 10, huber_delta: float = 5.991 ** 0.5,
                      n_fixed: int = 1, min_observations: int = 2, on_device: bool = True):

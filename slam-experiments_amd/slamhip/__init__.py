@@ -34,6 +34,15 @@ from .matching import (  # noqa: F401
     window_match_arrays,
     window_match_filtered,
 )
+from .pose_graph import (  # noqa: F401
+    loop_edges_from_two_view,
+    optimize_pose_graph,
+    pose_graph_hmul,
+    pose_graph_linearize,
+    pose_graph_pcg,
+    read_g2o,
+    write_g2o,
+)
 from .reproj import PoseOnlyProblem, ReprojProblem, build_linearization, poses_to_rt12  # noqa: F401
 from .two_view import (  # noqa: F401
     estimate_two_view,

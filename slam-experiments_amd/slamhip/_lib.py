@@ -106,6 +106,18 @@ SIGNATURES = {
     "slam_tv_recover_pose_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double,
                                          c_double, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
     "slam_tv_triangulate_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_pg_workspace": (c_int, [c_int64, c_int64, POINTER(c_uint64)]),
+    "slam_pg_plan": (c_int, [c_int64, c_int64, POINTER(c_int32)]),
+    "slam_pg_linearize_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_double, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32)]),
+    "slam_pg_hmul_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_double, c_void_p, c_void_p]),
+    "slam_pg_pcg_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_double, c_double, c_int, c_void_p, c_void_p]),
+    "slam_pg_optimize_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p]),
+    "slam_pg_optimize_host_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                          c_double, c_double, c_int, c_void_p, c_void_p]),
     "slam_bf_match_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_double,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "slam_index_errors": (c_int, [c_void_p, POINTER(c_int64)]),

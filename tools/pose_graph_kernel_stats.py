@@ -1,0 +1,36 @@
+#!/usr/bin/env python3
+"""Durations of the pg_* kernels from kernel traces of tools/pose_graph_time.py, one trace per graph:
+
+    for s in sphere loop_closure large; do
+        rocprofv3 --kernel-trace -d trace_$s -o pg -- python tools/pose_graph_time.py --scenes $s --no-reference
+    done
+    python tools/pose_graph_kernel_stats.py sphere=trace_sphere loop_closure=trace_loop_closure large=trace_large \\
+        > profiles/pose_graph_kernel_stats.txt
+
+Reads the `kernels` view of the trace databases (*_results.db) and prints, per graph and kernel: calls, average / min / max
+duration in microseconds.  pg_hmul_kernel<0> is the product alone (the calls of slam_pg_hmul_f64 the timing script makes);
+pg_hmul_kernel<1> and the two CG vector kernels include the launches that return at once after convergence."""
+import glob
+import os
+import sqlite3
+import sys
+
+
+def main():
+    print("# durations of the pg_* kernels (rocprofv3 --kernel-trace of tools/pose_graph_time.py --scenes NAME --no-reference)")
+    print("# calls, average / min / max in us, kernel")
+    for arg in sys.argv[1:]:
+        label, _, where = arg.partition("=")
+        dbs = sorted(glob.glob(os.path.join(where, "**", "*_results.db"), recursive=True))
+        if not dbs:
+            raise SystemExit(f"no *_results.db under {where}")
+        db = sqlite3.connect(dbs[-1])
+        print(f"\n== {label}")
+        rows = db.execute("select name, count(*), avg(duration), min(duration), max(duration) from kernels "
+                          "where name like '%pg\\_%' escape '\\' group by name order by sum(duration) desc")
+        for name, calls, avg, lo, hi in rows:
+            print(f"{calls:7d} {avg / 1e3:9.2f} {lo / 1e3:9.2f} {hi / 1e3:9.2f}  {name.split('(')[0].replace('void ', '')}")
+
+
+if __name__ == "__main__":
+    main()
