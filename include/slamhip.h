@@ -401,7 +401,11 @@ SLAM_API int slam_pose_optimize_batch_f64(slam_ctx* ctx, int64_t B, const double
 /* The five-point minimal solver on its own (what cv2.findEssentialMat runs per RANSAC sample, utils.py:24): for each of
  * S samples all real essential matrices through five correspondences d_x1 / d_x2 [S,5,2] (normalised).  d_E [S,10,9]:
  * each with Frobenius norm 1, in ascending order of the root variable (the coefficient of the third null-space vector
- * in the solver's own basis), unused slots zero; d_nroots int32 [S] (0..10). */
+ * in the solver's own basis), unused slots zero; d_nroots int32 [S] (0..10).  Whatever the sample (repeated or collinear
+ * points, a pure rotation, NaN / inf / 1e150 coordinates) every returned matrix is finite with norm 1 and a sample that
+ * yields none returns 0 roots; every loop of the solver is bounded, so the time of a call does not depend on the data
+ * by more than a small factor (a sample whose elimination meets a pivot below 1e-4 is solved a second time in
+ * another basis: a few in a thousand). */
 SLAM_API int slam_tv_fivepoint_f64(slam_ctx* ctx, int64_t S, const double* d_x1, const double* d_x2, double* d_E,
                                    int32_t* d_nroots);
 
@@ -428,7 +432,10 @@ SLAM_API int slam_tv_fivepoint_f64(slam_ctx* ctx, int64_t S, const double* d_x1,
  *   given (matches, intrinsics, H, threshold, seed) whatever B and whatever order the workgroups finish in.
  * Outputs: d_E [B,9] the winner (Frobenius norm 1), d_inlier uint8 [M] its mask (entries outside every pair: 0),
  * d_stats int32 [B,4] = {inlier count, winning hypothesis, winning root, number of (hypothesis, root) models scored}.
- * A pair of fewer than 5 matches (frontend.py:116) yields E = 0, mask 0, stats {0, -1, -1, 0} and is not an error. */
+ * A pair of fewer than 5 matches (frontend.py:116) yields E = 0, mask 0, stats {0, -1, -1, 0} and is not an error.
+ * Non-finite coordinates are data: a match with a NaN / inf coordinate scores NaN and is never an inlier, a hypothesis
+ * that drew one yields no model, d_E is always finite (norm 1, or zero with stats {0, -1, -1, models} when no
+ * hypothesis gave a model), and one pair's matches never change another pair's result. */
 SLAM_API int slam_tv_essential_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_px1,
                                           const double* d_px2, int64_t M, double fx, double fy, double cx, double cy,
                                           int H, double threshold_px, uint64_t seed, double* d_E, uint8_t* d_inlier,
@@ -442,7 +449,10 @@ SLAM_API int slam_tv_essential_ransac_f64(slam_ctx* ctx, int64_t B, const int32_
  * slam_tv_triangulate_f64, P1 = [I|0], P2 = [R|t]) under the candidates (R1,t), (R2,t), (R1,-t), (R2,-t); a point is
  * good if its depth is in (0, distance_thresh) in both cameras (OpenCV: 50); most good points win, ties to the lower
  * candidate.  d_pose [B,12], d_inlier_out uint8 [M] (good under the winner; outside every pair: 0), d_stats int32 [B,2]
- * = {good count, candidate}.  E = 0 (no model) gives the identity pose, mask 0, stats {0, -1}. */
+ * = {good count, candidate}.  E = 0 (no model) gives the identity pose, mask 0, stats {0, -1}; so does any E whose
+ * sum of squares is not a positive finite double (a NaN entry; entries near 1e-200 or 1e+200, whose squares under- or
+ * overflow).  Any other 3x3 input, essential or not (rank 1, rank 3, unequal singular values), gives a finite pose
+ * with R orthonormal, det R = +1 and |t| = 1.  No good point under any candidate: candidate 0, count 0. */
 SLAM_API int slam_tv_recover_pose_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_px1,
                                       const double* d_px2, int64_t M, double fx, double fy, double cx, double cy,
                                       const double* d_E, const uint8_t* d_inlier_in, double distance_thresh,
@@ -451,7 +461,9 @@ SLAM_API int slam_tv_recover_pose_f64(slam_ctx* ctx, int64_t B, const int32_t* d
 /* cv2.triangulatePoints as utils.py:49-53 uses it: per point the 4x4 DLT matrix (x P[2] - P[0], y P[2] - P[1] for both
  * views; d_P1 / d_P2 [12] row-major 3x4, d_x1 / d_x2 [N,2] in the coordinates the projections expect, 16-byte aligned),
  * v = its right singular vector of the smallest singular value (eigenvector of A^T A by cyclic Jacobi), |v| = 1,
- * v[3] >= 0; d_X [N,3] = v[:3] / v[3] (utils.py:52-53) and d_w [N] = v[3], so a caller can see points at infinity. */
+ * v[3] >= 0; d_X [N,3] = v[:3] / v[3] (utils.py:52-53) and d_w [N] = v[3], so a caller can see points at infinity:
+ * for finite input d_w is finite and in [0, 1]; parallel rays give d_w near 0 and a d_X that is huge or infinite, identical
+ * cameras (a two-dimensional null space) some unit vector of it. */
 SLAM_API int slam_tv_triangulate_f64(slam_ctx* ctx, int64_t N, const double* d_P1, const double* d_P2,
                                      const double* d_x1, const double* d_x2, double* d_X, double* d_w);
 

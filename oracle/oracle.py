@@ -557,3 +557,170 @@ def ba_lm_c(poses12, points, obs_pose, obs_point, meas, fx, fy, cx, cy, iteratio
     T[:, :3, :4] = Pout.reshape(K, 3, 4)
     return T, Xout, float(stats[0]), float(stats[1]), int(stats[2]), int(stats[3])
 
+
+
+# ---------------------------------------------------------------- the host twin of csrc/two_view.hip (two_view_twin.cpp)
+_TWIN_PATH = os.path.join(_HERE, "libtvtwin.so")
+TWIN_SAN_PATH = os.path.join(_HERE, "tv_twin_san")
+TWIN_LDS_PER_LANE = 236
+TWIN_STAGES = ("tv_null_space", "tv_constraints", "tv_eliminate", "tv_bpoly", "tv_real_roots")
+_twin = None
+
+
+def _load_twin():
+    """libtvtwin.so: the kernel file's own routines compiled for the host (contraction off, no FMA).  Where there is a
+    compiler, make runs first (a no-op when up to date), so an edit of two_view.hip is never compared with a stale twin; a
+    machine that only received the built library loads it as it is."""
+    import shutil
+
+    global _twin
+    if _twin is not None:
+        return _twin
+    if shutil.which("make") and shutil.which(os.environ.get("CXX", "g++")):
+        subprocess.check_call(["make", "-C", _HERE, "-s", "all"])
+    elif not os.path.exists(_TWIN_PATH):
+        raise RuntimeError("libtvtwin.so is missing and there is no compiler to build it (make -C oracle)")
+    lib = ctypes.CDLL(_TWIN_PATH)
+    i64, i32, u64, vp, dbl = ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_double
+    lib.tvt_set_fill.argtypes = [dbl]
+    lib.tvt_set_fill.restype = None
+    lib.tvt_solve.argtypes = [i64, vp, vp, vp, vp, vp]
+    lib.tvt_solve_stages.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.tvt_sampson_sq.argtypes = [vp, i64, vp, vp, vp]
+    lib.tvt_draw_sample.argtypes = [u64, i32, i32, vp]
+    lib.tvt_decompose.argtypes = [vp, vp, vp, vp]
+    lib.tvt_cheirality.argtypes = [vp, vp, i64, vp, vp, dbl, vp]
+    lib.tvt_triangulate.argtypes = [i64, vp, vp, vp, vp, vp, vp]
+    lib.tvt_ransac.argtypes = [i64, vp, vp, dbl, dbl, dbl, dbl, i32, dbl, u64, vp, vp, vp]
+    lib.tvt_recover_pose.argtypes = [i64, vp, vp, dbl, dbl, dbl, dbl, vp, vp, dbl, vp, vp, vp, vp]
+    for f in (lib.tvt_sampson_sq, lib.tvt_draw_sample, lib.tvt_decompose, lib.tvt_cheirality, lib.tvt_triangulate):
+        f.restype = None
+    _twin = lib
+    return lib
+
+
+def _f64(a, shape=None):
+    a = np.ascontiguousarray(a, np.float64)
+    return a if shape is None else np.ascontiguousarray(a.reshape(shape))
+
+
+def tv_twin_solve(x1, x2, fill: float = 0.0, timed: bool = False):
+    """``tv_solve`` per sample on the host: x1, x2 [S,5,2] -> (E [S,10,9], nroots int32 [S]) and, if ``timed``, the wall
+    seconds of each solve.  ``fill`` is what the stand-in for LDS holds beforehand (the result must not depend on it)."""
+    x1, x2 = _f64(x1, (-1, 5, 2)), _f64(x2, (-1, 5, 2))
+    S = len(x1)
+    E, n, sec = np.zeros((S, 10, 9)), np.zeros(S, np.int32), np.zeros(S)
+    lib = _load_twin()
+    lib.tvt_set_fill(float(fill))
+    try:
+        assert lib.tvt_solve(S, _p(x1), _p(x2), _p(E), _p(n), _p(sec) if timed else None) == 0
+    finally:
+        lib.tvt_set_fill(0.0)
+    return (E, n, sec) if timed else (E, n)
+
+
+def tv_twin_stages(x1, x2):
+    """One sample through the solver routine by routine: (dump [5,236] the lane's memory after each of TWIN_STAGES,
+    number of polynomial roots, E [10,9], nroots)."""
+    x1, x2 = _f64(x1, (5, 2)), _f64(x2, (5, 2))
+    dump, nz, E, n = np.zeros((5, TWIN_LDS_PER_LANE)), np.zeros(1, np.int32), np.zeros((10, 9)), np.zeros(1, np.int32)
+    assert _load_twin().tvt_solve_stages(_p(x1), _p(x2), _p(dump), _p(nz), _p(E), _p(n)) == 0
+    return dump, int(nz[0]), E, int(n[0])
+
+
+def tv_twin_sampson_sq(E, x1, x2):
+    E, x1, x2 = _f64(E, (9,)), _f64(x1, (-1, 2)), _f64(x2, (-1, 2))
+    out = np.zeros(len(x1))
+    _load_twin().tvt_sampson_sq(_p(E), len(x1), _p(x1), _p(x2), _p(out))
+    return out
+
+
+def tv_twin_draw_sample(seed: int, h: int, n: int):
+    idx = np.zeros(5, np.int32)
+    _load_twin().tvt_draw_sample(int(seed) & ((1 << 64) - 1), int(h), int(n), _p(idx))
+    return idx.tolist()
+
+
+def tv_twin_decompose(E):
+    R1, R2, t = np.zeros((3, 3)), np.zeros((3, 3)), np.zeros(3)
+    _load_twin().tvt_decompose(_p(_f64(E, (9,))), _p(R1), _p(R2), _p(t))
+    return R1, R2, t
+
+
+def tv_twin_cheirality(R, t, x1, x2, dist: float = 50.0):
+    x1, x2 = _f64(x1, (-1, 2)), _f64(x2, (-1, 2))
+    good = np.zeros(len(x1), np.uint8)
+    _load_twin().tvt_cheirality(_p(_f64(R, (9,))), _p(_f64(t, (3,))), len(x1), _p(x1), _p(x2), float(dist), _p(good))
+    return good.astype(bool)
+
+
+def tv_twin_triangulate(P1, P2, x1, x2):
+    x1, x2 = _f64(x1, (-1, 2)), _f64(x2, (-1, 2))
+    X, w = np.zeros((len(x1), 3)), np.zeros(len(x1))
+    _load_twin().tvt_triangulate(len(x1), _p(_f64(P1, (12,))), _p(_f64(P2, (12,))), _p(x1), _p(x2), _p(X), _p(w))
+    return X, w
+
+
+def tv_twin_ransac(px1, px2, K, hypotheses: int = 256, threshold: float = 1.0, seed: int = 0):
+    """``slam_tv_essential_ransac_f64`` for one pair, every hypothesis in turn: (E [9], mask bool [n], stats int32 [4])."""
+    px1, px2 = _f64(px1, (-1, 2)), _f64(px2, (-1, 2))
+    n = len(px1)
+    E, mask, st = np.zeros(9), np.zeros(max(n, 1), np.uint8), np.zeros(4, np.int32)
+    rc = _load_twin().tvt_ransac(n, _p(px1), _p(px2), *[float(v) for v in K], int(hypotheses), float(threshold),
+                                 int(seed) & ((1 << 64) - 1), _p(E), _p(mask), _p(st))
+    assert rc == 0
+    return E, mask[:n].astype(bool), st
+
+
+def tv_twin_recover_pose(E, px1, px2, K, inlier=None, distance_thresh: float = 50.0):
+    """``slam_tv_recover_pose_f64`` for one pair: (pose [3,4], good bool [n], stats int32 [2], votes int32 [4])."""
+    px1, px2 = _f64(px1, (-1, 2)), _f64(px2, (-1, 2))
+    n = len(px1)
+    inl = None if inlier is None else np.ascontiguousarray(np.asarray(inlier).astype(np.uint8).reshape(-1))
+    pose, good, st, votes = np.zeros((3, 4)), np.zeros(max(n, 1), np.uint8), np.zeros(2, np.int32), np.zeros(4, np.int32)
+    rc = _load_twin().tvt_recover_pose(n, _p(px1), _p(px2), *[float(v) for v in K], _p(_f64(E, (9,))), _p(inl),
+                                       float(distance_thresh), _p(pose), _p(good), _p(st), _p(votes))
+    assert rc == 0
+    return pose, good[:n].astype(bool), st, votes
+
+
+def _twin_san_run(job: bytes):
+    """Run the sanitized program on a job: (exit code, its stderr, the result file's bytes)."""
+    import tempfile
+
+    _load_twin()
+    with tempfile.TemporaryDirectory() as d:
+        jp, rp = os.path.join(d, "job"), os.path.join(d, "result")
+        with open(jp, "wb") as f:
+            f.write(job)
+        r = subprocess.run([TWIN_SAN_PATH, jp, rp], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        out = open(rp, "rb").read() if os.path.exists(rp) else b""
+    return r.returncode, r.stderr.decode(errors="replace"), out
+
+
+def tv_twin_san_solve(x1, x2):
+    """The solver through the sanitized program: (exit code, report, E [S,10,9], nroots)."""
+    x1, x2 = _f64(x1, (-1, 5, 2)), _f64(x2, (-1, 5, 2))
+    S = len(x1)
+    rc, err, out = _twin_san_run(np.array([0, S], np.int64).tobytes() + x1.tobytes() + x2.tobytes())
+    if len(out) != S * (4 + 720):
+        return rc, err, None, None
+    return rc, err, np.frombuffer(out, np.float64, 90 * S, 4 * S).reshape(S, 10, 9), np.frombuffer(out, np.int32, S)
+
+
+def tv_twin_san_pair(px1, px2, K, hypotheses: int, threshold: float, seed: int, distance_thresh: float = 50.0):
+    """RANSAC + recoverPose of one pair through the sanitized program: (exit code, report, dict of results or None)."""
+    px1, px2 = _f64(px1, (-1, 2)), _f64(px2, (-1, 2))
+    n = len(px1)
+    job = (np.array([1, n, hypotheses], np.int64).tobytes() + np.array([int(seed) & ((1 << 64) - 1)], np.uint64).tobytes()
+           + np.array([*K, threshold, distance_thresh], np.float64).tobytes() + px1.tobytes() + px2.tobytes())
+    rc, err, out = _twin_san_run(job)
+    if len(out) != 72 + 16 + n + 96 + 8 + n:
+        return rc, err, None
+    o = 0
+    res = {}
+    for name, dt, cnt in (("E", np.float64, 9), ("stats", np.int32, 4), ("mask", np.uint8, n), ("pose", np.float64, 12),
+                          ("pose_stats", np.int32, 2), ("good", np.uint8, n)):
+        res[name] = np.frombuffer(out[o:o + cnt * np.dtype(dt).itemsize], dt).copy()
+        o += cnt * np.dtype(dt).itemsize
+    return rc, err, res

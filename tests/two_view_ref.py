@@ -346,3 +346,296 @@ def solver_quantities(E, nroots, x1, x2, E_gt=None):
             if E_gt is not None:
                 comp[s] = min(comp[s], np.linalg.norm(E[s, r] - E_gt[s]), np.linalg.norm(E[s, r] + E_gt[s]))
     return dict(epipolar=epi, cubic=cubic, det=det, frobenius=fro), comp
+
+
+# ---------------------------------------------------------------- scene families at the edges (tests/test_two_view_edges_*.py)
+# Each generator is deterministic in (variant, seed, n) and returns make_scene's dict plus "K", "family", "variant" and what
+# makes it special.  "E" / "R" / "t" are the ground truth where the geometry defines one ("t" is the unit direction; for a
+# pure rotation E and t are zero).  What each family IS (rank, plane residual, the truth among numpy's roots) is asserted in
+# tests/test_two_view_cpu.py on numpy alone.
+def _project(X, K):
+    fx, fy, cx, cy = K
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.stack([fx * X[:, 0] / X[:, 2] + cx, fy * X[:, 1] / X[:, 2] + cy], 1)
+
+
+def _visible(P, K, lo=0.0, hi=np.inf):
+    px = _project(P, K)
+    return (P[:, 2] > lo) & (P[:, 2] < hi) & (px[:, 0] >= 0) & (px[:, 0] < IMAGE[0]) & (px[:, 1] >= 0) & (px[:, 1] < IMAGE[1])
+
+
+def scene_from_points(X, R, t, K=EUROC, **extra):
+    """The scene dict of points X (frame 1) under X2 = R X1 + t; E from the direction of t (zero if t is zero)."""
+    X = np.asarray(X, np.float64)
+    nt = np.linalg.norm(t)
+    E = essential_from_pose(R, t / nt) if nt > 0 else np.zeros(9)
+    sc = dict(px1=_project(X, K), px2=_project(X @ R.T + t, K), R=R, t=t / nt if nt > 0 else np.zeros(3), E=E, X=X,
+              true_inlier=np.ones(len(X), bool), K=K)
+    sc.update(extra)
+    return sc
+
+
+def _general_motion(rng):
+    R = _rodrigues(rng.normal(size=3), np.radians(rng.uniform(MIN_ROTATION_DEG, MAX_ROTATION_DEG)))
+    t = rng.normal(size=3)
+    return R, t / np.linalg.norm(t)
+
+
+def _sample_points(rng, n, R, t, K, depth, keep=None):
+    """n points drawn in camera 1 (uniform pixel, depth from depth(rng, m)) that camera 2 sees in front of it as well."""
+    fx, fy, cx, cy = K
+    X = np.zeros((0, 3))
+    for _ in range(1000):
+        m = 4 * n
+        u, v = rng.uniform(0, IMAGE[0], m), rng.uniform(0, IMAGE[1], m)
+        z = depth(rng, m, (u - cx) / fx, (v - cy) / fy)
+        P = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], 1)
+        ok = (z > 0) & np.isfinite(z) & _visible(P @ R.T + t, K, 0.5)
+        if keep is not None:
+            ok &= keep(P)
+        X = np.concatenate([X, P[ok]])
+        if len(X) >= n:
+            return X[:n]
+    raise RuntimeError("scene family: no visible points")
+
+
+def _uniform_depth(lo, hi):
+    return lambda rng, m, a, b: rng.uniform(lo, hi, m)
+
+
+def scenes_planar(seed=0, n=200):
+    """All points on one plane, general motion: fronto-parallel (Z = 6) and tilted by 60 degrees about the y axis through (0, 0, 8)."""
+    out = []
+    for name, tilt, d0 in (("fronto", 0.0, 6.0), ("tilt60", 60.0, 8.0)):
+        rng = np.random.default_rng([seed, 101, int(tilt)])
+        R, t = _general_motion(rng)
+        nrm = np.array([np.sin(np.radians(tilt)), 0.0, np.cos(np.radians(tilt))])
+        dist = nrm[2] * d0
+
+        def depth(rng, m, a, b, nrm=nrm, dist=dist):
+            den = nrm[0] * a + nrm[1] * b + nrm[2]
+            with np.errstate(divide="ignore"):
+                z = dist / den
+            return np.where((z > MIN_DEPTH) & (z < 2 * MAX_DEPTH), z, -1.0)
+
+        X = _sample_points(rng, n, R, t, EUROC, depth)
+        out.append(scene_from_points(X, R, t, family="planar", variant=name, plane=(nrm, dist)))
+    return out
+
+
+def scenes_pure_rotation(seed=0, n=200):
+    """t = 0 exactly, and a baseline of 1e-6 and 1e-3 of the depth (10): the camera standing still, or nearly."""
+    out = []
+    for name, ratio in (("t0", 0.0), ("b1e-6", 1e-6), ("b1e-3", 1e-3)):
+        rng = np.random.default_rng([seed, 102])
+        R, d = _general_motion(rng)
+        t = d * ratio * 10.0
+        X = _sample_points(rng, n, R, t, EUROC, _uniform_depth(8.0, 12.0))
+        out.append(scene_from_points(X, R, t, family="pure_rotation", variant=name, baseline_over_depth=ratio))
+    return out
+
+
+def _scenes_translation(family, t, seed, n):
+    rng = np.random.default_rng([seed, 103])
+    X = _sample_points(rng, n, np.eye(3), t, EUROC, _uniform_depth(MIN_DEPTH + 1.0, MAX_DEPTH))
+    return [scene_from_points(X, np.eye(3), t, family=family, variant="unit")]
+
+
+def scenes_forward(seed=0, n=200):
+    """R = I, t along z: both epipoles at the principal point, inside the image."""
+    return _scenes_translation("forward", np.array([0.0, 0.0, 1.0]), seed, n)
+
+
+def scenes_sideways(seed=0, n=200):
+    """R = I, t along x: both epipoles at infinity."""
+    return _scenes_translation("sideways", np.array([1.0, 0.0, 0.0]), seed, n)
+
+
+def scenes_large_rotation(seed=0, n=200):
+    """Rotation by 90, 170, 180 degrees about the y axis through the scene's centre C: X2 = R (X1 - C) + C, scaled to |t| = 1."""
+    out = []
+    for deg in (90, 170, 180):
+        rng = np.random.default_rng([seed, 104, deg])
+        R = _rodrigues(np.array([0.0, 1.0, 0.0]), np.radians(deg))
+        C = np.array([0.0, 0.0, 6.0])
+        t = C - R @ C
+        s = 1.0 / np.linalg.norm(t)
+        P = C + rng.uniform(-1.5, 1.5, (4 * n, 3))
+        ok = _visible(P, EUROC, 0.5) & _visible((P - C) @ R.T + C, EUROC, 0.5)
+        X = P[ok][:n] * s
+        assert len(X) == n
+        out.append(scene_from_points(X, R, t * s, family="large_rotation", variant=f"{deg}deg"))
+    return out
+
+
+def scenes_far(seed=0, n=200):
+    """Depths of 1e2 - 1e4 baselines (log-uniform; beyond recoverPose's distance_thresh = 50), and half near (2 - 20), half far.
+
+    NARROWED for completeness: with every point far the numpy solver itself is above ILL_CONDITIONED on 22 % of the samples
+    (cap: 1 %), and no depth range mends that - 1e2 - 1e3 leaves 10 %, 1e2 - 2e2 16 % (less depth variation is worse), a far
+    share of 0.9 / 0.8 / 0.7 leaves 12 % / 7.5 % / 5 %: a sample with four or five far points is a pure rotation to seven
+    digits whatever the range.  The variant inside the cap is "mixed" (a far share of 0.5: 0.4 % left out), and the true
+    matrix is asked of the solver there.  "all_far" keeps the contract, the exact scoring, the pose and the distance filter.
+    On it the kernel's solver is weaker than numpy's: of the 798 samples in 1024 where numpy finds the true matrix to 1e-6
+    the kernel's arithmetic misses it on 24 (a near-singular 10x10 block in its elimination order, smallest singular value
+    3e-7 - 2e-5, in either basis); tests/test_two_view_edges_cpu.py prints that count.  pure_rotation/b1e-3 (12 samples)
+    and epipole_match (20: the sample holds a match at both epipoles, which constrains nothing) show the same."""
+    out = []
+    for name, share in (("all_far", 1.0), ("mixed", 0.5)):
+        rng = np.random.default_rng([seed, 105])
+        R, t = _general_motion(rng)
+
+        def depth(rng, m, a, b, share=share):
+            far = 10.0 ** rng.uniform(2, 4, m)
+            return np.where(rng.uniform(size=m) < share, far, rng.uniform(MIN_DEPTH, MAX_DEPTH, m))
+
+        X = _sample_points(rng, n, R, t, EUROC, depth)
+        out.append(scene_from_points(X, R, t, family="far", variant=name))
+    return out
+
+
+def scenes_duplicates(seed=0, n=200):
+    """n matches of which only 5, 6, 8 are distinct (match i is distinct match i mod k), and all n identical (k = 1)."""
+    out = []
+    for k in (5, 6, 8, 1):
+        sc = make_scene(np.random.default_rng([seed, 106]), 8)
+        idx = np.arange(n) % k
+        out.append(dict(px1=sc["px1"][idx], px2=sc["px2"][idx], R=sc["R"], t=sc["t"], E=sc["E"], X=sc["X"][idx],
+                        true_inlier=np.ones(n, bool), K=EUROC, family="duplicates", variant=f"{k}distinct", distinct=k))
+    return out
+
+
+def scenes_collinear(seed=0, n=200):
+    """The image points of frame 1 on one line (the points in a plane through camera 1's centre); and the points on one line
+    in space, so that both images are collinear."""
+    out = []
+    rng = np.random.default_rng([seed, 107])
+    R, t = _general_motion(rng)
+    fx, fy, cx, cy = EUROC
+    X = np.zeros((0, 3))
+    while len(X) < n:
+        u = rng.uniform(0, IMAGE[0], 4 * n)
+        v = 100.0 + 0.35 * u
+        z = rng.uniform(MIN_DEPTH, MAX_DEPTH, 4 * n)
+        P = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], 1)
+        X = np.concatenate([X, P[_visible(P @ R.T + t, EUROC, 0.5)]])
+    out.append(scene_from_points(X[:n], R, t, family="collinear", variant="frame1"))
+    a, b = np.array([-2.0, -1.0, 6.0]), np.array([2.5, 1.2, 9.0])
+    P = a + rng.uniform(0, 1, (8 * n, 1)) * (b - a)
+    P = P[_visible(P, EUROC, 0.5) & _visible(P @ R.T + t, EUROC, 0.5)]
+    assert len(P) >= n
+    out.append(scene_from_points(P[:n], R, t, family="collinear", variant="both"))
+    return out
+
+
+def scenes_integer_pixels(seed=0, n=200):
+    """A general scene with every coordinate rounded to a whole pixel: counts of different hypotheses tie exactly."""
+    sc = make_scene(np.random.default_rng([seed, 108]), n)
+    sc.update(px1=np.round(sc["px1"]), px2=np.round(sc["px2"]), K=EUROC, family="integer_pixels", variant="rounded")
+    return [sc]
+
+
+def epipoles_px(R, t, K=EUROC):
+    """(epipole in image 1, epipole in image 2) in pixels: the images of the other camera's centre."""
+    return _project((-R.T @ t)[None], K)[0], _project(np.asarray(t, np.float64)[None], K)[0]
+
+
+def scenes_epipole_match(seed=0, n=200):
+    """A general scene, and a forward motion (epipoles exactly at the principal point), each with three matches placed at
+    (epipole 1, epipole 2): E x1 = 0 and E^T x2 = 0 there, the Sampson distance is 0 / 0."""
+    out = []
+    for name, sc in (("general", make_scene(np.random.default_rng([seed, 109]), n - 3)),
+                     ("forward", scenes_forward(seed, n - 3)[0])):
+        e1, e2 = epipoles_px(sc["R"], sc["t"])
+        sc = dict(sc)
+        sc.update(px1=np.concatenate([sc["px1"], np.tile(e1, (3, 1))]), px2=np.concatenate([sc["px2"], np.tile(e2, (3, 1))]),
+                  X=np.concatenate([sc["X"], np.full((3, 3), np.nan)]), true_inlier=np.r_[sc["true_inlier"], np.zeros(3, bool)],
+                  K=EUROC, family="epipole_match", variant=name, at_epipole=np.arange(n - 3, n))
+        out.append(sc)
+    return out
+
+
+def scenes_non_finite(seed=0, n=200):
+    """A general scene with one match NaN in frame 1, and with ten matches holding NaN, +inf, -inf in either frame."""
+    out = []
+    for name, k in (("one", 1), ("some", 10)):
+        rng = np.random.default_rng([seed, 110])
+        sc = make_scene(rng, n)
+        bad = np.sort(rng.choice(n, k, replace=False))
+        vals = [np.nan, np.inf, -np.inf]
+        for j, i in enumerate(bad):
+            (sc["px1"] if j % 2 == 0 else sc["px2"])[i, (j // 2) % 2] = vals[j % 3]
+        sc["true_inlier"][bad] = False
+        sc.update(K=EUROC, family="non_finite", variant=name, bad=bad)
+        out.append(sc)
+    return out
+
+
+def scenes_off_image(seed=0, n=200):
+    """A general scene with ten matches whose coordinates have magnitude 1e6, and 1e150, pixels; and a general scene under
+    intrinsics with fx / fy = 1e3."""
+    out = []
+    for name, mag in (("1e6", 1e6), ("1e150", 1e150)):
+        rng = np.random.default_rng([seed, 111])
+        sc = make_scene(rng, n)
+        bad = np.sort(rng.choice(n, 10, replace=False))
+        sc["px1"][bad] = mag * rng.choice([-1.0, 1.0], (10, 2)) * rng.uniform(0.5, 1.0, (10, 2))
+        sc["px2"][bad[::2]] = mag * rng.choice([-1.0, 1.0], (5, 2)) * rng.uniform(0.5, 1.0, (5, 2))
+        sc["true_inlier"][bad] = False
+        sc.update(K=EUROC, family="off_image", variant=name, bad=bad)
+        out.append(sc)
+    K = (14500.0, 14.5, EUROC[2], EUROC[3])
+    sc = make_scene(np.random.default_rng([seed, 112]), n, K=K)
+    sc.update(K=K, family="off_image", variant="fx_over_fy_1e3", bad=np.zeros(0, int))
+    out.append(sc)
+    return out
+
+
+def scenes_minimal(seed=0, n=None):
+    """n = 5, 6, 7 matches of a general scene: every hypothesis draws nearly the same sample."""
+    out = []
+    for k in (5, 6, 7):
+        sc = make_scene(np.random.default_rng([seed, 113, k]), k)
+        sc.update(K=EUROC, family="minimal", variant=f"n{k}")
+        out.append(sc)
+    return out
+
+
+def scenes_general(seed=0, n=200):
+    sc = make_scene(np.random.default_rng([seed, 100]), n)
+    sc.update(K=EUROC, family="general", variant="clean")
+    return [sc]
+
+
+FAMILIES = dict(general=scenes_general, planar=scenes_planar, pure_rotation=scenes_pure_rotation, forward=scenes_forward,
+                sideways=scenes_sideways, large_rotation=scenes_large_rotation, far=scenes_far, duplicates=scenes_duplicates,
+                collinear=scenes_collinear, integer_pixels=scenes_integer_pixels, epipole_match=scenes_epipole_match,
+                non_finite=scenes_non_finite, off_image=scenes_off_image, minimal=scenes_minimal)
+# families whose geometry defines the answer: the true E must be among the solver's roots (integer_pixels: of its own
+# rounded points, so no exact truth - completeness is not asked of it, pose recovery is)
+DEFINED_ANSWER = ("planar", "forward", "sideways", "large_rotation", "far", "integer_pixels", "minimal")
+COMPLETE = ("planar", "forward", "sideways", "large_rotation", "far", "minimal")
+# families where degeneracy is the point: no accuracy is claimed, only "returns, finite or absent, nothing else"
+DEGENERATE = (("pure_rotation", "t0"), ("duplicates", None), ("collinear", None), ("non_finite", None))
+
+
+def is_degenerate(sc):
+    return any(sc["family"] == f and v in (None, sc["variant"]) for f, v in DEGENERATE)
+
+
+def all_family_scenes(seed=0, n=200):
+    return [sc for name, fn in FAMILIES.items() for sc in fn(seed, n)]
+
+
+def family_samples(sc, seed, S):
+    """The five-point samples hypotheses 0 .. S-1 draw from the scene under this seed: (idx [S,5], x1 [S,5,2], x2 [S,5,2])."""
+    x1, x2 = normalise(sc["px1"], sc["K"]), normalise(sc["px2"], sc["K"])
+    idx = np.array([draw_sample(seed, 0, h, len(x1)) for h in range(S)])
+    return idx, x1[idx], x2[idx]
+
+
+def epipolar_rows(x1, x2):
+    """The 5x9 systems [S,5,9] of samples x1, x2 [S,5,2]."""
+    h1 = np.concatenate([x1, np.ones(x1.shape[:2] + (1,))], -1)
+    h2 = np.concatenate([x2, np.ones(x2.shape[:2] + (1,))], -1)
+    return (h2[:, :, :, None] * h1[:, :, None, :]).reshape(-1, 5, 9)
