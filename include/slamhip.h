@@ -608,14 +608,16 @@ SLAM_API int slam_ba_optimize_host_f64(slam_ctx* ctx, int64_t K, int64_t L, int6
  * that do not match the edges are found on the device before any kernel follows them: SLAM_ERR_INVALID, outputs untouched.
  * All arithmetic is f64 without contraction and without floating-point atomics: results are pure functions of the inputs.
  * Workspace: the context's grow-only block; the calls serialise on the context's call lock.  Angles of r beyond 3.1 rad
- * are outside the contract and reported (SLAM_PG_STATUS_ANGLE) instead of producing NaN. */
+ * are outside the contract and reported (SLAM_PG_STATUS_ANGLE) instead of producing NaN.  An edge that is reported - its
+ * angle beyond 3.1 rad, a pose or measurement that is not finite, or a robust cost that is not finite (an inf or NaN in
+ * Omega) - leaves the sums: it adds 0 to the cost, and its W_e and its shares of H_vv and b are finite zeros. */
 #define SLAM_PG_MAX_VERTICES (1 << 24)
 #define SLAM_PG_MAX_EDGES (1 << 25)
 #define SLAM_PG_STATUS_INDEX 1      /* bad edge index / vertex list (the call returns SLAM_ERR_INVALID) */
 #define SLAM_PG_STATUS_ANGLE 2      /* a residual's rotation angle is beyond 3.1 rad: that edge was given weight 0 */
 #define SLAM_PG_STATUS_PRECOND 4    /* a diagonal block H_vv + lambda I was not positive definite (identity used) */
 #define SLAM_PG_STATUS_BREAKDOWN 8  /* CG met p.Ap <= 0 and stopped */
-#define SLAM_PG_STATUS_NONFINITE 16 /* a non-finite cost or CG scalar */
+#define SLAM_PG_STATUS_NONFINITE 16 /* a non-finite cost, right-hand side or CG scalar */
 /* bytes of context workspace a graph of V vertices and E edges takes; needs no device */
 SLAM_API int slam_pg_workspace(int64_t V, int64_t E, uint64_t* bytes);
 /* the launch plan, without a device: plan[8] = {blocks of the product's main path (= partial sums per dot product),
@@ -634,7 +636,10 @@ SLAM_API int slam_pg_hmul_f64(slam_ctx* ctx, int64_t V, int64_t E, const int32_t
                               const int32_t* d_vtx_adj, const uint8_t* d_fixed, const double* d_Hdiag, const double* d_W,
                               double lambda, const double* d_x, double* d_y);
 /* Preconditioned CG on (H + lambda I) x = -d_b over the free vertices, stopping at |r| <= tol |b| or max_iter; alpha, beta
- * and the stop decision stay on the device.  h_stats[4] = {iterations, converged, |r| / |b| of the recurrence, status}. */
+ * and the stop decision stay on the device.  h_stats[4] = {iterations, converged, |r| / |b| of the recurrence, status}.
+ * converged = 1 exactly when the tolerance was met: a finite |r|^2 <= tol^2 |b|^2 (b = 0 meets it with x = 0 and no iteration).  A solve that stopped for
+ * another reason - max_iter, SLAM_PG_STATUS_BREAKDOWN, a b or a CG scalar that is not finite - reports 0, and a |b| that is
+ * not finite reports a |r| / |b| that is not finite. */
 SLAM_API int slam_pg_pcg_f64(slam_ctx* ctx, int64_t V, int64_t E, const int32_t* d_edges, const int32_t* d_vtx_ptr,
                              const int32_t* d_vtx_adj, const uint8_t* d_fixed, const double* d_Hdiag, const double* d_W,
                              const double* d_b, double lambda, double tol, int max_iter, double* d_x, double* h_stats);

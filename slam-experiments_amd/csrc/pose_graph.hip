@@ -410,7 +410,10 @@ __global__ __launch_bounds__(64) void pg_edge_kernel(int E, const double* __rest
             const double en = sqrt(chi2);
             if (en > huber) { w = huber / en; rho = 2.0 * huber * en - huber * huber; }
         }
-        if (!ok || !isfinite(rho)) { atomicOr(&sc->status, ok ? PG_ST_NONFINITE : PG_ST_ANGLE); rho = 0.0; w = 0.0; }
+        // an edge that is reported leaves the sums: its cost is 0 and its blocks are finite zeros, by a select (0 * inf is NaN,
+        // and one NaN block would reach every CG scalar)
+        const bool live = ok && isfinite(rho);
+        if (!live) { atomicOr(&sc->status, ok ? PG_ST_NONFINITE : PG_ST_ANGLE); rho = 0.0; w = 0.0; }
         if (FULL) {
             double Ji[36], OJi[36], OJj[36];
             {
@@ -429,7 +432,7 @@ __global__ __launch_bounds__(64) void pg_edge_kernel(int E, const double* __rest
             for (int a = 0; a < 6; a++)
 #pragma unroll
                 for (int b = 0; b < 6; b++) {
-                    const double v = w * pg_atb(Ji, OJj, a, b);       // W_e = w J_i^T Omega J_j
+                    const double v = live ? w * pg_atb(Ji, OJj, a, b) : 0.0;       // W_e = w J_i^T Omega J_j
                     Si[a * 6 + b] = v;
                     Sj[b * 6 + a] = v;
                     if (W_out) W_out[36 * (size_t)e + a * 6 + b] = v;
@@ -439,8 +442,8 @@ __global__ __launch_bounds__(64) void pg_edge_kernel(int E, const double* __rest
             for (int a = 0; a < 6; a++)
 #pragma unroll
                 for (int b = a; b < 6; b++) {
-                    Di[t] = w * pg_atb(Ji, OJi, a, b);
-                    Dj[t] = w * pg_atb(Jj, OJj, a, b);
+                    Di[t] = live ? w * pg_atb(Ji, OJi, a, b) : 0.0;
+                    Dj[t] = live ? w * pg_atb(Jj, OJj, a, b) : 0.0;
                     t++;
                 }
 #pragma unroll
@@ -448,8 +451,8 @@ __global__ __launch_bounds__(64) void pg_edge_kernel(int E, const double* __rest
                 double gi = Ji[a] * Or[0], gj = Jj[a] * Or[0];
 #pragma unroll
                 for (int k = 1; k < 6; k++) { gi += Ji[k * 6 + a] * Or[k]; gj += Jj[k * 6 + a] * Or[k]; }
-                Di[21 + a] = w * gi;
-                Dj[21 + a] = w * gj;
+                Di[21 + a] = live ? w * gi : 0.0;
+                Dj[21 + a] = live ? w * gj : 0.0;
             }
         }
     }
@@ -492,7 +495,10 @@ __global__ __launch_bounds__(PG_THREADS) void pg_finish_kernel(const double* __r
 __global__ __launch_bounds__(PG_THREADS) void pg_finish_bb_kernel(const double* __restrict__ part, int n, double tol, pg_scal* sc) {
     __shared__ double sh[PG_THREADS / 64];
     const double s = pg_sum_partials(part, n, sh);
-    if (threadIdx.x == 0) { sc->bb = s; sc->rr = s; sc->tol2bb = tol * tol * s; sc->done = 0; sc->iters = 0; }
+    if (threadIdx.x == 0) {
+        sc->bb = s; sc->rr = s; sc->tol2bb = tol * tol * s; sc->done = 0; sc->iters = 0;
+        if (!isfinite(s)) atomicOr(&sc->status, PG_ST_NONFINITE);      // a right-hand side that is not finite: no iteration will run
+    }
 }
 
 // edge-ordered W_e -> the slots of both ends (the hooks that are handed blocks instead of poses)
@@ -952,7 +958,9 @@ extern "C" int slam_pg_pcg_f64(slam_ctx* ctx, int64_t V, int64_t E, const int32_
     if (int rc = pg_pcg(ctx, G, d_Hdiag, d_b, lambda, tol, max_iter, d_x, hs)) return rc;
     SLAM_HIP(hipMemcpyAsync(hs, G.sc, sizeof(pg_scal), hipMemcpyDeviceToHost, ctx->stream));
     SLAM_HIP(hipStreamSynchronize(ctx->stream));
-    h_stats[0] = hs->iters; h_stats[1] = hs->done; h_stats[2] = hs->bb > 0.0 ? sqrt(hs->rr / hs->bb) : 0.0; h_stats[3] = hs->status;
+    // converged = the tolerance was met by a finite residual; `done` is only the stop flag (breakdown and NaN set it too)
+    h_stats[0] = hs->iters; h_stats[1] = (isfinite(hs->rr) && hs->rr <= hs->tol2bb) ? 1.0 : 0.0;
+    h_stats[2] = hs->bb == 0.0 ? 0.0 : sqrt(hs->rr / hs->bb); h_stats[3] = hs->status;
     return SLAM_OK;
 }
 
