@@ -17,10 +17,12 @@
 //   * selection: the accumulator starts at C = 2 d2 - 256 (d2: the query's current 2nd-best distance), so D >= 0 <=>
 //     distance <= d2 - ties pass, the keys decide (rows of one query reach different lanes out of index order).  Lane
 //     (lane & 15, lane >> 4) of tile t holds query 16 t + (lane & 15) against rows 4 (lane >> 4) + r: the 16 results of a
-//     group fold with v_max3 into one compare, one ballot and one branch, the update (laid out as unlikely) is the VALU
-//     kernel's on packed keys (dist << 23 | row: med3 / min).  Each lane keeps the top-2 of ITS rows; the four lanes of a
-//     query are united (two xor shuffles) once per stage for the threshold, at each chunk start for the bound exchange,
-//     and at the end, where lane l takes query 64 wave + l - the layout of bf_top2_kernel's epilogue, which is shared.
+//     group fold as bit patterns with v_max3_i32 (exact integers: the sign of the signed maximum says "some D >= 0") into
+//     one compare and one branch; the update (laid out as unlikely) runs per tile, only for tiles whose own maximum passes,
+//     and is the VALU kernel's on packed keys (dist << 23 | row: med3 / min).  The accumulators and C live in VGPRs (the
+//     Makefile's -amdgpu-mfma-vgpr-form for this file): no AGPR round trip.  Each lane keeps the top-2 of ITS rows; the four
+//     lanes of a query are united (two xor shuffles) once per stage that fired for the threshold, at each chunk start for the
+//     bound exchange, and at the end, where lane l takes query 64 wave + l - the layout of bf_top2_kernel's epilogue, shared.
 //   * plan: the queue plan of bf_top2_kernel<1, true, true> with tickets drawn per BLOCK: grid = (query blocks, workers),
 //     the workers of a query block draw chunks of the boundary table by ticket, exchange the 2nd-best distance through
 //     bound[] at every chunk, merge with the two returning atomic minima and the last arriver decodes (bf_common.h).
@@ -110,7 +112,8 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
         const float c = (float)(2 * (int)d2[tt] - 256);
         cth[tt] = mx_v4f{c, c, c, c};
     };
-    // the top-2 of each tile's query over the rows of all four lanes that hold it
+    // the top-2 of each tile's query over the rows of all four lanes that hold it (ds_bpermute: it issues beside the VALU, which
+    // is what bounds this kernel; the v_permlane16/32_swap form costs two copies and a wait per swap there and measured slower)
     auto unite_lanes = [&](u32 (&u1)[4], u32 (&u2)[4]) {
 #pragma unroll
         for (int tt = 0; tt < 4; tt++) {
@@ -172,6 +175,8 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
             else if (tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int ng = __builtin_amdgcn_readfirstlane(min(SLAM_MX_STAGE / 16, (c1 - s0 + 15) >> 4));
             const uint4* tp = tile[buf];
+            const int lim = s1 > c1 ? c1 : 0x7fffffff;           // rows past the chunk: only in the last stage of the last chunk
+            bool fired = false;                                  // wave-uniform: some group of this stage took the update path
             for (int g = 0; g < ng; g++) {
                 const uint4 a0 = tp[g * 128 + lane], a1 = tp[g * 128 + 64 + lane];
                 mx_v4f acc[4];
@@ -179,24 +184,31 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
                 for (int tt = 0; tt < 4; tt++) acc[tt] = mx_dot(a0, qb[tt][0], cth[tt]);
 #pragma unroll
                 for (int tt = 0; tt < 4; tt++) acc[tt] = mx_dot(a1, qb[tt][1], acc[tt]);
-                float m = fmaxf(fmaxf(acc[0][0], acc[0][1]), acc[0][2]);
-                m = fmaxf(fmaxf(m, acc[0][3]), acc[1][0]);
-                m = fmaxf(fmaxf(m, acc[1][1]), acc[1][2]);
-                m = fmaxf(fmaxf(m, acc[1][3]), acc[2][0]);
-                m = fmaxf(fmaxf(m, acc[2][1]), acc[2][2]);
-                m = fmaxf(fmaxf(m, acc[2][3]), acc[3][0]);
-                m = fmaxf(fmaxf(m, acc[3][1]), acc[3][2]);
-                m = fmaxf(m, acc[3][3]);
-                if (__builtin_expect(__ballot(m >= 0.0f) != 0ull, 0)) {
+                // the results are exact integers in f32 (never -0): "any D >= 0" is the sign of the signed maximum of the bit
+                // patterns - eight three-input maxima, nothing to canonicalise
+                int p[4];
+#pragma unroll
+                for (int tt = 0; tt < 4; tt++)
+                    p[tt] = max(max(__float_as_int(acc[tt][0]), __float_as_int(acc[tt][1])), __float_as_int(acc[tt][2]));
+                int m = max(max(p[0], __float_as_int(acc[0][3])), p[1]);
+                m = max(max(m, __float_as_int(acc[1][3])), p[2]);
+                m = max(max(m, __float_as_int(acc[2][3])), p[3]);
+                m = max(m, __float_as_int(acc[3][3]));
+                if (__builtin_expect(__ballot(m >= 0) != 0ull, 0)) {
                     // D = dot + 2 d2 - 256, so the distance (256 - dot) / 2 is d2 - D / 2 (D is even); rows past the chunk -
-                    // the zero rows of a short stage - never enter
+                    // the zero rows of a short stage - never enter.  Only the tiles that hold a candidate are updated (wave-
+                    // uniform branches on the tile's own maximum), and only those get a new threshold
                     const int row0 = s0 + g * 16 + 4 * kg;
+                    fired = true;
 #pragma unroll
                     for (int tt = 0; tt < 4; tt++) {
+                        if (__ballot(max(p[tt], __float_as_int(acc[tt][3])) >= 0) == 0ull) continue;
+                        const u32 base = (d2[tt] << SLAM_KEY_IDX_BITS) + (u32)row0;
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
-                            const u32 dist = d2[tt] - (u32)((int)acc[tt][r] >> 1);
-                            const u32 key = row0 + r < c1 ? (dist << SLAM_KEY_IDX_BITS) | (u32)(row0 + r) : SLAM_KEY_NONE;
+                            // key = (d2 - D / 2) << 23 | row, D even: base + r + (-D << 22)
+                            u32 key = base + (u32)r + ((u32)(int)(-acc[tt][r]) << (SLAM_KEY_IDX_BITS - 1));
+                            key = row0 + r < lim ? key : SLAM_KEY_NONE;
                             b2[tt] = umed3(b1[tt], b2[tt], key);
                             b1[tt] = min(b1[tt], key);
                         }
@@ -204,7 +216,7 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
                     }
                 }
             }
-            {   // once per stage: the threshold of the query's four lanes together
+            if (fired) {   // once per stage in which a key changed: the threshold of the query's four lanes together
                 u32 u1[4], u2[4];
                 unite_lanes(u1, u2);
 #pragma unroll
