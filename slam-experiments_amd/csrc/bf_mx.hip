@@ -14,17 +14,32 @@
 //     rows (4 KiB, one 16-byte load per thread), expands them (8 VALU per word) straight into the operand order - group
 //     of 16 rows = [K-half][lane] x 16 bytes, so a lane's operand is one conflict-free ds_read_b128 - double buffered,
 //     one barrier per stage.  The compact train set (2 MiB at 65536 rows) stays what sits in the L2s.
-//   * selection: the accumulator starts at C = 2 d2 - 256 (d2: the query's current 2nd-best distance), so D >= 0 <=>
-//     distance <= d2 - ties pass, the keys decide (rows of one query reach different lanes out of index order).  Lane
-//     (lane & 15, lane >> 4) of tile t holds query 16 t + (lane & 15) against rows 4 (lane >> 4) + r: the 16 results of a
-//     group fold as bit patterns with v_max3_i32 (exact integers: the sign of the signed maximum says "some D >= 0") into
-//     one compare and one branch; the update (laid out as unlikely) runs per tile, only for tiles whose own maximum passes,
-//     and is the VALU kernel's on packed keys (dist << 23 | row: med3 / min).  The accumulators and C live in VGPRs (the
-//     Makefile's -amdgpu-mfma-vgpr-form for this file): no AGPR round trip.  Each lane keeps the top-2 of ITS rows; the four
-//     lanes of a query are united (two xor shuffles) once per stage that fired for the threshold, at each chunk start for the
-//     bound exchange, and at the end, where lane l takes query 64 wave + l - the layout of bf_top2_kernel's epilogue, shared.
+//   * selection: the accumulator starts at C = 2 e - 256 (e: the lane's inclusive threshold distance for the tile's query), so
+//     D >= 0 <=> distance <= e.  Lane (lane & 15, lane >> 4) of tile t holds query 16 t + (lane & 15) against rows
+//     4 (lane >> 4) + r: the 16 results of a group fold as bit patterns with v_max3_i32 (exact integers: the sign of the signed
+//     maximum says "some D >= 0") into one compare and one branch; the update (laid out as unlikely) runs per tile, only for
+//     tiles whose own maximum passes, and is the VALU kernel's on packed keys (dist << 23 | row: med3 / min); a key is
+//     (e << 23 | row) - (D << 22), exact modulo 2^32 for every lane of a fired tile, also a lane whose e is -1.  The
+//     accumulators and C live in VGPRs (the Makefile's -amdgpu-mfma-vgpr-form for this file): no AGPR round trip.  Each lane
+//     keeps the top-2 of ITS rows; the four lanes of a query are united (two xor shuffles) once per stage that fired, at each
+//     chunk start for the bound exchange, and at the end, where lane l takes query 64 wave + l - the layout of bf_top2_kernel's
+//     epilogue, shared.
+//   * distance ties stay out of the update path where they cannot win.  e only ever falls, to one of:
+//       - dist(own 2nd-best) - 1 after a fire, dist(2nd-best of the query's four lanes) - 1 after a stage that fired and at a
+//         chunk start: a worker's chunks ascend (tickets), and so do stages, groups and a lane's rows, hence every row the lane
+//         has still to see has a higher index than every row in those pairs;
+//       - dist(g) - (row(g) < c0 ? 1 : 0) for the key g read from bound[] at the start of the chunk that begins at row c0.
+//         bound[] holds the 2nd-best KEY some worker of the query block has published (this kernel's own exchange: bound[] is
+//         only read and written by the blocks of one launch, so the encoding is private to it; keys below 0x7F000000 only - at
+//         or above, the idle pattern 0x7F7F7F7F included, reads as "nobody has published" - and the epilogue is handed a
+//         distance or the idle pattern as before).  The row is TESTED: a worker can finish a later chunk and publish from it
+//         before a slower one reads the bound for an earlier chunk, and a tie against such a key can win.
+//     Why this is exact: a candidate is dropped only if some known 2nd-best key K has dist(K) < dist, or dist(K) == dist and
+//     row(K) < row.  Its key then exceeds K, and K is at least the final 2nd key, so the candidate is not in the final top-2.
+//     (The code keeps x = e + 1, which is what a key's distance field gives without a subtract and never goes below 0.)
+//     tests/test_mx_ties_cpu.py restates these rules in numpy and drives them over adversarial schedules.
 //   * plan: the queue plan of bf_top2_kernel<1, true, true> with tickets drawn per BLOCK: grid = (query blocks, workers),
-//     the workers of a query block draw chunks of the boundary table by ticket, exchange the 2nd-best distance through
+//     the workers of a query block draw chunks of the boundary table by ticket, exchange the 2nd-best key through
 //     bound[] at every chunk, merge with the two returning atomic minima and the last arriver decodes (bf_common.h).
 #include "internal.h"
 #include <vector>
@@ -33,6 +48,7 @@
 #include "bf_common.h"
 
 #define SLAM_MX_STAGE 128        // train rows per LDS stage: 16 KiB expanded, two stages per block
+#define SLAM_MX_BOUND_LIMIT 0x7F000000u   // bound[] of this kernel holds keys below this; at or above (the idle pattern): nobody has published
 #define SLAM_MX_RESIDENT 4       // blocks of bf_top2_mx_kernel a CU holds at once (the plan describe counts on it; launches ask)
 
 typedef int mx_v8i __attribute__((ext_vector_type(8)));
@@ -96,47 +112,59 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
         keep[2 * (size_t)qbase + 1] = q[2 * (size_t)qbase + 1];
     }
 
-    // per tile: the lane's own top-2 over its rows, the threshold distance d2 and the accumulator start 2 d2 - 256, and ub: the
-    // best bound known from elsewhere (the query's other lanes, the other blocks); d2 = min(own 2nd-best, ub)
-    u32 b1[4], b2[4], d2[4], ub[4];
+    // per tile: the lane's own top-2 over its rows and the EXCLUSIVE threshold distance x (a row passes when its distance is below
+    // x; x - 1 is the inclusive threshold e of the file header), kept as what a key's distance field gives without a subtract.
+    // The accumulator starts at 2 (x - 1) - 256.  x only ever falls.
+    u32 b1[4], b2[4], x[4];
     mx_v4f cth[4];
+    auto set_threshold = [&](int tt) {
+        const float c = (float)(2 * (int)x[tt] - 258);
+        cth[tt] = mx_v4f{c, c, c, c};
+    };
 #pragma unroll
     for (int tt = 0; tt < 4; tt++) {
         b1[tt] = b2[tt] = SLAM_KEY_NONE;
-        d2[tt] = ub[tt] = SLAM_KEY_NONE >> SLAM_KEY_IDX_BITS;
-        const float c = (float)(2 * (int)d2[tt] - 256);
-        cth[tt] = mx_v4f{c, c, c, c};
+        x[tt] = SLAM_KEY_NONE >> SLAM_KEY_IDX_BITS;              // 511: everything passes
+        set_threshold(tt);
     }
-    auto set_threshold = [&](int tt) {
-        d2[tt] = min(ub[tt], b2[tt] >> SLAM_KEY_IDX_BITS);
-        const float c = (float)(2 * (int)d2[tt] - 256);
-        cth[tt] = mx_v4f{c, c, c, c};
-    };
-    // the top-2 of each tile's query over the rows of all four lanes that hold it (ds_bpermute: it issues beside the VALU, which
+    // the top-2 of one tile's query over the rows of all four lanes that hold it (ds_bpermute: it issues beside the VALU, which
     // is what bounds this kernel; the v_permlane16/32_swap form costs two copies and a wait per swap there and measured slower)
-    auto unite_lanes = [&](u32 (&u1)[4], u32 (&u2)[4]) {
+    auto unite_tile = [&](int tt, u32& u1, u32& u2) {
+        u1 = b1[tt];
+        u2 = b2[tt];
 #pragma unroll
-        for (int tt = 0; tt < 4; tt++) {
-            u1[tt] = b1[tt];
-            u2[tt] = b2[tt];
-#pragma unroll
-            for (int off = 16; off <= 32; off <<= 1) {
-                const u32 c1 = (u32)__shfl_xor((int)u1[tt], off, 64), c2 = (u32)__shfl_xor((int)u2[tt], off, 64);
-                mx_unite(u1[tt], u2[tt], c1, c2);
-            }
+        for (int off = 16; off <= 32; off <<= 1) {
+            const u32 c1 = (u32)__shfl_xor((int)u1, off, 64), c2 = (u32)__shfl_xor((int)u2, off, 64);
+            mx_unite(u1, u2, c1, c2);
         }
     };
-    // exchange with the other workers of this query block through bound[] (share_bound; lane l speaks for query 64 wave + l)
-    u32 gk[1] = {SLAM_BOUND_IDLE}, pend[1] = {0u};
-    auto exchange = [&]() {
+    auto unite_lanes = [&](u32 (&u1)[4], u32 (&u2)[4]) {
+#pragma unroll
+        for (int tt = 0; tt < 4; tt++) unite_tile(tt, u1[tt], u2[tt]);
+    };
+    // Exchange with the other workers of this query block through bound[], at the start of the chunk that begins at row c0 (lane
+    // l speaks for query 64 wave + l).  This kernel's own form of share_bound (bf_common.h): bound[] holds the 2nd-best KEY, see
+    // the file header; the relaxed load, the parked returning minimum (pend) and "nothing before a 2nd neighbour" are as there.
+    u32 gkey = SLAM_BOUND_IDLE, pend[1] = {0u};
+    auto exchange = [&](int c0) {
         u32 u1[4], u2[4];
         unite_lanes(u1, u2);
-        u32 own[1] = {mx_pick(u2, kg)}, init[1];
-        share_bound<1>(st.bound, qbase, N, own, init, gk, pend);
+        if (qbase < N) {
+            const u32 own = mx_pick(u2, kg);
+            asm volatile("" ::"v"(pend[0]));
+            const u32 g = __hip_atomic_load(&st.bound[qbase], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (own < g && own < SLAM_MX_BOUND_LIMIT) pend[0] = atomicMin(&st.bound[qbase], own);
+            gkey = g;
+        }
 #pragma unroll
         for (int tt = 0; tt < 4; tt++) {
-            const u32 g = (u32)__shfl((int)gk[0], tt * 16 + col, 64);
-            ub[tt] = min(ub[tt], min(g, u2[tt] >> SLAM_KEY_IDX_BITS));
+            // the united pair comes from this worker's earlier chunks, rows below c0: ties against it lose.  Another worker's
+            // key excludes ties only when ITS row is below c0 - the row is tested, not inferred from the ticket order: a worker
+            // can publish from a later chunk before a slower one reads the bound for an earlier chunk
+            const u32 g = (u32)__shfl((int)gkey, tt * 16 + col, 64);
+            const u32 gx = g < SLAM_MX_BOUND_LIMIT ? (g >> SLAM_KEY_IDX_BITS) + ((g & SLAM_KEY_IDX_MASK) < (u32)c0 ? 0u : 1u)
+                                                   : SLAM_KEY_NONE >> SLAM_KEY_IDX_BITS;
+            x[tt] = min(x[tt], min(gx, u2[tt] >> SLAM_KEY_IDX_BITS));
             set_threshold(tt);
         }
     };
@@ -163,7 +191,7 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
     while (ci < nchunks) {
         const int c0 = tbl[ci], c1 = tbl[ci + 1];
         uint4 nx = load_stage(c0, c1);
-        exchange();
+        exchange(c0);
         store_stage(0, nx);
         __syncthreads();
         int buf = 0;
@@ -175,8 +203,8 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
             else if (tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int ng = __builtin_amdgcn_readfirstlane(min(SLAM_MX_STAGE / 16, (c1 - s0 + 15) >> 4));
             const uint4* tp = tile[buf];
-            const int lim = s1 > c1 ? c1 : 0x7fffffff;           // rows past the chunk: only in the last stage of the last chunk
-            bool fired = false;                                  // wave-uniform: some group of this stage took the update path
+            const bool ragged = s1 > c1;                        // rows past the chunk: only in the last stage of the last chunk
+            u32 fired = 0;                                       // wave-uniform: the tiles that took the update path in this stage
             for (int g = 0; g < ng; g++) {
                 const uint4 a0 = tp[g * 128 + lane], a1 = tp[g * 128 + 64 + lane];
                 mx_v4f acc[4];
@@ -195,35 +223,46 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
                 m = max(max(m, __float_as_int(acc[2][3])), p[3]);
                 m = max(m, __float_as_int(acc[3][3]));
                 if (__builtin_expect(__ballot(m >= 0) != 0ull, 0)) {
-                    // D = dot + 2 d2 - 256, so the distance (256 - dot) / 2 is d2 - D / 2 (D is even); rows past the chunk -
-                    // the zero rows of a short stage - never enter.  Only the tiles that hold a candidate are updated (wave-
-                    // uniform branches on the tile's own maximum), and only those get a new threshold
+                    // D = dot + 2 e - 256, so the distance (256 - dot) / 2 is e - D / 2 (D is even).  Only the tiles that hold a
+                    // candidate are updated (wave-uniform branches on the tile's own maximum), and only those get a new
+                    // threshold: below the lane's own 2nd-best, whose row is below every row the lane has still to see
                     const int row0 = s0 + g * 16 + 4 * kg;
-                    fired = true;
 #pragma unroll
                     for (int tt = 0; tt < 4; tt++) {
                         if (__ballot(max(p[tt], __float_as_int(acc[tt][3])) >= 0) == 0ull) continue;
-                        const u32 base = (d2[tt] << SLAM_KEY_IDX_BITS) + (u32)row0;
+                        fired |= 1u << tt;
+                        // key = (e - D / 2) << 23 | row with e = x - 1: base + r + (-D << 22), exact modulo 2^32 also for x = 0
+                        const u32 base = (x[tt] << SLAM_KEY_IDX_BITS) + (u32)(row0 - (1 << SLAM_KEY_IDX_BITS));
+                        if (ragged) {                            // the zero rows of a short stage never enter
 #pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            // key = (d2 - D / 2) << 23 | row, D even: base + r + (-D << 22)
-                            u32 key = base + (u32)r + ((u32)(int)(-acc[tt][r]) << (SLAM_KEY_IDX_BITS - 1));
-                            key = row0 + r < lim ? key : SLAM_KEY_NONE;
-                            b2[tt] = umed3(b1[tt], b2[tt], key);
-                            b1[tt] = min(b1[tt], key);
+                            for (int r = 0; r < 4; r++) {
+                                u32 key = base + (u32)r + ((u32)(int)(-acc[tt][r]) << (SLAM_KEY_IDX_BITS - 1));
+                                key = row0 + r < c1 ? key : SLAM_KEY_NONE;
+                                b2[tt] = umed3(b1[tt], b2[tt], key);
+                                b1[tt] = min(b1[tt], key);
+                            }
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 4; r++) {
+                                const u32 key = base + (u32)r + ((u32)(int)(-acc[tt][r]) << (SLAM_KEY_IDX_BITS - 1));
+                                b2[tt] = umed3(b1[tt], b2[tt], key);
+                                b1[tt] = min(b1[tt], key);
+                            }
                         }
+                        x[tt] = min(x[tt], b2[tt] >> SLAM_KEY_IDX_BITS);
                         set_threshold(tt);
                     }
                 }
             }
-            if (fired) {   // once per stage in which a key changed: the threshold of the query's four lanes together
-                u32 u1[4], u2[4];
-                unite_lanes(u1, u2);
+            // once per stage in which a key changed, for the tiles it changed in: the threshold of the query's four lanes together
+            // (their rows lie in this stage or before it, below every row still to come)
 #pragma unroll
-                for (int tt = 0; tt < 4; tt++) {
-                    ub[tt] = min(ub[tt], u2[tt] >> SLAM_KEY_IDX_BITS);
-                    set_threshold(tt);
-                }
+            for (int tt = 0; tt < 4; tt++) {
+                if (!(fired >> tt & 1u)) continue;
+                u32 u1, u2;
+                unite_tile(tt, u1, u2);
+                x[tt] = min(x[tt], u2 >> SLAM_KEY_IDX_BITS);
+                set_threshold(tt);
             }
             if (more) store_stage(buf ^ 1, nx);
             __syncthreads();
@@ -235,6 +274,8 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
     u32 u1[4], u2[4];
     unite_lanes(u1, u2);
     const u32 f1[1] = {mx_pick(u1, kg)}, f2[1] = {mx_pick(u2, kg)};
+    // the epilogue's skip test takes a DISTANCE that bounds the final 2nd-best one, or the idle pattern when there is none
+    const u32 gk[1] = {gkey < SLAM_MX_BOUND_LIMIT ? gkey >> SLAM_KEY_IDX_BITS : SLAM_BOUND_IDLE};
     bf_top2_epilogue<1, true>(st, bx, tid, lane, qbase, false, false, f1, f2, gk, pend, N, (int)gridDim.y, train_base, out_idx,
                               out_dist, sel, s_last);
 }
