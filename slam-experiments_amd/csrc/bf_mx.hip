@@ -1,7 +1,8 @@
 // bf_mx.hip — the top-2 Hamming search of large searches on the MATRIX cores of gfx950 (MI355X), as a dot product of
 // +-1 vectors in FP4.  Same results as bf_top2_kernel (bf_hamming.hip), bit for bit; see DESIGN.md §3c.
 //
-//   * encoding: descriptor bit 1 -> FP4 (E2M1) +1.0 (nibble 0x2), bit 0 -> -1.0 (nibble 0xA).  For 256-bit rows a, b:
+//   * encoding: descriptor bit 1 -> FP4 (E2M1) -1.0 (nibble 0xA), bit 0 -> +1.0 (nibble 0x2): the bit lands in the nibble's sign
+//     bit as it stands (a product of two +-1 values does not change when both signs flip, so no NOT).  For 256-bit rows a, b:
 //         hamming(a, b) = (256 - <a+-, b+->) / 2
 //     Every product is +-1 and every partial sum an integer of magnitude <= 256 + 1022 (the threshold rides in the
 //     accumulator, below): the f32 accumulator is exact.  Which bit goes to which K position does not matter as long as
@@ -34,6 +35,9 @@
 //         or above, the idle pattern 0x7F7F7F7F included, reads as "nobody has published" - and the epilogue is handed a
 //         distance or the idle pattern as before).  The row is TESTED: a worker can finish a later chunk and publish from it
 //         before a slower one reads the bound for an earlier chunk, and a tie against such a key can win.
+//       - the same, with the first row of the stage to come in place of c0, at the early exchanges (SLAM_MX_EARLY): after the
+//         stage at whose end the block has scanned 128, 256 or 512 rows since launch, unless a chunk start follows anyway.  Until
+//         then a worker knows only its own rows.  That stage start is the first row the lane has still to see.
 //     Why this is exact: a candidate is dropped only if some known 2nd-best key K has dist(K) < dist, or dist(K) == dist and
 //     row(K) < row.  Its key then exceeds K, and K is at least the final 2nd key, so the candidate is not in the final top-2.
 //     (The code keeps x = e + 1, which is what a key's distance field gives without a subtract and never goes below 0.)
@@ -49,19 +53,24 @@
 
 #define SLAM_MX_STAGE 128        // train rows per LDS stage: 16 KiB expanded, two stages per block
 #define SLAM_MX_BOUND_LIMIT 0x7F000000u   // bound[] of this kernel holds keys below this; at or above (the idle pattern): nobody has published
+// Early bound exchanges: bit k set = the workers of a query block also exchange after the stage at whose end a block has scanned
+// 128 k rows since launch (k < 32).  Until its first exchange with news in it a worker knows only its own rows, and nearly every
+// tile of its first chunk takes the update path; the rule is in the file header, the measured choice in DESIGN.md 3c.
+#define SLAM_MX_EARLY 0x16u      // after 128, 256 and 512 rows
+#define SLAM_MX_UNROLL 4         // groups of 16 rows per trip of the scan loop
 #define SLAM_MX_RESIDENT 4       // blocks of bf_top2_mx_kernel a CU holds at once (the plan describe counts on it; launches ask)
 
 typedef int mx_v8i __attribute__((ext_vector_type(8)));
 typedef float mx_v4f __attribute__((ext_vector_type(4)));
 
-// 32 descriptor bits -> 32 FP4 elements (+1.0 for a set bit, -1.0 for a clear one): nibble n of word w = bit 4n + w
+// 32 descriptor bits -> 32 FP4 elements (-1.0 for a set bit, +1.0 for a clear one: the bit is the sign bit as it stands): nibble
+// n of word w = bit 4n + w
 __device__ __forceinline__ uint4 mx_expand(u32 x) {
-    const u32 n = ~x;
     uint4 r;
-    r.x = ((n << 3) & 0x88888888u) | 0x22222222u;
-    r.y = ((n << 2) & 0x88888888u) | 0x22222222u;
-    r.z = ((n << 1) & 0x88888888u) | 0x22222222u;
-    r.w = (n & 0x88888888u) | 0x22222222u;
+    r.x = ((x << 3) & 0x88888888u) | 0x22222222u;
+    r.y = ((x << 2) & 0x88888888u) | 0x22222222u;
+    r.z = ((x << 1) & 0x88888888u) | 0x22222222u;
+    r.w = (x & 0x88888888u) | 0x22222222u;
     return r;
 }
 
@@ -188,6 +197,7 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
     if (tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     int ci = __builtin_amdgcn_readfirstlane((int)s_ticket);
+    int scanned = 0;                                             // wave-uniform: the rows this block has scanned since launch
     while (ci < nchunks) {
         const int c0 = tbl[ci], c1 = tbl[ci + 1];
         uint4 nx = load_stage(c0, c1);
@@ -205,7 +215,7 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
             const uint4* tp = tile[buf];
             const bool ragged = s1 > c1;                        // rows past the chunk: only in the last stage of the last chunk
             u32 fired = 0;                                       // wave-uniform: the tiles that took the update path in this stage
-            for (int g = 0; g < ng; g++) {
+            auto group = [&](int g) {
                 const uint4 a0 = tp[g * 128 + lane], a1 = tp[g * 128 + 64 + lane];
                 mx_v4f acc[4];
 #pragma unroll
@@ -226,7 +236,9 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
                     // D = dot + 2 e - 256, so the distance (256 - dot) / 2 is e - D / 2 (D is even).  Only the tiles that hold a
                     // candidate are updated (wave-uniform branches on the tile's own maximum), and only those get a new
                     // threshold: below the lane's own 2nd-best, whose row is below every row the lane has still to see
-                    const int row0 = s0 + g * 16 + 4 * kg;
+                    // (the group's first row is taken from the scalar side here: as a per-lane value it would be carried, and
+                    // advanced, through every group that does not fire)
+                    const int row0 = __builtin_amdgcn_readfirstlane(s0 + g * 16) + 4 * kg;
 #pragma unroll
                     for (int tt = 0; tt < 4; tt++) {
                         if (__ballot(max(p[tt], __float_as_int(acc[tt][3])) >= 0) == 0ull) continue;
@@ -253,7 +265,18 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
                         set_threshold(tt);
                     }
                 }
+            };
+            // SLAM_MX_UNROLL groups per trip share one LDS address (ds_read_b128 takes the rest as an immediate offset); the
+            // barriers keep a group's operand reads behind the group before it, or the registers of four waves per SIMD run out
+            int g = 0;
+            for (; g + SLAM_MX_UNROLL <= ng; g += SLAM_MX_UNROLL) {
+#pragma unroll
+                for (int k = 0; k < SLAM_MX_UNROLL; k++) {
+                    group(g + k);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
+            for (; g < ng; g++) group(g);
             // once per stage in which a key changed, for the tiles it changed in: the threshold of the query's four lanes together
             // (their rows lie in this stage or before it, below every row still to come)
 #pragma unroll
@@ -264,6 +287,10 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
                 x[tt] = min(x[tt], u2 >> SLAM_KEY_IDX_BITS);
                 set_threshold(tt);
             }
+            // an early exchange (SLAM_MX_EARLY): per wave, no barrier; every row still to come is at or above s1.  Not after a
+            // chunk's last stage: the chunk-start exchange follows anyway
+            scanned += min(s1, c1) - s0;
+            if (more && scanned < 32 * SLAM_MX_STAGE && (SLAM_MX_EARLY >> (scanned / SLAM_MX_STAGE) & 1u)) exchange(s1);
             if (more) store_stage(buf ^ 1, nx);
             __syncthreads();
             buf ^= 1;
