@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from hamming_families import ref_radius
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -16,29 +17,6 @@ RADII = (-1.0, float("nan"), 0.0, 40.0, 64.5, 96.0, 104.0, 128.0, 255.0, 256.0, 
 
 def rand_desc(rng, n):
     return rng.integers(0, 256, (n, 32), dtype=np.uint8)
-
-
-def ref_radius(q, t, radii, step=16384):
-    """{radius: (offsets, idx, dist)} by brute force over the full distance matrix, in chunks of train rows."""
-    from slamhip import radius_threshold
-
-    ths = {r: radius_threshold(r) for r in radii}
-    parts = {r: [] for r in radii}
-    for a in range(0, t.shape[0], step):
-        d = oracle.hamming_matrix_np(q, t[a:a + step])
-        for r, th in ths.items():
-            qi, ti = np.nonzero(d < th)
-            parts[r].append((qi.astype(np.int64), (ti + a).astype(np.int32), d[qi, ti].astype(np.int32)))
-    out = {}
-    for r in radii:
-        qi = np.concatenate([p[0] for p in parts[r]]) if parts[r] else np.zeros(0, np.int64)
-        ti = np.concatenate([p[1] for p in parts[r]]) if parts[r] else np.zeros(0, np.int32)
-        di = np.concatenate([p[2] for p in parts[r]]) if parts[r] else np.zeros(0, np.int32)
-        order = np.lexsort((ti, di, qi))
-        off = np.zeros(q.shape[0] + 1, np.int64)
-        np.cumsum(np.bincount(qi, minlength=q.shape[0]), out=off[1:])
-        out[r] = (off, ti[order], di[order])
-    return out
 
 
 def assert_csr(got, want, what):

@@ -4,6 +4,7 @@ on the host and the device paths, over fuzzed shapes and the edges of the window
 import numpy as np
 import pytest
 
+from hamming_families import ref_window
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -13,35 +14,6 @@ NONE_IDX, NONE_DIST = -1, np.iinfo(np.int32).max
 
 def rand_desc(rng, n):
     return rng.integers(0, 256, (n, 32), dtype=np.uint8)
-
-
-def ref_window(q, t, qxy, txy, radius, k, rows=None):
-    """(idx, dist) int32 [len(rows), k] of the k nearest in-window train rows of each query row, by definition."""
-    n, m = q.shape[0], t.shape[0]
-    rows = np.arange(n) if rows is None else np.asarray(rows)
-    qxy, txy = np.asarray(qxy, np.float32).reshape(-1, 2), np.asarray(txy, np.float32).reshape(-1, 2)
-    r = np.broadcast_to(np.asarray(radius, np.float32), (m,))
-    idx = np.full((rows.size, k), NONE_IDX, np.int32)
-    dist = np.full((rows.size, k), NONE_DIST, np.int32)
-    if m == 0:
-        return idx, dist
-    step = max(1, (1 << 22) // m)
-    for a in range(0, rows.size, step):
-        rr = rows[a:a + step]
-        with np.errstate(invalid="ignore"):
-            w = ((np.abs(qxy[rr, 0][:, None] - txy[None, :, 0]) <= r[None, :])
-                 & (np.abs(qxy[rr, 1][:, None] - txy[None, :, 1]) <= r[None, :]))
-        cols = np.flatnonzero(w.any(0))
-        if cols.size == 0:
-            continue
-        d = oracle.hamming_matrix_np(q[rr], t[cols]).astype(np.int64)
-        key = np.where(w[:, cols], (d << 23) | cols[None, :], np.int64(1) << 40)
-        top = np.sort(key, axis=1, kind="stable")[:, :k]
-        ok = top < (np.int64(1) << 40)
-        kk = top.shape[1]
-        idx[a:a + rr.size, :kk] = np.where(ok, top & ((1 << 23) - 1), NONE_IDX)
-        dist[a:a + rr.size, :kk] = np.where(ok, top >> 23, NONE_DIST)
-    return idx, dist
 
 
 def run_device(ctx, q, t, qxy, txy, radius, k, cells=0):
