@@ -20,6 +20,8 @@
  *                          (frontend.py:298-393)
  *   slam_tv_*              cv2.findEssentialMat / recoverPose / triangulatePoints behind
  *                          pose_estimation_2d2d and triangulation (utils.py:10-55)
+ *   slam_orb_*             cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26),
+ *                          called from Frontend._detect_features (frontend.py:245)
  *   slam_comm_*            no reference counterpart (the reference is single
  *                          process); RCCL all-gather of per-shard top-2 rows
  *
@@ -466,6 +468,55 @@ SLAM_API int slam_tv_recover_pose_f64(slam_ctx* ctx, int64_t B, const int32_t* d
  * cameras (a two-dimensional null space) some unit vector of it. */
 SLAM_API int slam_tv_triangulate_f64(slam_ctx* ctx, int64_t N, const double* d_P1, const double* d_P2,
                                      const double* d_x1, const double* d_x2, double* d_X, double* d_w);
+
+/* ---- ORB feature extraction (orb.hip): cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26), which
+ * Frontend._detect_features calls on every frame with a mask (frontend.py:245) -------------------------------------------
+ * A batch of B grayscale u8 images [B,H,W] (any W) goes through the integer-exact specification of DESIGN.md 4d: an L-level
+ * pyramid resampled from level 0, FAST-9/16 with score and strict 3x3 non-maximum suppression, integer Harris ranking with
+ * a per-level quota under the total order (R descending, y ascending, x ascending), a 32-bin intensity-centroid
+ * orientation decided by cross-product signs, and 256 steered comparisons on the binomially blurred level.  PARITY
+ * UNPINNED against cv2.ORB (absent here, and its learned pattern is not shipped): the result is a pure function of the
+ * arguments and equals the numpy restatement of the specification bit for bit.  The host computes the level sizes, the
+ * quotas and the steered pattern table once and passes them in, so every party sees the same numbers:
+ *   h_level_w / h_level_h  int32 [L], level 0 = (W, H), each level no larger than the one before, all >= 1
+ *   h_quota                int32 [L], keypoints kept per level; N_max = their sum (<= SLAM_ORB_MAX_FEATURES)
+ *   table                  int8 [32,256,4] = (ax, ay, bx, by) per orientation bin, every coordinate in [-15, 15]
+ * Four launches per call, whatever B and L. */
+#define SLAM_ORB_MAX_LEVELS 16
+#define SLAM_ORB_MAX_SIDE 8192
+#define SLAM_ORB_MAX_BATCH 65535
+#define SLAM_ORB_MAX_FEATURES 65536      /* the largest quota sum (and B * sum <= 2^28) */
+#define SLAM_ORB_TABLE_BYTES 32768
+
+/* Workspace size and layout for slam_orb_extract_u8 (feature_detectors.py:18-26 / frontend.py:245), no device needed.
+ * *bytes = the size to allocate.  h_layout (optional) uint64 [4 + 6 L]: {offset of image 0's block, stride between
+ * image blocks, offset of the int32 [B,16] candidate counts, offset of the selection scratch}, then per level
+ * {level image, blurred level, score map, candidate list (offsets inside an image block), row pitch in bytes of the
+ * three planes (a multiple of 4), capacity of the candidate list}.  A candidate is 16 bytes: int64 R, uint32 x | y << 16,
+ * uint32 0.  Argument errors as below. */
+SLAM_API int slam_orb_workspace(int64_t B, int64_t H, int64_t W, int L, const int32_t* h_level_w, const int32_t* h_level_h,
+                                int64_t n_max, uint64_t* bytes, uint64_t* h_layout);
+
+/* OrbFeatureDetector.detect_and_compute (feature_detectors.py:18-26 / frontend.py:245) for B device-resident images.
+ * d_mask (optional) u8 [B,H,W] if mask_batched else [H,W], non-zero = allowed (utils.py:58-74); a keypoint is dropped
+ * when its level-0 position is masked out.  Outputs, rows ordered by (level, rank): d_count int32 [B]; d_kp int32
+ * [B,N_max,4] = (x, y, level, bin) in level coordinates; d_resp int64 [B,N_max] = R; d_desc u8 [B,N_max,32]; slots past
+ * the count are zero.  d_workspace: at least slam_orb_workspace bytes, 16-byte aligned like d_table, d_kp, d_resp, d_desc.
+ * Asynchronous on the ctx stream.  SLAM_ERR_INVALID, with nothing launched and no output written: null pointers, B outside
+ * [0, 65535], H or W outside [1, 8192], L outside [1, 16], level sizes that break the rules above, a negative quota, a
+ * quota sum above SLAM_ORB_MAX_FEATURES, fast_threshold outside [1, 254], a workspace that is too small or misaligned.
+ * B = 0 is not an error and does nothing. */
+SLAM_API int slam_orb_extract_u8(slam_ctx* ctx, const uint8_t* d_images, int64_t B, int64_t H, int64_t W, const uint8_t* d_mask,
+                                 int mask_batched, int L, const int32_t* h_level_w, const int32_t* h_level_h,
+                                 const int32_t* h_quota, int fast_threshold, const int8_t* d_table, void* d_workspace,
+                                 uint64_t workspace_bytes, int32_t* d_count, int32_t* d_kp, int64_t* d_resp, uint8_t* d_desc);
+
+/* The same call on host buffers (feature_detectors.py:18-26 / frontend.py:245): one upload, four launches, one download,
+ * one wait; workspace and staging are the context's (the call holds its lock). */
+SLAM_API int slam_orb_extract_u8_host(slam_ctx* ctx, const uint8_t* h_images, int64_t B, int64_t H, int64_t W,
+                                      const uint8_t* h_mask, int mask_batched, int L, const int32_t* h_level_w,
+                                      const int32_t* h_level_h, const int32_t* h_quota, int fast_threshold,
+                                      const int8_t* h_table, int32_t* h_count, int32_t* h_kp, int64_t* h_resp, uint8_t* h_desc);
 
 /* ---- per-frame calls on caller-owned host buffers: one upload, one download, one wait (frame-sized: zero-copy, polled) ---- */
 /* BruteForceFeatureMatcher.match (feature_matchers.py:36-44; cv2.BFMatcher.match + the min-distance filter) in

@@ -34,6 +34,13 @@ from .matching import (  # noqa: F401
     window_match_arrays,
     window_match_filtered,
 )
+from .orb import (  # noqa: F401
+    OrbExtractor,
+    OrbFeatureDetector,
+    OrbParams,
+    OrbResult,
+    orb_extract_arrays,
+)
 from .pose_graph import (  # noqa: F401
     loop_edges_from_two_view,
     optimize_pose_graph,

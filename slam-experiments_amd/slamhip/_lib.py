@@ -118,6 +118,11 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p]),
     "slam_pg_optimize_host_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                           c_double, c_double, c_int, c_void_p, c_void_p]),
+    "slam_orb_workspace": (c_int, [c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, POINTER(c_uint64), c_void_p]),
+    "slam_orb_extract_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_orb_extract_u8_host": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "slam_bf_match_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_double,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "slam_index_errors": (c_int, [c_void_p, POINTER(c_int64)]),
