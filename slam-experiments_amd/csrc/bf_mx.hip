@@ -12,7 +12,7 @@
 //     over K = 128 bits; two of them per 256-bit pair.  A wave holds 64 queries as the B operands of four 16-query tiles
 //     (2 K-halves x 4 VGPRs each: 32 VGPRs, expanded once from the 32-byte rows); per 16 train rows it issues 8 MFMAs.
 //   * train rows reach the A operand through an LDS stage shared by the block's four waves: the block loads 128 compact
-//     rows (4 KiB, one 16-byte load per thread), expands them (8 VALU per word) straight into the operand order - group
+//     rows (4 KiB, one 16-byte load per thread), expands them (7 VALU per word) straight into the operand order - group
 //     of 16 rows = [K-half][lane] x 16 bytes, so a lane's operand is one conflict-free ds_read_b128 - double buffered,
 //     one barrier per stage.  The compact train set (2 MiB at 65536 rows) stays what sits in the L2s.
 //   * selection: the accumulator starts at C = 2 e - 256 (e: the lane's inclusive threshold distance for the tile's query), so
@@ -42,12 +42,24 @@
 //     row(K) < row.  Its key then exceeds K, and K is at least the final 2nd key, so the candidate is not in the final top-2.
 //     (The code keeps x = e + 1, which is what a key's distance field gives without a subtract and never goes below 0.)
 //     tests/test_mx_ties_cpu.py restates these rules in numpy and drives them over adversarial schedules.
+//   * row gates: a tile that takes the update path keys and merges, of a lane's four rows, only those at which SOME lane of the
+//     tile passes (one compare and one wave-uniform branch per row; on random rows fewer than two of the four).  Why this is
+//     exact: a skipped row has D < 0, a distance at or above x, in every lane of the tile, so by the rules above it is not in
+//     the final top-2 - the argument that lets a group that does not fire skip all of its rows.  Fewer losing rows now enter a
+//     lane's pair, so its 2nd-best key, x, the united pairs and the published keys can be larger than without the gates; they
+//     are still keys of real rows, hence valid bounds, and the final tables do not move (tests/test_mx_rowgate_cpu.py asserts
+//     both).  The test for rows past the chunk runs only in the groups that the unrolled trips of whole groups leave over.
+//     Open: where nearly every row passes (a worker's first stages, and so the short searches at the corners of bf_mx_auto) the
+//     four gates are pure cost, 1-3 % there; skipping them until the first exchange with news in it has not been tried.
+//   * staging: the load address is a scalar row base plus the thread's fixed offset, the rows are tested against the chunk end
+//     only in a stage that is not whole, and each expanded word is one shift and one v_and_or_b32 (28 per thread and stage).
 //   * plan: the queue plan of bf_top2_kernel<1, true, true> with tickets drawn per BLOCK: grid = (query blocks, workers),
 //     the workers of a query block draw chunks of the boundary table by ticket, exchange the 2nd-best key through
 //     bound[] at every chunk, merge with the two returning atomic minima and the last arriver decodes (bf_common.h).
 #include "internal.h"
 #include <vector>
 #include <atomic>
+#include <type_traits>
 
 #include "bf_common.h"
 
@@ -64,7 +76,8 @@ typedef int mx_v8i __attribute__((ext_vector_type(8)));
 typedef float mx_v4f __attribute__((ext_vector_type(4)));
 
 // 32 descriptor bits -> 32 FP4 elements (-1.0 for a set bit, +1.0 for a clear one: the bit is the sign bit as it stands): nibble
-// n of word w = bit 4n + w
+// n of word w = bit 4n + w.  The query rows go through this form; the kernel's staging has the same map as one shift and one
+// inline-asm v_and_or_b32 per word (its `expand`): a change of the map changes both.
 __device__ __forceinline__ uint4 mx_expand(u32 x) {
     uint4 r;
     r.x = ((x << 3) & 0x88888888u) | 0x22222222u;
@@ -103,6 +116,7 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int kg = lane >> 4, col = lane & 15;
+    const u32 lanek = (u32)(4 * kg - (1 << SLAM_KEY_IDX_BITS));  // the lane's first row in a group of 16, less the 2^23 a key built from x owes
     const int bx = ((int)blockIdx.x + (int)blockIdx.y) % (int)gridDim.x;
     const int qbase = bx * 256 + wave * 64 + lane;              // the lane's query in the epilogue (and in the bound exchange)
 
@@ -181,16 +195,31 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
     // staging: thread tid carries half (tid & 1) of row (tid >> 1) of a stage, i.e. the source words 4 h .. 4 h + 3, which
     // become the operand words of lanes 16 g + (row & 15), g = 0..3, of K-half h in the row's group of 16
     const int srow = tid >> 1, sh = tid & 1;
+    // The load address is a wave-uniform row base (scalar side) plus the thread's fixed offset, and rows are tested against the
+    // chunk end only in a stage that is not whole: the table's chunks are whole stages except at the end of the train set.
     auto load_stage = [&](int s, int c1) -> uint4 {
-        const int row = s + srow;
-        return row < c1 ? t[2 * (size_t)row + sh] : make_uint4(0, 0, 0, 0);
+        const uint4* ts = t + 2 * (size_t)s;
+        if (s + SLAM_MX_STAGE <= c1) return ts[(u32)tid];
+        return s + srow < c1 ? ts[(u32)tid] : make_uint4(0, 0, 0, 0);
     };
+    // mx_expand with one v_and_or_b32 per output word.  A VOP3 instruction of gfx950 reads at most one scalar or literal operand,
+    // so the compiler, given both masks as constants, splits each into an AND and an OR: the OR mask is held in a VGPR here.
+    const u32 fill = 0x22222222u;
+    auto expand = [&](u32 v) -> uint4 {
+        uint4 r;
+        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r.x) : "v"(v << 3), "s"(0x88888888u), "v"(fill));
+        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r.y) : "v"(v << 2), "s"(0x88888888u), "v"(fill));
+        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r.z) : "v"(v << 1), "s"(0x88888888u), "v"(fill));
+        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r.w) : "v"(v), "s"(0x88888888u), "v"(fill));
+        return r;
+    };
+    uint4* const dst0 = tile[0] + (srow >> 4) * 128 + sh * 64 + (srow & 15);
     auto store_stage = [&](int b, uint4 v) {
-        uint4* dst = tile[b] + (srow >> 4) * 128 + sh * 64 + (srow & 15);
-        dst[0] = mx_expand(v.x);
-        dst[16] = mx_expand(v.y);
-        dst[32] = mx_expand(v.z);
-        dst[48] = mx_expand(v.w);
+        uint4* dst = dst0 + b * (SLAM_MX_STAGE * 8);
+        dst[0] = expand(v.x);
+        dst[16] = expand(v.y);
+        dst[32] = expand(v.z);
+        dst[48] = expand(v.w);
     };
 
     u32* const cursor = st.cursor + (size_t)(4 * bx) * SLAM_CURSOR_STRIDE;
@@ -213,9 +242,8 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
             else if (tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int ng = __builtin_amdgcn_readfirstlane(min(SLAM_MX_STAGE / 16, (c1 - s0 + 15) >> 4));
             const uint4* tp = tile[buf];
-            const bool ragged = s1 > c1;                        // rows past the chunk: only in the last stage of the last chunk
             u32 fired = 0;                                       // wave-uniform: the tiles that took the update path in this stage
-            auto group = [&](int g) {
+            auto group = [&](int g, auto rag) {
                 const uint4 a0 = tp[g * 128 + lane], a1 = tp[g * 128 + 64 + lane];
                 mx_v4f acc[4];
 #pragma unroll
@@ -238,28 +266,23 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
                     // threshold: below the lane's own 2nd-best, whose row is below every row the lane has still to see
                     // (the group's first row is taken from the scalar side here: as a per-lane value it would be carried, and
                     // advanced, through every group that does not fire)
-                    const int row0 = __builtin_amdgcn_readfirstlane(s0 + g * 16) + 4 * kg;
+                    const u32 rowk = (u32)__builtin_amdgcn_readfirstlane(s0 + g * 16) + lanek;
 #pragma unroll
                     for (int tt = 0; tt < 4; tt++) {
                         if (__ballot(max(p[tt], __float_as_int(acc[tt][3])) >= 0) == 0ull) continue;
                         fired |= 1u << tt;
                         // key = (e - D / 2) << 23 | row with e = x - 1: base + r + (-D << 22), exact modulo 2^32 also for x = 0
-                        const u32 base = (x[tt] << SLAM_KEY_IDX_BITS) + (u32)(row0 - (1 << SLAM_KEY_IDX_BITS));
-                        if (ragged) {                            // the zero rows of a short stage never enter
+                        const u32 base = (x[tt] << SLAM_KEY_IDX_BITS) + rowk;
+                        // row gates: of a lane's four rows only those at which SOME lane of the tile passes are keyed and merged
+                        // (wave-uniform branches); see "row gates" in the file header
 #pragma unroll
-                            for (int r = 0; r < 4; r++) {
-                                u32 key = base + (u32)r + ((u32)(int)(-acc[tt][r]) << (SLAM_KEY_IDX_BITS - 1));
-                                key = row0 + r < c1 ? key : SLAM_KEY_NONE;
-                                b2[tt] = umed3(b1[tt], b2[tt], key);
-                                b1[tt] = min(b1[tt], key);
-                            }
-                        } else {
-#pragma unroll
-                            for (int r = 0; r < 4; r++) {
-                                const u32 key = base + (u32)r + ((u32)(int)(-acc[tt][r]) << (SLAM_KEY_IDX_BITS - 1));
-                                b2[tt] = umed3(b1[tt], b2[tt], key);
-                                b1[tt] = min(b1[tt], key);
-                            }
+                        for (int r = 0; r < 4; r++) {
+                            if (__ballot(__float_as_int(acc[tt][r]) >= 0) == 0ull) continue;
+                            u32 key = base + (u32)r + ((u32)(int)(-acc[tt][r]) << (SLAM_KEY_IDX_BITS - 1));
+                            if constexpr (decltype(rag)::value)   // the zero rows of a short stage never enter
+                                key = (int)rowk + r < c1 - (1 << SLAM_KEY_IDX_BITS) ? key : SLAM_KEY_NONE;
+                            b2[tt] = umed3(b1[tt], b2[tt], key);
+                            b1[tt] = min(b1[tt], key);
                         }
                         x[tt] = min(x[tt], b2[tt] >> SLAM_KEY_IDX_BITS);
                         set_threshold(tt);
@@ -267,16 +290,21 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
                 }
             };
             // SLAM_MX_UNROLL groups per trip share one LDS address (ds_read_b128 takes the rest as an immediate offset); the
-            // barriers keep a group's operand reads behind the group before it, or the registers of four waves per SIMD run out
+            // barriers keep a group's operand reads behind the group before it, or the registers of four waves per SIMD run out.
+            //
+            // The unrolled trips take whole groups only.  What they leave of a stage runs in the loop below, with the test for
+            // rows past the chunk: up to seven groups, the whole ones among them too (correct there, only slower), and only in
+            // a short stage - the last stage of the train set.
+            const int nwhole = __builtin_amdgcn_readfirstlane(min(SLAM_MX_STAGE / 16, (c1 - s0) >> 4));
             int g = 0;
-            for (; g + SLAM_MX_UNROLL <= ng; g += SLAM_MX_UNROLL) {
+            for (; g + SLAM_MX_UNROLL <= nwhole; g += SLAM_MX_UNROLL) {
 #pragma unroll
                 for (int k = 0; k < SLAM_MX_UNROLL; k++) {
-                    group(g + k);
+                    group(g + k, std::false_type{});
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            for (; g < ng; g++) group(g);
+            for (; g < ng; g++) group(g, std::true_type{});
             // once per stage in which a key changed, for the tiles it changed in: the threshold of the query's four lanes together
             // (their rows lie in this stage or before it, below every row still to come)
 #pragma unroll
