@@ -53,6 +53,19 @@
 //     four gates are pure cost, 1-3 % there; skipping them until the first exchange with news in it has not been tried.
 //   * staging: the load address is a scalar row base plus the thread's fixed offset, the rows are tested against the chunk end
 //     only in a stage that is not whole, and each expanded word is one shift and one v_and_or_b32 (28 per thread and stage).
+//   * the scan loop overlaps a wave's own serial chain with its MFMAs (DESIGN.md 3c "Operand reads and staging behind the MFMAs"):
+//       - operand reads: whole groups run in trips; inside a trip the A operands rotate through three register quads - the first
+//         K-half of group g + 1 is read before the MFMAs of group g, its second K-half into the quad that g's four first-half
+//         MFMAs free - so the LDS latency of a group's operands runs behind the MFMAs and the fold of the group before it.  The
+//         last group of a trip reads nothing ahead, so no read leaves the stage's own buffer or comes before its barrier.
+//       - staging: a stage that another follows (always a whole stage) runs as ONE trip of eight groups, and its groups 4-7 each
+//         expand and store one of the thread's four source words of the next stage between their second-half MFMAs, in issue
+//         slots the pipe-paced MFMAs leave empty.  The other buffer is free from the barrier that opened the stage; each word is
+//         loaded one group before it is used, so no staged row is held in registers through the scan.  A chunk's first stage is
+//         stored at the chunk start as before; a chunk's last stage runs trips of four and stores nothing.
+//       - registers (126 of the 128 that four waves per SIMD leave; amdgpu_waves_per_eu holds the allocator to them): the third
+//         operand quad is paid for by x, which is no longer kept (threshold_x reads it back from the accumulator start in the
+//         update path), the staged row (a word at a time), and the lane's query and the group's row base, recomputed where used.
 //   * plan: the queue plan of bf_top2_kernel<1, true, true> with tickets drawn per BLOCK: grid = (query blocks, workers),
 //     the workers of a query block draw chunks of the boundary table by ticket, exchange the 2nd-best key through
 //     bound[] at every chunk, merge with the two returning atomic minima and the last arriver decodes (bf_common.h).
@@ -107,7 +120,7 @@ __device__ __forceinline__ u32 mx_pick(const u32 (&v)[4], int i) {
 
 // grid = (query blocks, workers).  Block (x, y) works for query block (x + y) mod grid.x: the workers of a query block are
 // spread over the XCDs, as in the VALU queue plan.
-__global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict__ q, int N, const uint4* __restrict__ t,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void bf_top2_mx_kernel(const uint4* __restrict__ q, int N, const uint4* __restrict__ t,
                                                          const int* __restrict__ tbl, bf_state st, int train_base,
                                                          int2* __restrict__ out_idx, int2* __restrict__ out_dist,
                                                          uint4* __restrict__ keep, int nchunks, bf_select sel) {
@@ -118,7 +131,13 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
     const int kg = lane >> 4, col = lane & 15;
     const u32 lanek = (u32)(4 * kg - (1 << SLAM_KEY_IDX_BITS));  // the lane's first row in a group of 16, less the 2^23 a key built from x owes
     const int bx = ((int)blockIdx.x + (int)blockIdx.y) % (int)gridDim.x;
-    const int qbase = bx * 256 + wave * 64 + lane;              // the lane's query in the epilogue (and in the bound exchange)
+    // the lane's query in the epilogue and in the bound exchange: worked out afresh at each of them (the empty asm hides that the
+    // value repeats), or it and the addresses built on it hold registers through the scan
+    auto lane_query = [&]() -> int {
+        int v = tid;
+        asm volatile("" : "+v"(v));
+        return bx * 256 + v;
+    };
 
     // the wave's 64 queries as B operands: tile tt, K-half h = words 4 h + (lane >> 4) of query 64 wave + 16 tt + (lane & 15)
     uint4 qb[4][2];
@@ -130,7 +149,7 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
 #pragma unroll
         for (int h = 0; h < 2; h++) qb[tt][h] = mx_expand(qw[(size_t)qi * 8 + h * 4 + kg]);
     }
-    if (keep && blockIdx.y == 0 && qbase < N) {                  // the caller wants the query rows left in device memory
+    if (const int qbase = lane_query(); keep && blockIdx.y == 0 && qbase < N) {   // the caller wants the query rows left in device memory
         keep[2 * (size_t)qbase] = q[2 * (size_t)qbase];
         keep[2 * (size_t)qbase + 1] = q[2 * (size_t)qbase + 1];
     }
@@ -138,17 +157,18 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
     // per tile: the lane's own top-2 over its rows and the EXCLUSIVE threshold distance x (a row passes when its distance is below
     // x; x - 1 is the inclusive threshold e of the file header), kept as what a key's distance field gives without a subtract.
     // The accumulator starts at 2 (x - 1) - 256.  x only ever falls.
-    u32 b1[4], b2[4], x[4];
+    // x is not kept: it is read back from the accumulator start where a tile's threshold moves (threshold_x), which is rare.
+    u32 b1[4], b2[4];
     mx_v4f cth[4];
-    auto set_threshold = [&](int tt) {
-        const float c = (float)(2 * (int)x[tt] - 258);
+    auto set_threshold = [&](int tt, u32 x) {
+        const float c = (float)(2 * (int)x - 258);
         cth[tt] = mx_v4f{c, c, c, c};
     };
+    auto threshold_x = [&](int tt) -> u32 { return (u32)((int)cth[tt][0] + 258) >> 1; };
 #pragma unroll
     for (int tt = 0; tt < 4; tt++) {
         b1[tt] = b2[tt] = SLAM_KEY_NONE;
-        x[tt] = SLAM_KEY_NONE >> SLAM_KEY_IDX_BITS;              // 511: everything passes
-        set_threshold(tt);
+        set_threshold(tt, SLAM_KEY_NONE >> SLAM_KEY_IDX_BITS);   // 511: everything passes
     }
     // the top-2 of one tile's query over the rows of all four lanes that hold it (ds_bpermute: it issues beside the VALU, which
     // is what bounds this kernel; the v_permlane16/32_swap form costs two copies and a wait per swap there and measured slower)
@@ -172,7 +192,7 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
     auto exchange = [&](int c0) {
         u32 u1[4], u2[4];
         unite_lanes(u1, u2);
-        if (qbase < N) {
+        if (const int qbase = lane_query(); qbase < N) {
             const u32 own = mx_pick(u2, kg);
             asm volatile("" ::"v"(pend[0]));
             const u32 g = __hip_atomic_load(&st.bound[qbase], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -187,8 +207,7 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
             const u32 g = (u32)__shfl((int)gkey, tt * 16 + col, 64);
             const u32 gx = g < SLAM_MX_BOUND_LIMIT ? (g >> SLAM_KEY_IDX_BITS) + ((g & SLAM_KEY_IDX_MASK) < (u32)c0 ? 0u : 1u)
                                                    : SLAM_KEY_NONE >> SLAM_KEY_IDX_BITS;
-            x[tt] = min(x[tt], min(gx, u2[tt] >> SLAM_KEY_IDX_BITS));
-            set_threshold(tt);
+            set_threshold(tt, min(threshold_x(tt), min(gx, u2[tt] >> SLAM_KEY_IDX_BITS)));
         }
     };
 
@@ -229,27 +248,25 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
     int scanned = 0;                                             // wave-uniform: the rows this block has scanned since launch
     while (ci < nchunks) {
         const int c0 = tbl[ci], c1 = tbl[ci + 1];
-        uint4 nx = load_stage(c0, c1);
+        const uint4 first = load_stage(c0, c1);
         exchange(c0);
-        store_stage(0, nx);
+        store_stage(0, first);
         __syncthreads();
         int buf = 0;
         for (int s0 = c0; s0 < c1; s0 += SLAM_MX_STAGE) {
             const int s1 = s0 + SLAM_MX_STAGE;
             const bool more = s1 < c1;
-            if (more) nx = load_stage(s1, c1);
             // the next ticket is drawn while the chunk's last stage is scanned; read behind the stage's barrier
-            else if (tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!more && tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int ng = __builtin_amdgcn_readfirstlane(min(SLAM_MX_STAGE / 16, (c1 - s0 + 15) >> 4));
             const uint4* tp = tile[buf];
             u32 fired = 0;                                       // wave-uniform: the tiles that took the update path in this stage
-            auto group = [&](int g, auto rag) {
-                const uint4 a0 = tp[g * 128 + lane], a1 = tp[g * 128 + 64 + lane];
-                mx_v4f acc[4];
+            auto dots0 = [&](const uint4& a, mx_v4f (&acc)[4]) {
 #pragma unroll
-                for (int tt = 0; tt < 4; tt++) acc[tt] = mx_dot(a0, qb[tt][0], cth[tt]);
-#pragma unroll
-                for (int tt = 0; tt < 4; tt++) acc[tt] = mx_dot(a1, qb[tt][1], acc[tt]);
+                for (int tt = 0; tt < 4; tt++) acc[tt] = mx_dot(a, qb[tt][0], cth[tt]);
+            };
+            // fold the 16 results of group g and, where some lane passes, take the update path
+            auto fold = [&](int g, mx_v4f (&acc)[4], auto rag) {
                 // the results are exact integers in f32 (never -0): "any D >= 0" is the sign of the signed maximum of the bit
                 // patterns - eight three-input maxima, nothing to canonicalise
                 int p[4];
@@ -266,44 +283,113 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
                     // threshold: below the lane's own 2nd-best, whose row is below every row the lane has still to see
                     // (the group's first row is taken from the scalar side here: as a per-lane value it would be carried, and
                     // advanced, through every group that does not fire)
-                    const u32 rowk = (u32)__builtin_amdgcn_readfirstlane(s0 + g * 16) + lanek;
+                    // (and kept there: folded into lanek it would be one more register per group of an unrolled trip)
+                    int row0 = s0 + g * 16;
+                    asm("" : "+s"(row0));
+                    const u32 rowk = (u32)row0 + lanek;
 #pragma unroll
                     for (int tt = 0; tt < 4; tt++) {
                         if (__ballot(max(p[tt], __float_as_int(acc[tt][3])) >= 0) == 0ull) continue;
                         fired |= 1u << tt;
                         // key = (e - D / 2) << 23 | row with e = x - 1: base + r + (-D << 22), exact modulo 2^32 also for x = 0
-                        const u32 base = (x[tt] << SLAM_KEY_IDX_BITS) + rowk;
+                        const u32 xt = threshold_x(tt);
+                        const u32 base = (xt << SLAM_KEY_IDX_BITS) + rowk;
                         // row gates: of a lane's four rows only those at which SOME lane of the tile passes are keyed and merged
                         // (wave-uniform branches); see "row gates" in the file header
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
                             if (__ballot(__float_as_int(acc[tt][r]) >= 0) == 0ull) continue;
                             u32 key = base + (u32)r + ((u32)(int)(-acc[tt][r]) << (SLAM_KEY_IDX_BITS - 1));
-                            if constexpr (decltype(rag)::value)   // the zero rows of a short stage never enter
+                            if constexpr (decltype(rag)::value)   // the rows past the end of a short stage never enter
                                 key = (int)rowk + r < c1 - (1 << SLAM_KEY_IDX_BITS) ? key : SLAM_KEY_NONE;
                             b2[tt] = umed3(b1[tt], b2[tt], key);
                             b1[tt] = min(b1[tt], key);
                         }
-                        x[tt] = min(x[tt], b2[tt] >> SLAM_KEY_IDX_BITS);
-                        set_threshold(tt);
+                        set_threshold(tt, min(xt, b2[tt] >> SLAM_KEY_IDX_BITS));
                     }
                 }
             };
-            // SLAM_MX_UNROLL groups per trip share one LDS address (ds_read_b128 takes the rest as an immediate offset); the
-            // barriers keep a group's operand reads behind the group before it, or the registers of four waves per SIMD run out.
-            //
-            // The unrolled trips take whole groups only.  What they leave of a stage runs in the loop below, with the test for
-            // rows past the chunk: up to seven groups, the whole ones among them too (correct there, only slower), and only in
-            // a short stage - the last stage of the train set.
+            auto group = [&](int g, auto rag) {
+                const uint4 a0 = tp[g * 128 + lane], a1 = tp[g * 128 + 64 + lane];
+                mx_v4f acc[4];
+                dots0(a0, acc);
+#pragma unroll
+                for (int tt = 0; tt < 4; tt++) acc[tt] = mx_dot(a1, qb[tt][1], acc[tt]);
+                fold(g, acc, rag);
+            };
+            // A trip of NG whole groups from group g0 on.  The A operands rotate through three quads: the first K-half of group
+            // g + 1 is read before the MFMAs of group g, its second K-half once g's four first-half MFMAs have issued (into the
+            // quad they free), so a group's operand reads run behind the MFMAs and the fold of the group before it.  The last
+            // group of a trip reads nothing ahead: a trip stays inside its own stage buffer.  The barriers keep this order, or
+            // the registers of four waves per SIMD run out.
+            // With `shadow`, the trip's last four groups also expand and store one source word each of the NEXT stage (into
+            // buffer buf ^ 1, free since the barrier that opened this stage) between their second-half MFMAs, in issue slots the
+            // pipe-paced MFMAs leave empty.
+            auto trip = [&](int g0, auto ngc, auto shadow) {
+                constexpr int NG = decltype(ngc)::value;
+                constexpr bool SH = decltype(shadow)::value;
+                const uint4* ap = tp + g0 * 128 + lane;
+                uint4* const dst = dst0 + (buf ^ 1) * (SLAM_MX_STAGE * 8);
+                // the thread's four source words of the next stage, loaded one group ahead of the group that expands them.  Were
+                // the next stage not whole, the rows past the chunk end would read its last row instead (what such a row holds never
+                // matters, the scan tests its index); the planner's tails make every short stage a chunk of its own, so this only
+                // keeps the loads inside the train set whatever the table
+                const u32* nw = (const u32*)(t + 2 * (size_t)s1) + 8 * min(srow, c1 - 1 - s1) + 4 * sh;
+                u32 w = 0;
+                uint4 a0 = ap[0], a1 = ap[64];
+#pragma unroll
+                for (int k = 0; k < NG; k++) {
+                    uint4 a0n = a0, a1n = a1;
+                    mx_v4f acc[4];
+                    if (k + 1 < NG) a0n = ap[(k + 1) * 128];
+                    const u32 v = w;
+                    if (SH && k >= NG - 5 && k < NG - 1) w = nw[k - (NG - 5)];
+                    __builtin_amdgcn_sched_barrier(0);
+                    dots0(a0, acc);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (SH && k >= NG - 4) {
+                        const int j = k - (NG - 4);
+                        uint4 e;
+                        acc[0] = mx_dot(a1, qb[0][1], acc[0]);
+                        __builtin_amdgcn_sched_barrier(0);
+                        asm volatile("v_lshlrev_b32 %0, 3, %1\n\tv_and_or_b32 %0, %0, %2, %3" : "=v"(e.x) : "v"(v), "s"(0x88888888u), "v"(fill));
+                        asm volatile("v_lshlrev_b32 %0, 2, %1" : "=v"(e.y) : "v"(v));
+                        __builtin_amdgcn_sched_barrier(0);
+                        acc[1] = mx_dot(a1, qb[1][1], acc[1]);
+                        __builtin_amdgcn_sched_barrier(0);
+                        asm volatile("v_and_or_b32 %0, %1, %2, %3" : "=v"(e.y) : "v"(e.y), "s"(0x88888888u), "v"(fill));
+                        asm volatile("v_lshlrev_b32 %0, 1, %1\n\tv_and_or_b32 %0, %0, %2, %3" : "=v"(e.z) : "v"(v), "s"(0x88888888u), "v"(fill));
+                        __builtin_amdgcn_sched_barrier(0);
+                        acc[2] = mx_dot(a1, qb[2][1], acc[2]);
+                        __builtin_amdgcn_sched_barrier(0);
+                        asm volatile("v_and_or_b32 %0, %1, %2, %3" : "=v"(e.w) : "v"(v), "s"(0x88888888u), "v"(fill));
+                        dst[16 * j] = e;
+                        if (k + 1 < NG) a1n = ap[(k + 1) * 128 + 64];
+                        __builtin_amdgcn_sched_barrier(0);
+                        acc[3] = mx_dot(a1, qb[3][1], acc[3]);
+                    } else {
+                        if (k + 1 < NG) a1n = ap[(k + 1) * 128 + 64];
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int tt = 0; tt < 4; tt++) acc[tt] = mx_dot(a1, qb[tt][1], acc[tt]);
+                    }
+                    fold(g0 + k, acc, std::false_type{});
+                    __builtin_amdgcn_sched_barrier(0);
+                    a0 = a0n;
+                    a1 = a1n;
+                }
+            };
+            // The trips take whole groups only.  A whole stage that another follows runs as one trip of eight with the next
+            // stage's staging in its shadow; every other stage runs trips of SLAM_MX_UNROLL and stages at its end.  What the
+            // trips leave of a stage runs in the loop below, with the test for rows past the chunk: up to seven groups, the
+            // whole ones among them too (correct there, only slower), and only in a short stage - the last stage of the train set.
             const int nwhole = __builtin_amdgcn_readfirstlane(min(SLAM_MX_STAGE / 16, (c1 - s0) >> 4));
             int g = 0;
-            for (; g + SLAM_MX_UNROLL <= nwhole; g += SLAM_MX_UNROLL) {
-#pragma unroll
-                for (int k = 0; k < SLAM_MX_UNROLL; k++) {
-                    group(g + k, std::false_type{});
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+            if (more) {                                          // then this stage is whole
+                trip(0, std::integral_constant<int, SLAM_MX_STAGE / 16>{}, std::true_type{});
+                g = SLAM_MX_STAGE / 16;
             }
+            for (; g + SLAM_MX_UNROLL <= nwhole; g += SLAM_MX_UNROLL) trip(g, std::integral_constant<int, SLAM_MX_UNROLL>{}, std::false_type{});
             for (; g < ng; g++) group(g, std::true_type{});
             // once per stage in which a key changed, for the tiles it changed in: the threshold of the query's four lanes together
             // (their rows lie in this stage or before it, below every row still to come)
@@ -312,14 +398,12 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
                 if (!(fired >> tt & 1u)) continue;
                 u32 u1, u2;
                 unite_tile(tt, u1, u2);
-                x[tt] = min(x[tt], u2 >> SLAM_KEY_IDX_BITS);
-                set_threshold(tt);
+                set_threshold(tt, min(threshold_x(tt), u2 >> SLAM_KEY_IDX_BITS));
             }
             // an early exchange (SLAM_MX_EARLY): per wave, no barrier; every row still to come is at or above s1.  Not after a
             // chunk's last stage: the chunk-start exchange follows anyway
             scanned += min(s1, c1) - s0;
             if (more && scanned < 32 * SLAM_MX_STAGE && (SLAM_MX_EARLY >> (scanned / SLAM_MX_STAGE) & 1u)) exchange(s1);
-            if (more) store_stage(buf ^ 1, nx);
             __syncthreads();
             buf ^= 1;
         }
@@ -331,7 +415,7 @@ __global__ __launch_bounds__(256) void bf_top2_mx_kernel(const uint4* __restrict
     const u32 f1[1] = {mx_pick(u1, kg)}, f2[1] = {mx_pick(u2, kg)};
     // the epilogue's skip test takes a DISTANCE that bounds the final 2nd-best one, or the idle pattern when there is none
     const u32 gk[1] = {gkey < SLAM_MX_BOUND_LIMIT ? gkey >> SLAM_KEY_IDX_BITS : SLAM_BOUND_IDLE};
-    bf_top2_epilogue<1, true>(st, bx, tid, lane, qbase, false, false, f1, f2, gk, pend, N, (int)gridDim.y, train_base, out_idx,
+    bf_top2_epilogue<1, true>(st, bx, tid, lane, lane_query(), false, false, f1, f2, gk, pend, N, (int)gridDim.y, train_base, out_idx,
                               out_dist, sel, s_last);
 }
 
