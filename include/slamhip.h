@@ -20,6 +20,8 @@
  *                          (frontend.py:298-393)
  *   slam_tv_*              cv2.findEssentialMat / recoverPose / triangulatePoints behind
  *                          pose_estimation_2d2d and triangulation (utils.py:10-55)
+ *   slam_pnp_*             cv2.solvePnPRansac (P3P); no call site in the reference (nearest:
+ *                          Frontend._reinitialize_from_keyframe, frontend.py:223-229)
  *   slam_orb_*             cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26),
  *                          called from Frontend._detect_features (frontend.py:245)
  *   slam_comm_*            no reference counterpart (the reference is single
@@ -468,6 +470,53 @@ SLAM_API int slam_tv_recover_pose_f64(slam_ctx* ctx, int64_t B, const int32_t* d
  * cameras (a two-dimensional null space) some unit vector of it. */
 SLAM_API int slam_tv_triangulate_f64(slam_ctx* ctx, int64_t N, const double* d_P1, const double* d_P2,
                                      const double* d_x1, const double* d_x2, double* d_X, double* d_w);
+
+/* ---- absolute pose (f64): cv2.solvePnPRansac (SOLVEPNP_P3P), batched ---------------------------------------------------
+ * A camera pose from 2D-3D correspondences, for B candidates per call.  The reference has NO call site: the nearest is
+ * Frontend._reinitialize_from_keyframe (frontend.py:223-229), which drops the map because it has no such estimate.  Uses:
+ * relocalisation candidates, and loop edges with a metric translation (a two-view translation has unit length).
+ * Conventions: world points X [M,3], pixels px [M,2], normalised x = ((u - cx) / fx, (v - cy) / fy); the pose is [12]
+ * row-major 3x4 like d_pose above with X_cam = R X + t.  PARITY UNPINNED against OpenCV (absent here): restated from the
+ * algorithm's definition; OpenCV's own RANSAC draws, its early termination and its final refit are not reproduced.
+ * All calls are asynchronous on the ctx stream; workspace comes from the ctx block, nothing is allocated per call. */
+
+/* The P3P minimal solver on its own: for each of S samples every pose that sees the three world points d_X [S,3,3] along
+ * the three normalised image points d_x [S,3,2] with all three depths positive.  d_pose [S,4,12]: the 0..4 solutions in
+ * ascending order of the solver's root variable (v = depth of point 3 / depth of point 1), unused slots zero;
+ * d_nsol int32 [S].  Every returned R is orthonormal with det +1 (to rounding: it is built from two orthonormal frames)
+ * and every entry finite.  0 solutions: repeated or collinear world points and repeated image points (sin^2 of the angle
+ * below 1e-20), NaN / inf coordinates or coordinates whose squares sum to 1e200 or more (1e150), a world point at the
+ * camera centre (its image point is not finite), a quartic whose leading coefficient vanishes.  Every loop of the solver
+ * is bounded.  Only + - * / sqrt are used, none of them fused: a host build of the same source gives the same bits. */
+SLAM_API int slam_pnp_p3p_f64(slam_ctx* ctx, int64_t S, const double* d_X, const double* d_x, double* d_pose,
+                              int32_t* d_nsol);
+
+/* cv2.solvePnPRansac(points, px, K, None, flags=SOLVEPNP_P3P) for B candidates in one call.  Candidate b owns the
+ * correspondences [d_offsets[b], d_offsets[b+1]) of d_X [M,3] / d_px [M,2]; d_offsets int32 [B+1] under the contract of
+ * slam_pose_optimize_batch_f64 (a table that is not ascending or leaves [0, M] never causes an access outside the
+ * arrays: the candidate shrinks to the part inside and slam_index_errors counts it).  B <= 65535.
+ * Per candidate: H hypotheses (1 <= H <= 2^20), no early termination.  Hypothesis h draws three DISTINCT indices of the
+ * candidate's n correspondences with the generator stated at slam_tv_essential_ransac_f64 (splitmix, word(seed, h, d),
+ * index(d) = ((word(seed, h, d) >> 32) * n) >> 32, d = 0, 1, 2, ...: an index already drawn is skipped, until there are
+ * three, in that order).  The candidate index b is NOT mixed in.
+ * Every solution of every hypothesis is scored on all n correspondences, evaluated without fused multiply-adds in
+ * exactly this order (pose row-major p0..p11, point (X, Y, Z), pixel (u, v)):
+ *     xc = ((p0*X + p1*Y) + p2*Z) + p3;   yc = ((p4*X + p5*Y) + p6*Z) + p7;   zc = ((p8*X + p9*Y) + p10*Z) + p11;
+ *     du = (fx * (xc / zc) + cx) - u;     dv = (fy * (yc / zc) + cy) - v;
+ *   inlier iff zc > 0 and du*du + dv*dv < threshold_px * threshold_px (OpenCV's reprojectionError, default 8).
+ *   Winner: most inliers, ties to the lower hypothesis index, then the lower solution index - found with packed integer
+ *   keys, so the result is bit-identical for given (correspondences, intrinsics, H, threshold, seed) whatever B and
+ *   whatever order the workgroups finish in.  The winning hypothesis is solved again when the result is written.
+ * Outputs: d_pose [B,12] the winner, d_inlier uint8 [M] its mask (entries outside every candidate: 0), d_stats int32
+ * [B,4] = {inlier count, winning hypothesis, winning solution, number of (hypothesis, solution) models scored}.
+ * A candidate of fewer than 3 correspondences yields the identity pose, mask 0, stats {0, -1, -1, 0} and is not an
+ * error; so does one where no hypothesis gives a model.  Non-finite coordinates are data: a correspondence with a NaN /
+ * inf coordinate is never an inlier, a hypothesis that drew one yields no model, d_pose is always finite, and one
+ * candidate's data never changes another candidate's result. */
+SLAM_API int slam_pnp_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_X,
+                                 const double* d_px, int64_t M, double fx, double fy, double cx, double cy, int H,
+                                 double threshold_px, uint64_t seed, double* d_pose, uint8_t* d_inlier,
+                                 int32_t* d_stats);
 
 /* ---- ORB feature extraction (orb.hip): cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26), which
  * Frontend._detect_features calls on every frame with a mask (frontend.py:245) -------------------------------------------

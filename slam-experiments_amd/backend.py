@@ -22,6 +22,7 @@ from typing import Optional
 import numpy as np
 
 from slamhip import ba as _ba
+from slamhip import pnp as _pnp
 from slamhip import pose_graph as _pg
 from slamhip import pose_opt as _po
 from slamhip import reproj as _r
@@ -141,6 +142,19 @@ class Backend:
         poses = np.tile(np.eye(4), (len(R), 1, 1))
         poses[:, :3, :3] = R
         poses[:, :3, 3] = t
+        return poses, counts, masks
+
+    def relocalize(self, candidates, fx, fy, cx, cy, hypotheses: int = _pnp.DEFAULT_HYPOTHESES,
+                   threshold: float = _pnp.DEFAULT_THRESHOLD, seed: int = 0, refine: bool = True):
+        """Absolute pose of the current frame against many candidate keyframes in one call (what
+        ``Frontend._reinitialize_from_keyframe``, ``frontend.py:223-229``, lacks and drops the map for): ``candidates`` =
+        list of ``(map points [N_b,3], pixels [N_b,2])``, the candidate's map points matched in the current frame ->
+        (poses [B,4,4] world -> camera, inlier counts [B], list of inlier masks).  P3P RANSAC, then (``refine``) the pose-only
+        optimisation of ``correct_frame_pose`` on the inliers.  A candidate of fewer than three correspondences, or
+        without a model, comes back with the identity and a count of 0."""
+        T, masks, counts, _, _ = _pnp.solve_pnp_ransac_batch(candidates, (fx, fy, cx, cy), hypotheses, threshold, seed, refine, ctx=self._ctx)
+        poses = np.tile(np.eye(4), (len(T), 1, 1))
+        poses[:, :3, :] = T
         return poses, counts, masks
 
     def triangulate(self, pose1, pose2, px1, px2, fx, fy, cx, cy, reference_projection: bool = False):

@@ -41,6 +41,13 @@ from .orb import (  # noqa: F401
     OrbResult,
     orb_extract_arrays,
 )
+from .pnp import (  # noqa: F401
+    loop_edges_from_pnp,
+    p3p_arrays,
+    solve_pnp_ransac,
+    solve_pnp_ransac_batch,
+    solve_pnp_ransac_offsets,
+)
 from .pose_graph import (  # noqa: F401
     loop_edges_from_two_view,
     optimize_pose_graph,

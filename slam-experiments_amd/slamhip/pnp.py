@@ -1,0 +1,217 @@
+"""Absolute pose from 2D-3D correspondences on the GPU (``slam_pnp_*``): ``cv2.solvePnPRansac`` with ``SOLVEPNP_P3P`` for
+many candidates per call.
+
+The reference has no call site: the nearest is ``Frontend._reinitialize_from_keyframe`` (``frontend.py:223-229``), which drops
+the map because it has no such estimate.  A keyframe's map points matched against another frame's keypoints are 3D-2D
+correspondences; a pose from those is in map scale with all six degrees of freedom, which a two-view estimate (unit
+translation, arbitrary under pure rotation) is not.  ``X_cam = R X + t``.
+
+PARITY UNPINNED: cv2 is absent here, so the call is restated from the algorithm's definition (P3P minimal solver, reprojection
+error in pixels against OpenCV's ``reprojectionError``).  OpenCV's own random draws, its early termination and its final
+refit are not reproduced: a fixed number of hypotheses from a documented counter-based generator is scored instead, so a
+result is a pure function of (correspondences, intrinsics, hypotheses, threshold, seed).  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import numpy as np
+
+from ._lib import check
+from .device import Context, default_context
+from .pose_opt import CHI2_THRESHOLD, HUBER_DELTA
+from .two_view import MAX_PAIRS, _Buffers, _check_ransac_args, _intrinsics, _points
+
+DEFAULT_HYPOTHESES = 256        # as the essential-matrix RANSAC; ln(0.001) / ln(1 - 0.5**3) = 52 would do at 50 % inliers
+DEFAULT_THRESHOLD = 8.0         # pixels, cv2.solvePnPRansac's reprojectionError default
+REFINE_ROUNDS, REFINE_ITERATIONS = 4, 10        # Frontend._correct_current_pose (frontend.py:298-393)
+
+
+def _points3(a, name: str) -> np.ndarray:
+    try:
+        a = np.asarray(a, np.float64)
+    except (TypeError, ValueError) as exc:
+        raise TypeError(f"{name} must be numeric") from exc
+    if a.size == 0:
+        return np.zeros((0, 3))
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"{name} must have shape [N,3], got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _cand_arrays(cands):
+    Xs, ps, off = [], [], [0]
+    for i, c in enumerate(cands):
+        if len(c) != 2:
+            raise ValueError(f"candidate {i}: expected (points, px)")
+        X, p = _points3(c[0], f"candidate {i} points"), _points(c[1], f"candidate {i} px")
+        if len(X) != len(p):
+            raise ValueError(f"candidate {i}: {len(X)} points but {len(p)} pixels")
+        Xs.append(X)
+        ps.append(p)
+        off.append(off[-1] + len(X))
+    if off[-1] >= 1 << 28:
+        raise ValueError("more than 2^28 correspondences in one call")
+    return (np.concatenate(Xs) if Xs else np.zeros((0, 3)), np.concatenate(ps) if ps else np.zeros((0, 2)),
+            np.asarray(off, np.int32))
+
+
+def p3p_arrays(X, x, ctx: Optional[Context] = None):
+    """Every pose that sees three world points along three normalised image points, per sample (``slam_pnp_p3p_f64``):
+    ``X`` [S,3,3] (or [3,3]), ``x`` [S,3,2] (or [3,2]) -> (pose [S,4,3,4], unused slots zero; nsol int32 [S])."""
+    X, x = np.asarray(X, np.float64), np.asarray(x, np.float64)
+    if X.shape[-2:] != (3, 3) or x.shape[-2:] != (3, 2) or X.ndim not in (2, 3) or x.ndim != X.ndim or X.shape[:-2] != x.shape[:-2]:
+        raise ValueError(f"X must have shape [S,3,3] and x [S,3,2], got {X.shape} and {x.shape}")
+    X, x = np.ascontiguousarray(X.reshape(-1, 3, 3)), np.ascontiguousarray(x.reshape(-1, 3, 2))
+    S = X.shape[0]
+    if S == 0:
+        return np.zeros((0, 4, 3, 4)), np.zeros(0, np.int32)
+    ctx = ctx or default_context()
+    m = _Buffers(ctx)
+    try:
+        dX, dx = m.up(X), m.up(x)
+        dp, dn = m.new(S * 384), m.new(S * 4)
+        check(ctx.lib.slam_pnp_p3p_f64(ctx.handle, S, dX.ptr, dx.ptr, dp.ptr, dn.ptr))
+        return dp.download(np.float64, (S, 4, 3, 4)), dn.download(np.int32, (S,))
+    finally:
+        m.free()
+
+
+def solve_pnp_ransac_offsets(points, px, offsets, K, hypotheses: int = DEFAULT_HYPOTHESES, threshold: float = DEFAULT_THRESHOLD,
+                             seed: int = 0, ctx: Optional[Context] = None):
+    """``slam_pnp_ransac_f64`` on concatenated correspondences: candidate b owns ``[offsets[b], offsets[b+1])``.
+    Returns (pose [B,3,4], inlier bool [M], stats int32 [B,4])."""
+    fx, fy, cx, cy = _intrinsics(K)
+    H, thr, seed = _check_ransac_args(hypotheses, threshold, seed)
+    points, px = _points3(points, "points"), _points(px, "px")
+    if len(points) != len(px):
+        raise ValueError(f"{len(points)} points but {len(px)} pixels")
+    offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+    B, M = len(offsets) - 1, len(points)
+    if B < 0:
+        raise ValueError("offsets must have B + 1 entries")
+    if B > MAX_PAIRS:
+        raise ValueError(f"at most {MAX_PAIRS} candidates per call")
+    if B == 0:
+        return np.zeros((0, 3, 4)), np.zeros(M, bool), np.zeros((0, 4), np.int32)
+    ctx = ctx or default_context()
+    m = _Buffers(ctx)
+    try:
+        dX, dp, do = m.up(points), m.up(px), m.up(offsets)
+        dT, dm, ds = m.new(B * 96), m.new(M), m.new(B * 16)
+        check(ctx.lib.slam_pnp_ransac_f64(ctx.handle, B, do.ptr, dX.ptr, dp.ptr, M, fx, fy, cx, cy, H, thr, seed, dT.ptr, dm.ptr, ds.ptr))
+        pose, st = dT.download(np.float64, (B, 3, 4)), ds.download(np.int32, (B, 4))
+        mask = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
+        return pose, mask, st
+    finally:
+        m.free()
+
+
+def solve_pnp_ransac_batch(cands: Sequence, K, hypotheses: int = DEFAULT_HYPOTHESES, threshold: float = DEFAULT_THRESHOLD,
+                           seed: int = 0, refine: bool = True, ctx: Optional[Context] = None):
+    """``cv2.solvePnPRansac(points, px, K, None, flags=cv2.SOLVEPNP_P3P)`` for a list of ``(points [N_b,3], px [N_b,2])``
+    candidates in one call: (poses [B,3,4], list of bool masks, inlier counts int [B], stats int32 [B,4], refined counts).
+
+    The masks and the inlier counts are the RANSAC vote.  With ``refine`` the RANSAC inliers of every candidate that has a
+    model go, from the RANSAC pose, through ``slam_pose_optimize_batch_f64`` in one launch (4 rounds x 10 LM iterations,
+    chi2 gate 5.991^2, as ``Frontend._correct_current_pose``); the returned poses are then the refined ones and the fifth
+    value holds the refinement's inlier counts int [B] (None without ``refine``).  A candidate of fewer than 3
+    correspondences, or one where no hypothesis gave a model, comes back with the identity, an empty vote, stats
+    {0, -1, -1, 0} and is not refined."""
+    fx, fy, cx, cy = _intrinsics(K)
+    H, thr, seed = _check_ransac_args(hypotheses, threshold, seed)
+    X, px, off = _cand_arrays(cands)
+    B, M = len(off) - 1, len(X)
+    if B > MAX_PAIRS:
+        raise ValueError(f"at most {MAX_PAIRS} candidates per call")
+    if B == 0:
+        return np.zeros((0, 3, 4)), [], np.zeros(0, np.int64), np.zeros((0, 4), np.int32), (np.zeros(0, np.int64) if refine else None)
+    ctx = ctx or default_context()
+    m = _Buffers(ctx)
+    try:
+        dX, dp, do = m.up(X), m.up(px), m.up(off)
+        dT, dm, ds = m.new(B * 96), m.new(M), m.new(B * 16)
+        check(ctx.lib.slam_pnp_ransac_f64(ctx.handle, B, do.ptr, dX.ptr, dp.ptr, M, fx, fy, cx, cy, H, thr, seed, dT.ptr, dm.ptr, ds.ptr))
+        pose, st = dT.download(np.float64, (B, 3, 4)), ds.download(np.int32, (B, 4))
+        mask = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
+        refined = None
+        if refine:
+            # the optimiser takes whole slices: the inliers are packed on the host (the vote has to come down anyway) and
+            # the refinement starts from the RANSAC poses still on the device
+            keep = np.flatnonzero(mask)
+            off2 = np.searchsorted(keep, off).astype(np.int32)
+            O = len(keep)
+            refined = np.zeros(B, np.int64)
+            if O:
+                dX2, dp2, do2 = m.up(np.ascontiguousarray(X[keep])), m.up(np.ascontiguousarray(px[keep])), m.up(off2)
+                dT2, di2, dc2, ds2 = m.new(B * 96), m.new(O), m.new(O * 8), m.new(B * 8)
+                check(ctx.lib.slam_pose_optimize_batch_f64(ctx.handle, B, dT.ptr, dX2.ptr, dp2.ptr, do2.ptr, O, fx, fy, cx, cy,
+                                                           REFINE_ROUNDS, REFINE_ITERATIONS, CHI2_THRESHOLD, HUBER_DELTA,
+                                                           dT2.ptr, di2.ptr, dc2.ptr, ds2.ptr))
+                out, rs = dT2.download(np.float64, (B, 3, 4)), ds2.download(np.int32, (B, 2))
+                has = (st[:, 1] >= 0) & (np.diff(off2) > 0) & np.isfinite(out).all((1, 2))
+                pose[has] = out[has]
+                refined[has] = rs[has, 0]
+    finally:
+        m.free()
+    return pose, [mask[off[b]:off[b + 1]].copy() for b in range(B)], st[:, 0].astype(np.int64), st, refined
+
+
+def solve_pnp_ransac(points, px, K, hypotheses: int = DEFAULT_HYPOTHESES, threshold: float = DEFAULT_THRESHOLD, seed: int = 0,
+                     refine: bool = True, ctx: Optional[Context] = None):
+    """One candidate: (ok, pose [3,4], inlier mask bool [N]); ``ok`` is False (identity, empty vote) when there are fewer than
+    3 correspondences or no hypothesis gave a model."""
+    pose, masks, _, st, _ = solve_pnp_ransac_batch([(points, px)], K, hypotheses, threshold, seed, refine, ctx)
+    return bool(st[0, 1] >= 0), pose[0], masks[0]
+
+
+def _pose44(a, name):
+    a = np.asarray(a, np.float64)
+    if a.ndim == 2 and a.shape[1] == 12:
+        a = a.reshape(-1, 3, 4)
+    if a.ndim != 3 or a.shape[1:] not in ((3, 4), (4, 4)):
+        raise ValueError(f"{name} must have shape [N,3,4], [N,4,4] or [N,12], got {a.shape}")
+    T = np.tile(np.eye(4), (len(a), 1, 1))
+    T[:, :3, :] = a[:, :3, :]
+    return T
+
+
+def loop_edges_from_pnp(pairs, poses, inlier_counts, map_poses, min_inliers: int = 20, rotation_sigma: float = 0.01,
+                        translation_sigma: float = 0.1):
+    """Edges from ``solve_pnp_ransac_batch`` output, in the format of ``loop_edges_from_two_view``: ``pairs`` int [B,2] with
+    ``pairs[b] = (i, j)``, ``poses[b]`` the estimated world -> camera j pose (from keyframe i's map points matched in frame
+    j), ``map_poses[i]`` the world -> camera i pose the map holds -> (edges int32 [E,2], meas [E,3,4], info [E,6,6]) for the
+    pairs with at least ``min_inliers`` inliers and i != j.
+
+    The measurement is the relative pose ``T_j T_i^-1`` (``X_j = R X_i + t``), what ``optimize_pose_graph`` expects.  The
+    pose is in map scale, so BOTH blocks of the information are set: ``inliers / min_inliers / sigma^2`` times the
+    identity, with the rotation and the translation sigma."""
+    pairs = np.asarray(pairs)
+    if pairs.size == 0:
+        pairs = np.zeros((0, 2), np.int64)
+    if pairs.dtype.kind not in "iu" or pairs.ndim != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"pairs must be integers of shape [B,2], got {pairs.dtype} {pairs.shape}")
+    B = len(pairs)
+    T = _pose44(poses, "poses") if B else np.zeros((0, 4, 4))
+    Tm = _pose44(map_poses, "map_poses")
+    n = np.asarray(inlier_counts).reshape(-1)
+    if not (len(T) == len(n) == B):
+        raise ValueError(f"{B} pairs but {len(T)} poses and {len(n)} inlier counts")
+    if min_inliers < 1 or rotation_sigma <= 0 or translation_sigma <= 0:
+        raise ValueError("min_inliers >= 1 and positive sigmas")
+    if B and (pairs.min() < 0 or pairs.max() >= len(Tm)):
+        raise ValueError(f"pair index outside the {len(Tm)} map poses")
+    k = np.flatnonzero((n >= min_inliers) & (pairs[:, 0] != pairs[:, 1]))
+    meas = np.zeros((len(k), 3, 4))
+    for e, b in enumerate(k):
+        Ti = Tm[pairs[b, 0]]
+        inv = np.eye(4)
+        inv[:3, :3] = Ti[:3, :3].T
+        inv[:3, 3] = -Ti[:3, :3].T @ Ti[:3, 3]
+        meas[e] = (T[b] @ inv)[:3]
+    info = np.zeros((len(k), 6, 6))
+    w = n[k] / float(min_inliers)
+    for a in range(3):
+        info[:, a, a] = w / rotation_sigma ** 2
+        info[:, 3 + a, 3 + a] = w / translation_sigma ** 2
+    return np.ascontiguousarray(pairs[k], np.int32), meas, info
