@@ -1,5 +1,6 @@
-// bf_common.h - device helpers and merge state shared by the Hamming searches of libslamhip.so: the top-2 search
-// (bf_hamming.hip) and the top-k search (bf_topk.hip).  Not part of the C ABI.
+// bf_common.h - device helpers and merge state shared by the Hamming searches of libslamhip.so: the top-2 searches
+// (bf_hamming.hip, bf_mx.hip) and the top-k, radius and window searches (bf_topk.hip, bf_radius.hip, bf_window.hip).  Not
+// part of the C ABI.
 #pragma once
 #include "internal.h"
 #include <vector>
@@ -97,6 +98,67 @@ __device__ __forceinline__ void row_acc(const u32 (&q)[R][8], uint4 a, uint4 b, 
 #pragma unroll
     for (int r = 0; r < R; r++) acc[r] = bcnt_acc(q[r][7] ^ b.w, acc[r]);
 }
+
+// ---- pieces the one-query-per-lane searches share (bf_topk.hip, bf_radius.hip, bf_window.hip) -------------------------
+
+// query row qi (two uint4) into the lane's eight registers
+__device__ __forceinline__ void bf_load_query(const uint4* q, int qi, u32 (&qr)[8]) {
+    const uint4 x = q[2 * (size_t)qi], y = q[2 * (size_t)qi + 1];
+    qr[0] = x.x; qr[1] = x.y; qr[2] = x.z; qr[3] = x.w;
+    qr[4] = y.x; qr[5] = y.y; qr[6] = y.z; qr[7] = y.w;
+}
+
+// One group of U rows of the LDS tile tp from row j, read rolling one row ahead through one LDS address + immediate
+// offsets (bf_top2_block): a0 / c0 hold row j on entry and row j + U on return.
+template <int U>
+__device__ __forceinline__ void bf_group_acc(const u32 (&qr)[1][8], const uint4* tp, int j, uint4& a0, uint4& c0,
+                                             const u32 (&ini)[1], u32 (&acc)[U][1]) {
+    u32 base = lds_addr(tp + 2 * j);
+#pragma unroll
+    for (int u = 0; u < U; u += 2) {
+        const uint4 a1 = lds_read16(base, (2 * u + 2) * 16), c1 = lds_read16(base, (2 * u + 3) * 16);
+        row_acc<1>(qr, a0, c0, ini, acc[u]);
+        asm volatile("" : "+v"(base) : "v"(acc[u][0]));
+        a0 = lds_read16(base, (2 * u + 4) * 16);
+        c0 = lds_read16(base, (2 * u + 5) * 16);
+        row_acc<1>(qr, a1, c1, ini, acc[u + 1]);
+        asm volatile("" : "+v"(base) : "v"(acc[u + 1][0]));
+    }
+}
+
+// a packed key dist << 23 | row as its row (+ base) and its distance; SLAM_KEY_NONE as "no match"
+__device__ __forceinline__ int bf_key_idx(u32 key, int base) {
+    return key == SLAM_KEY_NONE ? SLAM_NO_MATCH_IDX : (int)(key & SLAM_KEY_IDX_MASK) + base;
+}
+__device__ __forceinline__ int bf_key_dist(u32 key) {
+    return key == SLAM_KEY_NONE ? SLAM_NO_MATCH_DIST : (int)(key >> SLAM_KEY_IDX_BITS);
+}
+
+// exclusive scan of one value per thread over a 256-thread block (lds4: four words of LDS); *total = the block's sum
+template <typename T>
+__device__ __forceinline__ T bf_block_excl_scan(T v, T* lds4, T* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const T y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) lds4[wave] = x;
+    __syncthreads();
+    T before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        before += w < wave ? lds4[w] : 0;
+        all += lds4[w];
+    }
+    __syncthreads();
+    *total = all;
+    return before + x - v;
+}
+
+// A wave's own LDS operations complete in order, so waiting for them is all the hand-off between its lanes needs.
+__device__ __forceinline__ void bf_wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // Exchange the 2nd-best distance of the lane's queries with the blocks scanning other train chunks.
 // bound[q] only ever holds the 2nd-best distance over some subset of the train rows, i.e. an upper

@@ -5,7 +5,7 @@
 // Design: the threshold is known before the first row, so the scan is the top-k search's without a list
 // and without any exchange between blocks; the new part is output of variable length, in compressed-row (CSR) form.
 //   1. count   bf_radius_scan_kernel<false>: grid = query blocks x train chunks, one query per lane, train rows through
-//              the LDS tile of bf_topk_kernel, row_acc<1> with init = 2^31 - th (d < th <=> sign bit clear), one ballot
+//              the LDS tile of bf_topk_kernel (bf_group_acc), row_acc<1> with init = 2^31 - th (d < th <=> sign bit clear), one ballot
 //              per group of 16 rows; only a group that fires pays for the per-lane count.  Plain stores into a
 //              [chunks][N] table: no atomics, no bound[].
 //   2. scan    three small kernels: each query's chunk counts become its per-chunk prefixes (in place), and an exclusive
@@ -53,7 +53,7 @@ struct radius_args {
 };
 
 // One block = 256 queries (one per lane) x one chunk of train rows.  EMIT = false counts the rows with d < th, EMIT = true
-// writes them.  The tile feed and the 16-row group are bf_topk_kernel's.
+// writes them.  The tile feed is bf_topk_kernel's, the 16-row group bf_group_acc.
 template <bool EMIT>
 __global__ __launch_bounds__(256) void bf_radius_scan_kernel(const radius_args a) {
     __shared__ uint4 tile[2][SLAM_TILE_ROWS * 2 + 4];
@@ -64,12 +64,7 @@ __global__ __launch_bounds__(256) void bf_radius_scan_kernel(const radius_args a
     const bool valid = qbase < N;
 
     u32 qr[1][8];
-    {
-        const int qi = valid ? qbase : N - 1;                       // clamp: tail lanes compute a duplicate and never store
-        const uint4 x = a.q[2 * (size_t)qi], y = a.q[2 * (size_t)qi + 1];
-        qr[0][0] = x.x; qr[0][1] = x.y; qr[0][2] = x.z; qr[0][3] = x.w;
-        qr[0][4] = y.x; qr[0][5] = y.y; qr[0][6] = y.z; qr[0][7] = y.w;
-    }
+    bf_load_query(a.q, valid ? qbase : N - 1, qr[0]);               // clamp: tail lanes compute a duplicate and never store
     const u32 init[1] = {a.init};
     int count = 0;
     int2* out = nullptr;
@@ -116,19 +111,8 @@ __global__ __launch_bounds__(256) void bf_radius_scan_kernel(const radius_args a
         int j = 0;
         uint4 a0 = tp[0], c0 = tp[1];
         for (; j + U <= cnt; j += U) {
-            // one group of U rows, read rolling one row ahead through one LDS address + immediate offsets (bf_topk_kernel)
             u32 acc[U][1];
-            u32 base = lds_addr(tp + 2 * j);
-#pragma unroll
-            for (int u = 0; u < U; u += 2) {
-                const uint4 a1 = lds_read16(base, (2 * u + 2) * 16), c1 = lds_read16(base, (2 * u + 3) * 16);
-                row_acc<1>(qr, a0, c0, init, acc[u]);
-                asm volatile("" : "+v"(base) : "v"(acc[u][0]));
-                a0 = lds_read16(base, (2 * u + 4) * 16);
-                c0 = lds_read16(base, (2 * u + 5) * 16);
-                row_acc<1>(qr, a1, c1, init, acc[u + 1]);
-                asm volatile("" : "+v"(base) : "v"(acc[u + 1][0]));
-            }
+            bf_group_acc<U>(qr, tp, j, a0, c0, init, acc);
             u32 m = acc[0][0];
 #pragma unroll
             for (int u = 1; u < U; u++) m &= acc[u][0];
@@ -156,28 +140,6 @@ __global__ __launch_bounds__(256) void bf_radius_scan_kernel(const radius_args a
 
 // ---- the scan: chunk counts -> per-chunk prefixes, list lengths -> offsets[N + 1] -------------------------------------
 
-// exclusive scan of one int64 per thread over a 256-thread block; *total = the block's sum
-__device__ __forceinline__ int64_t block_excl_scan(int64_t v, int64_t* lds4, int64_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) lds4[wave] = x;
-    __syncthreads();
-    int64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        before += w < wave ? lds4[w] : 0;
-        all += lds4[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before + x - v;
-}
-
 // one thread per query: its chunk counts become exclusive prefixes (in place) and its list length goes to len[q];
 // per block of 256 queries the sums of (entries, long lists, tiles of long lists) go to bsum[3 * block]
 __global__ __launch_bounds__(256) void bf_radius_prefix_kernel(int32_t* __restrict__ cnt, int S, int N, int32_t* __restrict__ len,
@@ -198,7 +160,7 @@ __global__ __launch_bounds__(256) void bf_radius_prefix_kernel(int32_t* __restri
     const int64_t v[3] = {run, lng ? 1 : 0, lng ? (run + SLAM_RADIUS_SHORT - 1) / SLAM_RADIUS_SHORT : 0};
     for (int i = 0; i < 3; i++) {
         int64_t tot;
-        (void)block_excl_scan(v[i], lds4, &tot);
+        (void)bf_block_excl_scan<int64_t>(v[i], lds4, &tot);
         if (threadIdx.x == 0) bsum[3 * (size_t)blockIdx.x + i] = tot;
     }
 }
@@ -213,7 +175,7 @@ __global__ __launch_bounds__(256) void bf_radius_blocks_kernel(int64_t* __restri
         int64_t s = 0;
         for (int64_t b = b0; b < b1; b++) s += bsum[3 * b + i];
         int64_t all;
-        int64_t run = block_excl_scan(s, lds4, &all);
+        int64_t run = bf_block_excl_scan<int64_t>(s, lds4, &all);
         for (int64_t b = b0; b < b1; b++) {
             const int64_t v = bsum[3 * b + i];
             bsum[3 * b + i] = run;
@@ -236,9 +198,9 @@ __global__ __launch_bounds__(256) void bf_radius_offsets_kernel(const int32_t* _
     const bool lng = n > SLAM_RADIUS_SHORT;
     const int64_t tiles = lng ? (n + SLAM_RADIUS_SHORT - 1) / SLAM_RADIUS_SHORT : 0;
     int64_t tot;
-    const int64_t off = bsum[3 * (size_t)blockIdx.x] + block_excl_scan(n, lds4, &tot);
-    const int64_t rank = bsum[3 * (size_t)blockIdx.x + 1] + block_excl_scan(lng ? 1 : 0, lds4, &tot);
-    const int64_t tbeg = bsum[3 * (size_t)blockIdx.x + 2] + block_excl_scan(tiles, lds4, &tot);
+    const int64_t off = bsum[3 * (size_t)blockIdx.x] + bf_block_excl_scan<int64_t>(n, lds4, &tot);
+    const int64_t rank = bsum[3 * (size_t)blockIdx.x + 1] + bf_block_excl_scan<int64_t>(lng ? 1 : 0, lds4, &tot);
+    const int64_t tbeg = bsum[3 * (size_t)blockIdx.x + 2] + bf_block_excl_scan<int64_t>(tiles, lds4, &tot);
     if (q < N) {
         offsets[q] = off;
         if (lng) {
@@ -250,15 +212,13 @@ __global__ __launch_bounds__(256) void bf_radius_offsets_kernel(const int32_t* _
 
 // ---- the order: stable counting sort by distance -----------------------------------------------------------------
 
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 // h[0 .. 256] = histogram of the distances of src[0 .. n) (one wave)
 __device__ __forceinline__ void wave_histogram(int32_t* h, const int2* __restrict__ src, int n) {
     const int lane = threadIdx.x & 63;
     for (int b = lane; b < SLAM_RADIUS_BINS; b += 64) h[b] = 0;
-    wave_lds_sync();
+    bf_wave_lds_sync();
     for (int i = lane; i < n; i += 64) atomicAdd(&h[src[i].y], 1);
-    wave_lds_sync();
+    bf_wave_lds_sync();
 }
 
 // h[0 .. 256] -> its exclusive scan (one wave: four bins per lane, bin 256 last)
@@ -279,7 +239,7 @@ __device__ __forceinline__ void wave_excl_scan_bins(int32_t* h) {
     h[4 * lane + 3] = e + v0 + v1 + v2;
     const int32_t all = __shfl(x, 63, 64);
     if (lane == 0) h[256] = all;
-    wave_lds_sync();
+    bf_wave_lds_sync();
 }
 
 // Write src[0 .. n) to dst_* [dst0 + base[d] + (rank among the earlier entries of distance d)], 64 entries per round in
@@ -301,13 +261,13 @@ __device__ __forceinline__ void wave_stable_scatter(int32_t* base, const int2* _
             same &= bit ? m : ~m;
         }
         const int32_t pos = in ? base[e.y] + __popcll(same & lt) : 0;
-        wave_lds_sync();
+        bf_wave_lds_sync();
         if (in) {
             dst_idx[dst0 + pos] = e.x;
             dst_dist[dst0 + pos] = e.y;
             if (63 - __clzll(same) == lane) base[e.y] = pos + 1;     // the group's last lane: one past its last entry
         }
-        wave_lds_sync();
+        bf_wave_lds_sync();
     }
 }
 
@@ -403,7 +363,7 @@ __global__ __launch_bounds__(256) void bf_radius_sort_scatter_kernel(const int2*
     const int64_t s = (w - first) * SLAM_RADIUS_SHORT;
     int32_t* h = hist[wave];
     for (int b = lane; b < SLAM_RADIUS_BINS; b += 64) h[b] = ghist[w * SLAM_RADIUS_BINS + b];
-    wave_lds_sync();
+    bf_wave_lds_sync();
     wave_stable_scatter(h, stage + o + s, (int)min((int64_t)SLAM_RADIUS_SHORT, n - s), idx, dist, o);
 }
 
@@ -418,43 +378,18 @@ struct radius_plan {
 };
 
 // A pure function of the CU count and the shape (slam_bf_radius_plan_describe exposes it without a device): the top-k
-// search's rule (topk_plan_core) - one round of resident blocks, query blocks x chunks = num_cu x resident, chunks of at
-// least one tile, no more chunks than the count table's cap allows - over ALL train rows: the row index is a plain int32
-// here, so there are no passes.
+// search's rule (bf_chunk_rule), chunks of at least one tile and under the count table's cap, over ALL train rows: the
+// row index is a plain int32 here, so there are no passes.
 static radius_plan radius_plan_core(int num_cu, int resident, int64_t N, int64_t M) {
     radius_plan p;
     p.resident = resident;
-    p.qblocks = (int)((N + 255) / 256);
-    const int64_t slots = (int64_t)(num_cu > 0 ? num_cu : 1) * resident;
-    const int64_t qb = p.qblocks > 0 ? p.qblocks : 1;
-    int64_t chunks = (slots + qb - 1) / qb;
-    const int64_t by_rows = (M + SLAM_RADIUS_MIN_CHUNK - 1) / SLAM_RADIUS_MIN_CHUNK;
-    if (chunks > by_rows) chunks = by_rows;
     const int64_t per = N * 4;                                      // one chunk's counts
-    const int64_t by_cap = (int64_t)SLAM_RADIUS_WS_CAP / (per > 0 ? per : 1);
-    if (chunks > by_cap) chunks = by_cap;
-    if (chunks < 1) chunks = 1;
-    int64_t rows = (M + chunks - 1) / chunks;
-    rows = (rows + 15) / 16 * 16;
-    if (rows < 16) rows = 16;
-    p.chunk = rows;
-    p.chunks = (int)((M + rows - 1) / rows);
-    if (p.chunks < 1) p.chunks = 1;
+    const bf_chunks c = bf_chunk_rule(num_cu, resident, N, M, SLAM_RADIUS_MIN_CHUNK, per, SLAM_RADIUS_WS_CAP);
+    p.qblocks = c.qblocks;
+    p.chunks = c.chunks;
+    p.chunk = c.chunk;
     p.ws = (int64_t)p.chunks * per;
     return p;
-}
-
-static int radius_occupancy(int* out) {
-    static std::atomic<int> once{0};                                 // a property of the kernel and the architecture
-    int occ = once.load(std::memory_order_relaxed);
-    if (!occ) {
-        int o = 0;
-        SLAM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, bf_radius_scan_kernel<false>, 256, 0));
-        occ = o > 0 ? o : 1;
-        once.store(occ, std::memory_order_relaxed);
-    }
-    *out = occ;
-    return SLAM_OK;
 }
 
 extern "C" int slam_bf_radius_plan_describe(int num_cu, int64_t N, int64_t M, int32_t* h_plan) {
@@ -469,8 +404,6 @@ extern "C" int slam_bf_radius_plan_describe(int num_cu, int64_t N, int64_t M, in
     return SLAM_OK;
 }
 
-static inline uint64_t radius_align(uint64_t v) { return (v + 255) / 256 * 256; }
-
 // the context's grow-only block for the count table and the scan's arrays (kept apart from slam_workspace, which the
 // staging area of the emit step grows once the total is known)
 static int radius_tables(slam_ctx* ctx, uint64_t bytes, void** out) {    // (under ctx->call_mu)
@@ -484,12 +417,6 @@ static int radius_tables(slam_ctx* ctx, uint64_t bytes, void** out) {    // (und
         ctx->radius_mem_bytes = want;
     }
     *out = ctx->radius_mem;
-    return SLAM_OK;
-}
-
-static int radius_launch_check(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return slam_set_error(SLAM_ERR_HIP, "radius %s launch failed: %s", what, hipGetErrorString(e));
     return SLAM_OK;
 }
 
@@ -517,14 +444,15 @@ static int radius_search(slam_ctx* ctx, const void* d_query, int64_t N, const vo
         SLAM_HIP(hipStreamSynchronize(ctx->stream));
         return SLAM_OK;
     }
+    static std::atomic<int> once{0};
     int occ = 0;
-    if (int rc = radius_occupancy(&occ)) return rc;
+    if (int rc = slam_occupancy_once((const void*)bf_radius_scan_kernel<false>, &once, &occ)) return rc;
     const radius_plan p = radius_plan_core(ctx->num_cu, occ < SLAM_RADIUS_RESIDENT ? occ : SLAM_RADIUS_RESIDENT, N, M);
     // tables: counts [chunks][N] i32 | len [N] i32 | bsum [B][3] i64 | tot [3] i64 | lq_id [N] i32 | lq_tile_end [N] i64
     const int64_t B = (N + 255) / 256;
-    const uint64_t o_len = radius_align((uint64_t)p.ws), o_bsum = o_len + radius_align(N * 4ull),
-                   o_tot = o_bsum + radius_align(B * 24ull), o_lq = o_tot + 256, o_lqe = o_lq + radius_align(N * 4ull),
-                   tbytes = o_lqe + radius_align(N * 8ull);
+    const uint64_t o_len = slam_align_up((uint64_t)p.ws), o_bsum = o_len + slam_align_up(N * 4ull),
+                   o_tot = o_bsum + slam_align_up(B * 24ull), o_lq = o_tot + 256, o_lqe = o_lq + slam_align_up(N * 4ull),
+                   tbytes = o_lqe + slam_align_up(N * 8ull);
     void* tmem = nullptr;
     if (int rc = radius_tables(ctx, tbytes, &tmem)) return rc;
     char* tb = (char*)tmem;
@@ -554,7 +482,7 @@ static int radius_search(slam_ctx* ctx, const void* d_query, int64_t N, const vo
     bf_radius_prefix_kernel<<<dim3((unsigned)B), block, 0, ctx->stream>>>(cnt, p.chunks, (int)N, len, bsum);
     bf_radius_blocks_kernel<<<dim3(1), block, 0, ctx->stream>>>(bsum, B, tot, d_offsets, (int)N);
     bf_radius_offsets_kernel<<<dim3((unsigned)B), block, 0, ctx->stream>>>(len, (int)N, bsum, d_offsets, lq_id, lq_tile_end);
-    if (int rc = radius_launch_check("count")) return rc;
+    if (int rc = slam_launch_check("radius count")) return rc;
     int64_t h_tot[3] = {0, 0, 0};                                    // entries, long lists, tiles of long lists
     SLAM_HIP(hipMemcpyAsync(h_tot, tot, sizeof(h_tot), hipMemcpyDeviceToHost, ctx->stream));
     SLAM_HIP(hipStreamSynchronize(ctx->stream));
@@ -563,7 +491,7 @@ static int radius_search(slam_ctx* ctx, const void* d_query, int64_t N, const vo
 
     // staging area [total] int2 | long-list tile histograms [tiles][257] i32, in the context's workspace
     const int64_t T = h_tot[0], L = h_tot[1], tiles = h_tot[2];
-    const uint64_t o_hist = radius_align((uint64_t)T * 8);
+    const uint64_t o_hist = slam_align_up((uint64_t)T * 8);
     void* ws = nullptr;
     if (int rc = slam_workspace(ctx, o_hist + (uint64_t)tiles * SLAM_RADIUS_BINS * 4, &ws)) return rc;
     int2* stage = (int2*)ws;
@@ -577,7 +505,7 @@ static int radius_search(slam_ctx* ctx, const void* d_query, int64_t N, const vo
         bf_radius_sort_scan_kernel<<<dim3((unsigned)L), block, 0, ctx->stream>>>(lq_tile_end, ghist);
         bf_radius_sort_scatter_kernel<<<tg, block, 0, ctx->stream>>>(stage, d_offsets, lq_id, lq_tile_end, L, tiles, ghist, d_idx, d_dist);
     }
-    return radius_launch_check("emit / sort");
+    return slam_launch_check("radius emit / sort");
 }
 
 extern "C" int slam_bf_radius_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, float max_distance,
@@ -602,8 +530,8 @@ extern "C" int slam_bf_radius_u256_host(slam_ctx* ctx, const uint8_t* h_query, i
     const int64_t cap = capacity < N * M ? capacity : N * M;         // (no list holds more than M entries)
     const uint64_t qbytes = (uint64_t)N * SLAM_DESC_BYTES, tbytes = (uint64_t)M * SLAM_DESC_BYTES, obytes = (uint64_t)(N + 1) * 8,
                    rbytes = (uint64_t)cap * 4;
-    const uint64_t off_t = radius_align(qbytes), off_o = off_t + radius_align(tbytes), off_i = off_o + radius_align(obytes),
-                   off_d = off_i + radius_align(rbytes), total = off_d + radius_align(rbytes);
+    const uint64_t off_t = slam_align_up(qbytes), off_o = off_t + slam_align_up(tbytes), off_i = off_o + slam_align_up(obytes),
+                   off_d = off_i + slam_align_up(rbytes), total = off_d + slam_align_up(rbytes);
     void *dev = nullptr, *host = nullptr;
     if (int rc = slam_io_arena(ctx, total, total, &dev, &host)) return rc;
     uint8_t* hb = (uint8_t*)host;

@@ -85,12 +85,7 @@ __global__ __launch_bounds__(256) void bf_topk_kernel(const topk_args a) {
     const int pad = K - a.k;                                        // leading slots pinned to key 0
 
     u32 qr[1][8];
-    {
-        const int qi = qbase < N ? qbase : N - 1;                   // clamp: tail lanes compute a duplicate and never store
-        const uint4 x = a.q[2 * (size_t)qi], y = a.q[2 * (size_t)qi + 1];
-        qr[0][0] = x.x; qr[0][1] = x.y; qr[0][2] = x.z; qr[0][3] = x.w;
-        qr[0][4] = y.x; qr[0][5] = y.y; qr[0][6] = y.z; qr[0][7] = y.w;
-    }
+    bf_load_query(a.q, qbase < N ? qbase : N - 1, qr[0]);          // clamp: tail lanes compute a duplicate and never store
     u32 keys[K];
 #pragma unroll
     for (int i = 0; i < K; i++) keys[i] = i < pad ? 0u : SLAM_KEY_NONE;
@@ -130,20 +125,8 @@ __global__ __launch_bounds__(256) void bf_topk_kernel(const topk_args a) {
         int j = 0;
         uint4 a0 = tp[0], c0 = tp[1];
         constexpr int U = SLAM_GROUP_PAIRS;
-        // one group of U rows, read rolling one row ahead through one LDS address + immediate offsets (bf_top2_block)
-        auto group = [&](const u32 (&ini)[1], u32 (&acc)[U][1]) {
-            u32 base = lds_addr(tp + 2 * j);
-#pragma unroll
-            for (int u = 0; u < U; u += 2) {
-                const uint4 a1 = lds_read16(base, (2 * u + 2) * 16), c1 = lds_read16(base, (2 * u + 3) * 16);
-                row_acc<1>(qr, a0, c0, ini, acc[u]);
-                asm volatile("" : "+v"(base) : "v"(acc[u][0]));
-                a0 = lds_read16(base, (2 * u + 4) * 16);
-                c0 = lds_read16(base, (2 * u + 5) * 16);
-                row_acc<1>(qr, a1, c1, ini, acc[u + 1]);
-                asm volatile("" : "+v"(base) : "v"(acc[u + 1][0]));
-            }
-        };
+        // (through a lambda: called directly, the two call sites compile to other code than they did with the read written here)
+        auto group = [&](const u32 (&ini)[1], u32 (&acc)[U][1]) { bf_group_acc<U>(qr, tp, j, a0, c0, ini, acc); };
         // the bound is re-read after 16, 32, 64 and 128 rows of the chunk, later once per tile
         int seg_end = tb == t0 ? 16 : cnt;
         if (tb == t0 && a.cold >= U && (nobound || nobody_published())) {
@@ -197,9 +180,8 @@ __global__ __launch_bounds__(256) void bf_topk_kernel(const topk_args a) {
 #pragma unroll
         for (int i = 0; i < K; i++)
             if (i >= pad) {
-                const u32 key = keys[i];
-                oi[i - pad] = key == SLAM_KEY_NONE ? SLAM_NO_MATCH_IDX : (int)(key & SLAM_KEY_IDX_MASK) + a.train_base;
-                od[i - pad] = key == SLAM_KEY_NONE ? SLAM_NO_MATCH_DIST : (int)(key >> SLAM_KEY_IDX_BITS);
+                oi[i - pad] = bf_key_idx(keys[i], a.train_base);
+                od[i - pad] = bf_key_dist(keys[i]);
             }
     }
 }
@@ -240,9 +222,8 @@ __global__ __launch_bounds__(256) void bf_topk_merge_kernel(const u32* __restric
 #pragma unroll
     for (int i = 0; i < K; i++)
         if (i >= pad) {
-            const u32 key = keys[i];
-            oi[i - pad] = key == SLAM_KEY_NONE ? SLAM_NO_MATCH_IDX : (int)(key & SLAM_KEY_IDX_MASK) + train_base;
-            od[i - pad] = key == SLAM_KEY_NONE ? SLAM_NO_MATCH_DIST : (int)(key >> SLAM_KEY_IDX_BITS);
+            oi[i - pad] = bf_key_idx(keys[i], train_base);
+            od[i - pad] = bf_key_dist(keys[i]);
         }
     if (bound) bound[n] = SLAM_BOUND_IDLE;                          // (the next search is ordered behind this kernel by the stream)
 }
@@ -298,54 +279,41 @@ struct topk_plan {
 };
 
 // A pure function of the CU count, the blocks per CU and the shape (slam_bf_topk_plan_describe exposes it without a device).
-// One round of resident blocks fills the chip: query blocks x chunks = num_cu x resident, chunks of at least one tile, and
-// no more chunks than the partial tables' cap allows.  The plan of the first (largest) pass serves every pass.
+// The chunks are bf_chunk_rule's, of at least one tile and under the partial tables' cap.  The plan of the first (largest)
+// pass serves every pass.
 static topk_plan topk_plan_core(int num_cu, int resident, int64_t N, int64_t M, int k) {
     topk_plan p;
     p.K = topk_width(k);
     p.resident = resident;
     const int64_t PASS = SLAM_MAX_TRAIN_PER_PASS;
     p.passes = (int)((M + PASS - 1) / PASS);
-    const int64_t Mp = M < PASS ? M : PASS;
-    p.qblocks = (int)((N + 255) / 256);
-    const int64_t slots = (int64_t)(num_cu > 0 ? num_cu : 1) * resident;
-    const int64_t qb = p.qblocks > 0 ? p.qblocks : 1;
-    int64_t chunks = (slots + qb - 1) / qb;
-    const int64_t by_rows = (Mp + SLAM_TOPK_MIN_CHUNK - 1) / SLAM_TOPK_MIN_CHUNK;
-    if (chunks > by_rows) chunks = by_rows;
     const int64_t per = N * k * 4;                                  // one chunk's partial table
-    const int64_t by_cap = (int64_t)SLAM_TOPK_WS_CAP / (per > 0 ? per : 1);
-    if (chunks > by_cap) chunks = by_cap;
-    if (chunks < 1) chunks = 1;
-    int64_t rows = (Mp + chunks - 1) / chunks;
-    rows = (rows + 15) / 16 * 16;
-    if (rows < 16) rows = 16;
-    p.chunk = (int)rows;
-    p.chunks = (int)((Mp + rows - 1) / rows);
-    if (p.chunks < 1) p.chunks = 1;
+    const bf_chunks c = bf_chunk_rule(num_cu, resident, N, M < PASS ? M : PASS, SLAM_TOPK_MIN_CHUNK, per, SLAM_TOPK_WS_CAP);
+    p.qblocks = c.qblocks;
+    p.chunks = c.chunks;
+    p.chunk = (int)c.chunk;
     p.ws = p.chunks > 1 ? (int64_t)p.chunks * per : 0;
     return p;
 }
 
-template <int K>
-static int topk_occupancy(int* out) {
-    static std::atomic<int> once{0};                                 // a property of the kernel and the architecture
-    int occ = once.load(std::memory_order_relaxed);
-    if (!occ) {
-        int o = 0;
-        SLAM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, bf_topk_kernel<K>, 256, 0));
-        occ = o > 0 ? o : 1;
-        once.store(occ, std::memory_order_relaxed);
+// f(std::integral_constant<int, K>()) for the instantiation K (topk_width)
+template <typename F>
+static int topk_dispatch(int K, F f) {
+    switch (K) {
+        case 4: return f(std::integral_constant<int, 4>());
+        case 8: return f(std::integral_constant<int, 8>());
+        case 16: return f(std::integral_constant<int, 16>());
+        default: return f(std::integral_constant<int, 32>());
     }
-    *out = occ;
-    return SLAM_OK;
 }
 
 static int topk_make_plan(slam_ctx* ctx, int64_t N, int64_t M, int k, topk_plan* p) {
     const int K = topk_width(k);
     int occ = 0;
-    int rc = K == 4 ? topk_occupancy<4>(&occ) : K == 8 ? topk_occupancy<8>(&occ) : K == 16 ? topk_occupancy<16>(&occ)
-                                                                                             : topk_occupancy<32>(&occ);
+    const int rc = topk_dispatch(K, [&](auto Kc) -> int {
+        static std::atomic<int> once{0};                             // one per instantiation
+        return slam_occupancy_once((const void*)bf_topk_kernel<Kc()>, &once, &occ);
+    });
     if (rc) return rc;
     const int res = topk_resident(K);
     *p = topk_plan_core(ctx->num_cu, occ < res ? occ : res, N, M, k);
@@ -383,42 +351,27 @@ static int topk_pass(slam_ctx* ctx, const topk_plan& p, const void* d_query, int
     const dim3 grid(p.qblocks, chunks), block(256);
     SLAM_HIP(hipGetLastError());
     if (int rc = slam_prof_begin(ctx)) return rc;
-    switch (p.K) {
-        case 4: bf_topk_kernel<4><<<grid, block, 0, ctx->stream>>>(a); break;
-        case 8: bf_topk_kernel<8><<<grid, block, 0, ctx->stream>>>(a); break;
-        case 16: bf_topk_kernel<16><<<grid, block, 0, ctx->stream>>>(a); break;
-        default: bf_topk_kernel<32><<<grid, block, 0, ctx->stream>>>(a); break;
-    }
-    if (chunks > 1) {
-        const dim3 mg((unsigned)((N + 255) / 256));
-        const int tb = (int)train_base;
-        switch (p.K) {
-            case 4: bf_topk_merge_kernel<4><<<mg, block, 0, ctx->stream>>>(part, chunks, (int)N, k, tb, bound, d_idx, d_dist); break;
-            case 8: bf_topk_merge_kernel<8><<<mg, block, 0, ctx->stream>>>(part, chunks, (int)N, k, tb, bound, d_idx, d_dist); break;
-            case 16: bf_topk_merge_kernel<16><<<mg, block, 0, ctx->stream>>>(part, chunks, (int)N, k, tb, bound, d_idx, d_dist); break;
-            default: bf_topk_merge_kernel<32><<<mg, block, 0, ctx->stream>>>(part, chunks, (int)N, k, tb, bound, d_idx, d_dist); break;
-        }
-    }
+    const dim3 mg((unsigned)((N + 255) / 256));
+    topk_dispatch(p.K, [&](auto Kc) -> int {
+        bf_topk_kernel<Kc()><<<grid, block, 0, ctx->stream>>>(a);
+        if (chunks > 1)
+            bf_topk_merge_kernel<Kc()><<<mg, block, 0, ctx->stream>>>(part, chunks, (int)N, k, a.train_base, bound, d_idx, d_dist);
+        return SLAM_OK;
+    });
     if (int rc = slam_prof_end(ctx)) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        (void)bf_state_reset(ctx);
-        return slam_set_error(SLAM_ERR_HIP, "top-k kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return SLAM_OK;
+    const int rc = slam_launch_check("top-k kernel");
+    if (rc) (void)bf_state_reset(ctx);
+    return rc;
 }
 
 static int topk_merge_launch(slam_ctx* ctx, const int32_t* d_idx_parts, const int32_t* d_dist_parts, int64_t G, int64_t N, int k,
                              int32_t* d_idx, int32_t* d_dist) {
     const dim3 grid((unsigned)((N + 255) / 256)), block(256);
-    switch (topk_width(k)) {
-        case 4: bf_merge_topk_kernel<4><<<grid, block, 0, ctx->stream>>>(d_idx_parts, d_dist_parts, (int)G, (int)N, k, d_idx, d_dist); break;
-        case 8: bf_merge_topk_kernel<8><<<grid, block, 0, ctx->stream>>>(d_idx_parts, d_dist_parts, (int)G, (int)N, k, d_idx, d_dist); break;
-        case 16: bf_merge_topk_kernel<16><<<grid, block, 0, ctx->stream>>>(d_idx_parts, d_dist_parts, (int)G, (int)N, k, d_idx, d_dist); break;
-        default: bf_merge_topk_kernel<32><<<grid, block, 0, ctx->stream>>>(d_idx_parts, d_dist_parts, (int)G, (int)N, k, d_idx, d_dist); break;
-    }
-    SLAM_HIP(hipGetLastError());
-    return SLAM_OK;
+    return topk_dispatch(topk_width(k), [&](auto Kc) -> int {
+        bf_merge_topk_kernel<Kc()><<<grid, block, 0, ctx->stream>>>(d_idx_parts, d_dist_parts, (int)G, (int)N, k, d_idx, d_dist);
+        SLAM_HIP(hipGetLastError());
+        return SLAM_OK;
+    });
 }
 
 // slam_bf_knn_u256 without the call lock
@@ -487,8 +440,6 @@ extern "C" int slam_bf_merge_topk(slam_ctx* ctx, const int32_t* d_idx_parts, con
     return topk_merge_launch(ctx, d_idx_parts, d_dist_parts, G, N, K, d_idx, d_dist);
 }
 
-static inline uint64_t topk_align(uint64_t v) { return (v + 255) / 256 * 256; }
-
 // upload, search, download, one stream synchronisation (through the context's host-buffer arena)
 extern "C" int slam_bf_knn_u256_host(slam_ctx* ctx, const uint8_t* h_query, int64_t N, const uint8_t* h_train, int64_t M, int K,
                                      int32_t* h_idx, int32_t* h_dist) {
@@ -500,8 +451,8 @@ extern "C" int slam_bf_knn_u256_host(slam_ctx* ctx, const uint8_t* h_query, int6
     std::lock_guard<std::mutex> lk(ctx->call_mu);
     SLAM_HIP(hipSetDevice(ctx->device));
     const uint64_t qbytes = (uint64_t)N * SLAM_DESC_BYTES, tbytes = (uint64_t)M * SLAM_DESC_BYTES, table = (uint64_t)N * K * 4;
-    const uint64_t off_t = topk_align(qbytes), off_i = off_t + topk_align(tbytes), off_d = off_i + topk_align(table);
-    const uint64_t total = off_d + topk_align(table);
+    const uint64_t off_t = slam_align_up(qbytes), off_i = off_t + slam_align_up(tbytes), off_d = off_i + slam_align_up(table);
+    const uint64_t total = off_d + slam_align_up(table);
     void *dev = nullptr, *host = nullptr;
     if (int rc = slam_io_arena(ctx, total, total, &dev, &host)) return rc;
     uint8_t* hb = (uint8_t*)host;

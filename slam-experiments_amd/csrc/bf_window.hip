@@ -246,28 +246,6 @@ __global__ __launch_bounds__(256) void win_scatter_kernel(const win_args a) {
 
 // ---- exclusive scans of the histograms and the item counts ---------------------------------------------------------
 
-template <typename T>
-__device__ __forceinline__ T win_block_scan(T v, T* lds4, T* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const T y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) lds4[wave] = x;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        before += w < wave ? lds4[w] : 0;
-        all += lds4[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before + x - v;
-}
-
 // one block: exclusive scan of d[0 .. n) in place (each thread a contiguous run), plus `add`
 template <typename T>
 __global__ __launch_bounds__(256) void win_scan_block_kernel(T* __restrict__ d, int64_t n) {
@@ -277,7 +255,7 @@ __global__ __launch_bounds__(256) void win_scan_block_kernel(T* __restrict__ d, 
     T s = 0;
     for (int64_t i = b0; i < b1; i++) s += d[i];
     T all;
-    T run = win_block_scan<T>(s, lds4, &all);
+    T run = bf_block_excl_scan<T>(s, lds4, &all);
     for (int64_t i = b0; i < b1; i++) {
         const T v = d[i];
         d[i] = run;
@@ -293,7 +271,7 @@ __global__ __launch_bounds__(256) void win_scan_sum_kernel(const T* __restrict__
     T s = 0;
     for (int64_t i = p0 + threadIdx.x; i < min(n, p0 + SLAM_WIN_SCAN_PART); i += 256) s += d[i];
     T all;
-    (void)win_block_scan<T>(s, lds4, &all);
+    (void)bf_block_excl_scan<T>(s, lds4, &all);
     if (threadIdx.x == 0) bsum[blockIdx.x] = all;
 }
 
@@ -310,7 +288,7 @@ __global__ __launch_bounds__(256) void win_scan_apply_kernel(T* __restrict__ d, 
         s += v[k];
     }
     T all;
-    T run = bsum[blockIdx.x] + win_block_scan<T>(s, lds4, &all);
+    T run = bsum[blockIdx.x] + bf_block_excl_scan<T>(s, lds4, &all);
 #pragma unroll
     for (int k = 0; k < PER; k++) {
         if (b0 + k < n) d[b0 + k] = run;
@@ -319,9 +297,6 @@ __global__ __launch_bounds__(256) void win_scan_apply_kernel(T* __restrict__ d, 
 }
 
 // ---- the search ----------------------------------------------------------------------------------------------------
-
-// the wave's own LDS tile: its LDS operations complete in order, so waiting for them is all the hand-off between lanes needs
-__device__ __forceinline__ void win_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // One wave per range of work items [it0, it1): 64 queries of one tile (a lane each) against one chunk of its candidates.
 __global__ __launch_bounds__(256) void win_scan_kernel(const win_args a, int64_t capt) {
@@ -362,11 +337,7 @@ __global__ __launch_bounds__(256) void win_scan_kernel(const win_args a, int64_t
         const bool valid = qp < (int64_t)QS[t + 1] - qbase;
         const int qi = valid ? a.qs[qp] : a.qs[(int64_t)QS[t] - qbase];   // (tail lanes: a duplicate that never merges)
         u32 qr[8];
-        {
-            const uint4 x = a.q[2 * (size_t)qi], y = a.q[2 * (size_t)qi + 1];
-            qr[0] = x.x; qr[1] = x.y; qr[2] = x.z; qr[3] = x.w;
-            qr[4] = y.x; qr[5] = y.y; qr[6] = y.z; qr[7] = y.w;
-        }
+        bf_load_query(a.q, qi, qr);
         const float2 qxy = a.qxy[qi];
         u32 b1 = SLAM_KEY_NONE, b2 = SLAM_KEY_NONE;
         // the candidate positions [cc * CHUNK, (cc + 1) * CHUNK) of the concatenated runs
@@ -399,11 +370,11 @@ __global__ __launch_bounds__(256) void win_scan_kernel(const win_args a, int64_t
             }
             for (int base = s0; base < s1; base += SLAM_WIN_Q) {
                 const int n = min(SLAM_WIN_Q, s1 - base);
-                win_lds_sync();                                  // (the previous tile has been read)
+                bf_wave_lds_sync();                                  // (the previous tile has been read)
                 lm[lane] = nm;
                 la[lane] = na;
                 lb[lane] = nb;
-                win_lds_sync();
+                bf_wave_lds_sync();
                 const int nx = base + SLAM_WIN_Q + lane;
                 if (nx < s1) {
                     nm = a.tsm[nx];
@@ -445,14 +416,12 @@ __global__ __launch_bounds__(256) void win_decode_kernel(const unsigned long lon
     const unsigned long long v = best[q];
     const u32 key[2] = {(u32)(v >> 32), (u32)v};
     for (int s = 0; s < k; s++) {
-        idx[(size_t)q * k + s] = key[s] == SLAM_KEY_NONE ? SLAM_NO_MATCH_IDX : (int)(key[s] & SLAM_KEY_IDX_MASK);
-        dist[(size_t)q * k + s] = key[s] == SLAM_KEY_NONE ? SLAM_NO_MATCH_DIST : (int)(key[s] >> SLAM_KEY_IDX_BITS);
+        idx[(size_t)q * k + s] = bf_key_idx(key[s], 0);
+        dist[(size_t)q * k + s] = bf_key_dist(key[s]);
     }
 }
 
 // ---- host side -----------------------------------------------------------
-
-static inline uint64_t win_align(uint64_t v) { return (v + 255) / 256 * 256; }
 
 struct win_plan {
     int side;               // cells per axis at most
@@ -487,15 +456,15 @@ static win_plan win_plan_core(int num_cu, int64_t N, int64_t M, int64_t cells) {
     p.blocks = (int)(blocks < 1 ? 1 : blocks);
     p.o_par = 0;
     p.o_part = 256;
-    p.o_cnt = p.o_part + win_align(SLAM_WIN_BOUND_BLOCKS * 8 * 4);
-    p.o_items = p.o_cnt + win_align((uint64_t)(p.capc + p.capt) * 8);             // cnt and cur
-    p.o_bsa = p.o_items + win_align((uint64_t)(p.capt + 1) * 8);
-    p.o_bsb = p.o_bsa + win_align((uint64_t)(p.parts_a + 1) * 4);
-    p.o_tsd = p.o_bsb + win_align((uint64_t)(p.parts_b + 1) * 8);
-    p.o_tsm = p.o_tsd + win_align((uint64_t)M * SLAM_DESC_BYTES);
-    p.o_qs = p.o_tsm + win_align((uint64_t)M * 16);
-    p.o_best = p.o_qs + win_align((uint64_t)N * 4);
-    p.bytes = p.o_best + win_align((uint64_t)N * 8);
+    p.o_cnt = p.o_part + slam_align_up(SLAM_WIN_BOUND_BLOCKS * 8 * 4);
+    p.o_items = p.o_cnt + slam_align_up((uint64_t)(p.capc + p.capt) * 8);             // cnt and cur
+    p.o_bsa = p.o_items + slam_align_up((uint64_t)(p.capt + 1) * 8);
+    p.o_bsb = p.o_bsa + slam_align_up((uint64_t)(p.parts_a + 1) * 4);
+    p.o_tsd = p.o_bsb + slam_align_up((uint64_t)(p.parts_b + 1) * 8);
+    p.o_tsm = p.o_tsd + slam_align_up((uint64_t)M * SLAM_DESC_BYTES);
+    p.o_qs = p.o_tsm + slam_align_up((uint64_t)M * 16);
+    p.o_best = p.o_qs + slam_align_up((uint64_t)N * 4);
+    p.bytes = p.o_best + slam_align_up((uint64_t)N * 8);
     return p;
 }
 
@@ -513,12 +482,6 @@ extern "C" int slam_bf_window_plan_describe(int num_cu, int64_t N, int64_t M, in
     const int64_t v[SLAM_WIN_PLAN] = {p.side, (int64_t)p.side * p.side, p.capt - 1, SLAM_WIN_Q, SLAM_WIN_CHUNK, p.blocks,
                                       p.parts_a, p.parts_b, (int64_t)p.bytes, SLAM_WIN_TILE_MAX};
     memcpy(h_plan, v, sizeof(v));
-    return SLAM_OK;
-}
-
-static int win_launch_check(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return slam_set_error(SLAM_ERR_HIP, "window %s launch failed: %s", what, hipGetErrorString(e));
     return SLAM_OK;
 }
 
@@ -593,12 +556,12 @@ static int window_search(slam_ctx* ctx, const void* d_query, int64_t N, const vo
     win_scan<int32_t>(ctx, a.cnt, p.capc + p.capt, p.parts_a, (int32_t*)(w + p.o_bsa));
     win_scatter_kernel<<<gb, 256, 0, ctx->stream>>>(a);
     win_scan<int64_t>(ctx, a.items, p.capt + 1, p.parts_b, (int64_t*)(w + p.o_bsb));
-    if (int rc = win_launch_check("binning")) return rc;
+    if (int rc = slam_launch_check("window binning")) return rc;
     if (int rc = slam_prof_begin(ctx)) return rc;
     win_scan_kernel<<<(unsigned)p.blocks, 256, 0, ctx->stream>>>(a, p.capt);
     if (int rc = slam_prof_end(ctx)) return rc;
     win_decode_kernel<<<(unsigned)((N + 255) / 256), 256, 0, ctx->stream>>>(a.best, (int)N, k, d_idx, d_dist);
-    return win_launch_check("search");
+    return slam_launch_check("window search");
 }
 
 extern "C" int slam_bf_window_knn_u256(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M,
@@ -621,8 +584,8 @@ extern "C" int slam_bf_window_knn_u256_host(slam_ctx* ctx, const uint8_t* h_quer
     SLAM_HIP(hipSetDevice(ctx->device));
     const uint64_t qb = (uint64_t)N * SLAM_DESC_BYTES, tb = (uint64_t)M * SLAM_DESC_BYTES, qxb = (uint64_t)N * 8,
                    txb = (uint64_t)M * 8, rb = h_radius ? (uint64_t)M * 4 : 0, ob = (uint64_t)N * k * 4;
-    const uint64_t o_t = win_align(qb), o_qx = o_t + win_align(tb), o_tx = o_qx + win_align(qxb), o_r = o_tx + win_align(txb),
-                   in_bytes = o_r + rb, o_i = win_align(in_bytes), o_d = o_i + win_align(ob), total = o_d + win_align(ob);
+    const uint64_t o_t = slam_align_up(qb), o_qx = o_t + slam_align_up(tb), o_tx = o_qx + slam_align_up(qxb), o_r = o_tx + slam_align_up(txb),
+                   in_bytes = o_r + rb, o_i = slam_align_up(in_bytes), o_d = o_i + slam_align_up(ob), total = o_d + slam_align_up(ob);
     void *dev = nullptr, *host = nullptr;
     if (int rc = slam_io_arena(ctx, total, total, &dev, &host)) return rc;
     uint8_t* hb = (uint8_t*)host;

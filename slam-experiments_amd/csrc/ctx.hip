@@ -209,6 +209,45 @@ int slam_io_arena(slam_ctx* ctx, uint64_t dev_bytes, uint64_t host_bytes, void**
     return SLAM_OK;
 }
 
+int slam_launch_check(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return slam_set_error(SLAM_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+    return SLAM_OK;
+}
+
+int slam_occupancy_once(const void* kernel, std::atomic<int>* once, int* out) {
+    int occ = once->load(std::memory_order_relaxed);
+    if (!occ) {
+        int o = 0;
+        SLAM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, 256, 0));
+        occ = o > 0 ? o : 1;
+        once->store(occ, std::memory_order_relaxed);
+    }
+    *out = occ;
+    return SLAM_OK;
+}
+
+bf_chunks bf_chunk_rule(int num_cu, int resident, int64_t N, int64_t rows, int64_t min_chunk, int64_t bytes_per_chunk,
+                        int64_t cap_bytes) {
+    bf_chunks c;
+    c.qblocks = (int)((N + 255) / 256);
+    const int64_t slots = (int64_t)(num_cu > 0 ? num_cu : 1) * resident;
+    const int64_t qb = c.qblocks > 0 ? c.qblocks : 1;
+    int64_t chunks = (slots + qb - 1) / qb;
+    const int64_t by_rows = (rows + min_chunk - 1) / min_chunk;
+    if (chunks > by_rows) chunks = by_rows;
+    const int64_t by_cap = cap_bytes / (bytes_per_chunk > 0 ? bytes_per_chunk : 1);
+    if (chunks > by_cap) chunks = by_cap;
+    if (chunks < 1) chunks = 1;
+    int64_t chunk = (rows + chunks - 1) / chunks;
+    chunk = (chunk + 15) / 16 * 16;
+    if (chunk < 16) chunk = 16;
+    c.chunk = chunk;
+    c.chunks = (int)((rows + chunk - 1) / chunk);
+    if (c.chunks < 1) c.chunks = 1;
+    return c;
+}
+
 extern "C" int slam_index_errors(slam_ctx* ctx, int64_t* count) {
     SLAM_REQUIRE(ctx && count, "slam_index_errors: null argument");
     SLAM_HIP(hipSetDevice(ctx->device));

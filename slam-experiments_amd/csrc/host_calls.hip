@@ -14,7 +14,6 @@
 #include <string.h>
 #include <vector>
 
-static inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
 // Pinned host memory is device-accessible: for frame-sized inputs the kernels pull the few KB over PCIe and push
 // the result back themselves, which measured 3-6 us (7-13 %) faster per call than two more copy calls
@@ -30,8 +29,8 @@ extern "C" int slam_bf_knn2_u256_host(slam_ctx* ctx, const uint8_t* h_query, int
     std::lock_guard<std::mutex> lk(ctx->call_mu);
     SLAM_HIP(hipSetDevice(ctx->device));
     const uint64_t qbytes = (uint64_t)N * SLAM_DESC_BYTES, tbytes = (uint64_t)M * SLAM_DESC_BYTES;
-    const uint64_t off_t = align_up(qbytes, 256), off_i = off_t + align_up(tbytes, 256);
-    const uint64_t off_d = off_i + (uint64_t)N * 8, off_k = off_d + (uint64_t)N * 8, total = align_up(off_k + (uint64_t)N, 256);
+    const uint64_t off_t = slam_align_up(qbytes, 256), off_i = off_t + slam_align_up(tbytes, 256);
+    const uint64_t off_d = off_i + (uint64_t)N * 8, off_k = off_d + (uint64_t)N * 8, total = slam_align_up(off_k + (uint64_t)N, 256);
     void *dev = nullptr, *host = nullptr;
     if (int rc = slam_io_arena(ctx, total, total, &dev, &host)) return rc;
     uint8_t* hb = (uint8_t*)host;
@@ -87,10 +86,10 @@ extern "C" int slam_bf_match_host(slam_ctx* ctx, const uint8_t* h_query, int64_t
     }
     // device arena: [query | train | idx int32[N,2] | dist int32[N,2] | keep u8[N]]; staging mirrors it
     // (crossCheck, mode 3: ... | dist int32[N,2] | reverse tables int32[M,2] x 2 | idx int32[N] | dist int32[N])
-    const uint64_t off_t = align_up(qbytes, 256), off_i = off_t + align_up(tbytes, 256);
+    const uint64_t off_t = slam_align_up(qbytes, 256), off_i = off_t + slam_align_up(tbytes, 256);
     const uint64_t off_d = off_i + (uint64_t)N * 8, off_k = off_d + (uint64_t)N * 8;
-    const uint64_t off_r = align_up(off_k, 256), off_o = align_up(off_r + (uint64_t)M * 16, 256);
-    const uint64_t total = mode == 3 ? align_up(off_o + (uint64_t)N * 8, 256) : align_up(off_k + N, 256);
+    const uint64_t off_r = slam_align_up(off_k, 256), off_o = slam_align_up(off_r + (uint64_t)M * 16, 256);
+    const uint64_t total = mode == 3 ? slam_align_up(off_o + (uint64_t)N * 8, 256) : slam_align_up(off_k + N, 256);
     void *dev = nullptr, *host = nullptr;
     if (int rc = slam_io_arena(ctx, total, total, &dev, &host)) return rc;
     uint8_t* hb = (uint8_t*)host;
@@ -229,9 +228,9 @@ extern "C" int slam_pose_optimize_host_f64(slam_ctx* ctx, const double* h_pose_i
     SLAM_HIP(hipSetDevice(ctx->device));
     // in: [pose 12 | points 3O | pad | meas 2O]   out: [pose 12 | chi2 O | stats (2 x int32) | inlier u8[O]]
     const uint64_t o = (uint64_t)O;
-    const uint64_t off_p = 96, off_m = align_up(off_p + 24 * o, 16), in_bytes = align_up(off_m + 16 * o, 256);
+    const uint64_t off_p = 96, off_m = slam_align_up(off_p + 24 * o, 16), in_bytes = slam_align_up(off_m + 16 * o, 256);
     const uint64_t out_pose = in_bytes, out_chi2 = out_pose + 96, out_stats = out_chi2 + 8 * o, out_inl = out_stats + 8;
-    const uint64_t total = align_up(out_inl + o + 1, 256);
+    const uint64_t total = slam_align_up(out_inl + o + 1, 256);
     void *dev = nullptr, *host = nullptr;
     if (int rc = slam_io_arena(ctx, total, total, &dev, &host)) return rc;
     uint8_t* hb = (uint8_t*)host;
@@ -300,12 +299,12 @@ extern "C" int slam_ba_optimize_host_f64(slam_ctx* ctx, int64_t K, int64_t L, in
     std::lock_guard<std::mutex> lk(ctx->call_mu);
     SLAM_HIP(hipSetDevice(ctx->device));
     // staging layout (16-byte aligned pieces): obs_pose | obs_point | meas | pt_ptr | pt_obs | ps_ptr | ps_obs | free | poses2 | points2 | stats
-    const uint64_t o4 = align_up((uint64_t)(O ? O : 1) * 4, 16);
-    const uint64_t off_op = 0, off_ol = off_op + o4, off_m = off_ol + o4, off_ptp = off_m + align_up((uint64_t)(O ? O : 1) * 16, 16);
-    const uint64_t off_pto = off_ptp + align_up((uint64_t)(L + 1) * 4, 16), off_psp = off_pto + o4;
-    const uint64_t off_pso = off_psp + align_up((uint64_t)(K + 1) * 4, 16), off_fr = off_pso + o4;
-    const uint64_t off_T = off_fr + align_up((uint64_t)(n_free ? n_free : 1) * 4, 16), off_X = off_T + align_up((uint64_t)K * 192, 16);
-    const uint64_t off_st = off_X + align_up((uint64_t)L * 48, 16), in_bytes = off_st, total = off_st + 64;
+    const uint64_t o4 = slam_align_up((uint64_t)(O ? O : 1) * 4, 16);
+    const uint64_t off_op = 0, off_ol = off_op + o4, off_m = off_ol + o4, off_ptp = off_m + slam_align_up((uint64_t)(O ? O : 1) * 16, 16);
+    const uint64_t off_pto = off_ptp + slam_align_up((uint64_t)(L + 1) * 4, 16), off_psp = off_pto + o4;
+    const uint64_t off_pso = off_psp + slam_align_up((uint64_t)(K + 1) * 4, 16), off_fr = off_pso + o4;
+    const uint64_t off_T = off_fr + slam_align_up((uint64_t)(n_free ? n_free : 1) * 4, 16), off_X = off_T + slam_align_up((uint64_t)K * 192, 16);
+    const uint64_t off_st = off_X + slam_align_up((uint64_t)L * 48, 16), in_bytes = off_st, total = off_st + 64;
     uint64_t work = 0;
     if (int rc = slam_ba_optimize_workspace(K, L, O, &work)) return rc;
     void *dev = nullptr, *host = nullptr, *ws = nullptr;

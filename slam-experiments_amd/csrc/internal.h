@@ -84,6 +84,22 @@ int slam_set_error(int code, const char* fmt, ...);
 int slam_workspace(slam_ctx* ctx, uint64_t bytes, void** out);
 // device arena + pinned staging of at least these sizes for one host-buffer call (stream-synchronising when they grow)
 int slam_io_arena(slam_ctx* ctx, uint64_t dev_bytes, uint64_t host_bytes, void** dev, void** host);
+// v rounded up to a multiple of a: the blocks of a workspace or staging layout start on 256 bytes
+static inline uint64_t slam_align_up(uint64_t v, uint64_t a = 256) { return (v + a - 1) / a * a; }
+// hipGetLastError as the library's error "<what> launch failed: <HIP's text>"
+int slam_launch_check(const char* what);
+// blocks of `kernel` (256 threads, no dynamic LDS) one CU holds: a property of the kernel and the architecture, queried
+// once and kept in the kernel's own `once`
+int slam_occupancy_once(const void* kernel, std::atomic<int>* once, int* out);
+// The chunk rule of the top-k and radius searches: one round of resident blocks fills the chip (query blocks x chunks =
+// num_cu x resident), chunks of at least min_chunk rows, no more chunks than cap_bytes of bytes_per_chunk tables allow,
+// rows per chunk a multiple of 16.
+struct bf_chunks {
+    int qblocks, chunks;
+    int64_t chunk;      // rows per chunk
+};
+bf_chunks bf_chunk_rule(int num_cu, int resident, int64_t N, int64_t rows, int64_t min_chunk, int64_t bytes_per_chunk,
+                        int64_t cap_bytes);
 // slam_bf_knn2_u256 that also leaves a copy of the query rows at d_keep (32*N bytes of device memory; M must be > 0
 // for the copy to happen: with no train rows no kernel reads the queries)
 int slam_bf_knn2_keep(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, int64_t train_base,
