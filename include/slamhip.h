@@ -22,6 +22,8 @@
  *                          pose_estimation_2d2d and triangulation (utils.py:10-55)
  *   slam_pnp_*             cv2.solvePnPRansac (P3P); no call site in the reference (nearest:
  *                          Frontend._reinitialize_from_keyframe, frontend.py:223-229)
+ *   slam_hg_*              cv2.findHomography / decomposeHomographyMat and the H / E model
+ *                          choice: the unwritten branch of pose_estimation_2d2d (utils.py:27-29)
  *   slam_orb_*             cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26),
  *                          called from Frontend._detect_features (frontend.py:245)
  *   slam_comm_*            no reference counterpart (the reference is single
@@ -517,6 +519,97 @@ SLAM_API int slam_pnp_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offs
                                  const double* d_px, int64_t M, double fx, double fy, double cx, double cy, int H,
                                  double threshold_px, uint64_t seed, double* d_pose, uint8_t* d_inlier,
                                  int32_t* d_stats);
+
+/* ---- homography (f64): the unwritten branch of pose_estimation_2d2d (utils.py:27-29), batched ---------------------------
+ * utils.py:27-29 raises NotImplementedError above a commented-out cv2.findHomography(source_pts, query_pts, method=RANSAC,
+ * ransacReprojThreshold=3).  Conventions as the two-view section: points 1 = source_pts, points 2 = query_pts, H [9]
+ * row-major h0..h8 with p2 ~ H p1 in PIXELS, poses [12] row-major 3x4 with X2 = R X1 + t, |t| = 1, plane normals n in
+ * frame 1 (n . X1 = d > 0 on the plane, H ~ K (R + t n^T / d) K^-1).  PARITY UNPINNED against OpenCV (absent here):
+ * restated from the algorithms' definitions; OpenCV's own draws, its early termination and its refit on the inliers
+ * (Levenberg-Marquardt) are not reproduced.  Only + - * / sqrt are used, none of them fused: a host build of the same
+ * source gives the same bits.  All calls are asynchronous on the ctx stream; workspace comes from the ctx block, nothing
+ * is allocated per call. */
+
+/* The four-point minimal solver on its own (what cv2.findHomography runs per RANSAC sample): d_p1 / d_p2 [S,4,2] in any
+ * units (pixels are fine: the points are Hartley-normalised inside), d_H [S,9] with p2 ~ H p1, Frobenius norm 1, the sign
+ * that makes the projective weights h6 x + h7 y + h8 of all four sample points positive; d_ok int32 [S].  The null
+ * vector of the 8x9 system is taken in closed form by cofactors (four points in general position are a projective
+ * basis: with p_i, q_i the normalised homogeneous points, the one opposite the largest triangle taken as the fourth, l = adj([p0 p1 p2]) p3, m = adj([q0 q1 q2]) q3, both from
+ * coordinate differences, H_n = sum over cyclic (i,j,k) of (m_i l_j l_k) q_i (p_j x p_k)^T), so no entry of H is assumed
+ * non-zero and there is no elimination order.  No model (ok = 0, H = 0): any three of the four points collinear or
+ * repeated in either image (sin^2 of an angle of the triangle below 1e-20); a triple with opposite orientation in the
+ * two images (OpenCV's subset check); a NaN / inf coordinate or squared coordinates that sum to 1e200 or more (1e150).
+ * Every returned H is finite. */
+SLAM_API int slam_hg_fourpoint_f64(slam_ctx* ctx, int64_t S, const double* d_p1, const double* d_p2, double* d_H,
+                                   int32_t* d_ok);
+
+/* cv2.findHomography(source_pts, query_pts, cv2.RANSAC, threshold_px) for B pairs in one call, in pixels, without
+ * intrinsics (the reference's branch for camera=None).  Pair b owns the matches [d_offsets[b], d_offsets[b+1]) of
+ * d_px1 / d_px2 [M,2]; d_offsets int32 [B+1] under the contract of slam_pose_optimize_batch_f64 (a table that is not
+ * ascending or leaves [0, M] never causes an access outside the arrays: the pair shrinks to the part inside and
+ * slam_index_errors counts it).  B <= 65535.  Per pair: H hypotheses (1 <= H <= 2^20), no early termination.
+ * Hypothesis h draws four DISTINCT indices of the pair's n matches with the generator stated at
+ * slam_tv_essential_ransac_f64 (splitmix, word(seed, h, d), index(d) = ((word(seed, h, d) >> 32) * n) >> 32,
+ * d = 0, 1, 2, ...: an index already drawn is skipped, until there are four, in that order).  The pair index b is NOT
+ * mixed in.  Every hypothesis with a model is scored on all n matches, without fused operations in exactly this order
+ * (point 1 (x, y), point 2 (u, v)):
+ *     w = (h6*x + h7*y) + h8;   du = ((h0*x + h1*y) + h2) / w - u;   dv = ((h3*x + h4*y) + h5) / w - v;
+ *   inlier iff w > 0 and du*du + dv*dv < threshold_px * threshold_px (OpenCV's one-way transfer error; the reference's
+ *   comment has 3).  Winner: most inliers, ties to the lower hypothesis - found with packed integer keys, so the result
+ *   is bit-identical for given (matches, H, threshold, seed) whatever B and whatever order the workgroups finish in.  The
+ *   winning hypothesis is solved again when the result is written.  There is NO refit on the inliers.
+ * Outputs: d_H [B,9] the winner, d_inlier uint8 [M] its mask (entries outside every pair: 0), d_stats int32 [B,4] =
+ * {inlier count, winning hypothesis, 0, number of hypotheses that gave a model}.  A pair of fewer than 4 matches yields
+ * H = 0, mask 0, stats {0, -1, -1, 0}; one where no hypothesis gave a model H = 0, mask 0, {0, -1, -1, 0}; neither is
+ * an error.  Non-finite coordinates are data: such a match is never an inlier, a hypothesis that drew one yields no
+ * model, d_H is always finite, and one pair's matches never change another pair's result. */
+SLAM_API int slam_hg_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_px1,
+                                const double* d_px2, int64_t M, int H, double threshold_px, uint64_t seed, double* d_H,
+                                uint8_t* d_inlier, int32_t* d_stats);
+
+/* cv2.decomposeHomographyMat(H, K) and the cheirality vote of cv2.recoverPose, for B pairs (offsets as above; one
+ * workgroup per pair).  Hn = K^-1 H K: G = H K by columns (g.0 = fx h.0, g.1 = fy h.1, g.2 = (cx h.0 + cy h.1) + h.2), then
+ * rows Hn0 = (G0 - cx G2) / fx, Hn1 = (G1 - cy G2) / fy, Hn2 = G2.  Its singular values s1 >= s2 >= s3 (d_sv [B,3], before
+ * any scaling) are the square roots of the eigenvalues of Hn^T Hn by cyclic Jacobi, v1 / v3 the eigenvectors of s1 / s3,
+ * each with its largest-magnitude component (first of equals) positive, v2 = v3 x v1.  Hs = +-Hn / s2, the sign for which
+ * x2^T Hs x1 > 0 holds for more of the matches with d_inlier_in != 0 (null: all) than x2^T Hs x1 < 0 (a tie: +).
+ * Candidates (Ma, Soatto, Kosecka, Sastry): with a = sqrt(1 - (s3/s2)^2), b = sqrt((s1/s2)^2 - 1), ua = unit(a v1 + b v3),
+ * ub = unit(a v1 - b v3); per u: n = v2 x u, w1 = unit(Hs v2), w2 = unit(Hs u - (w1 . Hs u) w1), w3 = w1 x w2,
+ * R = w1 v2^T + w2 u^T + w3 n^T (orthonormal, det +1, to rounding), t = unit((Hs - R) n), and (t, n) take the sign that
+ * makes the largest-magnitude component of n positive.  Ra is the rotation of ua.  d_pose_all [B,4,12] / d_normal_all
+ * [B,4,3] hold (Ra, ta, na), (Ra, -ta, -na), (Rb, tb, nb), (Rb, -tb, -nb).  Each candidate triangulates the selected
+ * matches exactly as slam_tv_triangulate_f64 does (P1 = [I|0], P2 = [R|t], normalised coordinates) and counts the points
+ * with depth in (0, distance_thresh) in both cameras: d_count int32 [B,4].  Most points win, ties to the lower candidate:
+ * d_pose [B,12], d_inlier_out uint8 [M] (good under the winner; outside every pair or not selected: 0), d_stats int32
+ * [B,4] = {best count, best candidate, second-best count, number of candidates}: best = second-best is the two-fold
+ * ambiguity of a plane seen fronto-parallel, and is reported, not hidden.
+ * Rotation only: (s1 - s3) / s2 < 1e-9 (the numpy reference measures 2.4e-16 on a camera turning on the spot and 1.25e-6 on a
+ * baseline of 1e-6 depths) returns ONE candidate (R, 0) with n = 0, R = U V^T the nearest rotation of Hs, counts 0, mask 0,
+ * stats {0, -2, 0, 1}.  H = 0, a NaN entry, a sum of squares of H or Hn that is not a positive finite double, or an s2
+ * that is not one: the identity pose, no candidates (all zero), d_sv = 0, stats {0, -1, 0, 0}. */
+SLAM_API int slam_hg_decompose_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_px1,
+                                   const double* d_px2, int64_t M, double fx, double fy, double cx, double cy,
+                                   const double* d_H, const uint8_t* d_inlier_in, double distance_thresh,
+                                   double* d_pose_all, double* d_normal_all, int32_t* d_count, double* d_pose,
+                                   double* d_sv, uint8_t* d_inlier_out, int32_t* d_stats);
+
+/* The model scores of ORB-SLAM's initialiser (Mur-Artal et al. 2015, IV) for B pairs (offsets as above), every match of
+ * the pair, in pixels.  With T(A; x, y -> u, v) = du*du + dv*dv of the transfer stated at slam_hg_ransac_f64 under the
+ * matrix A, and s2 = sigma * sigma:
+ *   S_H: the terms T(H; p1 -> p2) / s2 and T(A; p2 -> p1) / s2, A the adjugate of H entry by entry
+ *        a0 = h4*h8 - h5*h7; a1 = h2*h7 - h1*h8; a2 = h1*h5 - h2*h4; a3 = h5*h6 - h3*h8; a4 = h0*h8 - h2*h6;
+ *        a5 = h2*h3 - h0*h5; a6 = h3*h7 - h4*h6; a7 = h1*h6 - h0*h7; a8 = h0*h4 - h1*h3;   gate 5.991;
+ *   S_E: F = K^-T E K^-1 (columns of E K^-1: a.0 = e.0 / fx, a.1 = e.1 / fy, a.2 = e.2 - (cx a.0 + cy a.1); rows of F:
+ *        F0 = A0 / fx, F1 = A1 / fy, F2 = A2 - (cx F0 + cy F1));  l = F p1: l0 = (f0*x + f1*y) + f2, l1, l2 alike;
+ *        m0 = (f0*u + f3*v) + f6, m1 = (f1*u + f4*v) + f7;  r = (u*l0 + v*l1) + l2;  the terms (r*r / (l0*l0 + l1*l1)) / s2
+ *        and (r*r / (m0*m0 + m1*m1)) / s2;   gate 3.841.
+ * A term c below its gate contributes (int64)((5.991 - c) * 1048576.0), any other (NaN too) nothing; the contributions are
+ * summed in 64-bit integers, so a sum is exact and independent of the order in which lanes finish.  d_score int64 [B,2] =
+ * {S_H, S_E}; d_ratio [B] = (double)S_H / (double)(S_H + S_E), 0 if both are 0.  H = 0 or E = 0 scores 0. */
+SLAM_API int slam_hg_model_score_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_px1,
+                                     const double* d_px2, int64_t M, double fx, double fy, double cx, double cy,
+                                     const double* d_H, const double* d_E, double sigma, int64_t* d_score,
+                                     double* d_ratio);
 
 /* ---- ORB feature extraction (orb.hip): cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26), which
  * Frontend._detect_features calls on every frame with a mask (frontend.py:245) -------------------------------------------

@@ -34,6 +34,18 @@ from .matching import (  # noqa: F401
     window_match_arrays,
     window_match_filtered,
 )
+from .homography import (  # noqa: F401
+    decompose_homography_arrays,
+    decompose_homography_batch,
+    decompose_homography_offsets,
+    estimate_two_view_auto,
+    find_homography_arrays,
+    find_homography_batch,
+    find_homography_offsets,
+    fourpoint_homography_arrays,
+    model_scores_offsets,
+    verify_pairs_auto,
+)
 from .orb import (  # noqa: F401
     OrbExtractor,
     OrbFeatureDetector,

@@ -109,6 +109,14 @@ SIGNATURES = {
     "slam_pnp_p3p_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "slam_pnp_ransac_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double,
                                     c_int, c_double, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "slam_hg_fourpoint_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_hg_ransac_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_uint64, c_void_p,
+                                   c_void_p, c_void_p]),
+    "slam_hg_decompose_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double,
+                                      c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    "slam_hg_model_score_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double,
+                                        c_double, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "slam_pg_workspace": (c_int, [c_int64, c_int64, POINTER(c_uint64)]),
     "slam_pg_plan": (c_int, [c_int64, c_int64, POINTER(c_int32)]),
     "slam_pg_linearize_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
