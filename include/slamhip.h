@@ -24,6 +24,8 @@
  *                          Frontend._reinitialize_from_keyframe, frontend.py:223-229)
  *   slam_hg_*              cv2.findHomography / decomposeHomographyMat and the H / E model
  *                          choice: the unwritten branch of pose_estimation_2d2d (utils.py:27-29)
+ *   slam_sim3_*            ORB-SLAM's Sim3Solver (Horn three-point RANSAC) and a least-squares refit; no call
+ *                          site in the reference (nearest: euroc.py:63-66 compares unaligned translations)
  *   slam_orb_*             cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26),
  *                          called from Frontend._detect_features (frontend.py:245)
  *   slam_comm_*            no reference counterpart (the reference is single
@@ -610,6 +612,82 @@ SLAM_API int slam_hg_model_score_f64(slam_ctx* ctx, int64_t B, const int32_t* d_
                                      const double* d_px2, int64_t M, double fx, double fy, double cx, double cy,
                                      const double* d_H, const double* d_E, double sigma, int64_t* d_score,
                                      double* d_ratio);
+
+/* ---- Sim(3) alignment of map points (f64): ORB-SLAM's Sim3Solver and a least-squares refit, batched ----------------------
+ * A monocular map drifts in scale, so the constraint between two keyframes that each hold their own copy of the same map
+ * points is a similarity.  The reference has NO call site: it closes no loops, and its driver compares the estimated
+ * translation with the ground truth without any alignment (euroc.py:63-66).  Conventions: the two copies of the matched
+ * map points are d_X1 / d_X2 [M,3], each in its own camera frame; a model is [13]: the row-major 3x4 [R | t] (like d_pose
+ * above) followed by s, and means X2 = s R X1 + t with R orthonormal, det R = +1, s > 0.  R is the rotation of the unit
+ * quaternion that is the eigenvector of the largest eigenvalue of Horn's symmetric 4x4 matrix (Horn 1987), found by cyclic
+ * Jacobi with a fixed number of sweeps; s = trace(R^T M) / sum |x1 - c1|^2 with M = sum (x2 - c2)(x1 - c1)^T (Umeyama's
+ * least-squares scale); t = c2 - s R c1.  A quaternion cannot express a reflection: mirror-image point sets get the best
+ * proper rotation.  PARITY UNPINNED against ORB-SLAM's Sim3Solver and OpenCV (both absent here): restated from the
+ * algorithm's definition; Sim3Solver's own draws, its early termination and its per-octave sigma table are not reproduced
+ * (d_sigma2 is where a caller puts the latter).  Only + - * / sqrt are used, none of them fused: a host build of the same
+ * source gives the same bits.  All calls are asynchronous on the ctx stream; workspace comes from the ctx block, nothing
+ * is allocated per call. */
+
+/* The three-point minimal solver on its own: d_X1 / d_X2 [S,3,3] -> d_model [S,13], d_ok int32 [S].  fix_scale != 0 forces
+ * s = 1 (ORB-SLAM's mbFixScale: stereo / RGB-D).  No model (ok = 0, the identity with s = 1): a repeated or collinear
+ * triple in either set (sin^2 of an angle of the triangle below 1e-20, the rule of slam_pnp_p3p_f64); NaN / inf
+ * coordinates or coordinates whose squares sum to 1e200 or more (1e150); a scale that is not finite and positive. */
+SLAM_API int slam_sim3_threepoint_f64(slam_ctx* ctx, int64_t S, const double* d_X1, const double* d_X2, int fix_scale,
+                                      double* d_model, int32_t* d_ok);
+
+/* Sim3Solver for B candidates in one call.  Candidate b owns the correspondences [d_offsets[b], d_offsets[b+1]) of d_X1 /
+ * d_X2 [M,3]; d_offsets int32 [B+1] under the contract of slam_pose_optimize_batch_f64 (a table that is not ascending or
+ * leaves [0, M] never causes an access outside the arrays: the candidate shrinks to the part inside and slam_index_errors
+ * counts it).  B <= 65535.  Per candidate: H hypotheses (1 <= H <= 2^20), no early termination.  Hypothesis h draws three
+ * DISTINCT indices of the candidate's n correspondences with the generator stated at slam_tv_essential_ransac_f64
+ * (splitmix, word(seed, h, d), index(d) = ((word(seed, h, d) >> 32) * n) >> 32, d = 0, 1, 2, ...: an index already drawn
+ * is skipped, until there are three, in that order).  The candidate index b is NOT mixed in.
+ * Every hypothesis with a model is scored on all n correspondences by ORB-SLAM's rule, in both images, without fused
+ * operations in exactly this order.  Per correspondence (X1 = (a0, a1, a2), X2 = (b0, b1, b2); d_sigma2 double [M,2] =
+ * the squared keypoint sigmas in image 1 and image 2, NULL = all 1):
+ *     u1 = fx * (a0 / a2) + cx;  v1 = fy * (a1 / a2) + cy;  u2 = fx * (b0 / b2) + cx;  v2 = fy * (b1 / b2) + cy;
+ *     g1 = chi2_gate * sigma2[i][0];  g2 = chi2_gate * sigma2[i][1];  both 0 unless a2 > 0 and b2 > 0;
+ *   per model, A = s R entry by entry (A_k = s * r_k, R row-major r0..r8, t = (t0, t1, t2)):
+ *     x = ((A0*a0 + A1*a1) + A2*a2) + t0;  y = ((A3*a0 + A4*a1) + A5*a2) + t1;  z = ((A6*a0 + A7*a1) + A8*a2) + t2;
+ *     du2 = (fx * (x / z) + cx) - u2;  dv2 = (fy * (y / z) + cy) - v2;                  (s R X1 + t seen in image 2)
+ *     y0 = b0 - t0;  y1 = b1 - t1;  y2 = b2 - t2;
+ *     wx = (r0*y0 + r3*y1) + r6*y2;  wy = (r1*y0 + r4*y1) + r7*y2;  wz = (r2*y0 + r5*y1) + r8*y2;
+ *     du1 = (fx * (wx / wz) + cx) - u1;  dv1 = (fy * (wy / wz) + cy) - v1;              (R^T (X2 - t) / s seen in image 1:
+ *                                         the division by s > 0 changes neither the projection nor the sign of the depth)
+ *   inlier iff z > 0 and wz > 0 and du2*du2 + dv2*dv2 < g2 and du1*du1 + dv1*dv1 < g1: all four depths positive and both
+ *   squared pixel errors below chi2_gate * sigma2 (ORB-SLAM: 9.210, chi-square of 2 degrees of freedom at 99 %).
+ *   Winner: most inliers, ties to the lower hypothesis - found with packed integer keys, so the result is bit-identical for
+ *   given (correspondences, sigmas, intrinsics, H, gate, fix_scale, seed) whatever B and whatever order the workgroups finish
+ *   in.  The winning hypothesis is solved again when the result is written.  There is no refit here: slam_sim3_refit_f64.
+ * Outputs: d_model [B,13] the winner, d_inlier uint8 [M] its mask (entries outside every candidate: 0), d_stats int32
+ * [B,4] = {inlier count, winning hypothesis, 0, number of hypotheses that gave a model}.  A candidate of fewer than 3
+ * correspondences, or one where no hypothesis gave a model, yields the identity with s = 1, mask 0, stats {0, -1, -1, 0}
+ * and is not an error.  Non-finite coordinates are data: such a correspondence is never an inlier, a hypothesis that drew
+ * one yields no model, d_model is always finite, and one candidate's data never changes another candidate's result. */
+SLAM_API int slam_sim3_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_X1,
+                                  const double* d_X2, int64_t M, const double* d_sigma2, double fx, double fy, double cx,
+                                  double cy, int H, double chi2_gate, int fix_scale, uint64_t seed, double* d_model,
+                                  uint8_t* d_inlier, int32_t* d_stats);
+
+/* The least-squares fit (Horn / Umeyama) over the correspondences of candidate b with d_mask != 0 (uint8 [M]; NULL: all),
+ * one workgroup per candidate (offsets as above, counted alike; B <= 2^24): the refit after RANSAC, a direct fit of clean
+ * data, the alignment of a trajectory to its ground truth.  The sums are formed in this order, which the result's bits
+ * depend on and nothing else (not B, not the order in which workgroups finish; there are no floating-point atomics):
+ *   pass 1: lane l of 256 starts from 0 and adds the coordinates of the selected correspondences at the positions l,
+ *           l + 256, l + 512, ... of the candidate, ascending (an unselected position adds nothing); the 256 lanes are
+ *           combined by the tree "for stride = 128, 64, ..., 1: lane l < stride adds lane l + stride to its own"; the
+ *           centroids c1, c2 are lane 0's sums divided by the number of selected correspondences;
+ *   pass 2: the same order and tree for p = X1 - c1, q = X2 - c2 (component by component): M_ij += q_i * p_j,
+ *           d1 += (p0*p0 + p1*p1) + p2*p2, d2 += (q0*q0 + q1*q1) + q2*q2.
+ * Centring before the products is what keeps the digits at coordinates of 1e4 (a one-pass covariance loses them).
+ * d_model [B,13], d_stats int32 [B,2] = {points used, ok}.  ok = 0 gives the identity with s = 1: fewer than 3 selected
+ * points; selected points that are collinear or repeated in either set - the two largest eigenvalues l1 >= l2 of Horn's
+ * matrix differ by 2 (s2 + s3 sign(det M)) in the singular values of M, and l1 - l2 <= 1e-10 * l1 (the second singular
+ * value too small against the first: the sine of the rule above, not its square) means the rotation is not determined;
+ * NaN / inf among the selected data or sums of squares of 1e200 or more; a scale that is not finite and positive. */
+SLAM_API int slam_sim3_refit_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_X1,
+                                 const double* d_X2, int64_t M, const uint8_t* d_mask, int fix_scale, double* d_model,
+                                 int32_t* d_stats);
 
 /* ---- ORB feature extraction (orb.hip): cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26), which
  * Frontend._detect_features calls on every frame with a mask (frontend.py:245) -------------------------------------------

@@ -70,6 +70,16 @@ from .pose_graph import (  # noqa: F401
     write_g2o,
 )
 from .reproj import PoseOnlyProblem, ReprojProblem, build_linearization, poses_to_rt12  # noqa: F401
+from .sim3 import (  # noqa: F401
+    align_trajectory,
+    estimate_sim3,
+    estimate_sim3_batch,
+    estimate_sim3_offsets,
+    fit_sim3,
+    fit_sim3_offsets,
+    loop_edges_from_sim3,
+    sim3_threepoint_arrays,
+)
 from .two_view import (  # noqa: F401
     estimate_two_view,
     find_essential_arrays,

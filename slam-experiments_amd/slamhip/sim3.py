@@ -1,0 +1,253 @@
+"""Sim(3) alignment of two copies of the same map points on the GPU (``slam_sim3_*``): ORB-SLAM's ``Sim3Solver`` (Horn's
+three-point closed form under RANSAC) for many loop candidates per call, and a least-squares refit on the inliers.
+
+The reference has no call site: it closes no loops, and its driver prints the estimated translation beside the ground truth
+with no alignment at all (``euroc.py:63-66``), which for a monocular run compares nothing - gauge and scale are free.  A
+monocular map drifts in scale, so the constraint between two keyframes that each hold their own copy of the same map points
+is a similarity ``X2 = s R X1 + t``; the same closed form aligns an estimated trajectory to its ground truth (ATE).
+
+PARITY UNPINNED: ORB-SLAM and cv2 are absent here, so the calls are restated from the algorithm's definition (Horn 1987,
+Umeyama 1991; ORB-SLAM's two-sided reprojection test).  ``Sim3Solver``'s own random draws, its early termination and its
+per-octave sigma table are not reproduced: a fixed number of hypotheses from a documented counter-based generator is scored,
+and ``sigma2`` is where a caller puts the squared keypoint sigmas.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import numpy as np
+
+from ._lib import check
+from .device import Context, default_context
+from .pnp import _points3
+from .two_view import MAX_PAIRS, _Buffers, _check_ransac_args, _intrinsics
+
+DEFAULT_HYPOTHESES = 256        # as the other RANSAC calls; ORB-SLAM's Sim3Solver: at most 300 iterations
+DEFAULT_CHI2_GATE = 9.210       # chi-square of 2 degrees of freedom at 99 %, ORB-SLAM's Sim3Solver
+DEFAULT_MAX_LOG_SCALE = 0.05    # |log s| an SE(3) edge may hide: 5 % of scale, about the noise of a 20-inlier scale estimate
+
+
+def _split(model: np.ndarray):
+    """(s [B], R [B,3,3], t [B,3]) of models [B,13]."""
+    T = model[:, :12].reshape(-1, 3, 4)
+    return model[:, 12].copy(), np.ascontiguousarray(T[:, :, :3]), np.ascontiguousarray(T[:, :, 3])
+
+
+def _sigma2(sigma2, M: int):
+    if sigma2 is None:
+        return None
+    try:
+        a = np.asarray(sigma2, np.float64)
+    except (TypeError, ValueError) as exc:
+        raise TypeError("sigma2 must be numeric") from exc
+    if a.size == 0 and M == 0:
+        return np.zeros((0, 2))
+    if a.ndim != 2 or a.shape != (M, 2):
+        raise ValueError(f"sigma2 must have shape [{M},2], got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _offsets(offsets, cap: int):
+    offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+    B = len(offsets) - 1
+    if B < 0:
+        raise ValueError("offsets must have B + 1 entries")
+    if B > cap:
+        raise ValueError(f"at most {cap} candidates per call")
+    return offsets, B
+
+
+def _pair(X1, X2):
+    X1, X2 = _points3(X1, "X1"), _points3(X2, "X2")
+    if len(X1) != len(X2):
+        raise ValueError(f"{len(X1)} points in frame 1 but {len(X2)} in frame 2")
+    if len(X1) >= 1 << 28:
+        raise ValueError("more than 2^28 correspondences in one call")
+    return X1, X2
+
+
+def sim3_threepoint_arrays(X1, X2, fix_scale: bool = False, ctx: Optional[Context] = None):
+    """The similarity through three correspondences per sample (``slam_sim3_threepoint_f64``): ``X1``, ``X2`` [S,3,3] (or
+    [3,3]) -> (s [S], R [S,3,3], t [S,3], ok int32 [S]); a sample without a model has the identity, s = 1 and ok = 0."""
+    X1, X2 = np.asarray(X1, np.float64), np.asarray(X2, np.float64)
+    if X1.shape != X2.shape or X1.shape[-2:] != (3, 3) or X1.ndim not in (2, 3):
+        raise ValueError(f"X1 and X2 must both have shape [S,3,3], got {X1.shape} and {X2.shape}")
+    X1, X2 = np.ascontiguousarray(X1.reshape(-1, 3, 3)), np.ascontiguousarray(X2.reshape(-1, 3, 3))
+    S = X1.shape[0]
+    if S == 0:
+        return np.zeros(0), np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros(0, np.int32)
+    ctx = ctx or default_context()
+    m = _Buffers(ctx)
+    try:
+        d1, d2 = m.up(X1), m.up(X2)
+        dm, do = m.new(S * 104), m.new(S * 4)
+        check(ctx.lib.slam_sim3_threepoint_f64(ctx.handle, S, d1.ptr, d2.ptr, int(bool(fix_scale)), dm.ptr, do.ptr))
+        return _split(dm.download(np.float64, (S, 13))) + (do.download(np.int32, (S,)),)
+    finally:
+        m.free()
+
+
+def estimate_sim3_offsets(X1, X2, offsets, K, hypotheses: int = DEFAULT_HYPOTHESES, chi2_gate: float = DEFAULT_CHI2_GATE,
+                          sigma2=None, fix_scale: bool = False, seed: int = 0, refit: bool = True, ctx: Optional[Context] = None):
+    """``slam_sim3_ransac_f64`` on concatenated correspondences: candidate b owns ``[offsets[b], offsets[b+1])`` of ``X1`` /
+    ``X2`` [M,3]; ``sigma2`` [M,2] are the squared keypoint sigmas in image 1 and image 2 (None: all 1).
+    Returns (s [B], R [B,3,3], t [B,3], inlier bool [M], stats int32 [B,4], refit stats int32 [B,2] or None).
+
+    The mask and ``stats = {inlier count, winning hypothesis, 0, models scored}`` are the RANSAC vote.  With ``refit`` the
+    RANSAC inliers of every candidate go through ``slam_sim3_refit_f64`` while everything is still on the device (one
+    upload, the mask never leaves it); a candidate whose refit is ok (``refit stats = {points used, ok}``) returns the
+    least-squares model, any other the RANSAC one.  A candidate of fewer than 3 correspondences, or one where no hypothesis
+    gave a model, comes back with the identity, s = 1, an empty vote and stats {0, -1, -1, 0}."""
+    fx, fy, cx, cy = _intrinsics(K)
+    H, gate, seed = _check_ransac_args(hypotheses, chi2_gate, seed)
+    X1, X2 = _pair(X1, X2)
+    M = len(X1)
+    sg = _sigma2(sigma2, M)
+    offsets, B = _offsets(offsets, MAX_PAIRS)
+    if B == 0:
+        return (np.zeros(0), np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros(M, bool), np.zeros((0, 4), np.int32),
+                np.zeros((0, 2), np.int32) if refit else None)
+    ctx = ctx or default_context()
+    m = _Buffers(ctx)
+    try:
+        d1, d2, do = m.up(X1), m.up(X2), m.up(offsets)
+        dsg = m.up(sg) if sg is not None else None
+        dT, dm, ds = m.new(B * 104), m.new(M), m.new(B * 16)
+        fix = int(bool(fix_scale))
+        check(ctx.lib.slam_sim3_ransac_f64(ctx.handle, B, do.ptr, d1.ptr, d2.ptr, M, dsg.ptr if dsg is not None else None, fx, fy, cx, cy, H,
+                                           gate, fix, seed, dT.ptr, dm.ptr, ds.ptr))
+        rs = None
+        if refit:
+            dT2, ds2 = m.new(B * 104), m.new(B * 8)
+            check(ctx.lib.slam_sim3_refit_f64(ctx.handle, B, do.ptr, d1.ptr, d2.ptr, M, dm.ptr, fix, dT2.ptr, ds2.ptr))
+        model, st = dT.download(np.float64, (B, 13)), ds.download(np.int32, (B, 4))
+        mask = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
+        if refit:
+            fit, rs = dT2.download(np.float64, (B, 13)), ds2.download(np.int32, (B, 2))
+            use = (st[:, 1] >= 0) & (rs[:, 1] != 0)
+            model[use] = fit[use]
+    finally:
+        m.free()
+    return _split(model) + (mask, st, rs)
+
+
+def estimate_sim3_batch(cands: Sequence, K, hypotheses: int = DEFAULT_HYPOTHESES, chi2_gate: float = DEFAULT_CHI2_GATE,
+                        fix_scale: bool = False, seed: int = 0, refit: bool = True, ctx: Optional[Context] = None):
+    """ORB-SLAM's ``Sim3Solver`` for a list of ``(X1 [N_b,3], X2 [N_b,3])`` or ``(X1, X2, sigma2 [N_b,2])`` candidates in
+    one call: (s [B], R [B,3,3], t [B,3], list of bool masks, stats int32 [B,4], refit stats or None), as
+    ``estimate_sim3_offsets``."""
+    A, Bs, S, off, any_sigma = [], [], [], [0], False
+    for i, c in enumerate(cands):
+        if len(c) not in (2, 3):
+            raise ValueError(f"candidate {i}: expected (X1, X2) or (X1, X2, sigma2)")
+        a, b = _points3(c[0], f"candidate {i} X1"), _points3(c[1], f"candidate {i} X2")
+        if len(a) != len(b):
+            raise ValueError(f"candidate {i}: {len(a)} points in frame 1 but {len(b)} in frame 2")
+        sg = np.ones((len(a), 2)) if len(c) == 2 or c[2] is None else _sigma2(c[2], len(a))
+        any_sigma = any_sigma or (len(c) == 3 and c[2] is not None)
+        A.append(a); Bs.append(b); S.append(sg)
+        off.append(off[-1] + len(a))
+    cat = (lambda v, w: np.concatenate(v) if v else np.zeros((0, w)))
+    s, R, t, mask, st, rs = estimate_sim3_offsets(cat(A, 3), cat(Bs, 3), np.asarray(off, np.int64), K, hypotheses, chi2_gate,
+                                                  cat(S, 2) if any_sigma else None, fix_scale, seed, refit, ctx)
+    return s, R, t, [mask[off[b]:off[b + 1]].copy() for b in range(len(off) - 1)], st, rs
+
+
+def estimate_sim3(X1, X2, K, hypotheses: int = DEFAULT_HYPOTHESES, chi2_gate: float = DEFAULT_CHI2_GATE, sigma2=None,
+                  fix_scale: bool = False, seed: int = 0, refit: bool = True, ctx: Optional[Context] = None):
+    """One candidate: (ok, s, R [3,3], t [3], inlier mask bool [N]); ``ok`` is False (identity, s = 1, empty vote) when
+    there are fewer than 3 correspondences or no hypothesis gave a model."""
+    X1, X2 = _pair(X1, X2)
+    s, R, t, mask, st, _ = estimate_sim3_offsets(X1, X2, [0, len(X1)], K, hypotheses, chi2_gate, sigma2, fix_scale, seed, refit, ctx)
+    return bool(st[0, 1] >= 0), float(s[0]), R[0], t[0], mask
+
+
+def fit_sim3_offsets(X1, X2, offsets, mask=None, fix_scale: bool = False, ctx: Optional[Context] = None):
+    """``slam_sim3_refit_f64``: the least-squares similarity of every candidate's selected correspondences ->
+    (s [B], R [B,3,3], t [B,3], stats int32 [B,2] = {points used, ok})."""
+    X1, X2 = _pair(X1, X2)
+    M = len(X1)
+    offsets, B = _offsets(offsets, 1 << 24)
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.shape != (M,):
+            raise ValueError(f"mask must have shape [{M}], got {mask.shape}")
+        mask = np.ascontiguousarray(mask.astype(bool), np.uint8)
+    if B == 0:
+        return np.zeros(0), np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros((0, 2), np.int32)
+    ctx = ctx or default_context()
+    m = _Buffers(ctx)
+    try:
+        d1, d2, do = m.up(X1), m.up(X2), m.up(offsets)
+        dk = m.up(mask) if mask is not None else None
+        dT, ds = m.new(B * 104), m.new(B * 8)
+        check(ctx.lib.slam_sim3_refit_f64(ctx.handle, B, do.ptr, d1.ptr, d2.ptr, M, dk.ptr if dk is not None else None, int(bool(fix_scale)),
+                                          dT.ptr, ds.ptr))
+        return _split(dT.download(np.float64, (B, 13))) + (ds.download(np.int32, (B, 2)),)
+    finally:
+        m.free()
+
+
+def fit_sim3(X1, X2, mask=None, fix_scale: bool = False, ctx: Optional[Context] = None):
+    """The least-squares similarity ``X2 ~ s R X1 + t`` of two point sets [N,3] (the rows with ``mask``; None: all):
+    (ok, s, R [3,3], t [3]).  ``ok`` is False (identity, s = 1) with fewer than 3 selected points, collinear or repeated
+    points, or non-finite data."""
+    X1, X2 = _pair(X1, X2)
+    s, R, t, st = fit_sim3_offsets(X1, X2, [0, len(X1)], mask, fix_scale, ctx)
+    return bool(st[0, 1]), float(s[0]), R[0], t[0]
+
+
+def align_trajectory(estimated_xyz, ground_truth_xyz, fix_scale: bool = False, ctx: Optional[Context] = None):
+    """Absolute trajectory error after the least-squares Sim(3) alignment (SE(3) with ``fix_scale``) of the estimated
+    positions [N,3] to the ground truth [N,3]: (s, R, t, aligned [N,3] = s R x + t, ate_rmse).  What ``euroc.py:63-66``
+    should have done before comparing: a monocular estimate has a free gauge and a free scale.  A trajectory without a fit
+    (fewer than 3 poses, all on one line) raises ``ValueError``."""
+    est, gt = _pair(estimated_xyz, ground_truth_xyz)
+    ok, s, R, t = fit_sim3(est, gt, None, fix_scale, ctx)
+    if not ok:
+        raise ValueError("the trajectories have no unique alignment (fewer than 3 poses, collinear positions or non-finite data)")
+    aligned = s * (est @ R.T) + t
+    return s, R, t, aligned, float(np.sqrt(((aligned - gt) ** 2).sum(1).mean()))
+
+
+def loop_edges_from_sim3(pairs, models, inlier_counts, min_inliers: int = 20, max_log_scale: float = DEFAULT_MAX_LOG_SCALE,
+                         rotation_sigma: float = 0.01, translation_sigma: float = 0.1):
+    """Edges from ``estimate_sim3_batch`` output, in the format of ``loop_edges_from_pnp``: ``pairs`` int [B,2] with
+    ``pairs[b] = (i, j)``, ``models = (s [B], R [B,3,3], t [B,3])`` with ``X_j = s R X_i + t`` ->
+    (edges int32 [E,2], meas [E,3,4], info [E,6,6], scales [B]).
+
+    An edge is emitted for the pairs with at least ``min_inliers`` inliers, i != j and ``|log s| <= max_log_scale``: its
+    measurement is the SE(3) part in FRAME-1 SCALE, ``[R | t / s]`` (``X_j / s = R X_i + t / s``), what
+    ``optimize_pose_graph`` expects, with BOTH information blocks set (``inliers / min_inliers / sigma^2`` times the
+    identity).  ``scales`` holds s for ALL candidates: an SE(3) graph cannot absorb scale drift, so a candidate beyond
+    ``max_log_scale`` is reported there and gets no edge.  Edges with real scale drift wait for the Sim(3) pose graph."""
+    pairs = np.asarray(pairs)
+    if pairs.size == 0:
+        pairs = np.zeros((0, 2), np.int64)
+    if pairs.dtype.kind not in "iu" or pairs.ndim != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"pairs must be integers of shape [B,2], got {pairs.dtype} {pairs.shape}")
+    B = len(pairs)
+    if len(models) != 3:
+        raise ValueError("models must be (s [B], R [B,3,3], t [B,3])")
+    s = np.asarray(models[0], np.float64).reshape(-1)
+    R = np.asarray(models[1], np.float64).reshape(-1, 3, 3)
+    t = np.asarray(models[2], np.float64).reshape(-1, 3)
+    n = np.asarray(inlier_counts).reshape(-1)
+    if not (len(s) == len(R) == len(t) == len(n) == B):
+        raise ValueError(f"{B} pairs but {len(s)} scales, {len(R)} rotations, {len(t)} translations and {len(n)} inlier counts")
+    if min_inliers < 1 or rotation_sigma <= 0 or translation_sigma <= 0 or not max_log_scale >= 0:
+        raise ValueError("min_inliers >= 1, positive sigmas and max_log_scale >= 0")
+    if B and pairs.min() < 0:
+        raise ValueError("negative pair index")
+    with np.errstate(all="ignore"):
+        drift = np.abs(np.log(s))
+    k = np.flatnonzero((n >= min_inliers) & (pairs[:, 0] != pairs[:, 1]) & (s > 0) & (drift <= max_log_scale))
+    meas = np.zeros((len(k), 3, 4))
+    meas[:, :, :3] = R[k]
+    meas[:, :, 3] = t[k] / s[k, None]
+    info = np.zeros((len(k), 6, 6))
+    w = n[k] / float(min_inliers)
+    for a in range(3):
+        info[:, a, a] = w / rotation_sigma ** 2
+        info[:, 3 + a, 3 + a] = w / translation_sigma ** 2
+    return np.ascontiguousarray(pairs[k], np.int32), meas, info, s.copy()
