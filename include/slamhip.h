@@ -929,6 +929,75 @@ SLAM_API int slam_pg_optimize_host_f64(slam_ctx* ctx, int64_t V, int64_t E, cons
                                        double huber_delta, double pcg_tol, int pcg_max_iter, double* h_poses_out,
                                        double* h_stats);
 
+/* ---- Sim(3) pose-graph optimisation (sim3_graph.hip) ---------------------------------------------------------------
+ * ORB-SLAM's OptimizeEssentialGraph for this project's conventions: the 7-DoF graph that absorbs the scale drift of a
+ * monocular map, and the consumer of slam_sim3_* models.  Structure, guarantees, LM schedule, Huber, vertex lists, limits,
+ * workspace and call lock are those of the slam_pg_* section above with 7x7 blocks; what differs is stated here.
+ *
+ * Conventions.  A vertex is a similarity S = (s, R, t), X_cam = s R X_world + t, stored [13]: the row-major 3x4 [R|t], then
+ * s (the model layout of slam_sim3_*: their output feeds these calls unchanged).
+ *   composition   (s_a, R_a, t_a) o (s_b, R_b, t_b) = (s_a s_b, R_a R_b, s_a R_a t_b + t_a);  inverse (1/s, R^T, -R^T t / s)
+ *   tangent       d = [w, v, sigma], rotation first and scale last, 7 numbers
+ *   chart         Phi(d) = Exp_SE3(w, v) o Scale(e^sigma) = (e^sigma, Exp(w), V(w) v)
+ *   update        S <- Phi(d) o S:  s' = e^sigma s, R' = Exp(w) R, t' = e^sigma Exp(w) t + V(w) v
+ *   measurement   edge (i, j) carries Z_ij [13], a measured value of S_j S_i^-1;  D = S_j S_i^-1 Z^-1
+ *   residual      r = Phi^-1(D) = [Log_SE3(R_D, t_D), log s_D] in R^7
+ *   cost          F = sum rho(r^T Omega r), no factor 1/2; Omega [49] symmetric in [w, v, sigma] order; rho as slam_pg_*
+ *   Jacobians     dr/dd_j = J_j = [[Jl^-1, Jl^-1 (0; t_D)], [0, 1]], Jl^-1 the SE(3) inverse left Jacobian at r_1..6;
+ *                 dr/dd_i = -J_j Ad(A), A = S_j S_i^-1 = (s, R, t), Ad(A) = [[R, 0, 0], [t^ R, s R, -t], [0, 0, 1]]
+ *   system        H = sum w J^T Omega J, b = sum w J^T Omega r, solved as (H + lambda I) d = -b
+ *   fix_scale     (ORB-SLAM's mbFixScale) column 7 of both Jacobians is zeroed: b_sigma = 0, H_sigma,sigma = lambda, every
+ *                 d_sigma = 0 and every s comes back bit for bit
+ *   validity      s of both ends, of Z and of D must be finite and positive; otherwise the edge leaves the sums with finite
+ *                 zeros, as an angle beyond 3.1 rad does, and SLAM_S3G_STATUS_SCALE is raised
+ * The chart is the exact inverse of the retraction and reuses the SE(3) logarithm; with fix_scale, every s = 1 and a
+ * block-diagonal Omega the problem is the slam_pg_* one.  It differs from g2o's Sim3::log at second order in sigma * v:
+ * PARITY UNPINNED against g2o's EdgeSim3 / ORB-SLAM (absent here). */
+#define SLAM_S3G_MAX_VERTICES (1 << 24)
+#define SLAM_S3G_MAX_EDGES (1 << 25)
+#define SLAM_S3G_STATUS_INDEX 1      /* bad edge index / vertex list (the call returns SLAM_ERR_INVALID) */
+#define SLAM_S3G_STATUS_ANGLE 2      /* a residual's rotation angle is beyond 3.1 rad: that edge was given weight 0 */
+#define SLAM_S3G_STATUS_PRECOND 4    /* a diagonal block H_vv + lambda I was not positive definite (identity used) */
+#define SLAM_S3G_STATUS_BREAKDOWN 8  /* CG met p.Ap <= 0 and stopped */
+#define SLAM_S3G_STATUS_NONFINITE 16 /* a non-finite cost, right-hand side or CG scalar */
+#define SLAM_S3G_STATUS_SCALE 32     /* a scale (vertex, measurement or their product) not finite and positive: weight 0 */
+/* bytes of context workspace a graph of V vertices and E edges takes; needs no device */
+SLAM_API int slam_s3g_workspace(int64_t V, int64_t E, uint64_t* bytes);
+/* the launch plan, without a device: plan[8] = {blocks of the product's main path (= partial sums per dot product),
+ * extra blocks for hub vertices, vertices per block (seven lanes each, nine vertices per wave), slots above which a vertex
+ * is a hub, blocks of the edge kernel, CG iterations between two reads of the done flag, launches per CG iteration,
+ * doubles per stored row of a slot block} */
+SLAM_API int slam_s3g_plan(int64_t V, int64_t E, int32_t* plan);
+/* Linearisation at d_sims [V,13] (scale free): *d_cost = F, d_grad [V,7] = b, d_Hdiag [V,49] = the diagonal blocks H_vv,
+ * d_W [E,49] = the off-diagonal blocks w J_i^T Omega J_j.  *h_status = SLAM_S3G_STATUS_* bits (the call waits). */
+SLAM_API int slam_s3g_linearize_f64(slam_ctx* ctx, int64_t V, int64_t E, const double* d_sims, const int32_t* d_edges,
+                                    const double* d_meas, const double* d_info, const int32_t* d_vtx_ptr,
+                                    const int32_t* d_vtx_adj, double huber_delta, double* d_cost, double* d_grad,
+                                    double* d_Hdiag, double* d_W, int32_t* h_status);
+/* d_y [V,7] = (H + lambda I) d_x restricted to the free vertices (rows of fixed vertices 0, their columns ignored), H given
+ * by d_Hdiag and d_W as slam_s3g_linearize_f64 leaves them.  No alignment beyond that of a double is asked for. */
+SLAM_API int slam_s3g_hmul_f64(slam_ctx* ctx, int64_t V, int64_t E, const int32_t* d_edges, const int32_t* d_vtx_ptr,
+                               const int32_t* d_vtx_adj, const uint8_t* d_fixed, const double* d_Hdiag, const double* d_W,
+                               double lambda, const double* d_x, double* d_y);
+/* Preconditioned CG on (H + lambda I) x = -d_b over the free vertices, as slam_pg_pcg_f64 (7x7 LDL^T block-Jacobi).
+ * h_stats[4] = {iterations, converged, |r| / |b| of the recurrence, status}. */
+SLAM_API int slam_s3g_pcg_f64(slam_ctx* ctx, int64_t V, int64_t E, const int32_t* d_edges, const int32_t* d_vtx_ptr,
+                              const int32_t* d_vtx_adj, const uint8_t* d_fixed, const double* d_Hdiag, const double* d_W,
+                              const double* d_b, double lambda, double tol, int max_iter, double* d_x, double* h_stats);
+/* The LM loop on device buffers, as slam_pg_optimize_f64; fix_scale != 0 freezes every scale.  h_stats[8] = {initial chi2,
+ * final chi2, accepted LM iterations, LM trials, CG iterations in total, final lambda, status bits, 0}.  V = 0 or E = 0 is
+ * not an error (E = 0: the vertices are copied). */
+SLAM_API int slam_s3g_optimize_f64(slam_ctx* ctx, int64_t V, int64_t E, const double* d_sims, const int32_t* d_edges,
+                                   const double* d_meas, const double* d_info, const uint8_t* d_fixed, int64_t n_fixed,
+                                   const int32_t* d_vtx_ptr, const int32_t* d_vtx_adj, int iterations, double huber_delta,
+                                   double pcg_tol, int pcg_max_iter, int fix_scale, double* d_sims_out, double* h_stats);
+/* the same on HOST buffers: the vertex lists are built inside (slots in ascending edge order), one upload, one download.
+ * On SLAM_ERR_INVALID h_sims_out is not written. */
+SLAM_API int slam_s3g_optimize_host_f64(slam_ctx* ctx, int64_t V, int64_t E, const double* h_sims, const int32_t* h_edges,
+                                        const double* h_meas, const double* h_info, const uint8_t* h_fixed, int iterations,
+                                        double huber_delta, double pcg_tol, int pcg_max_iter, int fix_scale,
+                                        double* h_sims_out, double* h_stats);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

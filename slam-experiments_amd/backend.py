@@ -24,6 +24,7 @@ import numpy as np
 from slamhip import ba as _ba
 from slamhip import pnp as _pnp
 from slamhip import pose_graph as _pg
+from slamhip import sim3_graph as _s3g
 from slamhip import pose_opt as _po
 from slamhip import reproj as _r
 from slamhip import two_view as _tv
@@ -231,6 +232,23 @@ class Backend:
             mask = np.zeros(V, np.uint8)
             mask[np.asarray(fixed, np.int64).reshape(-1)] = 1
         return _pg.optimize_pose_graph(poses, edges, meas, info, mask, iterations, huber_delta, pcg_tol, pcg_max_iter, ctx=self.ctx)
+
+    def optimize_essential_graph(self, sims, edges, meas, info, fixed=(0,), iterations: int = _pg.DEFAULT_ITERATIONS,
+                                 huber_delta: float = 0.0, pcg_tol: float = _pg.DEFAULT_PCG_TOL,
+                                 pcg_max_iter: int = _pg.DEFAULT_PCG_MAX_ITER, fix_scale: bool = False):
+        """7-DoF pose-graph optimisation over keyframe similarities (ORB-SLAM's ``OptimizeEssentialGraph``): ``sims``
+        [V,13] (``[R|t]`` then ``s``) or the tuple ``(s, R, t)``, ``edges`` [E,2], ``meas`` the measured ``S_j S_i^-1`` per
+        edge (``estimate_sim3_batch`` models, ``lift_se3_graph`` for odometry), ``info`` [E,7,7] in ``[w, v, sigma]`` order,
+        ``fixed`` the vertex indices (or a bool mask of length V) that hold the gauge.
+        Returns (sims in the input's form, stats dict) from ``slamhip.optimize_sim3_graph``."""
+        V = len(sims[0]) if _s3g.is_srt(sims) else len(sims)
+        fx = np.asarray(fixed)
+        if fx.dtype == bool:
+            mask = fx.astype(np.uint8)
+        else:
+            mask = np.zeros(V, np.uint8)
+            mask[np.asarray(fixed, np.int64).reshape(-1)] = 1
+        return _s3g.optimize_sim3_graph(sims, edges, meas, info, mask, iterations, huber_delta, pcg_tol, pcg_max_iter, fix_scale, ctx=self.ctx)
 
     def optimize_map(self, map_, fx, fy, cx, cy, iterations: int = 10, huber_delta: float = 5.991 ** 0.5,
                      n_fixed: int = 1, min_observations: int = 2, on_device: bool = True):

@@ -80,6 +80,16 @@ from .sim3 import (  # noqa: F401
     loop_edges_from_sim3,
     sim3_threepoint_arrays,
 )
+from .sim3_graph import (  # noqa: F401
+    correct_points,
+    lift_se3_graph,
+    optimize_sim3_graph,
+    sim3_edges_from_sim3,
+    sim3_graph_hmul,
+    sim3_graph_linearize,
+    sim3_graph_pcg,
+    sims_to_poses,
+)
 from .two_view import (  # noqa: F401
     estimate_two_view,
     find_essential_arrays,

@@ -133,6 +133,18 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p]),
     "slam_pg_optimize_host_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                           c_double, c_double, c_int, c_void_p, c_void_p]),
+    "slam_s3g_workspace": (c_int, [c_int64, c_int64, POINTER(c_uint64)]),
+    "slam_s3g_plan": (c_int, [c_int64, c_int64, POINTER(c_int32)]),
+    "slam_s3g_linearize_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32)]),
+    "slam_s3g_hmul_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_double, c_void_p, c_void_p]),
+    "slam_s3g_pcg_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_double, c_double, c_int, c_void_p, c_void_p]),
+    "slam_s3g_optimize_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_int, c_void_p, c_void_p]),
+    "slam_s3g_optimize_host_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                           c_double, c_double, c_int, c_int, c_void_p, c_void_p]),
     "slam_orb_workspace": (c_int, [c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, POINTER(c_uint64), c_void_p]),
     "slam_orb_extract_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_int, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -220,7 +220,8 @@ def loop_edges_from_sim3(pairs, models, inlier_counts, min_inliers: int = 20, ma
     measurement is the SE(3) part in FRAME-1 SCALE, ``[R | t / s]`` (``X_j / s = R X_i + t / s``), what
     ``optimize_pose_graph`` expects, with BOTH information blocks set (``inliers / min_inliers / sigma^2`` times the
     identity).  ``scales`` holds s for ALL candidates: an SE(3) graph cannot absorb scale drift, so a candidate beyond
-    ``max_log_scale`` is reported there and gets no edge.  Edges with real scale drift wait for the Sim(3) pose graph."""
+    ``max_log_scale`` is reported there and gets no edge.  Edges with real scale drift go to the Sim(3) pose graph:
+    ``slamhip.sim3_graph.sim3_edges_from_sim3`` and ``optimize_sim3_graph``."""
     pairs = np.asarray(pairs)
     if pairs.size == 0:
         pairs = np.zeros((0, 2), np.int64)

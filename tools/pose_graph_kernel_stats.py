@@ -8,7 +8,8 @@
         > profiles/pose_graph_kernel_stats.txt
 
 Reads the `kernels` view of the trace databases (*_results.db) and prints, per graph and kernel: calls, average / min / max
-duration in microseconds.  pg_hmul_kernel<0> is the product alone (the calls of slam_pg_hmul_f64 the timing script makes);
+duration in microseconds.  A first argument --prefix=s3g reads the s3g_* kernels of tools/sim3_graph_time.py's children instead
+(rocprofv3 --kernel-trace -d DIR -o s3g -- python tools/sim3_graph_time.py --child hmul large).  pg_hmul_kernel<0> is the product alone (the calls of slam_pg_hmul_f64 the timing script makes);
 pg_hmul_kernel<1> and the two CG vector kernels include the launches that return at once after convergence."""
 import glob
 import os
@@ -17,9 +18,13 @@ import sys
 
 
 def main():
-    print("# durations of the pg_* kernels (rocprofv3 --kernel-trace of tools/pose_graph_time.py --scenes NAME --no-reference)")
+    args, prefix = sys.argv[1:], "pg"
+    if args and args[0].startswith("--prefix="):
+        prefix, args = args[0][9:], args[1:]
+    script = "tools/pose_graph_time.py --scenes NAME --no-reference" if prefix == "pg" else "tools/sim3_graph_time.py --child FIGURE NAME"
+    print(f"# durations of the {prefix}_* kernels (rocprofv3 --kernel-trace of {script})")
     print("# calls, average / min / max in us, kernel")
-    for arg in sys.argv[1:]:
+    for arg in args:
         label, _, where = arg.partition("=")
         dbs = sorted(glob.glob(os.path.join(where, "**", "*_results.db"), recursive=True))
         if not dbs:
@@ -27,7 +32,7 @@ def main():
         db = sqlite3.connect(dbs[-1])
         print(f"\n== {label}")
         rows = db.execute("select name, count(*), avg(duration), min(duration), max(duration) from kernels "
-                          "where name like '%pg\\_%' escape '\\' group by name order by sum(duration) desc")
+                          f"where name like '%{prefix}\\_%' escape '\\' group by name order by sum(duration) desc")
         for name, calls, avg, lo, hi in rows:
             print(f"{calls:7d} {avg / 1e3:9.2f} {lo / 1e3:9.2f} {hi / 1e3:9.2f}  {name.split('(')[0].replace('void ', '')}")
 
