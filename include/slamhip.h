@@ -998,6 +998,67 @@ SLAM_API int slam_s3g_optimize_host_f64(slam_ctx* ctx, int64_t V, int64_t E, con
                                         double huber_delta, double pcg_tol, int pcg_max_iter, int fix_scale,
                                         double* h_sims_out, double* h_stats);
 
+/* ---- sparse bundle adjustment (ba_sparse.hip) --------------------------------------------------------------------------
+ * The bundle adjustment behind a closed loop: the points are eliminated into a reduced camera system that exists only
+ * where two free poses see a common point, in the layout slam_pg_pcg_f64 / slam_pg_hmul_f64 take - d_Hdiag [K,36],
+ * d_W [E,36] over the covisibility edges (k1 < k2, row block k1, column block k2), the gradient d_b [K,6], the mask d_fixed -
+ * and the driver solves (S + lambda I) dp = -b with slam_pg_pcg_f64 as it is.  Conventions, residual, Jacobians and Huber
+ * weight are those of slam_ba_reduce_f64; poses [K,12], points [L,3], cost without a factor 1/2, update T <- Exp(dp) T.
+ *   Hpl_o   = w Jp^T Jq (6x3 row-major, [O,18])        Hll_l [L,6] packed upper triangle, bl_l [L,3]
+ *   Hpp_k   [K,21] packed upper triangle, bp_k [K,6]   E_l = (Hll_l + lambda I)^-1 [L,9], 0 for a point nobody observes
+ *   W_e     = - sum_{pairs (a, b) of edge e} Hpl_a E_l Hpl_b^T
+ *   Hdiag_k = Hpp_k - sum_{o of k} Hpl_o E_l Hpl_o^T   (no lambda: the solver adds lambda I)
+ *   b_k     = bp_k - sum_{o of k} Hpl_o E_l bl_l       dl_l = - E_l (bl_l + sum_{o of l} Hpl_o^T dp_pose(o))
+ * Index tables (int32, device): d_pt_ptr [L+1] / d_pt_obs [O] and d_ps_ptr [K+1] / d_ps_obs [O] list the observations of
+ * every point and pose in the order their sums are taken; d_pair_ptr [E+1] / d_pair_a [P] / d_pair_b [P] list, per edge
+ * (k1, k2), the observations (k1, l) and (k2, l) of every common point l (slamhip.covisibility builds them, ascending in l).
+ * Summation orders: a point's sums run down its list; a pose's sums give thread t of 256 the entries t, t + 256, .., then
+ * an xor tree inside each wave and the four waves in order; an edge's sum gives lane i of ONE wave the pairs i, i + 64, ..
+ * and the same xor tree - a function of the pair count alone, for one pair or thousands.  f64 without contraction and
+ * without floating-point atomics: results are pure functions of the inputs.  Every buffer is the caller's
+ * (slam_bas_workspace: their total); no call here takes the context's call lock or waits; all are asynchronous on the
+ * context's stream.  An index outside its range is counted (slam_index_errors) and never dereferenced; what it feeds
+ * becomes NaN.  Limits: K <= 2^24, E <= 2^25 (the solver's), L, O <= 2^28, P <= 2^30. */
+#define SLAM_BAS_MAX_POINTS (1 << 28)
+#define SLAM_BAS_MAX_OBS (1 << 28)
+#define SLAM_BAS_MAX_PAIRS (1 << 30)
+/* bytes of device memory one problem takes in all (tables, state and candidate, blocks, steps); needs no device */
+SLAM_API int slam_bas_workspace(int64_t K, int64_t L, int64_t O, int64_t E, int64_t P, uint64_t* bytes);
+/* the launch plan, without a device: plan[8] = {workgroups of the observation kernel, of the point kernels, of the pose
+ * kernels (one per pose), of the edge kernel (a wave per edge, four to a workgroup), of the candidate kernel (= partial sums
+ * of the gain-ratio denominator), threads per workgroup, lanes that share an edge's pairs, 0} */
+SLAM_API int slam_bas_plan(int64_t K, int64_t L, int64_t O, int64_t E, int64_t P, int32_t* plan);
+/* Linearisation at (d_poses, d_points): d_Hpl, d_Hll, d_bl, d_Hpp, d_bp, the robust cost per pose d_cost [K], and
+ * d_scal[0] = the cost, d_scal[1] = the largest diagonal entry of the Hpp of the free poses and of every Hll. */
+SLAM_API int slam_bas_linearize_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, const double* d_poses, const double* d_points,
+                                    const int32_t* d_obs_pose, const int32_t* d_obs_point, const double* d_meas,
+                                    const int32_t* d_pt_ptr, const int32_t* d_pt_obs, const int32_t* d_ps_ptr,
+                                    const int32_t* d_ps_obs, const uint8_t* d_fixed, double fx, double fy, double cx, double cy,
+                                    double huber_delta, double* d_Hpl, double* d_Hll, double* d_bl, double* d_Hpp, double* d_bp,
+                                    double* d_cost, double* d_scal);
+/* the robust cost alone at a state: d_cost [K] per pose, *d_total their sum (the sums of slam_bas_linearize_f64) */
+SLAM_API int slam_bas_cost_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, const double* d_poses, const double* d_points,
+                               const int32_t* d_obs_pose, const int32_t* d_obs_point, const double* d_meas,
+                               const int32_t* d_ps_ptr, const int32_t* d_ps_obs, double fx, double fy, double cx, double cy,
+                               double huber_delta, double* d_cost, double* d_total);
+/* the reduced system at damping lambda from the blocks of slam_bas_linearize_f64: d_E [L,9], d_Ebl [L,3] = E bl,
+ * d_Hdiag [K,36], d_W [E,36], d_b [K,6] (blocks of fixed poses are written too; the solver ignores them) */
+SLAM_API int slam_bas_reduce_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, int64_t E, int64_t P, const int32_t* d_obs_point,
+                                 const int32_t* d_pt_ptr, const int32_t* d_ps_ptr, const int32_t* d_ps_obs,
+                                 const int32_t* d_pair_ptr, const int32_t* d_pair_a, const int32_t* d_pair_b, const double* d_Hpl,
+                                 const double* d_Hll, const double* d_bl, const double* d_Hpp, const double* d_bp, double lambda,
+                                 double* d_E, double* d_Ebl, double* d_Hdiag, double* d_W, double* d_b);
+/* d_dl [L,3] from the pose steps d_dp [K,6] (0 for fixed poses, as slam_pg_pcg_f64 leaves them) */
+SLAM_API int slam_bas_backsub_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, const int32_t* d_pt_ptr, const int32_t* d_pt_obs,
+                                  const int32_t* d_obs_pose, const double* d_Hpl, const double* d_E, const double* d_bl,
+                                  const double* d_dp, double* d_dl);
+/* the candidate state T' = Exp(dp) T (fixed poses copied bit for bit), X' = X + dl, and *d_denominator =
+ * sum dp.(lambda dp - bp) over the free poses + sum dl.(lambda dl - bl), through d_part [plan[4]] partial sums */
+SLAM_API int slam_bas_candidate_f64(slam_ctx* ctx, int64_t K, int64_t L, const uint8_t* d_fixed, const double* d_poses,
+                                    const double* d_points, const double* d_dp, const double* d_dl, const double* d_bp,
+                                    const double* d_bl, double lambda, double* d_poses_out, double* d_points_out, double* d_part,
+                                    double* d_denominator);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

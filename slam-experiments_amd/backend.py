@@ -22,6 +22,7 @@ from typing import Optional
 import numpy as np
 
 from slamhip import ba as _ba
+from slamhip import ba_sparse as _bas
 from slamhip import pnp as _pnp
 from slamhip import pose_graph as _pg
 from slamhip import sim3_graph as _s3g
@@ -215,6 +216,17 @@ class Backend:
             fn = _ba.bundle_adjust_auto if one_launch else _ba.bundle_adjust_device
         return fn(poses, points, obs_pose_idx, obs_point_idx, meas, (fx, fy, cx, cy), iterations, fixed_poses,
                   huber_delta, ctx=self.ctx)
+
+    def global_bundle_adjust(self, poses, points, obs_pose_idx, obs_point_idx, meas, fx, fy, cx, cy, iterations: int = 10,
+                             fixed_poses=(0,), huber_delta: float = 0.0, pcg_tol: float = _bas.DEFAULT_PCG_TOL,
+                             pcg_max_iter: int = _bas.DEFAULT_PCG_MAX_ITER):
+        """Bundle adjustment over a whole map (ORB-SLAM's step after a closed loop; the reference's ``Backend`` has no
+        body, ``backend.py:101-103``): the arguments of ``optimize``, for thousands of keyframes.  The reduced camera
+        system is kept as 6x6 blocks over the covisibility graph and solved by the pose-graph PCG on the device
+        (``slamhip.bundle_adjust_sparse``); ``optimize`` and its routing are not involved.
+        Returns (``slamhip.ba.BAResult``, stats dict)."""
+        return _bas.bundle_adjust_sparse(poses, points, obs_pose_idx, obs_point_idx, meas, (fx, fy, cx, cy), iterations, fixed_poses,
+                                         huber_delta, pcg_tol, pcg_max_iter, ctx=self.ctx)
 
     def optimize_pose_graph(self, poses, edges, meas, info, fixed=(0,), iterations: int = _pg.DEFAULT_ITERATIONS,
                             huber_delta: float = 0.0, pcg_tol: float = _pg.DEFAULT_PCG_TOL,

@@ -60,6 +60,7 @@ from .pnp import (  # noqa: F401
     solve_pnp_ransac_batch,
     solve_pnp_ransac_offsets,
 )
+from .ba_sparse import SparseBAProblem, bundle_adjust_sparse, covisibility  # noqa: F401
 from .pose_graph import (  # noqa: F401
     loop_edges_from_two_view,
     optimize_pose_graph,

@@ -174,6 +174,13 @@ SIGNATURES = {
     "slam_ba_optimize_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double, c_double, c_int, c_void_p,
                                      c_void_p, c_void_p, c_uint64, c_void_p]),
+    "slam_bas_workspace": (c_int, [c_int64, c_int64, c_int64, c_int64, c_int64, POINTER(c_uint64)]),
+    "slam_bas_plan": (c_int, [c_int64, c_int64, c_int64, c_int64, c_int64, POINTER(c_int32)]),
+    "slam_bas_linearize_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64] + [c_void_p] * 10 + [c_double] * 5 + [c_void_p] * 7),
+    "slam_bas_cost_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64] + [c_void_p] * 7 + [c_double] * 5 + [c_void_p] * 2),
+    "slam_bas_reduce_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64] + [c_void_p] * 12 + [c_double] + [c_void_p] * 5),
+    "slam_bas_backsub_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64] + [c_void_p] * 8),
+    "slam_bas_candidate_f64": (c_int, [c_void_p, c_int64, c_int64] + [c_void_p] * 7 + [c_double] + [c_void_p] * 4),
     "slam_comm_version": (c_int, [POINTER(c_int)]),
     "slam_comm_unique_id": (c_int, [c_void_p]),
     "slam_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
