@@ -21,13 +21,13 @@
 //   ba_pose_kernel    one block per pose         : Hpp, bp, rhs, cost (over the pose's obs list)
 //   ba_pair_kernel    one block per (k1 <= k2)   : the S block (over k1's obs list, looking k2's up)
 //   ba_backsub_kernel one thread per point       : dl
+//
+// The linearisation of one observation (ba_linearise), the block sum, the damped 3x3 inverse and the pose update live in
+// ba_common.h, which ba_sparse.hip shares; this file includes it under the compiler's default contraction (see there).
 #include "internal.h"
 #include <atomic>
 #include <math.h>
-
-#define BA_THREADS 256
-
-struct ba_cam { double fx, fy, cx, cy; };
+#include "ba_common.h"
 
 // per-observation record written by ba_obs_kernel / ba_point_kernel (all f64)
 //   [0..17]  Hpl (6x3 row-major)      [18..35] Y = Hpl E (6x3)
@@ -50,44 +50,8 @@ struct ba_recs {
     __device__ __forceinline__ ba_rec_ref of(int o) const { return {p + (size_t)o * BA_REC}; }
 };
 
-__device__ __forceinline__ double ba_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // (the *_body functions take the block index as an argument: blockIdx.x of the per-phase kernels below, a loop variable
 // of the persistent kernel in ba_lm.hip's grid form at the end of this file)
-// one observation linearised: residual e, robust weight w and cost rho, the 2x6 pose Jacobian (rotation first) and the 2x3
-// point Jacobian, at pose P (3x4 row-major, any address space) and point p
-struct ba_lin { double e0, e1, w, rho, jp[2][6], jq[2][3]; };
-
-__device__ __forceinline__ void ba_linearise(const double* P, const double* p, const double2 m, const ba_cam& cam, const double delta,
-                                             ba_lin& q) {
-    const double X = P[0] * p[0] + P[1] * p[1] + P[2] * p[2] + P[3];
-    const double Y = P[4] * p[0] + P[5] * p[1] + P[6] * p[2] + P[7];
-    const double Z = P[8] * p[0] + P[9] * p[1] + P[10] * p[2] + P[11];
-    q.e0 = m.x - (cam.fx * X + cam.cx * Z) / Z;      // frontend.py:275-277
-    q.e1 = m.y - (cam.fy * Y + cam.cy * Z) / Z;
-    const double Zinv = 1.0 / (Z + 1e-18), Zinv2 = Zinv * Zinv;  // frontend.py:284-291
-    q.jp[0][0] = cam.fx * X * Y * Zinv2; q.jp[0][1] = -cam.fx - cam.fx * X * X * Zinv2; q.jp[0][2] = cam.fx * Y * Zinv;
-    q.jp[0][3] = -cam.fx * Zinv; q.jp[0][4] = 0.0; q.jp[0][5] = cam.fx * X * Zinv2;
-    q.jp[1][0] = cam.fy + cam.fy * Y * Y * Zinv2; q.jp[1][1] = -cam.fy * X * Y * Zinv2; q.jp[1][2] = -cam.fy * X * Zinv;
-    q.jp[1][3] = 0.0; q.jp[1][4] = -cam.fy * Zinv; q.jp[1][5] = cam.fy * Y * Zinv2;
-    const double A[2][3] = {{cam.fx * Zinv, 0.0, -cam.fx * X * Zinv2}, {0.0, cam.fy * Zinv, -cam.fy * Y * Zinv2}};
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        q.jq[0][c] = -(A[0][0] * P[c] + A[0][2] * P[8 + c]);
-        q.jq[1][c] = -(A[1][1] * P[4 + c] + A[1][2] * P[8 + c]);
-    }
-    const double c2 = q.e0 * q.e0 + q.e1 * q.e1;
-    q.w = 1.0; q.rho = c2;
-    if (delta > 0.0) {
-        const double en = sqrt(c2);
-        if (en > delta) { q.w = delta / en; q.rho = 2.0 * delta * en - delta * delta; }
-    }
-}
-
 __device__ __forceinline__ void ba_obs_body(const double* __restrict__ poses, const double* __restrict__ points,
                                             const int* __restrict__ obs_pose, const int* __restrict__ obs_point,
                                             const double2* __restrict__ meas, int O, ba_cam cam, double delta, int K, int L,
@@ -139,18 +103,6 @@ __global__ __launch_bounds__(BA_THREADS) void ba_obs_kernel(const double* __rest
     ba_obs_body(poses, points, obs_pose, obs_point, meas, O, cam, delta, K, L, index_errors, ba_recs{rec}, (int)(blockIdx.x * BA_THREADS + threadIdx.x));
 }
 
-// symmetric 3x3 inverse of H + lam I, H as its packed upper triangle (the identity for a point nobody observes)
-__device__ __forceinline__ void ba_damped_inverse(const double (&h)[6], const double lam, const bool seen, double (&e)[9]) {
-    double m00 = h[0] + lam, m01 = h[1], m02 = h[2], m11 = h[3] + lam, m12 = h[4], m22 = h[5] + lam;
-    if (!seen) { m00 = m11 = m22 = 1.0; m01 = m02 = m12 = 0.0; }
-    const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
-    const double det = m00 * c00 + m01 * c01 + m02 * c02;
-    const double id = 1.0 / det;
-    e[0] = c00 * id; e[1] = c01 * id; e[2] = c02 * id;
-    e[3] = e[1]; e[4] = (m00 * m22 - m02 * m02) * id; e[5] = (m01 * m02 - m00 * m12) * id;
-    e[6] = e[2]; e[7] = e[5]; e[8] = (m00 * m11 - m01 * m01) * id;
-}
-
 // per point: Hll, bl over its observations (CSR row, ascending), E = (Hll + lam I)^-1, Y_o = Hpl_o E
 __device__ __forceinline__ void ba_point_body(const int* __restrict__ pt_ptr, const int* __restrict__ pt_obs, int L, double lam,
                                               const ba_recs rec, double* __restrict__ E, double* __restrict__ bl,
@@ -192,21 +144,6 @@ __global__ __launch_bounds__(BA_THREADS) void ba_point_kernel(const int* __restr
                                                               double* __restrict__ bl,
                                                               double* __restrict__ hll_diag /*[L,3] or null*/) {
     ba_point_body(pt_ptr, pt_obs, L, lam, ba_recs{rec}, E, bl, hll_diag, (int)(blockIdx.x * BA_THREADS + threadIdx.x));
-}
-
-// block-wide fixed-order sum of NT per-thread accumulators into out[NT] (shared), all threads return after it
-template <int NT>
-__device__ __forceinline__ void ba_block_sum(const double (&acc)[NT], double (*sw)[NT], double* out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NT; i++) {
-        const double s = ba_wave_sum(acc[i]);
-        if (lane == 0) sw[wave][i] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NT) out[threadIdx.x] = ((sw[0][threadIdx.x] + sw[1][threadIdx.x]) + sw[2][threadIdx.x]) + sw[3][threadIdx.x];
-    __syncthreads();
 }
 
 // one block per pose k, or per slice [begin, end) of its observation list: Hpp (21), bp (6), y = sum Y_o bl (6) and the
@@ -859,33 +796,6 @@ __device__ __forceinline__ bool bg_factor_solve(double* __restrict__ S, double* 
     return ok;     // meaningful in wave 0 (thread 0 publishes it)
 }
 
-// exp([w, v]) * T for a 3x4 row-major pose (rotation first): the update the Jacobian of frontend.py:288-291 is the derivative for
-__device__ void bg_apply_update(const double* dx, const double* T, double* Tn) {
-    const double wx = dx[0], wy = dx[1], wz = dx[2];
-    const double th2 = wx * wx + wy * wy + wz * wz, th = sqrt(th2);
-    double sa, sb, sc;  // sin(th)/th, (1-cos)/th^2, (th-sin)/th^3
-    if (th < 1e-10) { sa = 1.0; sb = 0.5; sc = 1.0 / 6.0; }
-    else {
-        double sn, cs;
-        sincos(th, &sn, &cs);
-        sa = sn / th; sb = (1.0 - cs) / th2; sc = (th - sn) / (th2 * th);
-    }
-    const double Wm[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-    double W2[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) W2[i * 3 + j] = Wm[i * 3] * Wm[j] + Wm[i * 3 + 1] * Wm[3 + j] + Wm[i * 3 + 2] * Wm[6 + j];
-    double R[9], V[9];
-    for (int i = 0; i < 9; i++) {
-        const double I = (i % 4 == 0) ? 1.0 : 0.0;
-        R[i] = I + sa * Wm[i] + sb * W2[i];
-        V[i] = I + sb * Wm[i] + sc * W2[i];
-    }
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 4; j++) Tn[i * 4 + j] = R[i * 3] * T[j] + R[i * 3 + 1] * T[4 + j] + R[i * 3 + 2] * T[8 + j];
-        Tn[i * 4 + 3] += V[i * 3] * dx[3] + V[i * 3 + 1] * dx[4] + V[i * 3 + 2] * dx[5];
-    }
-}
-
 // sum over the four lanes of a quad (DPP quad_perm, no LDS): every lane gets (v0 + v1) + (v2 + v3) or its mirror image -
 // the same bits, addition being commutative.  All four lanes must be active.
 __device__ __forceinline__ double bg_quad_sum(double v) {
@@ -1128,7 +1038,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_lm_grid_kernel(const bg_args a)
         //      workgroup keeps the K candidate poses in LDS; workgroup 0 also stores them) --------------------------------------
         {
             for (int k = tid; k < K; k += BA_THREADS) {
-                bg_apply_update(sdp + (size_t)k * 6, sT + (size_t)k * 12, sTn + (size_t)k * 12);
+                ba_apply_update(sdp + (size_t)k * 6, sT + (size_t)k * 12, sTn + (size_t)k * 12);
                 if (blk == 0)
                     for (int x = 0; x < 12; x++) Tn[(size_t)k * 12 + x] = sTn[(size_t)k * 12 + x];
             }

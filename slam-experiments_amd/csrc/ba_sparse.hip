@@ -5,7 +5,7 @@
 // holds a keyframe window, not the map behind a closed loop.  Here the system exists only where two free poses see a common
 // point: diagonal blocks d_Hdiag [K,36], one block d_W [E,36] per covisibility edge (k1 < k2, row block k1, column block k2),
 // the gradient d_b [K,6] - and (S + lambda I) dp = -b is exactly what slam_pg_pcg_f64 solves.  With J = [Jp | Jq] per
-// observation and w its Huber weight (the arithmetic of reproj.hip / ba_schur.hip, restated in bas_linearise):
+// observation and w its Huber weight (the arithmetic of reproj.hip / ba_schur.hip: ba_linearise of ba_common.h):
 //   Hpp_k = sum w Jp^T Jp, bp_k = sum w Jp^T e (per pose)      Hll_l = sum w Jq^T Jq, bl_l = sum w Jq^T e (per point)
 //   Hpl_o = w Jp^T Jq (6x3, per observation)                   E_l = (Hll_l + lambda I)^-1 (0 for a point nobody observes)
 //   W_e     = - sum_{pairs (a, b) of e} Hpl_a E_l Hpl_b^T
@@ -17,7 +17,7 @@
 //   bas_obs_kernel      a thread per observation   Hpl_o; the two indices are checked here and counted (slam_index_errors)
 //   bas_point_kernel    a thread per point         Hll (6), bl (3) over its list pt_obs, in list order
 //   bas_pose_kernel     a workgroup per pose       Hpp (21), bp (6), cost: thread t takes entries t, t + 256, .. of ps_obs,
-//                                                  then bas_block_sum (xor tree inside a wave, the four waves in order)
+//                                                  then ba_block_sum (xor tree inside a wave, the four waves in order)
 //   bas_inverse_kernel  a thread per point         E_l, E_l bl_l
 //   bas_edge_kernel     a WAVE per edge            lane i takes pairs i, i + 64, .. of the edge's pair list, the 64 lane sums
 //                                                  meet in the xor tree: the order is a function of the pair count alone, an
@@ -27,51 +27,24 @@
 //   bas_candidate_kernel a thread per pose / point T' = exp(dp) T (fixed poses copied), X' = X + dl, the gain-ratio
 //                                                  denominator as one partial sum per workgroup
 //   bas_cost_kernel     a workgroup per pose       robust cost at a state, summed as bas_pose_kernel sums it
-//   bas_finish_kernel   one workgroup              partial sums -> one scalar (thread t takes t, t + 256, ..; bas_block_sum)
+//   bas_finish_kernel   one workgroup              partial sums -> one scalar (thread t takes t, t + 256, ..; ba_block_sum)
 // Hpl is kept (18 doubles per observation) because three phases of every trial read it while the state stands still;
 // the per-pose and per-point sums are consumed once, so their terms are linearised again instead of stored.
 //
 // No entry point here takes the context's call lock or its workspace: every buffer is the caller's (slam_bas_workspace says
 // how large), the launches are asynchronous on the context's stream, and slam_pg_pcg_f64 - which does take the lock - is
 // called by the driver between them.
+//
+// The linearisation of one observation, the block sum, the damped 3x3 inverse and the pose update are ba_schur.hip's, from
+// ba_common.h; it is included BEHIND the pragma below, so here they are compiled without contraction like everything else.
 #include "internal.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
+#include "ba_common.h"
 
-#define BAS_THREADS 256
-#define BAS_WAVES (BAS_THREADS / 64)
+#define BAS_WAVES (BA_THREADS / 64)
 #define BAS_MAX_PART 1024          // partial sums of the candidate kernel (its grid)
-
-struct bas_cam { double fx, fy, cx, cy; };
-struct bas_lin { double e0, e1, w, rho, jp[2][6], jq[2][3]; };
-
-// one observation linearised at pose P (3x4 row-major) and point p: ba_linearise of ba_schur.hip (frontend.py:272-291)
-__device__ __forceinline__ void bas_linearise(const double* P, const double* p, const double2 m, const bas_cam& cam, const double delta,
-                                              bas_lin& q) {
-    const double X = P[0] * p[0] + P[1] * p[1] + P[2] * p[2] + P[3];
-    const double Y = P[4] * p[0] + P[5] * p[1] + P[6] * p[2] + P[7];
-    const double Z = P[8] * p[0] + P[9] * p[1] + P[10] * p[2] + P[11];
-    q.e0 = m.x - (cam.fx * X + cam.cx * Z) / Z;
-    q.e1 = m.y - (cam.fy * Y + cam.cy * Z) / Z;
-    const double Zinv = 1.0 / (Z + 1e-18), Zinv2 = Zinv * Zinv;
-    q.jp[0][0] = cam.fx * X * Y * Zinv2; q.jp[0][1] = -cam.fx - cam.fx * X * X * Zinv2; q.jp[0][2] = cam.fx * Y * Zinv;
-    q.jp[0][3] = -cam.fx * Zinv; q.jp[0][4] = 0.0; q.jp[0][5] = cam.fx * X * Zinv2;
-    q.jp[1][0] = cam.fy + cam.fy * Y * Y * Zinv2; q.jp[1][1] = -cam.fy * X * Y * Zinv2; q.jp[1][2] = -cam.fy * X * Zinv;
-    q.jp[1][3] = 0.0; q.jp[1][4] = -cam.fy * Zinv; q.jp[1][5] = cam.fy * Y * Zinv2;
-    const double A[2][3] = {{cam.fx * Zinv, 0.0, -cam.fx * X * Zinv2}, {0.0, cam.fy * Zinv, -cam.fy * Y * Zinv2}};
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        q.jq[0][c] = -(A[0][0] * P[c] + A[0][2] * P[8 + c]);
-        q.jq[1][c] = -(A[1][1] * P[4 + c] + A[1][2] * P[8 + c]);
-    }
-    const double c2 = q.e0 * q.e0 + q.e1 * q.e1;
-    q.w = 1.0; q.rho = c2;
-    if (delta > 0.0) {
-        const double en = sqrt(c2);
-        if (en > delta) { q.w = delta / en; q.rho = 2.0 * delta * en - delta * delta; }
-    }
-}
 
 struct bas_obs_tab {
     const int* obs_pose; const int* obs_point; const double2* meas;
@@ -80,41 +53,20 @@ struct bas_obs_tab {
 
 // observation o of an index table linearised at (T, X); false (nothing dereferenced) when o or one of its indices is outside
 __device__ __forceinline__ bool bas_at(const bas_obs_tab& t, const double* __restrict__ T, const double* __restrict__ X, const int o,
-                                       const bas_cam& cam, const double delta, bas_lin& q, int& k, int& l) {
+                                       const ba_cam& cam, const double delta, ba_lin& q, int& k, int& l) {
     if ((unsigned)o >= (unsigned)t.O) return false;
     k = t.obs_pose[o]; l = t.obs_point[o];
     if ((unsigned)k >= (unsigned)t.K || (unsigned)l >= (unsigned)t.L) return false;
-    bas_linearise(T + (size_t)k * 12, X + (size_t)l * 3, t.meas[o], cam, delta, q);
+    ba_linearise(T + (size_t)k * 12, X + (size_t)l * 3, t.meas[o], cam, delta, q);
     return true;
 }
 
-__device__ __forceinline__ double bas_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// block-wide fixed-order sum of NT per-thread accumulators into out[NT] (shared); every thread returns behind it
-template <int NT>
-__device__ __forceinline__ void bas_block_sum(const double (&acc)[NT], double (*sw)[NT], double* out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NT; i++) {
-        const double s = bas_wave_sum(acc[i]);
-        if (lane == 0) sw[wave][i] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NT) out[threadIdx.x] = ((sw[0][threadIdx.x] + sw[1][threadIdx.x]) + sw[2][threadIdx.x]) + sw[3][threadIdx.x];
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(BAS_THREADS) void bas_obs_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                              bas_cam cam, double delta, unsigned int* __restrict__ index_errors,
+__global__ __launch_bounds__(BA_THREADS) void bas_obs_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
+                                                              ba_cam cam, double delta, unsigned int* __restrict__ index_errors,
                                                               double* __restrict__ Hpl /*[O,18]*/) {
-    const int o = (int)(blockIdx.x * BAS_THREADS + threadIdx.x);
+    const int o = (int)(blockIdx.x * BA_THREADS + threadIdx.x);
     if (o >= t.O) return;
-    bas_lin q;
+    ba_lin q;
     int k, l;
     double* h = Hpl + (size_t)o * 18;
     if (!bas_at(t, T, X, o, cam, delta, q, k, l)) {          // reported, never dereferenced; its block poisons what reads it
@@ -129,17 +81,17 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_obs_kernel(const bas_obs_tab 
         for (int c = 0; c < 3; c++) h[a * 3 + c] = q.w * (q.jp[0][a] * q.jq[0][c] + q.jp[1][a] * q.jq[1][c]);
 }
 
-__global__ __launch_bounds__(BAS_THREADS) void bas_point_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                                const int* __restrict__ pt_ptr, const int* __restrict__ pt_obs, bas_cam cam,
+__global__ __launch_bounds__(BA_THREADS) void bas_point_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
+                                                                const int* __restrict__ pt_ptr, const int* __restrict__ pt_obs, ba_cam cam,
                                                                 double delta, unsigned int* __restrict__ index_errors,
                                                                 double* __restrict__ Hll /*[L,6]*/, double* __restrict__ bl /*[L,3]*/) {
-    const int l = (int)(blockIdx.x * BAS_THREADS + threadIdx.x);
+    const int l = (int)(blockIdx.x * BA_THREADS + threadIdx.x);
     if (l >= t.L) return;
     double h[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
     int a0 = pt_ptr[l], a1 = pt_ptr[l + 1];
     if (a0 < 0 || a1 < a0 || a1 > t.O) { atomicAdd(index_errors, 1u); a1 = a0 = 0; }
     for (int i = a0; i < a1; i++) {
-        bas_lin q;
+        ba_lin q;
         int k, l2;
         if (!bas_at(t, T, X, pt_obs[i], cam, delta, q, k, l2)) { h[0] = __builtin_nan(""); continue; }
         int n = 0;
@@ -162,8 +114,8 @@ __device__ __forceinline__ void bas_pose_range(const int* __restrict__ ps_ptr, i
     if (a0 < 0 || a1 < a0 || a1 > O) a0 = a1 = 0;
 }
 
-__global__ __launch_bounds__(BAS_THREADS) void bas_pose_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                               const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs, bas_cam cam,
+__global__ __launch_bounds__(BA_THREADS) void bas_pose_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
+                                                               const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs, ba_cam cam,
                                                                double delta, double* __restrict__ Hpp /*[K,21]*/, double* __restrict__ bp /*[K,6]*/,
                                                                double* __restrict__ cost /*[K]*/) {
     __shared__ double sw[BAS_WAVES][28];
@@ -174,8 +126,8 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_pose_kernel(const bas_obs_tab
     for (int i = 0; i < 28; i++) acc[i] = 0.0;
     int a0, a1;
     bas_pose_range(ps_ptr, k, t.O, a0, a1);
-    for (int i = a0 + (int)threadIdx.x; i < a1; i += BAS_THREADS) {
-        bas_lin q;
+    for (int i = a0 + (int)threadIdx.x; i < a1; i += BA_THREADS) {
+        ba_lin q;
         int k2, l;
         if (!bas_at(t, T, X, ps_obs[i], cam, delta, q, k2, l)) { acc[27] = __builtin_nan(""); continue; }
         int n = 0;
@@ -187,14 +139,14 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_pose_kernel(const bas_obs_tab
         for (int a = 0; a < 6; a++) acc[21 + a] += q.w * (q.jp[0][a] * q.e0 + q.jp[1][a] * q.e1);
         acc[27] += q.rho;
     }
-    bas_block_sum<28>(acc, sw, out);
+    ba_block_sum<28>(acc, sw, out);
     if (threadIdx.x < 21) Hpp[(size_t)k * 21 + threadIdx.x] = out[threadIdx.x];
     else if (threadIdx.x < 27) bp[(size_t)k * 6 + threadIdx.x - 21] = out[threadIdx.x];
     else if (threadIdx.x == 27) cost[k] = out[27];
 }
 
-__global__ __launch_bounds__(BAS_THREADS) void bas_cost_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                               const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs, bas_cam cam,
+__global__ __launch_bounds__(BA_THREADS) void bas_cost_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
+                                                               const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs, ba_cam cam,
                                                                double delta, double* __restrict__ cost /*[K]*/) {
     __shared__ double sw[BAS_WAVES][1];
     __shared__ double out[1];
@@ -202,36 +154,36 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_cost_kernel(const bas_obs_tab
     double acc[1] = {0.0};
     int a0, a1;
     bas_pose_range(ps_ptr, k, t.O, a0, a1);
-    for (int i = a0 + (int)threadIdx.x; i < a1; i += BAS_THREADS) {
-        bas_lin q;
+    for (int i = a0 + (int)threadIdx.x; i < a1; i += BA_THREADS) {
+        ba_lin q;
         int k2, l;
         if (!bas_at(t, T, X, ps_obs[i], cam, delta, q, k2, l)) { acc[0] = __builtin_nan(""); continue; }
         acc[0] += q.rho;
     }
-    bas_block_sum<1>(acc, sw, out);
+    ba_block_sum<1>(acc, sw, out);
     if (threadIdx.x == 0) cost[k] = out[0];
 }
 
 // out[0] = sum of part[0..n) (thread t takes t, t + 256, ..); with diagonals given, out[1] = the largest diagonal entry of the
 // Hpp of the free poses and of every Hll (the maximum does not depend on an order)
-__global__ __launch_bounds__(BAS_THREADS) void bas_finish_kernel(const double* __restrict__ part, int n, double* __restrict__ out,
+__global__ __launch_bounds__(BA_THREADS) void bas_finish_kernel(const double* __restrict__ part, int n, double* __restrict__ out,
                                                                  const double* __restrict__ Hpp, const uint8_t* __restrict__ fixed, int K,
                                                                  const double* __restrict__ Hll, int L) {
     __shared__ double sw[BAS_WAVES][1];
     __shared__ double res[1];
     __shared__ double mx[BAS_WAVES];
     double acc[1] = {0.0};
-    for (int i = (int)threadIdx.x; i < n; i += BAS_THREADS) acc[0] += part[i];
-    bas_block_sum<1>(acc, sw, res);
+    for (int i = (int)threadIdx.x; i < n; i += BA_THREADS) acc[0] += part[i];
+    ba_block_sum<1>(acc, sw, res);
     if (threadIdx.x == 0) out[0] = res[0];
     if (!Hpp) return;
     double m = 0.0;
-    for (int k = (int)threadIdx.x; k < K; k += BAS_THREADS) {
+    for (int k = (int)threadIdx.x; k < K; k += BA_THREADS) {
         if (fixed[k]) continue;
         const double* h = Hpp + (size_t)k * 21;
         m = fmax(m, fmax(fmax(h[0], h[6]), fmax(fmax(h[11], h[15]), fmax(h[18], h[20]))));
     }
-    for (int l = (int)threadIdx.x; l < L; l += BAS_THREADS) {
+    for (int l = (int)threadIdx.x; l < L; l += BA_THREADS) {
         const double* h = Hll + (size_t)l * 6;
         m = fmax(m, fmax(h[0], fmax(h[3], h[5])));
     }
@@ -242,22 +194,18 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_finish_kernel(const double* _
     if (threadIdx.x == 0) out[1] = fmax(fmax(mx[0], mx[1]), fmax(mx[2], mx[3]));
 }
 
-// E_l = (Hll_l + lambda I)^-1 by cofactors (ba_damped_inverse of ba_schur.hip), 0 for a point nobody observes; Ebl = E bl
-__global__ __launch_bounds__(BAS_THREADS) void bas_inverse_kernel(int L, const int* __restrict__ pt_ptr, const double* __restrict__ Hll,
+// E_l = (Hll_l + lambda I)^-1 (ba_damped_inverse), 0 for a point nobody observes; Ebl = E bl
+__global__ __launch_bounds__(BA_THREADS) void bas_inverse_kernel(int L, const int* __restrict__ pt_ptr, const double* __restrict__ Hll,
                                                                   const double* __restrict__ bl, double lam, double* __restrict__ E /*[L,9]*/,
                                                                   double* __restrict__ Ebl /*[L,3]*/) {
-    const int l = (int)(blockIdx.x * BAS_THREADS + threadIdx.x);
+    const int l = (int)(blockIdx.x * BA_THREADS + threadIdx.x);
     if (l >= L) return;
-    const double* h = Hll + (size_t)l * 6;
     double e[9];
     if (pt_ptr[l + 1] > pt_ptr[l]) {
-        const double m00 = h[0] + lam, m01 = h[1], m02 = h[2], m11 = h[3] + lam, m12 = h[4], m22 = h[5] + lam;
-        const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
-        const double det = m00 * c00 + m01 * c01 + m02 * c02;
-        const double id = 1.0 / det;
-        e[0] = c00 * id; e[1] = c01 * id; e[2] = c02 * id;
-        e[3] = e[1]; e[4] = (m00 * m22 - m02 * m02) * id; e[5] = (m01 * m02 - m00 * m12) * id;
-        e[6] = e[2]; e[7] = e[5]; e[8] = (m00 * m11 - m01 * m01) * id;
+        double h[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) h[i] = Hll[(size_t)l * 6 + i];
+        ba_damped_inverse(h, lam, true, e);
     } else {
 #pragma unroll
         for (int i = 0; i < 9; i++) e[i] = 0.0;
@@ -278,7 +226,7 @@ __device__ __forceinline__ void bas_he(const double* __restrict__ h, const doubl
 }
 
 // a wave per edge: W_e = - sum over the edge's pairs of Hpl_a E_l Hpl_b^T
-__global__ __launch_bounds__(BAS_THREADS) void bas_edge_kernel(int E, int O, int L, int64_t P, const int* __restrict__ pair_ptr,
+__global__ __launch_bounds__(BA_THREADS) void bas_edge_kernel(int E, int O, int L, int64_t P, const int* __restrict__ pair_ptr,
                                                                const int* __restrict__ pair_a, const int* __restrict__ pair_b,
                                                                const int* __restrict__ obs_point, const double* __restrict__ Hpl,
                                                                const double* __restrict__ Einv, unsigned int* __restrict__ index_errors,
@@ -307,14 +255,14 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_edge_kernel(int E, int O, int
     double mine = 0.0;
 #pragma unroll
     for (int i = 0; i < 36; i++) {
-        const double s = bas_wave_sum(acc[i]);
+        const double s = ba_wave_sum(acc[i]);
         if (lane == i) mine = s;
     }
     if (lane < 36) W[(size_t)e * 36 + lane] = -mine;
 }
 
 // a workgroup per pose: Hdiag_k = Hpp_k - sum Hpl_o E_l Hpl_o^T (full symmetric 6x6), b_k = bp_k - sum Hpl_o (E_l bl_l)
-__global__ __launch_bounds__(BAS_THREADS) void bas_diag_kernel(int O, int L, const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs,
+__global__ __launch_bounds__(BA_THREADS) void bas_diag_kernel(int O, int L, const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs,
                                                                const int* __restrict__ obs_point, const double* __restrict__ Hpl,
                                                                const double* __restrict__ Einv, const double* __restrict__ Ebl,
                                                                const double* __restrict__ Hpp, const double* __restrict__ bp,
@@ -327,7 +275,7 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_diag_kernel(int O, int L, con
     for (int i = 0; i < 27; i++) acc[i] = 0.0;
     int a0, a1;
     bas_pose_range(ps_ptr, k, O, a0, a1);
-    for (int i = a0 + (int)threadIdx.x; i < a1; i += BAS_THREADS) {
+    for (int i = a0 + (int)threadIdx.x; i < a1; i += BA_THREADS) {
         const int o = ps_obs[i];
         if ((unsigned)o >= (unsigned)O) { acc[0] = __builtin_nan(""); continue; }
         const int l = obs_point[o];
@@ -344,7 +292,7 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_diag_kernel(int O, int L, con
 #pragma unroll
         for (int a = 0; a < 6; a++) acc[21 + a] += h[a * 3] * eb[0] + h[a * 3 + 1] * eb[1] + h[a * 3 + 2] * eb[2];
     }
-    bas_block_sum<27>(acc, sw, out);
+    ba_block_sum<27>(acc, sw, out);
     if (threadIdx.x < 36) {
         const int r = threadIdx.x / 6, c = threadIdx.x % 6, a = r < c ? r : c, d = r < c ? c : r;
         const int n = a * 6 - a * (a - 1) / 2 + (d - a);      // packed upper triangle, rows of 6, 5, .. entries
@@ -356,11 +304,11 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_diag_kernel(int O, int L, con
 }
 
 // a thread per point: dl_l = - E_l (bl_l + sum_{o of l} Hpl_o^T dp_pose(o)), in list order
-__global__ __launch_bounds__(BAS_THREADS) void bas_backsub_kernel(int K, int L, int O, const int* __restrict__ pt_ptr, const int* __restrict__ pt_obs,
+__global__ __launch_bounds__(BA_THREADS) void bas_backsub_kernel(int K, int L, int O, const int* __restrict__ pt_ptr, const int* __restrict__ pt_obs,
                                                                   const int* __restrict__ obs_pose, const double* __restrict__ Hpl,
                                                                   const double* __restrict__ Einv, const double* __restrict__ bl,
                                                                   const double* __restrict__ dp /*[K,6]*/, double* __restrict__ dl /*[L,3]*/) {
-    const int l = (int)(blockIdx.x * BAS_THREADS + threadIdx.x);
+    const int l = (int)(blockIdx.x * BA_THREADS + threadIdx.x);
     if (l >= L) return;
     double t[3] = {bl[(size_t)l * 3], bl[(size_t)l * 3 + 1], bl[(size_t)l * 3 + 2]};
     int a0 = pt_ptr[l], a1 = pt_ptr[l + 1];
@@ -382,41 +330,9 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_backsub_kernel(int K, int L, 
     for (int c = 0; c < 3; c++) dl[(size_t)l * 3 + c] = a1 > a0 ? -(e[c * 3] * t[0] + e[c * 3 + 1] * t[1] + e[c * 3 + 2] * t[2]) : 0.0;
 }
 
-// exp([w, v]) T for a 3x4 row-major pose (po_apply_update of pose_opt.hip)
-__device__ __forceinline__ void bas_apply_update(const double* dx, const double* T, double* Tn) {
-    const double wx = dx[0], wy = dx[1], wz = dx[2];
-    const double th2 = wx * wx + wy * wy + wz * wz, th = sqrt(th2);
-    double a, b, c;  // sin(th)/th, (1-cos)/th^2, (th-sin)/th^3
-    if (th < 1e-10) { a = 1.0; b = 0.5; c = 1.0 / 6.0; }
-    else {
-        double sn, cs;
-        sincos(th, &sn, &cs);
-        a = sn / th; b = (1.0 - cs) / th2; c = (th - sn) / (th2 * th);
-    }
-    const double W[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-    double W2[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) W2[i * 3 + j] = W[i * 3] * W[j] + W[i * 3 + 1] * W[3 + j] + W[i * 3 + 2] * W[6 + j];
-    double R[9], V[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        const double I = (i % 4 == 0) ? 1.0 : 0.0;
-        R[i] = I + a * W[i] + b * W2[i];
-        V[i] = I + b * W[i] + c * W2[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) Tn[i * 4 + j] = R[i * 3] * T[j] + R[i * 3 + 1] * T[4 + j] + R[i * 3 + 2] * T[8 + j];
-        Tn[i * 4 + 3] += V[i * 3] * dx[3] + V[i * 3 + 1] * dx[4] + V[i * 3 + 2] * dx[5];
-    }
-}
-
 // items 0..K-1 are the poses, K..K+L-1 the points; thread t of workgroup g takes items g * 256 + t + j * (grid * 256), its
-// terms of the gain-ratio denominator dp.(lambda dp - bp) / dl.(lambda dl - bl) summed in that order, then bas_block_sum
-__global__ __launch_bounds__(BAS_THREADS) void bas_candidate_kernel(int K, int L, const uint8_t* __restrict__ fixed, const double* __restrict__ T,
+// terms of the gain-ratio denominator dp.(lambda dp - bp) / dl.(lambda dl - bl) summed in that order, then ba_block_sum
+__global__ __launch_bounds__(BA_THREADS) void bas_candidate_kernel(int K, int L, const uint8_t* __restrict__ fixed, const double* __restrict__ T,
                                                                     const double* __restrict__ X, const double* __restrict__ dp,
                                                                     const double* __restrict__ dl, const double* __restrict__ bp,
                                                                     const double* __restrict__ bl, double lam, double* __restrict__ Tn,
@@ -424,8 +340,8 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_candidate_kernel(int K, int L
     __shared__ double sw[BAS_WAVES][1];
     __shared__ double out[1];
     double acc[1] = {0.0};
-    const int64_t n = (int64_t)K + L, step = (int64_t)gridDim.x * BAS_THREADS;
-    for (int64_t i = (int64_t)blockIdx.x * BAS_THREADS + threadIdx.x; i < n; i += step) {
+    const int64_t n = (int64_t)K + L, step = (int64_t)gridDim.x * BA_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * BA_THREADS + threadIdx.x; i < n; i += step) {
         if (i < K) {
             const size_t k = (size_t)i;
             if (fixed[k]) {
@@ -435,7 +351,7 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_candidate_kernel(int K, int L
                 double d[6];
 #pragma unroll
                 for (int j = 0; j < 6; j++) d[j] = dp[k * 6 + j];
-                bas_apply_update(d, T + k * 12, Tn + k * 12);
+                ba_apply_update(d, T + k * 12, Tn + k * 12);
                 double s = 0.0;
 #pragma unroll
                 for (int j = 0; j < 6; j++) s += d[j] * (lam * d[j] - bp[k * 6 + j]);
@@ -453,14 +369,14 @@ __global__ __launch_bounds__(BAS_THREADS) void bas_candidate_kernel(int K, int L
             acc[0] += s;
         }
     }
-    bas_block_sum<1>(acc, sw, out);
+    ba_block_sum<1>(acc, sw, out);
     if (threadIdx.x == 0) part[blockIdx.x] = out[0];
 }
 
 // ---- the C ABI -----------------------------------------------------------------------------------------------------------------------
-static inline int bas_blocks(int64_t n) { return (int)((n + BAS_THREADS - 1) / BAS_THREADS); }
+static inline int bas_blocks(int64_t n) { return (int)((n + BA_THREADS - 1) / BA_THREADS); }
 static inline int bas_cand_blocks(int64_t K, int64_t L) {
-    const int64_t n = (K + L + BAS_THREADS - 1) / BAS_THREADS;
+    const int64_t n = (K + L + BA_THREADS - 1) / BA_THREADS;
     return (int)(n < 1 ? 1 : n > BAS_MAX_PART ? BAS_MAX_PART : n);
 }
 static int bas_sizes(const char* who, int64_t K, int64_t L, int64_t O, int64_t E, int64_t P) {
@@ -496,7 +412,7 @@ extern "C" int slam_bas_plan(int64_t K, int64_t L, int64_t O, int64_t E, int64_t
     plan[2] = (int)K;                                     // pose kernels: a workgroup per pose
     plan[3] = (int)((E + BAS_WAVES - 1) / BAS_WAVES);     // edge kernel: a wave per edge, four to a workgroup
     plan[4] = bas_cand_blocks(K, L);                      // candidate kernel = partial sums of the gain-ratio denominator
-    plan[5] = BAS_THREADS;
+    plan[5] = BA_THREADS;
     plan[6] = 64;                                         // lanes that share an edge's pairs
     plan[7] = 0;
     return SLAM_OK;
@@ -517,13 +433,13 @@ extern "C" int slam_bas_linearize_f64(slam_ctx* ctx, int64_t K, int64_t L, int64
     SLAM_REQUIRE(huber_delta >= 0.0, "slam_bas_linearize_f64: huber_delta must not be negative");
     SLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const bas_cam cam = {fx, fy, cx, cy};
+    const ba_cam cam = {fx, fy, cx, cy};
     const bas_obs_tab t = {d_obs_pose, d_obs_point, (const double2*)d_meas, (int)K, (int)L, (int)O};
     unsigned int* ie = slam_index_error_counter(ctx);
-    if (O) bas_obs_kernel<<<bas_blocks(O), BAS_THREADS, 0, st>>>(t, d_poses, d_points, cam, huber_delta, ie, d_Hpl);
-    bas_point_kernel<<<bas_blocks(L), BAS_THREADS, 0, st>>>(t, d_poses, d_points, d_pt_ptr, d_pt_obs, cam, huber_delta, ie, d_Hll, d_bl);
-    bas_pose_kernel<<<(unsigned)K, BAS_THREADS, 0, st>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, huber_delta, d_Hpp, d_bp, d_cost);
-    bas_finish_kernel<<<1, BAS_THREADS, 0, st>>>(d_cost, (int)K, d_scal, d_Hpp, d_fixed, (int)K, d_Hll, (int)L);
+    if (O) bas_obs_kernel<<<bas_blocks(O), BA_THREADS, 0, st>>>(t, d_poses, d_points, cam, huber_delta, ie, d_Hpl);
+    bas_point_kernel<<<bas_blocks(L), BA_THREADS, 0, st>>>(t, d_poses, d_points, d_pt_ptr, d_pt_obs, cam, huber_delta, ie, d_Hll, d_bl);
+    bas_pose_kernel<<<(unsigned)K, BA_THREADS, 0, st>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, huber_delta, d_Hpp, d_bp, d_cost);
+    bas_finish_kernel<<<1, BA_THREADS, 0, st>>>(d_cost, (int)K, d_scal, d_Hpp, d_fixed, (int)K, d_Hll, (int)L);
     return slam_launch_check("slam_bas_linearize_f64");
 }
 
@@ -537,10 +453,10 @@ extern "C" int slam_bas_cost_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O,
                  "slam_bas_cost_f64: null device pointer");
     SLAM_REQUIRE(BAS_ALIGNED16(d_meas), "slam_bas_cost_f64: d_meas must be 16-byte aligned");
     SLAM_HIP(hipSetDevice(ctx->device));
-    const bas_cam cam = {fx, fy, cx, cy};
+    const ba_cam cam = {fx, fy, cx, cy};
     const bas_obs_tab t = {d_obs_pose, d_obs_point, (const double2*)d_meas, (int)K, (int)L, (int)O};
-    bas_cost_kernel<<<(unsigned)K, BAS_THREADS, 0, ctx->stream>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, huber_delta, d_cost);
-    bas_finish_kernel<<<1, BAS_THREADS, 0, ctx->stream>>>(d_cost, (int)K, d_total, nullptr, nullptr, 0, nullptr, 0);
+    bas_cost_kernel<<<(unsigned)K, BA_THREADS, 0, ctx->stream>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, huber_delta, d_cost);
+    bas_finish_kernel<<<1, BA_THREADS, 0, ctx->stream>>>(d_cost, (int)K, d_total, nullptr, nullptr, 0, nullptr, 0);
     return slam_launch_check("slam_bas_cost_f64");
 }
 
@@ -556,11 +472,11 @@ extern "C" int slam_bas_reduce_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t 
     SLAM_REQUIRE(lambda >= 0.0, "slam_bas_reduce_f64: lambda must not be negative");
     SLAM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    bas_inverse_kernel<<<bas_blocks(L), BAS_THREADS, 0, st>>>((int)L, d_pt_ptr, d_Hll, d_bl, lambda, d_E, d_Ebl);
+    bas_inverse_kernel<<<bas_blocks(L), BA_THREADS, 0, st>>>((int)L, d_pt_ptr, d_Hll, d_bl, lambda, d_E, d_Ebl);
     if (E)
-        bas_edge_kernel<<<(unsigned)((E + BAS_WAVES - 1) / BAS_WAVES), BAS_THREADS, 0, st>>>((int)E, (int)O, (int)L, P, d_pair_ptr, d_pair_a, d_pair_b,
+        bas_edge_kernel<<<(unsigned)((E + BAS_WAVES - 1) / BAS_WAVES), BA_THREADS, 0, st>>>((int)E, (int)O, (int)L, P, d_pair_ptr, d_pair_a, d_pair_b,
                                                                                          d_obs_point, d_Hpl, d_E, slam_index_error_counter(ctx), d_W);
-    bas_diag_kernel<<<(unsigned)K, BAS_THREADS, 0, st>>>((int)O, (int)L, d_ps_ptr, d_ps_obs, d_obs_point, d_Hpl, d_E, d_Ebl, d_Hpp, d_bp, d_Hdiag, d_b);
+    bas_diag_kernel<<<(unsigned)K, BA_THREADS, 0, st>>>((int)O, (int)L, d_ps_ptr, d_ps_obs, d_obs_point, d_Hpl, d_E, d_Ebl, d_Hpp, d_bp, d_Hdiag, d_b);
     return slam_launch_check("slam_bas_reduce_f64");
 }
 
@@ -571,7 +487,7 @@ extern "C" int slam_bas_backsub_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t
     if (int rc = bas_sizes("slam_bas_backsub_f64", K, L, O, 0, 0)) return rc;
     SLAM_REQUIRE(d_pt_ptr && d_pt_obs && d_obs_pose && d_Hpl && d_E && d_bl && d_dp && d_dl, "slam_bas_backsub_f64: null device pointer");
     SLAM_HIP(hipSetDevice(ctx->device));
-    bas_backsub_kernel<<<bas_blocks(L), BAS_THREADS, 0, ctx->stream>>>((int)K, (int)L, (int)O, d_pt_ptr, d_pt_obs, d_obs_pose, d_Hpl, d_E, d_bl, d_dp,
+    bas_backsub_kernel<<<bas_blocks(L), BA_THREADS, 0, ctx->stream>>>((int)K, (int)L, (int)O, d_pt_ptr, d_pt_obs, d_obs_pose, d_Hpl, d_E, d_bl, d_dp,
                                                                       d_dl);
     return slam_launch_check("slam_bas_backsub_f64");
 }
@@ -586,8 +502,8 @@ extern "C" int slam_bas_candidate_f64(slam_ctx* ctx, int64_t K, int64_t L, const
     SLAM_REQUIRE(d_poses != d_poses_out && d_points != d_points_out, "slam_bas_candidate_f64: the candidate must not alias the state");
     SLAM_HIP(hipSetDevice(ctx->device));
     const int nb = bas_cand_blocks(K, L);
-    bas_candidate_kernel<<<nb, BAS_THREADS, 0, ctx->stream>>>((int)K, (int)L, d_fixed, d_poses, d_points, d_dp, d_dl, d_bp, d_bl, lambda, d_poses_out,
+    bas_candidate_kernel<<<nb, BA_THREADS, 0, ctx->stream>>>((int)K, (int)L, d_fixed, d_poses, d_points, d_dp, d_dl, d_bp, d_bl, lambda, d_poses_out,
                                                              d_points_out, d_part);
-    bas_finish_kernel<<<1, BAS_THREADS, 0, ctx->stream>>>(d_part, nb, d_denominator, nullptr, nullptr, 0, nullptr, 0);
+    bas_finish_kernel<<<1, BA_THREADS, 0, ctx->stream>>>(d_part, nb, d_denominator, nullptr, nullptr, 0, nullptr, 0);
     return slam_launch_check("slam_bas_candidate_f64");
 }

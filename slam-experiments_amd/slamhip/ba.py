@@ -1,12 +1,14 @@
-"""Windowed bundle adjustment on top of the GPU residual/Jacobian kernel.
+"""Bundle adjustment of a keyframe window: four drivers with the same arguments, residuals, Huber
+weight and Levenberg-Marquardt schedule.  The reference has none (``Backend`` is an empty class, ``backend.py:101-103``;
+``Map`` keeps 7 keyframes, ``backend.py:11``); this is the extension BASELINE.json calls ``optimize()``.
 
-The reference has no bundle adjustment (``Backend`` is an empty class, ``backend.py:101-103``; ``Map``
-keeps a window of 7 keyframes, ``backend.py:11``); this is the extension BASELINE.json calls
-``optimize()``.  Every LM iteration evaluates e, J_pose (2x6) and J_point (2x3) for all observations on
-the GPU (``slam_reproj_rj_f64``); the Schur complement on the landmark blocks and the reduced camera
-solve run on the host in numpy, which is adequate for keyframe windows (tens of poses, 10^4-10^5
-observations).  No reference function or test pins this code: it is checked against synthetic scenes
-and finite differences only.
+``bundle_adjust``: e, J_pose (2x6), J_point (2x3) of every observation from the GPU (``slam_reproj_rj_f64``, reproj.hip); the
+Schur complement and the reduced camera solve on the host in numpy.
+``bundle_adjust_device``: the per-phase kernels of ba_schur.hip (``SchurProblem``: ``slam_ba_reduce_f64`` = ba_obs, ba_point,
+ba_pose, ba_pair; ``slam_ba_backsub_f64``; ``slam_ba_cost_f64``); the host solves the 6K x 6K system.  Any window.
+``bundle_adjust_one_launch``: the whole loop in ONE launch (``slam_ba_optimize_host_f64`` = ba_lm_grid_kernel, ba_schur.hip).
+``bundle_adjust_auto``: that, and the per-phase form when the device is busy.
+The first two and ``bundle_adjust_sparse`` (ba_sparse.py) run ``lm_schedule``, which the one-launch kernel states again.
 """
 from __future__ import annotations
 
@@ -46,20 +48,71 @@ def _robust_cost(e: np.ndarray, delta: float) -> float:
     return float(np.where(n <= delta, c2, 2 * delta * n - delta * delta).sum())
 
 
+def state_arrays(poses, points):
+    """``poses`` [K,12] or [K,4,4], ``points`` [L,3] -> (T12 [K,12], X [L,3] (a copy), K, L), contiguous float64."""
+    P = np.asarray(poses, np.float64)
+    T12 = np.ascontiguousarray((P.reshape(-1, 12) if P.ndim == 2 else poses_to_rt12(P)).reshape(-1, 12))
+    X = np.array(points, np.float64).reshape(-1, 3)
+    if T12.shape[0] < 1 or X.shape[0] < 1:
+        raise ValueError("need at least one pose and one point")
+    return T12, X, T12.shape[0], X.shape[0]
+
+
+def fixed_pose_mask(fixed_poses, K: int) -> np.ndarray:
+    """The indices ``fixed_poses`` as a bool mask [K]."""
+    mask = np.zeros(K, bool)
+    try:
+        mask[np.asarray(list(fixed_poses), np.int64).reshape(-1)] = True
+    except IndexError:
+        raise ValueError("fixed pose index out of range") from None
+    return mask
+
+
+def observation_lists(op: np.ndarray, ol: np.ndarray, K: int, L: int):
+    """(pt_ptr [L+1], pt_obs [O], ps_ptr [K+1], ps_obs [O]) int32: point l is seen in pt_obs[pt_ptr[l]:pt_ptr[l+1]], ascending."""
+    ptr = lambda idx, n: np.r_[0, np.cumsum(np.bincount(idx, minlength=n))].astype(np.int32)
+    obs = lambda idx: np.argsort(idx, kind="stable").astype(np.int32)
+    return ptr(ol, L), obs(ol), ptr(op, K), obs(op)
+
+
+def lm_schedule(iterations: int, cost: float, dmax: float, trial, accept, report=None):
+    """The Levenberg-Marquardt schedule, from the first cost and the largest diagonal entry of the first linearisation.
+    ``trial(lam, cost)`` -> (cost at the state: ``cost`` again, except that every reduction of the per-phase driver measures
+    it anew; cost at the candidate; gain-ratio denominator), the last two NaN where the solve failed: the damping grows
+    without a cost evaluation.  ``accept(iteration)`` makes the candidate the state; ``report(iteration, lam, cost, new, rho,
+    accepted)`` follows every trial.  -> (cost, damping, accepted steps)."""
+    lam, ni, accepted = 1e-5 * max(dmax, 1e-12), 2.0, 0
+    for it in range(int(iterations)):
+        for _trial in range(10):
+            cost, new, denominator = trial(lam, cost)
+            rho = (cost - new) / (denominator + 1e-3)
+            ok = bool(rho > 0 and np.isfinite(new))
+            if report is not None:
+                report(it, lam, cost, new, rho, ok)
+            if ok:
+                accept(it)
+                cost = new
+                lam *= max(1.0 / 3.0, min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0))
+                ni, accepted = 2.0, accepted + 1
+                break
+            lam *= ni; ni *= 2
+        else:                                 # an iteration without an accepted trial ends the run
+            break
+    return cost, lam, accepted
+
+
 def bundle_adjust(poses, points, obs_pose_idx, obs_point_idx, meas, intrinsics, iterations: int = 10,
                   fixed_poses: Sequence[int] = (0,), huber_delta: float = 0.0,
                   ctx: Optional[Context] = None) -> BAResult:
     ctx = ctx or default_context()
-    P = np.asarray(poses, np.float64)
-    T = np.tile(np.eye(4), (P.shape[0], 1, 1))
-    T[:, :3, :4] = (P.reshape(-1, 12) if P.ndim == 2 else poses_to_rt12(P)).reshape(-1, 3, 4)
-    X = np.array(points, np.float64).reshape(-1, 3)
-    op = np.ascontiguousarray(obs_pose_idx, np.int32)
-    ol = np.ascontiguousarray(obs_point_idx, np.int32)
-    K, L, O = T.shape[0], X.shape[0], op.shape[0]
-    free = np.ones(K, bool)
-    free[list(fixed_poses)] = False
-    prob = ReprojProblem(ctx, T[:, :3, :4].reshape(K, 12), X, op, ol, meas, intrinsics, with_point=True)
+    T12, X, K, L = state_arrays(poses, points)
+    T = np.tile(np.eye(4), (K, 1, 1))
+    T[:, :3, :4] = T12.reshape(K, 3, 4)
+    op, ol = np.ascontiguousarray(obs_pose_idx, np.int32), np.ascontiguousarray(obs_point_idx, np.int32)
+    fidx = np.flatnonzero(~fixed_pose_mask(fixed_poses, K))
+    prob = ReprojProblem(ctx, T12, X, op, ol, meas, intrinsics, with_point=True)
+    pt_ptr, pt_obs = observation_lists(op, ol, K, L)[:2]          # behind the problem's own check of the indices
+    seen = np.diff(pt_ptr) > 0
 
     def linearize(Tc, Xc):
         prob.set_poses(Tc[:, :3, :4].reshape(K, 12))
@@ -67,69 +120,59 @@ def bundle_adjust(poses, points, obs_pose_idx, obs_point_idx, meas, intrinsics, 
         prob.linearize()
         return prob.download()
 
+    def normal_equations(e, Jp, Jq):
+        w = _huber_weights(e, huber_delta)
+        Jpw = Jp * w[:, None, None]
+        Hpp = np.zeros((K, 6, 6)); bp = np.zeros((K, 6)); Hll = np.zeros((L, 3, 3)); bl = np.zeros((L, 3))
+        np.add.at(Hpp, op, np.einsum("oia,oib->oab", Jpw, Jp))
+        np.add.at(bp, op, np.einsum("oia,oi->oa", Jpw, e))
+        np.add.at(Hll, ol, np.einsum("oia,oib->oab", Jq * w[:, None, None], Jq))
+        np.add.at(bl, ol, np.einsum("oia,oi->oa", Jq * w[:, None, None], e))
+        return Hpp, bp, Hll, bl, np.einsum("oia,oib->oab", Jpw, Jq)        # Hpl [O,6,3]
+
+    def trial(lam, cost):
+        nonlocal cand
+        Hpp, bp, Hll, bl, Hpl = blocks
+        Hll_d = Hll + lam * np.eye(3)
+        Hll_d[~seen] = np.eye(3)
+        Hll_inv = np.linalg.inv(Hll_d)
+        Y = np.einsum("oab,obc->oac", Hpl, Hll_inv[ol])           # Hpl Hll^-1  [O,6,3]
+        S = np.zeros((K, K, 6, 6))
+        for k in range(K):
+            S[k, k] = Hpp[k] + lam * np.eye(6)
+        for a, b in zip(pt_ptr[:-1], pt_ptr[1:]):                # S[k1,k2] -= sum over landmarks seen by both of Y_o1 Hpl_o2^T
+            obs = pt_obs[a:b]
+            blk = np.einsum("iab,jcb->ijac", Y[obs], Hpl[obs])   # [n,n,6,6]
+            S[np.ix_(op[obs], op[obs])] -= blk
+        rhs = -bp + np.zeros((K, 6))
+        np.add.at(rhs, op, np.einsum("oab,ob->oa", Y, bl[ol]))
+        Sf = S[np.ix_(fidx, fidx)].transpose(0, 2, 1, 3).reshape(6 * len(fidx), 6 * len(fidx))
+        try:
+            dxp_f = np.linalg.solve(Sf, rhs[fidx].reshape(-1)).reshape(-1, 6)
+        except np.linalg.LinAlgError:
+            return cost, np.nan, np.nan
+        dxp = np.zeros((K, 6)); dxp[fidx] = dxp_f
+        tmp = -bl.copy()
+        np.subtract.at(tmp, ol, np.einsum("oab,oa->ob", Hpl, dxp[op]))
+        dxl = np.einsum("lab,lb->la", Hll_inv, tmp)
+        dxl[~seen] = 0
+        Tn, Xn = np.stack([se3_exp(dxp[k]) @ T[k] for k in range(K)]), X + dxl
+        cand = (Tn, Xn, linearize(Tn, Xn))
+        denominator = float((dxp * (lam * dxp - bp)).sum() + (dxl * (lam * dxl - bl)).sum())
+        return cost, _robust_cost(cand[2][0], huber_delta), denominator
+
+    def accept(it):
+        nonlocal T, X, blocks
+        T, X, lin = cand
+        if it + 1 < iterations:                                   # the blocks of a state once, however many dampings are tried
+            blocks = normal_equations(*lin)
+
     try:
-        e, Jp, Jq = linearize(T, X)
-        cost = _robust_cost(e, huber_delta)
-        cost0 = cost
-        lam, ni, accepted = None, 2.0, 0
-        for _ in range(iterations):
-            w = _huber_weights(e, huber_delta)
-            Jpw = Jp * w[:, None, None]
-            Hpp = np.zeros((K, 6, 6)); bp = np.zeros((K, 6)); Hll = np.zeros((L, 3, 3)); bl = np.zeros((L, 3))
-            np.add.at(Hpp, op, np.einsum("oia,oib->oab", Jpw, Jp))
-            np.add.at(bp, op, np.einsum("oia,oi->oa", Jpw, e))
-            np.add.at(Hll, ol, np.einsum("oia,oib->oab", Jq * w[:, None, None], Jq))
-            np.add.at(bl, ol, np.einsum("oia,oi->oa", Jq * w[:, None, None], e))
-            Hpl = np.einsum("oia,oib->oab", Jpw, Jq)                     # [O,6,3]
-            if lam is None:
-                lam = 1e-5 * max(Hpp[free].reshape(-1, 36)[:, ::7].max(initial=0.0), Hll.reshape(-1, 9)[:, ::4].max(initial=0.0), 1e-12)
-            step_ok = False
-            for _trial in range(10):
-                Hll_d = Hll + lam * np.eye(3)
-                seen = np.zeros(L, bool); seen[ol] = True
-                Hll_d[~seen] = np.eye(3)
-                Hll_inv = np.linalg.inv(Hll_d)
-                Y = np.einsum("oab,obc->oac", Hpl, Hll_inv[ol])           # Hpl Hll^-1  [O,6,3]
-                S = np.zeros((K, K, 6, 6))
-                for k in range(K):
-                    S[k, k] = Hpp[k] + lam * np.eye(6)
-                # S[k1,k2] -= sum over landmarks seen by both of Y_o1 Hpl_o2^T : group observations by landmark
-                order = np.argsort(ol, kind="stable")
-                starts = np.r_[0, np.flatnonzero(np.diff(ol[order])) + 1, O]
-                for a, b in zip(starts[:-1], starts[1:]):
-                    obs = order[a:b]
-                    blk = np.einsum("iab,jcb->ijac", Y[obs], Hpl[obs])   # [n,n,6,6]
-                    S[np.ix_(op[obs], op[obs])] -= blk
-                rhs = -bp + np.zeros((K, 6))
-                np.add.at(rhs, op, np.einsum("oab,ob->oa", Y, bl[ol]))
-                fidx = np.flatnonzero(free)
-                Sf = S[np.ix_(fidx, fidx)].transpose(0, 2, 1, 3).reshape(6 * len(fidx), 6 * len(fidx))
-                try:
-                    dxp_f = np.linalg.solve(Sf, rhs[fidx].reshape(-1)).reshape(-1, 6)
-                except np.linalg.LinAlgError:
-                    lam *= ni; ni *= 2
-                    continue
-                dxp = np.zeros((K, 6)); dxp[fidx] = dxp_f
-                tmp = -bl.copy()
-                np.subtract.at(tmp, ol, np.einsum("oab,oa->ob", Hpl, dxp[op]))
-                dxl = np.einsum("lab,lb->la", Hll_inv, tmp)
-                dxl[~seen] = 0
-                Tn = np.stack([se3_exp(dxp[k]) @ T[k] for k in range(K)])
-                Xn = X + dxl
-                en, Jpn, Jqn = linearize(Tn, Xn)
-                new = _robust_cost(en, huber_delta)
-                scale = float((dxp * (lam * dxp - bp)).sum() + (dxl * (lam * dxl - bl)).sum()) + 1e-3
-                rho = (cost - new) / scale
-                if rho > 0 and np.isfinite(new):
-                    T, X, e, Jp, Jq, cost = Tn, Xn, en, Jpn, Jqn, new
-                    lam *= max(1.0 / 3.0, min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0))
-                    ni = 2.0
-                    accepted += 1
-                    step_ok = True
-                    break
-                lam *= ni; ni *= 2
-            if not step_ok:
-                break
+        lin = linearize(T, X)
+        cost0 = _robust_cost(lin[0], huber_delta)
+        cand, blocks = None, normal_equations(*lin)               # the first damping comes from the first linearisation
+        dmax = max(blocks[0][fidx].reshape(-1, 36)[:, ::7].max(initial=0.0), blocks[2].reshape(-1, 9)[:, ::4].max(initial=0.0))
+        cost, _, accepted = lm_schedule(iterations, cost0, dmax, trial, accept)
     finally:
         prob.free()
     return BAResult(poses=T, points=X, chi2_initial=cost0, chi2_final=cost, iterations=accepted)
@@ -160,10 +203,7 @@ class SchurProblem:
             raise ValueError("a (pose, point) pair is observed more than once")
         self.K, self.L, self.O = K, L, O
         self.fx, self.fy, self.cx, self.cy = (float(v) for v in intrinsics)
-        pt_obs = np.argsort(ol, kind="stable").astype(np.int32)
-        ps_obs = np.argsort(op, kind="stable").astype(np.int32)
-        pt_ptr = np.zeros(L + 1, np.int32); pt_ptr[1:] = np.cumsum(np.bincount(ol, minlength=L))
-        ps_ptr = np.zeros(K + 1, np.int32); ps_ptr[1:] = np.cumsum(np.bincount(op, minlength=K))
+        pt_ptr, pt_obs, ps_ptr, ps_obs = observation_lists(op, ol, K, L)
         pad = lambda a: a if a.size else np.zeros(1, a.dtype)
         up = ctx.upload
         self.d_op, self.d_ol, self.d_meas = up(pad(op)), up(pad(ol)), up(meas if O else np.zeros((1, 2)))
@@ -277,20 +317,14 @@ def bundle_adjust_one_launch(poses, points, obs_pose_idx, obs_point_idx, meas, i
     ``bundle_adjust_device`` - per-phase kernels, no residency requirement - does the same adjustment (``bundle_adjust_auto``
     and ``Backend.optimize`` fall back to it by themselves)."""
     ctx = ctx or default_context()
-    P = np.asarray(poses, np.float64)
-    T12 = np.ascontiguousarray((P.reshape(-1, 12) if P.ndim == 2 else poses_to_rt12(P)).reshape(-1, 12))
-    X = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
-    K, L = T12.shape[0], X.shape[0]
+    T12, X, K, L = state_arrays(poses, points)
     op = np.ascontiguousarray(obs_pose_idx, np.int32).reshape(-1)
     ol = np.ascontiguousarray(obs_point_idx, np.int32).reshape(-1)
     meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 2)
     O = op.shape[0]
     if ol.shape[0] != O or meas.shape[0] != O:
         raise ValueError("obs_pose, obs_point and meas must have one row per observation")
-    if K < 1 or L < 1:
-        raise ValueError("need at least one pose and one point")
-    fixed = np.zeros(K, np.uint8)
-    fixed[list(fixed_poses)] = 1
+    fixed = fixed_pose_mask(fixed_poses, K).astype(np.uint8)
     fx, fy, cx, cy = (float(v) for v in intrinsics)
     Tout, Xout, st = np.empty((K, 12)), np.empty((L, 3)), np.empty(8)
     # ranges, the one-observation-per-(pose, point) rule and the index tables are the library's business (slam_ba_optimize_host_f64)
@@ -329,48 +363,34 @@ def bundle_adjust_device(poses, points, obs_pose_idx, obs_point_idx, meas, intri
     back-substitution on the GPU (``slam_ba_reduce_f64`` / ``slam_ba_backsub_f64``); the host only solves the
     6K x 6K reduced system and drives the same LM schedule."""
     ctx = ctx or default_context()
-    P = np.asarray(poses, np.float64)
-    T = np.tile(np.eye(4), (P.shape[0], 1, 1))
-    T[:, :3, :4] = (P.reshape(-1, 12) if P.ndim == 2 else poses_to_rt12(P)).reshape(-1, 3, 4)
-    X = np.array(points, np.float64).reshape(-1, 3)
-    K, L = T.shape[0], X.shape[0]
-    free = np.ones(K, bool)
-    free[list(fixed_poses)] = False
-    fidx = np.flatnonzero(free)
+    T12, X, K, L = state_arrays(poses, points)
+    T = np.tile(np.eye(4), (K, 1, 1))
+    T[:, :3, :4] = T12.reshape(K, 3, 4)
+    fidx = np.flatnonzero(~fixed_pose_mask(fixed_poses, K))
     prob = SchurProblem(ctx, K, L, obs_pose_idx, obs_point_idx, meas, intrinsics)
     rt = lambda Tc: Tc[:, :3, :4].reshape(K, 12)
+
+    def trial(lam, _cost):
+        nonlocal cand, S      # S outlives the trial: freed at every return it cost 10 ms in 140 at K = 200
+        S, rhs, bp, cost = prob.reduce(rt(T), X, huber_delta, lam)        # the cost as this reduction sums it
+        Sf = S[np.ix_(fidx, fidx)].transpose(0, 2, 1, 3).reshape(6 * len(fidx), 6 * len(fidx))
+        try:
+            dxp_f = np.linalg.solve(Sf, rhs[fidx].reshape(-1)).reshape(-1, 6)
+        except np.linalg.LinAlgError:
+            return cost, np.nan, np.nan
+        dxp = np.zeros((K, 6)); dxp[fidx] = dxp_f
+        dxl, bl = prob.back_substitute(dxp)
+        cand = (np.stack([se3_exp(dxp[k]) @ T[k] for k in range(K)]), X + dxl)
+        new = prob.cost(rt(cand[0]), cand[1], huber_delta)
+        return cost, new, float((dxp * (lam * dxp - bp)).sum() + (dxl * (lam * dxl - bl)).sum())
+
+    def accept(_it):
+        nonlocal T, X
+        T, X = cand
+
     try:
-        S, rhs, bp, cost = prob.reduce(rt(T), X, huber_delta, 1.0)
-        cost0 = cost
-        lam = 1e-5 * max(prob.diag_max(fidx), 1e-12)
-        ni, accepted = 2.0, 0
-        for _ in range(iterations):
-            step_ok = False
-            for _trial in range(10):
-                S, rhs, bp, cost = prob.reduce(rt(T), X, huber_delta, lam)
-                Sf = S[np.ix_(fidx, fidx)].transpose(0, 2, 1, 3).reshape(6 * len(fidx), 6 * len(fidx))
-                try:
-                    dxp_f = np.linalg.solve(Sf, rhs[fidx].reshape(-1)).reshape(-1, 6)
-                except np.linalg.LinAlgError:
-                    lam *= ni; ni *= 2
-                    continue
-                dxp = np.zeros((K, 6)); dxp[fidx] = dxp_f
-                dxl, bl = prob.back_substitute(dxp)
-                Tn = np.stack([se3_exp(dxp[k]) @ T[k] for k in range(K)])
-                Xn = X + dxl
-                new = prob.cost(rt(Tn), Xn, huber_delta)
-                scale = float((dxp * (lam * dxp - bp)).sum() + (dxl * (lam * dxl - bl)).sum()) + 1e-3
-                rho = (cost - new) / scale
-                if rho > 0 and np.isfinite(new):
-                    T, X, cost = Tn, Xn, new
-                    lam *= max(1.0 / 3.0, min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0))
-                    ni = 2.0
-                    accepted += 1
-                    step_ok = True
-                    break
-                lam *= ni; ni *= 2
-            if not step_ok:
-                break
+        cand, (S, _, _, cost0) = None, prob.reduce(rt(T), X, huber_delta, 1.0)
+        cost, _, accepted = lm_schedule(iterations, cost0, prob.diag_max(fidx), trial, accept)
     finally:
         prob.free()
     return BAResult(poses=T, points=X, chi2_initial=cost0, chi2_final=cost, iterations=accepted)

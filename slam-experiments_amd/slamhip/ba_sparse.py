@@ -14,10 +14,9 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._lib import addr, check, load
-from .ba import BAResult
+from .ba import BAResult, fixed_pose_mask, lm_schedule, observation_lists, state_arrays
 from .device import Context, default_context
 from .pose_graph import DEFAULT_PCG_MAX_ITER, MAX_EDGES, MAX_VERTICES, _check_solver_args, vertex_lists
-from .reproj import poses_to_rt12
 
 DEFAULT_PCG_TOL = 1e-10           # 1e-8, the pose graph's default, leaves the poses 1e-7 from a direct solve: outside the BA suite's bar
 MAX_POINTS = 1 << 28
@@ -139,10 +138,7 @@ class SparseBAProblem:
         self.edges, self.weights, pair_ptr, pair_a, pair_b = covisibility(op, ol, K, self.fixed, L)
         self.K, self.L, self.O, self.E, self.P = K, L, O, len(self.edges), len(pair_a)
         self.fx, self.fy, self.cx, self.cy = (float(v) for v in intrinsics)
-        pt_obs = np.argsort(ol, kind="stable").astype(np.int32)
-        ps_obs = np.argsort(op, kind="stable").astype(np.int32)
-        pt_ptr = np.zeros(L + 1, np.int32); pt_ptr[1:] = np.cumsum(np.bincount(ol, minlength=L))
-        ps_ptr = np.zeros(K + 1, np.int32); ps_ptr[1:] = np.cumsum(np.bincount(op, minlength=K))
+        pt_ptr, pt_obs, ps_ptr, ps_obs = observation_lists(op, ol, K, L)
         vtx_ptr, vtx_adj = vertex_lists(K, self.edges)
         pad = lambda a: a if a.size else np.zeros(4, a.dtype)
         up, new = ctx.upload, ctx.malloc
@@ -254,58 +250,38 @@ def bundle_adjust_sparse(poses, points, obs_pose_idx, obs_point_idx, meas, intri
     ``SLAM_PG_STATUS_*`` bits), unconverged (solves that stopped at ``pcg_max_iter`` or broke down: each counted as a failed
     trial, the damping grows), edges, pairs).  ``on_trial(dict)`` is called after every trial (timing tools).
     Raises ``ValueError`` for an index out of range, a (pose, point) pair observed twice or no fixed pose, before any launch."""
-    P = np.asarray(poses, np.float64)
-    T12 = np.ascontiguousarray((P.reshape(-1, 12) if P.ndim == 2 else poses_to_rt12(P)).reshape(-1, 12))
-    X = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
-    K, L = T12.shape[0], X.shape[0]
-    if K < 1 or L < 1:
-        raise ValueError("need at least one pose and one point")
+    T12, X, K, L = state_arrays(poses, points)
     _check_solver_args(iterations, huber_delta, pcg_tol, pcg_max_iter)
-    fidx = np.asarray(list(fixed_poses), np.int64).reshape(-1)
-    if len(fidx) and (fidx.min() < -K or fidx.max() >= K):
-        raise ValueError("fixed pose index out of range")
-    fixed = np.zeros(K, bool)
-    fixed[fidx] = True
+    fixed = fixed_pose_mask(fixed_poses, K)
     ctx = ctx or default_context()
     prob = SparseBAProblem(ctx, K, L, obs_pose_idx, obs_point_idx, meas, intrinsics, fixed)
     st = dict(trials=0, cg_iterations=0, lam=0.0, status=0, unconverged=0, edges=prob.E, pairs=prob.P)
+
+    def trial(lam, cost):
+        nonlocal cg
+        st["trials"] += 1
+        prob.reduce(lam)
+        cg = prob.solve(lam, pcg_tol, pcg_max_iter)
+        st["cg_iterations"] += cg["iterations"]
+        st["status"] |= cg["status"]
+        if not cg["converged"]:
+            st["unconverged"] += 1                            # never accepted: the damping grows and the trial is reported
+            return cost, np.nan, np.nan
+        denominator, new = prob.step(lam, huber_delta)
+        return cost, new, denominator
+
+    def accept(it):
+        prob.accept()
+        if it + 1 < int(iterations):
+            prob.linearize(huber_delta)
+
+    report = on_trial and (lambda it, lam, cost, new, rho, ok:
+                           on_trial(dict(iteration=it, lam=lam, cg=cg, cost=cost, new=new, rho=rho, accepted=ok)))
+
     try:
         prob.set_state(T12, X)
-        cost, dmax = prob.linearize(huber_delta)
-        cost0 = cost
-        lam = 1e-5 * max(dmax, 1e-12)
-        ni, accepted = 2.0, 0
-        for it in range(int(iterations)):
-            step_ok = False
-            for _trial in range(10):
-                st["trials"] += 1
-                prob.reduce(lam)
-                cg = prob.solve(lam, pcg_tol, pcg_max_iter)
-                st["cg_iterations"] += cg["iterations"]
-                st["status"] |= cg["status"]
-                new, rho = float("nan"), float("nan")
-                if cg["converged"]:
-                    denom, new = prob.step(lam, huber_delta)
-                    rho = (cost - new) / (denom + 1e-3)
-                else:
-                    st["unconverged"] += 1                # never accepted: the damping grows and the trial is reported
-                ok = bool(cg["converged"] and rho > 0 and np.isfinite(new))
-                if on_trial is not None:
-                    on_trial(dict(iteration=it, lam=lam, cg=cg, cost=cost, new=new, rho=rho, accepted=ok))
-                if ok:
-                    prob.accept()
-                    cost = new
-                    lam *= max(1.0 / 3.0, min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0))
-                    ni = 2.0
-                    accepted += 1
-                    step_ok = True
-                    if it + 1 < int(iterations):
-                        prob.linearize(huber_delta)
-                    break
-                lam *= ni; ni *= 2
-            if not step_ok:
-                break
-        st["lam"] = lam
+        cg, (cost0, dmax) = None, prob.linearize(huber_delta)
+        cost, st["lam"], accepted = lm_schedule(iterations, cost0, dmax, trial, accept, report)
         Tout, Xout = prob.state()
     finally:
         prob.free()

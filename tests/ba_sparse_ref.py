@@ -2,7 +2,7 @@
 diagonal and covisibility-edge blocks, back-substitution, and the Levenberg-Marquardt loop of bundle_adjust_device with a
 plain block-Jacobi preconditioned CG in place of the dense solve.  Residuals and Jacobians come from the C oracle
 (oracle.reproj_rj_c); the covisibility edges are built here by brute force, point by point, not by the product's function.
-Shared by tests/test_ba_sparse_cpu.py and tests/test_ba_sparse_gpu.py."""
+Shared by tests/test_ba_sparse_cpu.py and tests/test_ba_sparse_gpu.py; tests/test_ba_limits_gpu.py takes its scenes from here."""
 import numpy as np
 
 from oracle import oracle
@@ -212,7 +212,7 @@ def lm(T0, X0, op, ol, meas, intr, iterations, fixed_poses, delta, pcg_tol=1e-10
     return T, X, cost0, cost, accepted, st
 
 
-# ---- scenes (the recipe of tests/test_ba_limits_gpu.py: its intrinsics, shuffled observations, 0.3 px noise, its perturbations) -----
+# ---- scenes (`scene` and `window` also build the windows of tests/test_ba_limits_gpu.py: its intrinsics, shuffled observations, 0.3 px noise) -----
 FX, FY, CX, CY = 458.654, 457.296, 367.215, 248.375
 INTR = (FX, FY, CX, CY)
 
@@ -264,6 +264,28 @@ def tracks_window(rng, K, tracks, fixed):
 def sliding(rng, K, O, fixed=(0, 1), lo=2, hi=6):
     """A keyframe chain: every point seen by lo..hi consecutive poses, exactly O observations."""
     return tracks_window(rng, K, chain_tracks(rng, 0, K - 1, O, lo, hi), fixed)
+
+
+def uneven(rng):
+    """K = 7: poses 0 and 1 fixed and well observed (the gauge), pose 6 fixed with no observation; pose 2 moving with no
+    observation, pose 3 moving with two, pose 4 moving with more than half of all observations, pose 5 moving.  Points seen
+    by every pose that sees anything (0, 1, 4, 5; two of them by pose 3 too), points seen by pose 4 and one gauge pose,
+    by poses 4 and 5, by pose 4 alone, and points nobody sees."""
+    A, D, E, B, C = 1000, 11000, 4000, 3000, 500
+    L = A + D + E + B + C
+    T, X = scene(rng, 7, L)
+    a, d, e, b = np.arange(A), A + np.arange(D), A + D + np.arange(E), A + D + E + np.arange(B)
+    op = np.concatenate([np.repeat([0, 1, 4, 5], A), np.full(D, 4), d % 2, np.full(E, 4), np.full(E, 5), np.full(B, 4), [3, 3]])
+    ol = np.concatenate([np.tile(a, 4), d, d, e, e, b, [a[0], a[A // 2]]])
+    return window(rng, T, X, op, ol, (0, 1, 6))
+
+
+def smallest(rng):
+    """K = 3, poses 0 and 1 fixed, pose 2 moving; 12 points: pose 0 sees one of them, poses 1 and 2 all of them."""
+    T, X = scene(rng, 3, 12)
+    op = np.concatenate([[0], np.ones(12, int), np.full(12, 2)])
+    ol = np.concatenate([[5], np.arange(12), np.arange(12)])
+    return window(rng, T, X, op, ol, (0, 1))
 
 
 def case_edges(seed=23):

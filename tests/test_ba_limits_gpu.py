@@ -17,6 +17,7 @@ away from 0, where rounding could legitimately split the two sides (tools/fuzz_b
 import numpy as np
 import pytest
 
+from ba_sparse_ref import scene as _scene, smallest as _smallest, uneven as _uneven, window as _window
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -25,31 +26,6 @@ INTR = (FX, FY, CX, CY)
 MAX_OBS = 131072
 # 16 moving poses of 64, scattered: not a prefix, pose 0 holds the gauge, the last pose moves
 FREE64 = (3, 7, 11, 12, 18, 22, 29, 30, 37, 41, 44, 50, 53, 57, 60, 63)
-
-
-def _scene(rng, K, L):
-    from scipy.spatial.transform import Rotation
-
-    T = np.tile(np.eye(4), (K, 1, 1))
-    T[:, :3, :3] = Rotation.from_rotvec(rng.uniform(-0.15, 0.15, (K, 3))).as_matrix()
-    T[:, :3, 3] = rng.uniform(-0.5, 0.5, (K, 3))
-    X = np.c_[rng.uniform(-4, 4, (L, 2)), rng.uniform(6, 15, L)]
-    return T, X
-
-
-def _window(rng, T, X, op, ol, fixed, noise=0.3):
-    """Shuffle the observations, measure them with pixel noise, perturb the moving poses and every point."""
-    K = T.shape[0]
-    perm = rng.permutation(len(op))
-    op, ol = np.asarray(op, np.int32)[perm], np.asarray(ol, np.int32)[perm]
-    pc = np.einsum("oij,oj->oi", T[op, :3, :3], X[ol]) + T[op, :3, 3]
-    meas = np.c_[FX * pc[:, 0] / pc[:, 2] + CX, FY * pc[:, 1] / pc[:, 2] + CY] + rng.normal(0, noise, (len(op), 2))
-    T0 = T.copy()
-    for k in range(K):
-        if k not in fixed:
-            T0[k] = oracle.se3_exp_np(rng.normal(0, 0.01, 6)) @ T[k]
-    X0 = X + rng.normal(0, 0.05, X.shape)
-    return dict(T0=T0, X0=X0, op=op, ol=ol, meas=meas, fixed=tuple(fixed))
 
 
 def _all_pairs(rng, K, L, fixed):
@@ -86,28 +62,6 @@ def _sliding(rng, K, O, dense_points=0):
     op, ol = np.concatenate(op), np.concatenate(ol)
     fixed = [k for k in range(K) if k not in FREE64]
     return _window(rng, T, X, op, ol, fixed)
-
-
-def _uneven(rng):
-    """K = 7: poses 0 and 1 fixed and well observed (the gauge), pose 6 fixed with no observation; pose 2 moving with no
-    observation, pose 3 moving with two, pose 4 moving with more than half of all observations, pose 5 moving.  Points seen
-    by every pose that sees anything (0, 1, 4, 5; two of them by pose 3 too), points seen by pose 4 and one gauge pose,
-    by poses 4 and 5, by pose 4 alone, and points nobody sees."""
-    A, D, E, B, C = 1000, 11000, 4000, 3000, 500
-    L = A + D + E + B + C
-    T, X = _scene(rng, 7, L)
-    a, d, e, b = np.arange(A), A + np.arange(D), A + D + np.arange(E), A + D + E + np.arange(B)
-    op = np.concatenate([np.repeat([0, 1, 4, 5], A), np.full(D, 4), d % 2, np.full(E, 4), np.full(E, 5), np.full(B, 4), [3, 3]])
-    ol = np.concatenate([np.tile(a, 4), d, d, e, e, b, [a[0], a[A // 2]]])
-    return _window(rng, T, X, op, ol, (0, 1, 6))
-
-
-def _smallest(rng):
-    """K = 3, poses 0 and 1 fixed, pose 2 moving; 12 points: pose 0 sees one of them, poses 1 and 2 all of them."""
-    T, X = _scene(rng, 3, 12)
-    op = np.concatenate([[0], np.ones(12, int), np.full(12, 2)])
-    ol = np.concatenate([[5], np.arange(12), np.arange(12)])
-    return _window(rng, T, X, op, ol, (0, 1))
 
 
 def _shape(w):
