@@ -60,12 +60,15 @@
 //         last group of a trip reads nothing ahead, so no read leaves the stage's own buffer or comes before its barrier.
 //       - staging: a stage that another follows (always a whole stage) runs as ONE trip of eight groups, and its groups 4-7 each
 //         expand and store one of the thread's four source words of the next stage between their second-half MFMAs, in issue
-//         slots the pipe-paced MFMAs leave empty.  The other buffer is free from the barrier that opened the stage; each word is
-//         loaded one group before it is used, so no staged row is held in registers through the scan.  A chunk's first stage is
-//         stored at the chunk start as before; a chunk's last stage runs trips of four and stores nothing.
-//       - registers (126 of the 128 that four waves per SIMD leave; amdgpu_waves_per_eu holds the allocator to them): the third
+//         slots the pipe-paced MFMAs leave empty.  The other buffer is free from the barrier that opened the stage; the thread's
+//         16 source bytes are ONE load at the trip's start, so its latency runs behind groups 0-3 and the stage has one vector
+//         memory instruction and one wait where word-by-word loads had four (the kernel is bound by instruction issue: DESIGN.md
+//         3c "Where a wave's life goes").  A chunk's first stage is stored at the chunk start as before; a chunk's last stage
+//         runs trips of four and stores nothing.
+//       - registers (all 128 that four waves per SIMD leave; amdgpu_waves_per_eu holds the allocator to them): the third
 //         operand quad is paid for by x, which is no longer kept (threshold_x reads it back from the accumulator start in the
-//         update path), the staged row (a word at a time), and the lane's query and the group's row base, recomputed where used.
+//         update path), and the lane's query and the group's row base, recomputed where used; the staged row is held from the
+//         trip's start to the group that expands its last word.
 //   * plan: the queue plan of bf_top2_kernel<1, true, true> with tickets drawn per BLOCK: grid = (query blocks, workers),
 //     the workers of a query block draw chunks of the boundary table by ticket, exchange the 2nd-best key through
 //     bound[] at every chunk, merge with the two returning atomic minima and the last arriver decodes (bf_common.h).
@@ -84,6 +87,20 @@
 #define SLAM_MX_EARLY 0x16u      // after 128, 256 and 512 rows
 #define SLAM_MX_UNROLL 4         // groups of 16 rows per trip of the scan loop
 #define SLAM_MX_RESIDENT 4       // blocks of bf_top2_mx_kernel a CU holds at once (the plan describe counts on it; launches ask)
+
+// The phase probe (tools/mx_phase_probe.py): an experiment build (-DSLAM_MX_PROBE) in which every wave sums the shader clock
+// over the phases of its life and leaves the sums in a buffer of the tool's.  The shipped build executes no stamp.
+#ifdef SLAM_MX_PROBE
+__device__ unsigned long long* g_mx_probe = nullptr;
+extern "C" __attribute__((visibility("default"))) int slam_exp_set_mx_probe(void* p) {
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mx_probe), &p, sizeof(p));
+}
+// phases: 0 prologue, 1 chunk start, 2 quiet scan, 3 update paths, 4 stage end (unions, early exchange), 5 stage barrier
+// (arrival to release), 6 epilogue, 7 stage head (the ticket's draw and its wait)
+#define MX_STAMP(ph) do { const unsigned long long now_ = __builtin_readcyclecounter(); pacc[ph] += now_ - plast; plast = now_; } while (0)
+#else
+#define MX_STAMP(ph) do {} while (0)
+#endif
 
 typedef int mx_v8i __attribute__((ext_vector_type(8)));
 typedef float mx_v4f __attribute__((ext_vector_type(4)));
@@ -129,6 +146,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int kg = lane >> 4, col = lane & 15;
+#ifdef SLAM_MX_PROBE
+    unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, plast = __builtin_readcyclecounter();
+#endif
     const u32 lanek = (u32)(4 * kg - (1 << SLAM_KEY_IDX_BITS));  // the lane's first row in a group of 16, less the 2^23 a key built from x owes
     const int bx = ((int)blockIdx.x + (int)blockIdx.y) % (int)gridDim.x;
     // the lane's query in the epilogue and in the bound exchange: worked out afresh at each of them (the empty asm hides that the
@@ -246,18 +266,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     __syncthreads();
     int ci = __builtin_amdgcn_readfirstlane((int)s_ticket);
     int scanned = 0;                                             // wave-uniform: the rows this block has scanned since launch
+    MX_STAMP(0);
     while (ci < nchunks) {
         const int c0 = tbl[ci], c1 = tbl[ci + 1];
         const uint4 first = load_stage(c0, c1);
         exchange(c0);
         store_stage(0, first);
         __syncthreads();
+        MX_STAMP(1);
         int buf = 0;
         for (int s0 = c0; s0 < c1; s0 += SLAM_MX_STAGE) {
             const int s1 = s0 + SLAM_MX_STAGE;
             const bool more = s1 < c1;
             // the next ticket is drawn while the chunk's last stage is scanned; read behind the stage's barrier
             if (!more && tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            MX_STAMP(7);
             const int ng = __builtin_amdgcn_readfirstlane(min(SLAM_MX_STAGE / 16, (c1 - s0 + 15) >> 4));
             const uint4* tp = tile[buf];
             u32 fired = 0;                                       // wave-uniform: the tiles that took the update path in this stage
@@ -278,6 +301,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 m = max(max(m, __float_as_int(acc[2][3])), p[3]);
                 m = max(m, __float_as_int(acc[3][3]));
                 if (__builtin_expect(__ballot(m >= 0) != 0ull, 0)) {
+                    MX_STAMP(2);
                     // D = dot + 2 e - 256, so the distance (256 - dot) / 2 is e - D / 2 (D is even).  Only the tiles that hold a
                     // candidate are updated (wave-uniform branches on the tile's own maximum), and only those get a new
                     // threshold: below the lane's own 2nd-best, whose row is below every row the lane has still to see
@@ -307,6 +331,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                         }
                         set_threshold(tt, min(xt, b2[tt] >> SLAM_KEY_IDX_BITS));
                     }
+                    MX_STAMP(3);
                 }
             };
             auto group = [&](int g, auto rag) {
@@ -330,20 +355,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 constexpr bool SH = decltype(shadow)::value;
                 const uint4* ap = tp + g0 * 128 + lane;
                 uint4* const dst = dst0 + (buf ^ 1) * (SLAM_MX_STAGE * 8);
-                // the thread's four source words of the next stage, loaded one group ahead of the group that expands them.  Were
-                // the next stage not whole, the rows past the chunk end would read its last row instead (what such a row holds never
-                // matters, the scan tests its index); the planner's tails make every short stage a chunk of its own, so this only
-                // keeps the loads inside the train set whatever the table
-                const u32* nw = (const u32*)(t + 2 * (size_t)s1) + 8 * min(srow, c1 - 1 - s1) + 4 * sh;
-                u32 w = 0;
+                // the thread's 16 bytes of the next stage, one load at the trip's start: its latency runs behind groups 0-3, and
+                // groups 4-7 expand a word each.  Were the next stage not whole, the rows past the chunk end would read its last
+                // row instead (what such a row holds never matters, the scan tests its index); the planner's tails make every
+                // short stage a chunk of its own, so this only keeps the load inside the train set whatever the table
+                u32 nx[4] = {0, 0, 0, 0};
+                if (SH) {
+                    const uint4 x = (t + 2 * (size_t)s1)[2 * min(srow, c1 - 1 - s1) + sh];
+                    nx[0] = x.x; nx[1] = x.y; nx[2] = x.z; nx[3] = x.w;
+                }
                 uint4 a0 = ap[0], a1 = ap[64];
 #pragma unroll
                 for (int k = 0; k < NG; k++) {
                     uint4 a0n = a0, a1n = a1;
                     mx_v4f acc[4];
                     if (k + 1 < NG) a0n = ap[(k + 1) * 128];
-                    const u32 v = w;
-                    if (SH && k >= NG - 5 && k < NG - 1) w = nw[k - (NG - 5)];
+                    const u32 v = nx[SH && k >= NG - 4 ? k - (NG - 4) : 0];
                     __builtin_amdgcn_sched_barrier(0);
                     dots0(a0, acc);
                     __builtin_amdgcn_sched_barrier(0);
@@ -391,6 +418,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             }
             for (; g + SLAM_MX_UNROLL <= nwhole; g += SLAM_MX_UNROLL) trip(g, std::integral_constant<int, SLAM_MX_UNROLL>{}, std::false_type{});
             for (; g < ng; g++) group(g, std::true_type{});
+            MX_STAMP(2);
             // once per stage in which a key changed, for the tiles it changed in: the threshold of the query's four lanes together
             // (their rows lie in this stage or before it, below every row still to come)
 #pragma unroll
@@ -404,7 +432,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             // chunk's last stage: the chunk-start exchange follows anyway
             scanned += min(s1, c1) - s0;
             if (more && scanned < 32 * SLAM_MX_STAGE && (SLAM_MX_EARLY >> (scanned / SLAM_MX_STAGE) & 1u)) exchange(s1);
+            MX_STAMP(4);
             __syncthreads();
+            MX_STAMP(5);
             buf ^= 1;
         }
         ci = __builtin_amdgcn_readfirstlane((int)s_ticket);
@@ -417,6 +447,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const u32 gk[1] = {gkey < SLAM_MX_BOUND_LIMIT ? gkey >> SLAM_KEY_IDX_BITS : SLAM_BOUND_IDLE};
     bf_top2_epilogue<1, true>(st, bx, tid, lane, lane_query(), false, false, f1, f2, gk, pend, N, (int)gridDim.y, train_base, out_idx,
                               out_dist, sel, s_last);
+#ifdef SLAM_MX_PROBE
+    MX_STAMP(6);
+    if (g_mx_probe && lane == 0) {
+        unsigned long long* o = g_mx_probe + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8;
+        for (int i = 0; i < 8; i++) o[i] = pacc[i];
+    }
+#endif
 }
 
 // ---- host side -----------------------------------------------------------
