@@ -278,7 +278,8 @@ SLAM_API int slam_bf_plan_describe(int num_cu, const int32_t* h_knobs, int count
                                    int rows_on_host, int32_t* h_plan, int32_t* h_tbl, int64_t tbl_cap, int64_t* tbl_len);
 /* Which engine runs the top-2 search (slam_bf_knn2_u256 and the calls built on it) on this context: 0 = auto (the shipped
  * choice), 1 = the VALU popcount kernel always, 2 = the matrix-core kernel (a +-1 FP4 dot product on the MFMA units, same
- * results bit for bit) wherever it is eligible.  Eligible: one pass of at most 2^23 train rows in device memory with every
+ * results bit for bit) on 16x16x128 tiles wherever it is eligible, 3 = the matrix-core kernel on 32x32x64 tiles wherever 2
+ * would be eligible (same results again; slam_bf_mx_tile_describe says which of the two auto runs).  Eligible: one pass of at most 2^23 train rows in device memory with every
  * slam_bf_set_tuning knob at its shipped value (a forced knob describes a VALU plan); auto runs it on the shapes where it
  * measured faster (slam_bf_mx_plan_describe h_plan[7]).  The batch call, pinned-host frame-sized calls and
  * slam_bf_knn_u256 stay on the VALU kernels. */
@@ -289,6 +290,10 @@ SLAM_API int slam_bf_set_engine(slam_ctx* ctx, int engine);
  * ascending row indices from 0 to M) goes to h_tbl (up to tbl_cap entries; may be NULL) and its length to *tbl_len. */
 SLAM_API int slam_bf_mx_plan_describe(int num_cu, int64_t N, int64_t M, int32_t* h_plan, int32_t* h_tbl, int64_t tbl_cap,
                                       int64_t* tbl_len);
+/* Which matrix-core kernel a pass of N x M runs on under engine 0, 2 or 3, WITHOUT a device: *h_tile = 16 (16x16x128 tiles)
+ * or 32 (32x32x64 tiles).  Both kernels run the plan of slam_bf_mx_plan_describe.  For engine 0 this is the choice on the
+ * shapes that h_plan[7] sends to the matrix cores. */
+SLAM_API int slam_bf_mx_tile_describe(int engine, int64_t N, int64_t M, int32_t* h_tile);
 /* Restore the matcher's per-context merge state to its idle values.  Every search leaves it clean by itself;
  * call this after a search failed part-way (the library does so on a failed launch).  Stream-ordered. */
 SLAM_API int slam_bf_reset_state(slam_ctx* ctx);

@@ -78,15 +78,9 @@
 #include <type_traits>
 
 #include "bf_common.h"
+#include "bf_mx_common.h"   // the stage geometry, the expand map, the pair union: shared with bf_mx32.hip
 
-#define SLAM_MX_STAGE 128        // train rows per LDS stage: 16 KiB expanded, two stages per block
-#define SLAM_MX_BOUND_LIMIT 0x7F000000u   // bound[] of this kernel holds keys below this; at or above (the idle pattern): nobody has published
-// Early bound exchanges: bit k set = the workers of a query block also exchange after the stage at whose end a block has scanned
-// 128 k rows since launch (k < 32).  Until its first exchange with news in it a worker knows only its own rows, and nearly every
-// tile of its first chunk takes the update path; the rule is in the file header, the measured choice in DESIGN.md 3c.
-#define SLAM_MX_EARLY 0x16u      // after 128, 256 and 512 rows
 #define SLAM_MX_UNROLL 4         // groups of 16 rows per trip of the scan loop
-#define SLAM_MX_RESIDENT 4       // blocks of bf_top2_mx_kernel a CU holds at once (the plan describe counts on it; launches ask)
 
 // The phase probe (tools/mx_phase_probe.py): an experiment build (-DSLAM_MX_PROBE) in which every wave sums the shader clock
 // over the phases of its life and leaves the sums in a buffer of the tool's.  The shipped build executes no stamp.
@@ -102,33 +96,13 @@ extern "C" __attribute__((visibility("default"))) int slam_exp_set_mx_probe(void
 #define MX_STAMP(ph) do {} while (0)
 #endif
 
-typedef int mx_v8i __attribute__((ext_vector_type(8)));
 typedef float mx_v4f __attribute__((ext_vector_type(4)));
-
-// 32 descriptor bits -> 32 FP4 elements (-1.0 for a set bit, +1.0 for a clear one: the bit is the sign bit as it stands): nibble
-// n of word w = bit 4n + w.  The query rows go through this form; the kernel's staging has the same map as one shift and one
-// inline-asm v_and_or_b32 per word (its `expand`): a change of the map changes both.
-__device__ __forceinline__ uint4 mx_expand(u32 x) {
-    uint4 r;
-    r.x = ((x << 3) & 0x88888888u) | 0x22222222u;
-    r.y = ((x << 2) & 0x88888888u) | 0x22222222u;
-    r.z = ((x << 1) & 0x88888888u) | 0x22222222u;
-    r.w = (x & 0x88888888u) | 0x22222222u;
-    return r;
-}
 
 // c + A B over one K-half: A = 16 train rows, B = 16 queries, FP4 on both sides (format code 4), scales 2^0 (E8M0 127)
 __device__ __forceinline__ mx_v4f mx_dot(uint4 a, uint4 b, mx_v4f c) {
     const mx_v8i av = {(int)a.x, (int)a.y, (int)a.z, (int)a.w, 0, 0, 0, 0};
     const mx_v8i bv = {(int)b.x, (int)b.y, (int)b.z, (int)b.w, 0, 0, 0, 0};
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, c, 4, 4, 0, 127, 0, 127);
-}
-
-// top-2 of two top-2 pairs whose keys are distinct rows (or none)
-__device__ __forceinline__ void mx_unite(u32& b1, u32& b2, u32 c1, u32 c2) {
-    const u32 n2 = min(max(b1, c1), min(b2, c2));
-    b1 = min(b1, c1);
-    b2 = n2;
 }
 
 __device__ __forceinline__ u32 mx_pick(const u32 (&v)[4], int i) {
@@ -225,8 +199,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             // key excludes ties only when ITS row is below c0 - the row is tested, not inferred from the ticket order: a worker
             // can publish from a later chunk before a slower one reads the bound for an earlier chunk
             const u32 g = (u32)__shfl((int)gkey, tt * 16 + col, 64);
-            const u32 gx = g < SLAM_MX_BOUND_LIMIT ? (g >> SLAM_KEY_IDX_BITS) + ((g & SLAM_KEY_IDX_MASK) < (u32)c0 ? 0u : 1u)
-                                                   : SLAM_KEY_NONE >> SLAM_KEY_IDX_BITS;
+            const u32 gx = mx_bound_x(g, c0);
             set_threshold(tt, min(threshold_x(tt), min(gx, u2[tt] >> SLAM_KEY_IDX_BITS)));
         }
     };
@@ -241,17 +214,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         if (s + SLAM_MX_STAGE <= c1) return ts[(u32)tid];
         return s + srow < c1 ? ts[(u32)tid] : make_uint4(0, 0, 0, 0);
     };
-    // mx_expand with one v_and_or_b32 per output word.  A VOP3 instruction of gfx950 reads at most one scalar or literal operand,
-    // so the compiler, given both masks as constants, splits each into an AND and an OR: the OR mask is held in a VGPR here.
+    // mx_expand with one v_and_or_b32 per output word (mx_expand_op, bf_mx_common.h): the OR mask is held in a VGPR here
     const u32 fill = 0x22222222u;
-    auto expand = [&](u32 v) -> uint4 {
-        uint4 r;
-        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r.x) : "v"(v << 3), "s"(0x88888888u), "v"(fill));
-        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r.y) : "v"(v << 2), "s"(0x88888888u), "v"(fill));
-        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r.z) : "v"(v << 1), "s"(0x88888888u), "v"(fill));
-        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r.w) : "v"(v), "s"(0x88888888u), "v"(fill));
-        return r;
-    };
+    auto expand = [&](u32 v) -> uint4 { return mx_expand_op(v, fill); };
     uint4* const dst0 = tile[0] + (srow >> 4) * 128 + sh * 64 + (srow & 15);
     auto store_stage = [&](int b, uint4 v) {
         uint4* dst = dst0 + b * (SLAM_MX_STAGE * 8);
@@ -519,9 +484,30 @@ extern "C" int slam_bf_mx_plan_describe(int num_cu, int64_t N, int64_t M, int32_
     return SLAM_OK;
 }
 
+// Which of the two matrix-core kernels the shipped engine runs a shape on that bf_mx_auto sends to the matrix cores: true = the
+// 32x32x64 kernel (bf_mx32.hip).  The rule is measured, shape by shape (tools/ab_time.py lib:engine=2,lib:engine=3 --check, the
+// whole range of five rounds below the 16x16 kernel's; table in DESIGN.md 3c "The 32x32x64 kernel"); a shape where it is not
+// faster stays on the kernel it had.  Measured faster: the four corners of bf_mx_auto, 8192 x 65536, 20000 x 100000, 65536 x
+// 65536 and 131072 x 65536 - every measured shape up to 131072 queries (two or more workers per query block on 256 CUs) and
+// 200000 train rows.  Measured slower (0.5 %): 2^20 x 2^20, one worker per query block.  Nothing was measured between, so the
+// rule is the box the measured gains span.
+static bool bf_mx32_auto(int64_t N, int64_t M) {
+    return N <= 131072 && M <= 200000;
+}
+
+// The kernel a matrix-core pass of N x M runs under `engine` (0, 2 or 3; 1 never gets here): 16 or 32, the M and N of its tiles.
+extern "C" int slam_bf_mx_tile_describe(int engine, int64_t N, int64_t M, int32_t* h_tile) {
+    SLAM_REQUIRE(h_tile, "slam_bf_mx_tile_describe: null argument");
+    SLAM_REQUIRE(engine == 0 || engine == 2 || engine == 3, "engine must be 0 (auto), 2 or 3");
+    SLAM_REQUIRE(N >= 1 && M >= 1, "bad sizes");
+    *h_tile = engine == 3 || (engine == 0 && bf_mx32_auto(N, M)) ? 32 : 16;
+    return SLAM_OK;
+}
+
 extern "C" int slam_bf_set_engine(slam_ctx* ctx, int engine) {
     SLAM_REQUIRE(ctx, "slam_bf_set_engine: null ctx");
-    SLAM_REQUIRE(engine >= 0 && engine <= 2, "engine must be 0 (auto), 1 (VALU) or 2 (matrix cores where eligible)");
+    SLAM_REQUIRE(engine >= 0 && engine <= 3,
+                 "engine must be 0 (auto), 1 (VALU), 2 (16x16 matrix-core kernel where eligible) or 3 (32x32 matrix-core kernel where eligible)");
     std::lock_guard<std::mutex> g(ctx->mu);
     ctx->bf_engine = engine;
     return SLAM_OK;
@@ -534,25 +520,28 @@ bool bf_mx_route(slam_ctx* ctx, int64_t N, int64_t M, bool rows_on_host) {
     if (ctx->bf_engine == 1 || rows_on_host) return false;
     for (int i = 0; i < SLAM_BF_KNOBS; i++)
         if (ctx->bf_knob[i]) return false;
-    return ctx->bf_engine == 2 || bf_mx_auto(N, M);
+    return ctx->bf_engine == 2 || ctx->bf_engine == 3 || bf_mx_auto(N, M);
 }
 
 int bf_mx_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, int64_t train_base, int32_t* d_idx,
                int32_t* d_dist, void* d_keep, const bf_select& sel, int* qblocks_out) {
-    static std::atomic<int> occ_once{0};     // a property of the kernel and the architecture: asked once per process
-    int occ = occ_once.load(std::memory_order_relaxed);
-    if (!occ) {
-        int o = 0;
-        SLAM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, bf_top2_mx_kernel, 256, 0));
-        occ = o > 0 ? o : SLAM_MX_RESIDENT;
-        occ_once.store(occ, std::memory_order_relaxed);
-    }
-    std::vector<int> tbl;
-    int num_cu;
+    int num_cu, engine;
     {
         std::lock_guard<std::mutex> g(ctx->mu);
         num_cu = ctx->num_cu;
+        engine = ctx->bf_engine;
     }
+    const bool wide = engine == 3 || (engine == 0 && bf_mx32_auto(N, M));     // the 32x32x64 kernel
+    const auto kernel = wide ? bf_top2_mx32_kernel : bf_top2_mx_kernel;
+    static std::atomic<int> occ_once[2] = {{0}, {0}};     // a property of the kernel and the architecture: asked once per process
+    int occ = occ_once[wide].load(std::memory_order_relaxed);
+    if (!occ) {
+        int o = 0;
+        SLAM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, 256, 0));
+        occ = o > 0 ? o : SLAM_MX_RESIDENT;
+        occ_once[wide].store(occ, std::memory_order_relaxed);
+    }
+    std::vector<int> tbl;
     const bf_mx_plan p = make_mx_plan_core(num_cu, occ, N, M, &tbl);
     bf_state st;
     if (int rc = bf_state_get(ctx, N, &st)) return rc;
@@ -561,7 +550,7 @@ int bf_mx_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_trai
     if (qblocks_out) *qblocks_out = p.qblocks;
     SLAM_HIP(hipGetLastError());
     if (int rc = slam_prof_begin(ctx)) return rc;
-    bf_top2_mx_kernel<<<dim3(p.qblocks, p.workers), dim3(256), 0, ctx->stream>>>(
+    kernel<<<dim3(p.qblocks, p.workers), dim3(256), 0, ctx->stream>>>(
         (const uint4*)d_query, (int)N, (const uint4*)d_train, d_tbl, st, (int)train_base, (int2*)d_idx, (int2*)d_dist,
         (uint4*)d_keep, p.S, sel);
     if (int rc = slam_prof_end(ctx)) return rc;

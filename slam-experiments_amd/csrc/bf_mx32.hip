@@ -1,0 +1,297 @@
+// bf_mx32.hip — the matrix-core top-2 Hamming search of bf_mx.hip on 32x32x64 FP4 tiles.  Same results as bf_top2_kernel
+// (bf_hamming.hip) and as bf_top2_mx_kernel, bit for bit; see DESIGN.md §3c "The 32x32x64 kernel".
+//
+//   * why: the kernel of bf_mx.hip is bound by vector issue, and half of its issue floor is the hold of its MFMA instructions
+//     (12.4 cycles each, paid per instruction, not per MAC).  v_mfma_f32_32x32x64_f8f6f4 does twice the MACs per instruction in
+//     twice the cycles, and in the UNSCALED spelling (both scale operands of the builtin the constant 0) holds the vector issue
+//     for 8.2 of its 32 cycles (tools/ubench/mx_issue.hip): a group-equivalent is 4 instructions, not 8, and up to five plain
+//     vector instructions per MFMA issue in its shadow.
+//   * encoding: as bf_mx.hip - descriptor bit 1 -> FP4 -1.0, bit 0 -> +1.0, hamming(a, b) = (256 - <a+-, b+->) / 2, every
+//     partial sum an exact integer in f32.  mx_expand (bf_mx_common.h, the one copy) turns one 32-bit source word into the 16
+//     bytes a lane holds of one operand: for K-quarter q (64 bits) of a row, lane (row & 31) + 32 hk holds source word 2 q + hk.
+//     The query rows use the same map, so which bit meets which K position does not matter.
+//   * geometry: a wave holds its 64 queries as the B operands of two 32-query tiles (4 K-quarters x 4 VGPRs each: 32 VGPRs,
+//     expanded once).  A group is 32 train rows: 8 MFMAs, 2 tiles x 4 K-quarters, the first quarter with C = inline 0, the rest
+//     accumulating in place in VGPRs (16 per tile; the Makefile's -amdgpu-mfma-vgpr-form for this file).  Lane l holds query
+//     (l & 31) of the tile; its accumulator index 4 i + j is row 8 i + 4 (l >> 5) + j of the group (tests/test_mx32_gpu.py
+//     proves the map with planted pairs at every distance).  A lane's rows ascend with the accumulator index.
+//   * LDS stage: 128 rows as in bf_mx.hip, double buffered, one barrier per stage; a group of 32 rows is [K-quarter][lane] x
+//     16 bytes, so an operand is one conflict-free ds_read_b128.  Thread tid stages half (tid & 1) of row (tid >> 1): its four
+//     source words are the pieces of K-quarters 2 (tid & 1) and 2 (tid & 1) + 1.
+//   * selection: the accumulators hold the bare dot D = 256 - 2 dist.  A lane keeps, per tile, the EXCLUSIVE threshold distance x
+//     (a row passes when its distance is below x) and the bit pattern of the float 258 - 2 x beside it; the 16 results of a tile
+//     fold as bit patterns with eight signed-integer maxima and one compare against that pattern.  Dots are exact integers and
+//     never -0, so for 258 - 2 x >= 0 (x <= 129) the signed comparison of patterns is the comparison of the values: negative
+//     floats are negative integers, below every pattern of a value >= 0.  A signed maximum orders negative floats backwards, so
+//     for x > 129 (a worker's first groups, or rows that are all far) the pattern is INT_MIN and the tile fires unconditionally:
+//     the update path is exact whatever passes, since a key is built from D alone, key = (128 << 23 | row) - (D << 22).
+//     The compare is per tile, so the fire test per tile is free, and a threshold move is one conversion.
+//   * the tie rules of bf_mx.hip's header carry over unchanged, with two lanes per query where that kernel has four.  x only
+//     ever falls, to one of:
+//       - dist(own 2nd-best) after a fire, dist(2nd-best of the query's two lanes) after a stage that fired and at a chunk
+//         start: chunks, stages, groups and a lane's rows ascend, so every row the lane has still to see has a higher index
+//         than every row in those pairs, and a tie against them loses;
+//       - mx_bound_x(g, c0) for the key g read from bound[] at the start of the chunk that begins at row c0 (the row of g is
+//         TESTED against c0: a tie against a key from a later row can win), and the same with the first row of the stage to come
+//         at the early exchanges (SLAM_MX_EARLY).  bound[] holds 2nd-best keys below SLAM_MX_BOUND_LIMIT, as in bf_mx.hip.
+//     A candidate is dropped only if some known 2nd-best key K has dist(K) < dist, or dist(K) == dist and row(K) < row.
+//   * row gates: a fired tile keys and merges, of a lane's 16 rows, only those at which SOME lane of the tile passes (one
+//     compare and one wave-uniform branch per row).  A skipped row is below the threshold of every lane of the tile.
+//   * scan loop: a whole stage is one trip of four groups; the A operand of K-quarter q of group g + 1 is read into the
+//     registers that the two MFMAs of quarter q of group g have just freed, so the LDS latency runs behind six MFMAs.  A stage
+//     that another follows expands and stores the thread's four source words of the next stage (ONE 16-byte load at the trip's
+//     start) in groups 1 to 3, between MFMAs.  The last stage of the train set, if short, runs group by group with the test
+//     for rows past the chunk.
+//   * plan, tickets, bound exchange, epilogue: those of bf_top2_mx_kernel; bf_mx.hip plans and launches both kernels.
+#include "internal.h"
+#include <type_traits>
+
+#include "bf_common.h"
+#include "bf_mx_common.h"
+
+typedef float mx_v16f __attribute__((ext_vector_type(16)));
+
+// c + A B over one K-quarter: A = 32 train rows, B = 32 queries, FP4 on both sides (format code 4).  Both scale operands are the
+// constant 0: the compiler then selects the unscaled v_mfma_f32_32x32x64_f8f6f4, which holds the vector issue for a shorter time
+__device__ __forceinline__ mx_v16f mx32_dot(uint4 a, uint4 b, mx_v16f c) {
+    const mx_v8i av = {(int)a.x, (int)a.y, (int)a.z, (int)a.w, 0, 0, 0, 0};
+    const mx_v8i bv = {(int)b.x, (int)b.y, (int)b.z, (int)b.w, 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, c, 4, 4, 0, 0, 0, 0);
+}
+
+#define MX32_GROUP 32                                  // train rows per group
+#define MX32_GROUPS (SLAM_MX_STAGE / MX32_GROUP)       // groups per whole stage
+
+// grid = (query blocks, workers).  Block (x, y) works for query block (x + y) mod grid.x, as bf_top2_mx_kernel.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void bf_top2_mx32_kernel(
+    const uint4* __restrict__ q, int N, const uint4* __restrict__ t, const int* __restrict__ tbl, bf_state st, int train_base,
+    int2* __restrict__ out_idx, int2* __restrict__ out_dist, uint4* __restrict__ keep, int nchunks, bf_select sel) {
+    __shared__ uint4 tile[2][SLAM_MX_STAGE * 8];
+    __shared__ u32 s_ticket, s_last;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int hk = lane >> 5, col = lane & 31;
+    const int bx = ((int)blockIdx.x + (int)blockIdx.y) % (int)gridDim.x;
+    // the lane's query in the epilogue and in the bound exchange: worked out afresh at each of them (the empty asm hides that the
+    // value repeats), or it and the addresses built on it hold registers through the scan
+    auto lane_query = [&]() -> int {
+        int v = tid;
+        asm volatile("" : "+v"(v));
+        return bx * 256 + v;
+    };
+
+    // the wave's 64 queries as B operands: tile tt, K-quarter kq = word 2 kq + (lane >> 5) of query 64 wave + 32 tt + (lane & 31)
+    uint4 qb[2][4];
+    const u32* qw = (const u32*)q;
+#pragma unroll
+    for (int tt = 0; tt < 2; tt++) {
+        int qi = bx * 256 + wave * 64 + tt * 32 + col;
+        qi = qi < N ? qi : N - 1;                                // tail columns compute a duplicate and are never stored
+#pragma unroll
+        for (int kq = 0; kq < 4; kq++) qb[tt][kq] = mx_expand(qw[(size_t)qi * 8 + kq * 2 + hk]);
+    }
+    if (const int qbase = lane_query(); keep && blockIdx.y == 0 && qbase < N) {   // the caller wants the query rows left in device memory
+        keep[2 * (size_t)qbase] = q[2 * (size_t)qbase];
+        keep[2 * (size_t)qbase + 1] = q[2 * (size_t)qbase + 1];
+    }
+
+    // per tile: the lane's own top-2 over its rows, the exclusive threshold distance x and the pattern the fold compares against
+    u32 b1[2], b2[2], xs[2];
+    int thr[2];
+    auto set_threshold = [&](int tt, u32 x) {
+        xs[tt] = x;
+        thr[tt] = x > 129u ? (int)0x80000000u : __float_as_int((float)(258 - 2 * (int)x));
+    };
+#pragma unroll
+    for (int tt = 0; tt < 2; tt++) {
+        b1[tt] = b2[tt] = SLAM_KEY_NONE;
+        set_threshold(tt, SLAM_KEY_NONE >> SLAM_KEY_IDX_BITS);   // 511: everything passes
+    }
+    // the top-2 of one tile's query over the rows of the two lanes that hold it
+    auto unite_tile = [&](int tt, u32& u1, u32& u2) {
+        u1 = b1[tt];
+        u2 = b2[tt];
+        const u32 c1 = (u32)__shfl_xor((int)u1, 32, 64), c2 = (u32)__shfl_xor((int)u2, 32, 64);
+        mx_unite(u1, u2, c1, c2);
+    };
+    // Exchange with the other workers of this query block through bound[], at the start of the chunk (or stage) that begins at
+    // row c0; lane l speaks for query 64 wave + l, which tile (l >> 5) holds.  As bf_top2_mx_kernel's.
+    u32 gkey = SLAM_BOUND_IDLE, pend[1] = {0u};
+    auto exchange = [&](int c0) {
+        u32 u1[2], u2[2];
+#pragma unroll
+        for (int tt = 0; tt < 2; tt++) unite_tile(tt, u1[tt], u2[tt]);
+        if (const int qbase = lane_query(); qbase < N) {
+            const u32 own = hk ? u2[1] : u2[0];
+            asm volatile("" ::"v"(pend[0]));
+            const u32 g = __hip_atomic_load(&st.bound[qbase], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (own < g && own < SLAM_MX_BOUND_LIMIT) pend[0] = atomicMin(&st.bound[qbase], own);
+            gkey = g;
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; tt++) {
+            // the united pair comes from rows below c0: ties against it lose.  Another worker's key: mx_bound_x tests its row
+            const u32 g = (u32)__shfl((int)gkey, tt * 32 + col, 64);
+            set_threshold(tt, min(xs[tt], min(mx_bound_x(g, c0), u2[tt] >> SLAM_KEY_IDX_BITS)));
+        }
+    };
+
+    // staging: thread tid carries half (tid & 1) of row (tid >> 1) of a stage, i.e. the source words 4 sh + j, j = 0 .. 3: word
+    // j is the operand piece of K-quarter 2 sh + (j >> 1), lane (row & 31) + 32 (j & 1), in the row's group of 32
+    const int srow = tid >> 1, sh = tid & 1;
+    auto load_stage = [&](int s, int c1) -> uint4 {
+        const uint4* ts = t + 2 * (size_t)s;
+        if (s + SLAM_MX_STAGE <= c1) return ts[(u32)tid];
+        return s + srow < c1 ? ts[(u32)tid] : make_uint4(0, 0, 0, 0);
+    };
+    const u32 fill = 0x22222222u;
+    uint4* const dst0 = tile[0] + (srow >> 5) * 256 + sh * 128 + (srow & 31);
+    auto store_word = [&](uint4* dst, int j, u32 v) { dst[(j >> 1) * 64 + (j & 1) * 32] = mx_expand_op(v, fill); };
+    auto store_stage = [&](int b, uint4 v) {
+        uint4* dst = dst0 + b * (SLAM_MX_STAGE * 8);
+        store_word(dst, 0, v.x);
+        store_word(dst, 1, v.y);
+        store_word(dst, 2, v.z);
+        store_word(dst, 3, v.w);
+    };
+
+    u32* const cursor = st.cursor + (size_t)(4 * bx) * SLAM_CURSOR_STRIDE;
+    if (tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    int ci = __builtin_amdgcn_readfirstlane((int)s_ticket);
+    int scanned = 0;                                             // wave-uniform: the rows this block has scanned since launch
+    while (ci < nchunks) {
+        const int c0 = tbl[ci], c1 = tbl[ci + 1];
+        const uint4 first = load_stage(c0, c1);
+        exchange(c0);
+        store_stage(0, first);
+        __syncthreads();
+        int buf = 0;
+        for (int s0 = c0; s0 < c1; s0 += SLAM_MX_STAGE) {
+            const int s1 = s0 + SLAM_MX_STAGE;
+            const bool more = s1 < c1;
+            // the next ticket is drawn while the chunk's last stage is scanned; read behind the stage's barrier
+            if (!more && tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint4* tp = tile[buf];
+            u32 fired = 0;                                       // wave-uniform: the tiles that took the update path in this stage
+            // fold the 2 x 16 results of group g and, where some lane passes, take the update path
+            auto fold = [&](int g, const mx_v16f (&acc)[2], auto rag) {
+                int m[2];
+#pragma unroll
+                for (int tt = 0; tt < 2; tt++) {
+                    int p = max(max(__float_as_int(acc[tt][0]), __float_as_int(acc[tt][1])), __float_as_int(acc[tt][2]));
+#pragma unroll
+                    for (int i = 3; i < 15; i += 2) p = max(max(p, __float_as_int(acc[tt][i])), __float_as_int(acc[tt][i + 1]));
+                    m[tt] = max(p, __float_as_int(acc[tt][15]));
+                }
+                if (__builtin_expect(__ballot(m[0] >= thr[0] || m[1] >= thr[1]) != 0ull, 0)) {
+                    // the group's first row is taken from the scalar side here: as a per-lane value it would be carried through
+                    // every group that does not fire
+                    int row0 = s0 + g * MX32_GROUP;
+                    asm("" : "+s"(row0));
+                    const u32 rowk = (u32)row0 + (u32)(4 * hk);
+#pragma unroll
+                    for (int tt = 0; tt < 2; tt++) {
+                        if (__ballot(m[tt] >= thr[tt]) == 0ull) continue;
+                        fired |= 1u << tt;
+                        // key = (128 - D / 2) << 23 | row: base + (-D << 22), exact modulo 2^32 (D is an even integer)
+                        const u32 base = (128u << SLAM_KEY_IDX_BITS) + rowk;
+#pragma unroll
+                        for (int i = 0; i < 16; i++) {
+                            if (__ballot(__float_as_int(acc[tt][i]) >= thr[tt]) == 0ull) continue;
+                            const int off = 8 * (i >> 2) + (i & 3);
+                            u32 key = base + (u32)off + ((u32)(int)(-acc[tt][i]) << (SLAM_KEY_IDX_BITS - 1));
+                            if constexpr (decltype(rag)::value)   // the rows past the end of a short stage never enter
+                                key = (int)rowk + off < c1 ? key : SLAM_KEY_NONE;
+                            b2[tt] = umed3(b1[tt], b2[tt], key);
+                            b1[tt] = min(b1[tt], key);
+                        }
+                        set_threshold(tt, min(xs[tt], b2[tt] >> SLAM_KEY_IDX_BITS));
+                    }
+                }
+            };
+            const mx_v16f zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            auto group = [&](int g, auto rag) {
+                mx_v16f acc[2];
+#pragma unroll
+                for (int kq = 0; kq < 4; kq++) {
+                    const uint4 a = tp[g * 256 + kq * 64 + lane];
+#pragma unroll
+                    for (int tt = 0; tt < 2; tt++) acc[tt] = mx32_dot(a, qb[tt][kq], kq ? acc[tt] : zero);
+                }
+                fold(g, acc, rag);
+            };
+            // A whole stage: one trip of four groups.  The A operand of K-quarter kq of group k + 1 is read once the two MFMAs of
+            // quarter kq of group k have issued, into the registers they free; the last group reads nothing ahead, so no read
+            // leaves the stage's own buffer.  With `shadow`, groups 1 to 3 also expand and store the thread's four source words
+            // of the NEXT stage (into buffer buf ^ 1, free since the barrier that opened this stage) between their MFMAs.
+            auto trip = [&](auto shadow) {
+                constexpr bool SH = decltype(shadow)::value;
+                const uint4* ap = tp + lane;
+                uint4* const dst = dst0 + (buf ^ 1) * (SLAM_MX_STAGE * 8);
+                // the thread's 16 bytes of the next stage, one load at the trip's start: its latency runs behind group 0.  Were
+                // the next stage not whole, the rows past the chunk end would read its last row instead (what such a row holds
+                // never matters, the scan tests its index); this keeps the load inside the train set whatever the table
+                u32 nx[4] = {0, 0, 0, 0};
+                if (SH) {
+                    const uint4 x = (t + 2 * (size_t)s1)[2 * min(srow, c1 - 1 - s1) + sh];
+                    nx[0] = x.x; nx[1] = x.y; nx[2] = x.z; nx[3] = x.w;
+                }
+                uint4 a[4];
+#pragma unroll
+                for (int kq = 0; kq < 4; kq++) a[kq] = ap[kq * 64];
+#pragma unroll
+                for (int k = 0; k < MX32_GROUPS; k++) {
+                    mx_v16f acc[2];
+#pragma unroll
+                    for (int kq = 0; kq < 4; kq++) {
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int tt = 0; tt < 2; tt++) acc[tt] = mx32_dot(a[kq], qb[tt][kq], kq ? acc[tt] : zero);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (k + 1 < MX32_GROUPS) a[kq] = ap[(k + 1) * 256 + kq * 64];
+                        // the next stage's words: word 0 in group 1, word 1 in group 2, words 2 and 3 in group 3
+                        if (SH && k >= 1 && kq == 1) store_word(dst, k - 1, nx[k - 1]);
+                        if (SH && k == 3 && kq == 2) store_word(dst, 3, nx[3]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    fold(k, acc, std::false_type{});
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            if (more) {                                          // then this stage is whole
+                trip(std::true_type{});
+            } else if (s1 == c1) {
+                trip(std::false_type{});
+            } else {                                             // a short stage: the last of the train set
+                const int ng = __builtin_amdgcn_readfirstlane((c1 - s0 + MX32_GROUP - 1) / MX32_GROUP);
+                for (int g = 0; g < ng; g++) group(g, std::true_type{});
+            }
+            // once per stage in which a key changed, for the tiles it changed in: the threshold of the query's two lanes together
+            // (their rows lie in this stage or before it, below every row still to come)
+#pragma unroll
+            for (int tt = 0; tt < 2; tt++) {
+                if (!(fired >> tt & 1u)) continue;
+                u32 u1, u2;
+                unite_tile(tt, u1, u2);
+                set_threshold(tt, min(xs[tt], u2 >> SLAM_KEY_IDX_BITS));
+            }
+            // an early exchange (SLAM_MX_EARLY): per wave, no barrier; every row still to come is at or above s1.  Not after a
+            // chunk's last stage: the chunk-start exchange follows anyway
+            scanned += min(s1, c1) - s0;
+            if (more && scanned < 32 * SLAM_MX_STAGE && (SLAM_MX_EARLY >> (scanned / SLAM_MX_STAGE) & 1u)) exchange(s1);
+            __syncthreads();
+            buf ^= 1;
+        }
+        ci = __builtin_amdgcn_readfirstlane((int)s_ticket);
+    }
+
+    u32 u1[2], u2[2];
+#pragma unroll
+    for (int tt = 0; tt < 2; tt++) unite_tile(tt, u1[tt], u2[tt]);
+    const u32 f1[1] = {hk ? u1[1] : u1[0]}, f2[1] = {hk ? u2[1] : u2[0]};
+    // the epilogue's skip test takes a DISTANCE that bounds the final 2nd-best one, or the idle pattern when there is none
+    const u32 gk[1] = {gkey < SLAM_MX_BOUND_LIMIT ? gkey >> SLAM_KEY_IDX_BITS : SLAM_BOUND_IDLE};
+    bf_top2_epilogue<1, true>(st, bx, tid, lane, lane_query(), false, false, f1, f2, gk, pend, N, (int)gridDim.y, train_base, out_idx,
+                              out_dist, sel, s_last);
+}

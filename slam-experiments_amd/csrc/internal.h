@@ -32,7 +32,7 @@ struct slam_ctx {
     void* bf_state_mem = nullptr;                   // matcher merge state (best/bound/arrivals), clean between launches
     int64_t bf_state_rows = 0;
     int bf_knob[SLAM_BF_KNOBS] = {};                 // matcher tuning overrides (slam_bf_set_tuning), 0 = heuristic
-    int bf_engine = 0;                              // top-2 engine (slam_bf_set_engine): 0 = auto, 1 = VALU, 2 = matrix cores
+    int bf_engine = 0;                              // top-2 engine (slam_bf_set_engine): 0 = auto, 1 = VALU, 2 / 3 = the 16x16 / 32x32 matrix-core kernel
     // chunk boundary tables of the recent searches: a ring of small slots + one big slot, device and pinned host
     void* bf_tbl_dev = nullptr;
     void* bf_tbl_host = nullptr;

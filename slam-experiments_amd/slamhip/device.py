@@ -86,7 +86,8 @@ class Context:
 
     def set_engine(self, engine: int = 0) -> None:
         """Which engine runs the top-2 search on this context (``slam_bf_set_engine``): 0 = auto (shipped), 1 = the VALU
-        popcount kernel, 2 = the matrix-core kernel wherever it is eligible."""
+        popcount kernel, 2 = the matrix-core kernel on 16x16x128 tiles wherever it is eligible, 3 = the matrix-core kernel on
+        32x32x64 tiles wherever 2 would be eligible.  Every engine gives the same tables, bit for bit."""
         check(self.lib.slam_bf_set_engine(self.handle, int(engine)))
 
     def state_dirty(self) -> int:
@@ -158,6 +159,14 @@ def mx_plan_describe(n: int, m: int, num_cu: int = 256):
     check(lib.slam_bf_mx_plan_describe(num_cu, n, m, plan, tbl, cap, ctypes.byref(length)))
     names = ("qblocks", "workers", "chunk", "chunks", "tail_chunks", "stage_rows", "resident", "auto")
     return dict(zip(names, plan)), list(tbl[:min(length.value, cap)])
+
+
+def mx_tile_describe(n: int, m: int, engine: int = 0) -> int:
+    """Which matrix-core kernel a pass of n x m runs on under ``engine`` (0, 2 or 3), WITHOUT a device
+    (``slam_bf_mx_tile_describe``): 16 for the 16x16x128 kernel, 32 for the 32x32x64 kernel."""
+    tile = ctypes.c_int32(0)
+    check(_lib.load().slam_bf_mx_tile_describe(int(engine), n, m, ctypes.byref(tile)))
+    return tile.value
 
 
 def plan_describe(n: int, m: int, num_cu: int = 256, qb_all: int = 0, rows_on_host: bool = False, **knobs):

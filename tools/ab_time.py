@@ -4,7 +4,7 @@
     python tools/ab_time.py LIB[:k=v...][,LIB...] [NxM ...] [--rounds R] [--reps K] [--check]
 
 A library may carry tuning knobs of slam_bf_set_tuning, e.g. path/libslamhip.so:R=2:bpc=16 (R, bpc, lead, leadchunk, tail, feed, cold, chunk, queue),
-and the engine of slam_bf_set_engine, e.g. path/libslamhip.so:engine=1 (0 = auto, 1 = VALU, 2 = matrix cores where eligible).
+and the engine of slam_bf_set_engine, e.g. path/libslamhip.so:engine=1 (0 = auto, 1 = VALU, 2 / 3 = the 16x16x128 / 32x32x64 matrix-core kernel where eligible).
 
 Each library is dlopen'ed privately (RTLD_LOCAL; the builds export the same symbols), gets its own context and its
 own copy of the inputs.  Per round and library: K back-to-back searches between two HIP events.  --check compares

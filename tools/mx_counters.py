@@ -1,6 +1,9 @@
-"""Summarise rocprofv3 --pmc passes over tools/run_search.py for bf_top2_mx_kernel, per build (development aid).
+"""Summarise rocprofv3 --pmc passes over tools/run_search.py for a matrix-core top-2 kernel, per build (development aid).
 
-    python tools/mx_counters.py LABEL=DIR[,DIR...] [LABEL=DIR[,DIR...] ...] > profiles/<name>.json
+    python tools/mx_counters.py [--kernel NAME] [--mfma-per-group K] LABEL=DIR[,DIR...] [LABEL=DIR[,DIR...] ...] > profiles/<name>.json
+
+NAME: a substring of the kernel's name (default bf_top2_mx_kernel; bf_top2_mx32_kernel for the 32x32x64 kernel).  K: the MFMAs
+of a group-equivalent of 16 rows x 64 queries x 256 bits (default 8; 4 for the 32x32x64 kernel).
 
 Each DIR is the output directory of one pass (`rocprofv3 --pmc <set> --output-format csv -d DIR -- python3
 tools/run_search.py 65536x65536 20`, --pmc alone, SLAM_LIB choosing the build).  Per counter: the mean over the launches of
@@ -12,7 +15,17 @@ import os
 import sys
 from collections import defaultdict
 
-out = {"kernel": "bf_top2_mx_kernel", "per_launch": {}, "derived": {}}
+def opt(name, default):
+    if name in sys.argv:
+        i = sys.argv.index(name)
+        v = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
+        return type(default)(v)
+    return default
+
+
+KERNEL, PER_GROUP = opt("--kernel", "bf_top2_mx_kernel"), opt("--mfma-per-group", 8)
+out = {"kernel": KERNEL, "mfma_per_group": PER_GROUP, "per_launch": {}, "derived": {}}
 for spec in sys.argv[1:]:
     label, dirs = spec.split("=")
     per = {}
@@ -21,7 +34,7 @@ for spec in sys.argv[1:]:
             acc = defaultdict(float)
             with open(f, newline="") as fh:
                 for row in csv.DictReader(fh):
-                    if "bf_top2_mx_kernel" in row["Kernel_Name"]:
+                    if KERNEL in row["Kernel_Name"]:
                         acc[(row["Counter_Name"], row["Dispatch_Id"])] += float(row["Counter_Value"])
             vals = defaultdict(list)
             for (name, _), v in acc.items():
@@ -38,7 +51,9 @@ for spec in sys.argv[1:]:
     if g("SQ_VALU_MFMA_BUSY_CYCLES") and g("SQ_VALU_MFMA_COEXEC_CYCLES") is not None:
         dv["coexec_share_of_mfma_busy"] = g("SQ_VALU_MFMA_COEXEC_CYCLES") / g("SQ_VALU_MFMA_BUSY_CYCLES")
     if g("SQ_INSTS_MFMA"):
-        groups = g("SQ_INSTS_MFMA") / 8
+        groups = g("SQ_INSTS_MFMA") / PER_GROUP
+        if g("SQ_BUSY_CYCLES"):
+            dv["SQ_BUSY_CYCLES_per_group_and_simd"] = g("SQ_BUSY_CYCLES") / groups      # see profiles/README.md for the scale
         for n in ("SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS"):
             if g(n) is not None:
                 dv[n + "_per_group"] = g(n) / groups      # SQ_INSTS_VALU counts the MFMAs too

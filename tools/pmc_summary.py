@@ -59,7 +59,7 @@ except OSError:
 out = {
     "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE  and, separately,  --pmc WRITE_SIZE  -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline",
     "head": head or "unknown (no git on the GPU box: see the commit that added this file)",
-    "source_sha": {n: sha(n) for n in ("bf_hamming.hip", "bf_scan_sgpr.h", "bf_mx.hip", "reproj.hip")},
+    "source_sha": {n: sha(n) for n in ("bf_hamming.hip", "bf_scan_sgpr.h", "bf_mx.hip", "bf_mx32.hip", "bf_mx_common.h", "reproj.hip")},
     "units": "raw counter values are KB per launch",
     "corrections": "gfx950: FETCH_SIZE = TCC_EA0_RDREQ x 64 B while coalesced streaming reads travel as 128-B requests, so it "
                    "reports half their bytes (MI355X_MICROARCH.md, HBM section: measured for 16 B/lane reads) -> doubled for both "
@@ -68,8 +68,10 @@ out = {
                    "raw alone would be half the index and pixel streams the kernel cannot avoid reading). WRITE_SIZE exact. "
                    "The fabric-side counters include Infinity-Cache hits.",
 }
-# the headline search runs bf_top2_mx_kernel (the matrix-core search) since it was added; bench.py files it under bf_top2_kernel
-bf, rj = pick("bf_top2_mx_kernel") or pick("bf_top2_kernel"), pick("reproj_rj_kernel")
+# the headline search runs on the matrix cores since bf_mx.hip was added, on bf_top2_mx32_kernel since the shipped engine routes
+# it there (whichever of the two ran is picked; a run holds one of them); bench.py files it under bf_top2_kernel
+bf, rj = pick("bf_top2_mx32_kernel") or pick("bf_top2_mx_kernel") or pick("bf_top2_kernel"), pick("reproj_rj_kernel")
+out["search_kernel"] = next((n for n in ("bf_top2_mx32_kernel", "bf_top2_mx_kernel", "bf_top2_kernel") if pick(n)), None)
 if bf:
     f, w = 2 * 1024 * bf["FETCH_SIZE_KB_per_launch"]["median"], 1024 * bf["WRITE_SIZE_KB_per_launch"]["median"]
     out["bf_top2_kernel"] = {"fetch_bytes_corrected": f, "write_bytes": w, "traffic_bytes": f + w, "algorithmic_bytes": 5242880}

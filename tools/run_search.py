@@ -1,5 +1,6 @@
 """Run the top-2 search NxM `reps` times on device-resident rows (a target for rocprofv3 passes on sizes other than
-the bench's; development aid).    python tools/run_search.py NxM [reps] [knob=value,...]   (knobs of Context.set_tuning)"""
+the bench's; development aid).    python tools/run_search.py NxM [reps] [knob=value,...]   (knobs of Context.set_tuning, and
+engine=E for Context.set_engine)"""
 import os
 import sys
 
@@ -17,7 +18,12 @@ n, m = (int(v) for v in sys.argv[1].split("x"))
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 30
 ctx = slamhip.default_context()
 if len(sys.argv) > 3 and sys.argv[3]:
-    ctx.set_tuning(**{k: int(v) for k, v in (kv.split("=") for kv in sys.argv[3].split(","))})
+    knobs = {k: int(v) for k, v in (kv.split("=") for kv in sys.argv[3].split(","))}
+    engine = knobs.pop("engine", None)
+    if knobs:
+        ctx.set_tuning(**knobs)
+    if engine is not None:
+        ctx.set_engine(engine)
 q = slamhip.DeviceDescriptors(ctx, np.random.default_rng(228).integers(0, 256, (n, 32), dtype=np.uint8))
 t = slamhip.DeviceDescriptors(ctx, np.random.default_rng(229).integers(0, 256, (m, 32), dtype=np.uint8))
 tab = slamhip.Top2Table(ctx, n)

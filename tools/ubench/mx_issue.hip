@@ -3,18 +3,26 @@
 //
 // The body is the shipped group of 16 train rows: 8 x v_mfma_scale_f32_16x16x128_f8f6f4 cbsz:4 blgp:4 with VGPR accumulators -
 // four that start from the threshold quads, four that accumulate in place - on operands held in registers (random FP4 +-1
-// nibbles 0x2 / 0xA).  Beside every MFMA go k = 0 .. 4 independent v_max3_i32 fillers (no register of an MFMA in them):
+// nibbles 0x2 / 0xA).  Three more FORMs of the same 8-MFMA body stand beside it: the unscaled spelling of the same shape
+// (v_mfma_f32_16x16x128_f8f6f4), and the 32x32x64 shape, scaled by 2^0 and unscaled, as a group of 32 rows x 64 queries: two
+// 32-query tiles x four K-quarters, the first quarter of a tile with C = inline 0, the rest accumulating in place, the tiles
+// alternating.  A 32x32 MFMA does twice the MACs, so a group-equivalent (16 rows x 64 queries x 256 bits) is 8 MFMAs of the
+// 16x16 forms and 4 of the 32x32 ones.
+// Beside every MFMA go k = 0 .. 8 independent v_max3_i32 fillers (no register of an MFMA in them):
 //   (i)   interleaved: k fillers after each MFMA, in the wave's own stream;
 //   (ii)  bunched:     the 8 MFMAs, then 8 k fillers;
 //   (iii) cross-wave:  the waves in even wave slots of a SIMD run bare groups, the waves in odd slots run ONLY fillers for a fixed
 //                      1.5 M cycles of the shader clock - less than the MFMA waves need, so every filler counted was issued
 //                      beside them - in bursts of 8 k with (4 - k) s_nop 15 between bursts (k = 4: back to back).
-// at 1, 2 and 4 blocks per CU ((iii): 2 and 4).  Every wave records where it ran (HW_ID, XCC_ID), so a row is computed per
+// at 2, 3 and 4 blocks per CU; the shipped form also at 1, and (iii), with k = 0 .. 4, at 2 and 4.  Every wave records where it ran (HW_ID, XCC_ID), so a row is computed per
 // SIMD from the waves that really shared it: only SIMDs that held exactly the asked number of waves count, and the share of
 // their span in which all of them ran is printed beside (waves of equal priority are served by age).  Per row: the SIMD's cycles per MFMA (its span / its MFMAs, median over SIMDs), an MFMA wave's
 // own cycles per group, and for (iii) the fillers a filler wave issued per MFMA time of its SIMD.
-// It answers: how long an FP4 MFMA holds the vector issue, how many plain instructions per MFMA are free in-wave and
-// cross-wave, and what the floor of the shipped mix (8 MFMAs + 25 plain instructions per group) is.
+// After each sweep over k a line fits the SIMD's cycles per MFMA to max(T, H + 4 k): T is the k = 0 row, H the mean of
+// (cycles - 4 k) over the rows that lie a cycle or more above T, and the floor of a group-equivalent carrying the shipped
+// 25.8 plain instructions is max(n T, n H + 4 x 25.8) with n = 8 or 4 MFMAs.
+// It answers: how long an FP4 MFMA of either shape and spelling holds the vector issue, how many plain instructions per MFMA
+// are free in-wave and cross-wave, and what the issue floor of the shipped mix is in each form.
 // build: hipcc --offload-arch=gfx950 -O3 mx_issue.hip -o mx_issue
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -25,52 +33,116 @@
 #include <vector>
 #define CK(x) do{hipError_t e=(x); if(e!=hipSuccess){printf("%s: %s\n",#x,hipGetErrorString(e)); return 1;}}while(0)
 
-// registers, as in the shipped listing: B operands v[2:33] (tile tt, K-half h at 2 + 8 tt + 4 h), threshold quads v[34:49], A
-// operands v[50:53] / v[54:57], accumulators v[62:77], the scales in v96; the fillers use v[80:87] only
+// registers of the 16x16 forms, as in the shipped listing: B operands v[2:33] (tile tt, K-half h at 2 + 8 tt + 4 h), threshold
+// quads v[34:49], A operands v[50:53] / v[54:57], accumulators v[62:77].  Of the 32x32 forms: B operands v[2:33] (tile t,
+// K-quarter q at 2 + 16 t + 4 q), A operands v[34:49] (quarter q at 34 + 4 q), accumulators v[50:65] and v[66:81].  The scales
+// are in v96; the fillers use v[100:111] only
 #define CLOB "v2","v3","v4","v5","v6","v7","v8","v9","v10","v11","v12","v13","v14","v15","v16","v17","v18","v19","v20","v21","v22","v23", \
              "v24","v25","v26","v27","v28","v29","v30","v31","v32","v33","v34","v35","v36","v37","v38","v39","v40","v41","v42","v43","v44","v45", \
-             "v46","v47","v48","v49","v50","v51","v52","v53","v54","v55","v56","v57","v62","v63","v64","v65","v66","v67","v68","v69","v70","v71", \
-             "v72","v73","v74","v75","v76","v77","v80","v81","v82","v83","v84","v85","v86","v87","v96"
-#define MF(d, a, b, c) "v_mfma_scale_f32_16x16x128_f8f6f4 v[" d "], v[" a "], v[" b "], v[" c "], v96, v96 op_sel_hi:[0,0,0] cbsz:4 blgp:4\n"
-#define F1 "v_max3_i32 v80, v84, v85, v86\n"
-#define F2 F1 "v_max3_i32 v81, v85, v86, v87\n"
-#define F3 F2 "v_max3_i32 v82, v86, v87, v84\n"
-#define F4 F3 "v_max3_i32 v83, v87, v84, v85\n"
+             "v46","v47","v48","v49","v50","v51","v52","v53","v54","v55","v56","v57","v58","v59","v60","v61","v62","v63","v64","v65","v66","v67", \
+             "v68","v69","v70","v71","v72","v73","v74","v75","v76","v77","v78","v79","v80","v81","v96","v100","v101","v102","v103","v104","v105", \
+             "v106","v107","v108","v109","v110","v111"
+#define SC ", v96, v96 op_sel_hi:[0,0,0] cbsz:4 blgp:4\n"
+#define UN " cbsz:4 blgp:4\n"
+#define MF(d, a, b, c) "v_mfma_scale_f32_16x16x128_f8f6f4 v[" d "], v[" a "], v[" b "], v[" c "]" SC
+#define MU(d, a, b, c) "v_mfma_f32_16x16x128_f8f6f4 v[" d "], v[" a "], v[" b "], v[" c "]" UN
+#define WF(d, a, b, c) "v_mfma_scale_f32_32x32x64_f8f6f4 v[" d "], v[" a "], v[" b "], " c SC
+#define WU(d, a, b, c) "v_mfma_f32_32x32x64_f8f6f4 v[" d "], v[" a "], v[" b "], " c UN
 #define F0 ""
-#define M0 MF("62:65", "50:53", "2:5", "34:37")
-#define M1 MF("66:69", "50:53", "10:13", "38:41")
-#define M2 MF("70:73", "50:53", "18:21", "42:45")
-#define M3 MF("74:77", "50:53", "26:29", "46:49")
-#define M4 MF("62:65", "54:57", "6:9", "62:65")
-#define M5 MF("66:69", "54:57", "14:17", "66:69")
-#define M6 MF("70:73", "54:57", "22:25", "70:73")
-#define M7 MF("74:77", "54:57", "30:33", "74:77")
-#define INTER(F) M0 F M1 F M2 F M3 F M4 F M5 F M6 F M7 F
-#define BUNCH(F) M0 M1 M2 M3 M4 M5 M6 M7 F F F F F F F F
+#define F1 "v_max3_i32 v100, v108, v109, v110\n"
+#define F2 F1 "v_max3_i32 v101, v109, v110, v111\n"
+#define F3 F2 "v_max3_i32 v102, v110, v111, v108\n"
+#define F4 F3 "v_max3_i32 v103, v111, v108, v109\n"
+#define F5 F4 "v_max3_i32 v104, v108, v110, v109\n"
+#define F6 F5 "v_max3_i32 v105, v109, v111, v110\n"
+#define F7 F6 "v_max3_i32 v106, v110, v108, v111\n"
+#define F8 F7 "v_max3_i32 v107, v111, v109, v108\n"
+// the 8 MFMAs of a group, per form: A 16x16 scaled (shipped), B 16x16 unscaled, C 32x32 scaled, D 32x32 unscaled
+#define A0 MF("62:65", "50:53", "2:5", "34:37")
+#define A1 MF("66:69", "50:53", "10:13", "38:41")
+#define A2 MF("70:73", "50:53", "18:21", "42:45")
+#define A3 MF("74:77", "50:53", "26:29", "46:49")
+#define A4 MF("62:65", "54:57", "6:9", "62:65")
+#define A5 MF("66:69", "54:57", "14:17", "66:69")
+#define A6 MF("70:73", "54:57", "22:25", "70:73")
+#define A7 MF("74:77", "54:57", "30:33", "74:77")
+#define B0 MU("62:65", "50:53", "2:5", "34:37")
+#define B1 MU("66:69", "50:53", "10:13", "38:41")
+#define B2 MU("70:73", "50:53", "18:21", "42:45")
+#define B3 MU("74:77", "50:53", "26:29", "46:49")
+#define B4 MU("62:65", "54:57", "6:9", "62:65")
+#define B5 MU("66:69", "54:57", "14:17", "66:69")
+#define B6 MU("70:73", "54:57", "22:25", "70:73")
+#define B7 MU("74:77", "54:57", "30:33", "74:77")
+#define C0 WF("50:65", "34:37", "2:5", "0")
+#define C1 WF("66:81", "34:37", "18:21", "0")
+#define C2 WF("50:65", "38:41", "6:9", "v[50:65]")
+#define C3 WF("66:81", "38:41", "22:25", "v[66:81]")
+#define C4 WF("50:65", "42:45", "10:13", "v[50:65]")
+#define C5 WF("66:81", "42:45", "26:29", "v[66:81]")
+#define C6 WF("50:65", "46:49", "14:17", "v[50:65]")
+#define C7 WF("66:81", "46:49", "30:33", "v[66:81]")
+#define D0 WU("50:65", "34:37", "2:5", "0")
+#define D1 WU("66:81", "34:37", "18:21", "0")
+#define D2 WU("50:65", "38:41", "6:9", "v[50:65]")
+#define D3 WU("66:81", "38:41", "22:25", "v[66:81]")
+#define D4 WU("50:65", "42:45", "10:13", "v[50:65]")
+#define D5 WU("66:81", "42:45", "26:29", "v[66:81]")
+#define D6 WU("50:65", "46:49", "14:17", "v[50:65]")
+#define D7 WU("66:81", "46:49", "30:33", "v[66:81]")
+#define INTER_(P, F) P##0 F P##1 F P##2 F P##3 F P##4 F P##5 F P##6 F P##7 F
+#define BUNCH_(P, F) P##0 P##1 P##2 P##3 P##4 P##5 P##6 P##7 F F F F F F F F
+#define INTER_A(F) INTER_(A, F)
+#define INTER_B(F) INTER_(B, F)
+#define INTER_C(F) INTER_(C, F)
+#define INTER_D(F) INTER_(D, F)
+#define BUNCH_A(F) BUNCH_(A, F)
+#define BUNCH_B(F) BUNCH_(B, F)
+#define BUNCH_C(F) BUNCH_(C, F)
+#define BUNCH_D(F) BUNCH_(D, F)
 #define NOP16 "s_nop 15\n"
 #define X4(a) a a a a
 #define FILL_CYCLES 1500000ull
 
 struct stamp { unsigned long long c0, r0, c1, r1; unsigned role, hwid, xcc, count; };
 
+// FORM 0 16x16x128 scaled (shipped) | 1 16x16x128 unscaled | 2 32x32x64 scaled | 3 32x32x64 unscaled;
 // PLACE 0 interleaved | 1 bunched | 2 cross-wave; K fillers per MFMA
-template <int PLACE, int K>
+#define PICK(BODY)                                            \
+    {                                                         \
+        if (K == 0) asm volatile(X4(BODY(F0)) ::: CLOB);      \
+        if (K == 1) asm volatile(X4(BODY(F1)) ::: CLOB);      \
+        if (K == 2) asm volatile(X4(BODY(F2)) ::: CLOB);      \
+        if (K == 3) asm volatile(X4(BODY(F3)) ::: CLOB);      \
+        if (K == 4) asm volatile(X4(BODY(F4)) ::: CLOB);      \
+        if (K == 5) asm volatile(X4(BODY(F5)) ::: CLOB);      \
+        if (K == 6) asm volatile(X4(BODY(F6)) ::: CLOB);      \
+        if (K == 7) asm volatile(X4(BODY(F7)) ::: CLOB);      \
+        if (K == 8) asm volatile(X4(BODY(F8)) ::: CLOB);      \
+    }
+template <int FORM, int PLACE, int K>
 __global__ __launch_bounds__(256) void k(uint32_t* out, stamp* st, int iters) {
+    static_assert(PLACE < 2 || (FORM == 0 && K <= 4), "the cross-wave rows exist for the shipped form only");
     uint32_t seed = threadIdx.x * 2654435761u + blockIdx.x * 40503u + 1u;
     // FP4 +-1 operands: every nibble 0x2 or 0xA
 #define RND(r) "v_mul_lo_u32 %0, %0, %1\n v_and_b32 " r ", 0x88888888, %0\n v_or_b32 " r ", 0x22222222, " r "\n"
     asm volatile(RND("v2") RND("v3") RND("v4") RND("v5") RND("v6") RND("v7") RND("v8") RND("v9") RND("v10") RND("v11") RND("v12") RND("v13")
                  RND("v14") RND("v15") RND("v16") RND("v17") RND("v18") RND("v19") RND("v20") RND("v21") RND("v22") RND("v23") RND("v24")
-                 RND("v25") RND("v26") RND("v27") RND("v28") RND("v29") RND("v30") RND("v31") RND("v32") RND("v33") RND("v50") RND("v51")
-                 RND("v52") RND("v53") RND("v54") RND("v55") RND("v56") RND("v57")
+                 RND("v25") RND("v26") RND("v27") RND("v28") RND("v29") RND("v30") RND("v31") RND("v32") RND("v33") RND("v34") RND("v35")
+                 RND("v36") RND("v37") RND("v38") RND("v39") RND("v40") RND("v41") RND("v42") RND("v43") RND("v44") RND("v45") RND("v46")
+                 RND("v47") RND("v48") RND("v49") RND("v50") RND("v51") RND("v52") RND("v53") RND("v54") RND("v55") RND("v56") RND("v57")
                  : "+v"(seed) : "v"(1664525u) : CLOB);
-    // thresholds as in the kernel (2 x - 258 for some x), fillers' inputs, scale 2^0 on both sides
-    asm volatile("v_mov_b32 v34, 0xc2a00000\n v_mov_b32 v35, v34\n v_mov_b32 v36, v34\n v_mov_b32 v37, v34\n v_mov_b32 v38, v34\n v_mov_b32 v39, v34\n"
-                 "v_mov_b32 v40, v34\n v_mov_b32 v41, v34\n v_mov_b32 v42, v34\n v_mov_b32 v43, v34\n v_mov_b32 v44, v34\n v_mov_b32 v45, v34\n"
-                 "v_mov_b32 v46, v34\n v_mov_b32 v47, v34\n v_mov_b32 v48, v34\n v_mov_b32 v49, v34\n"
-                 "v_mov_b32 v84, %0\n v_mov_b32 v85, %0\n v_mov_b32 v86, %0\n v_mov_b32 v87, %0\n v_mov_b32 v80, 0\n v_mov_b32 v81, 0\n v_mov_b32 v82, 0\n"
-                 "v_mov_b32 v83, 0\n v_mov_b32 v96, 0x7f7f7f7f\n"
-                 M0 M1 M2 M3 "s_nop 15\n" ::"v"(seed) : CLOB);
+    // fillers' inputs, scale 2^0 on both sides
+    asm volatile("v_mov_b32 v108, %0\n v_mov_b32 v109, %0\n v_mov_b32 v110, %0\n v_mov_b32 v111, %0\n v_mov_b32 v100, 0\n v_mov_b32 v101, 0\n"
+                 "v_mov_b32 v102, 0\n v_mov_b32 v103, 0\n v_mov_b32 v104, 0\n v_mov_b32 v105, 0\n v_mov_b32 v106, 0\n v_mov_b32 v107, 0\n"
+                 "v_mov_b32 v96, 0x7f7f7f7f\n" ::"v"(seed) : CLOB);
+    // the 16x16 forms: thresholds as in the kernel (2 x - 258 for some x) where the 32x32 forms keep A operands
+    if (FORM < 2)
+        asm volatile("v_mov_b32 v34, 0xc2a00000\n v_mov_b32 v35, v34\n v_mov_b32 v36, v34\n v_mov_b32 v37, v34\n v_mov_b32 v38, v34\n v_mov_b32 v39, v34\n"
+                     "v_mov_b32 v40, v34\n v_mov_b32 v41, v34\n v_mov_b32 v42, v34\n v_mov_b32 v43, v34\n v_mov_b32 v44, v34\n v_mov_b32 v45, v34\n"
+                     "v_mov_b32 v46, v34\n v_mov_b32 v47, v34\n v_mov_b32 v48, v34\n v_mov_b32 v49, v34\n" A0 A1 A2 A3 "s_nop 15\n" ::: CLOB);
+    else
+        asm volatile(C0 C1 "s_nop 15\n s_nop 15\n" ::: CLOB);
     unsigned hwid, xcc, count = 0;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n s_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hwid), "=s"(xcc));
     const bool filler_wave = PLACE == 2 && (hwid & 1);             // HW_ID[3:0] = wave slot of the SIMD
@@ -78,21 +150,15 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, stamp* st, int iters) {
     asm volatile("s_memtime %0\n s_memrealtime %1\n s_waitcnt lgkmcnt(0)" : "=s"(c0), "=s"(r0)::"memory");
     if (!filler_wave) {
         for (int it = 0; it < iters; it += 4) {
-            if (PLACE == 1) {
-                if (K == 0) asm volatile(X4(BUNCH(F0)) ::: CLOB);
-                if (K == 1) asm volatile(X4(BUNCH(F1)) ::: CLOB);
-                if (K == 2) asm volatile(X4(BUNCH(F2)) ::: CLOB);
-                if (K == 3) asm volatile(X4(BUNCH(F3)) ::: CLOB);
-                if (K == 4) asm volatile(X4(BUNCH(F4)) ::: CLOB);
-            } else if (PLACE == 0) {
-                if (K == 0) asm volatile(X4(INTER(F0)) ::: CLOB);
-                if (K == 1) asm volatile(X4(INTER(F1)) ::: CLOB);
-                if (K == 2) asm volatile(X4(INTER(F2)) ::: CLOB);
-                if (K == 3) asm volatile(X4(INTER(F3)) ::: CLOB);
-                if (K == 4) asm volatile(X4(INTER(F4)) ::: CLOB);
-            } else {
-                asm volatile(X4(INTER(F0)) ::: CLOB);
-            }
+            if (PLACE == 2) asm volatile(X4(INTER_A(F0)) ::: CLOB);
+            else if (FORM == 0 && PLACE == 0) PICK(INTER_A)
+            else if (FORM == 0 && PLACE == 1) PICK(BUNCH_A)
+            else if (FORM == 1 && PLACE == 0) PICK(INTER_B)
+            else if (FORM == 1 && PLACE == 1) PICK(BUNCH_B)
+            else if (FORM == 2 && PLACE == 0) PICK(INTER_C)
+            else if (FORM == 2 && PLACE == 1) PICK(BUNCH_C)
+            else if (FORM == 3 && PLACE == 0) PICK(INTER_D)
+            else if (FORM == 3 && PLACE == 1) PICK(BUNCH_D)
         }
     } else {
         // bursts of 8 K fillers for FILL_CYCLES of the shader clock (looked at once per four bursts); count = bursts issued
@@ -110,8 +176,9 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, stamp* st, int iters) {
     }
     asm volatile("s_memtime %0\n s_memrealtime %1\n s_waitcnt lgkmcnt(0)" : "=s"(c1), "=s"(r1)::"memory");
     uint32_t s;
-    asm volatile("s_nop 15\n s_nop 15\n v_add_u32 %0, v62, v66\n v_add_u32 %0, %0, v70\n v_add_u32 %0, %0, v74\n v_add_u32 %0, %0, v80\n v_add_u32 %0, %0, v81\n"
-                 "v_add_u32 %0, %0, v82\n v_add_u32 %0, %0, v83" : "=v"(s)::CLOB);
+    asm volatile("s_nop 15\n s_nop 15\n v_add_u32 %0, v62, v66\n v_add_u32 %0, %0, v70\n v_add_u32 %0, %0, v74\n v_add_u32 %0, %0, v100\n v_add_u32 %0, %0, v101\n"
+                 "v_add_u32 %0, %0, v102\n v_add_u32 %0, %0, v103\n v_add_u32 %0, %0, v104\n v_add_u32 %0, %0, v105\n v_add_u32 %0, %0, v106\n"
+                 "v_add_u32 %0, %0, v107" : "=v"(s)::CLOB);
     out[blockIdx.x * 256 + threadIdx.x] = s;
     if ((threadIdx.x & 63) == 0) {
         stamp v = {c0, r0, c1, r1, filler_wave ? 1u : 0u, hwid, xcc, count};
@@ -122,19 +189,22 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, stamp* st, int iters) {
 static double median(std::vector<double>& v) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[v.size() / 2]; }
 
 static const int MAXW = 4, NCU = 256;
+static const char* const FORM_NAME[] = {"16x16x128 scaled", "16x16x128 plain ", "32x32x64 scaled ", "32x32x64 plain  "};
 
-template <int PLACE, int K> int run(int waves, uint32_t* out, stamp* d_st, double spin_s) {
+// one row; *cyc = the SIMD's cycles per MFMA (median over SIMDs)
+template <int FORM, int PLACE, int K> int run(int waves, uint32_t* out, stamp* d_st, double spin_s, double* cyc) {
     const int iters = 20000, blocks = NCU * waves;
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     CK(hipEventRecord(e0));
     float spun = 0;
     while (spun < spin_s * 1e3f) {                      // spin-up: back-to-back launches of the same body
-        for (int i = 0; i < 8; i++) k<PLACE, K><<<blocks, 256>>>(out, d_st, iters);
+        for (int i = 0; i < 8; i++) k<FORM, PLACE, K><<<blocks, 256>>>(out, d_st, iters);
         CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
         CK(hipEventElapsedTime(&spun, e0, e1));
     }
-    k<PLACE, K><<<blocks, 256>>>(out, d_st, iters);
+    k<FORM, PLACE, K><<<blocks, 256>>>(out, d_st, iters);
     CK(hipDeviceSynchronize());
+    CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1));
     std::vector<stamp> st(blocks * 4);
     CK(hipMemcpy(st.data(), d_st, st.size() * sizeof(stamp), hipMemcpyDeviceToHost));
     // group the waves by the SIMD they ran on: XCC, then HW_ID's SE / SH / CU (bits 15:8) and SIMD (bits 5:4)
@@ -171,9 +241,10 @@ template <int PLACE, int K> int run(int waves, uint32_t* out, stamp* d_st, doubl
     const double mclk = median(clk);
     const char* place[] = {"interleaved", "bunched", "cross-wave"};
     std::sort(grp.begin(), grp.end());
-    printf("%-11s k %d  blocks/CU %d: %4zu of %4zu SIMDs held %d waves, all running for %3.0f %% of the span | %6.2f cycles/MFMA/SIMD | an MFMA wave's own "
-           "group: p10 %6.1f median %6.1f p90 %6.1f cycles",
-           place[PLACE], K, waves, used, simd.size(), waves, 100 * median(together), median(per_mfma), grp[grp.size() / 10], median(grp),
+    *cyc = median(per_mfma);
+    printf("%s %-11s k %d  blocks/CU %d: %4zu of %4zu SIMDs held %d waves, all running for %3.0f %% of the span | %6.2f cycles/MFMA/SIMD | an MFMA "
+           "wave's own group: p10 %6.1f median %6.1f p90 %6.1f cycles",
+           FORM_NAME[FORM], place[PLACE], K, waves, used, simd.size(), waves, 100 * median(together), *cyc, grp[grp.size() / 10], median(grp),
            grp[grp.size() * 9 / 10]);
     if (PLACE == 2 && K) printf(" | fillers issued beside the MFMAs: %5.2f per MFMA time", median(fill_per_mfma));
     printf(" | clock %4.0f MHz\n", mclk);
@@ -181,22 +252,59 @@ template <int PLACE, int K> int run(int waves, uint32_t* out, stamp* d_st, doubl
     return 0;
 }
 
-template <int PLACE> int sweep(int waves, uint32_t* out, stamp* d_st, double spin_s) {
-    if (run<PLACE, 0>(waves, out, d_st, spin_s)) return 1;
-    if (run<PLACE, 1>(waves, out, d_st, spin_s)) return 1;
-    if (run<PLACE, 2>(waves, out, d_st, spin_s)) return 1;
-    if (run<PLACE, 3>(waves, out, d_st, spin_s)) return 1;
-    return run<PLACE, 4>(waves, out, d_st, spin_s);
+// the fit of max(T, H + 4 k) to the rows k = 0 .. 8 of one form and placement, and the issue floor of a group-equivalent
+static void fit(int form, int place, int waves, const double* c) {
+    double h = 0;
+    int n = 0;
+    for (int kk = 1; kk <= 8; kk++)
+        if (c[kk] >= c[0] + 1.0) { h += c[kk] - 4.0 * kk; n++; }
+    const int per_group = form < 2 ? 8 : 4;
+    if (n) {
+        h /= n;
+        printf("  fit %s %-11s blocks/CU %d: T %6.2f  H %6.2f (mean of cycles - 4 k over %d rows above T + 1) | group-equivalent of %d MFMAs + "
+               "25.8 plain: max(%5.1f, %5.1f) = %5.1f cycles\n",
+               FORM_NAME[form], place ? "bunched" : "interleaved", waves, c[0], h, n, per_group, per_group * c[0], per_group * h + 4 * 25.8,
+               std::max(per_group * c[0], per_group * h + 4 * 25.8));
+    } else {
+        printf("  fit %s %-11s blocks/CU %d: T %6.2f  no row above T + 1: H <= %6.2f | group-equivalent of %d MFMAs: %5.1f cycles\n",
+               FORM_NAME[form], place ? "bunched" : "interleaved", waves, c[0], c[0] - 32.0, per_group, per_group * c[0]);
+    }
+    fflush(stdout);
+}
+
+// k = 0 .. 8 of one form and placement and their fit; the cross-wave rows stop at k = 4 and have none
+template <int FORM, int PLACE> int sweep(int waves, uint32_t* out, stamp* d_st, double spin_s) {
+    double c[9] = {};
+    if (run<FORM, PLACE, 0>(waves, out, d_st, spin_s, c + 0)) return 1;
+    if (run<FORM, PLACE, 1>(waves, out, d_st, spin_s, c + 1)) return 1;
+    if (run<FORM, PLACE, 2>(waves, out, d_st, spin_s, c + 2)) return 1;
+    if (run<FORM, PLACE, 3>(waves, out, d_st, spin_s, c + 3)) return 1;
+    if (run<FORM, PLACE, 4>(waves, out, d_st, spin_s, c + 4)) return 1;
+    if constexpr (PLACE < 2) {
+        if (run<FORM, PLACE, 5>(waves, out, d_st, spin_s, c + 5)) return 1;
+        if (run<FORM, PLACE, 6>(waves, out, d_st, spin_s, c + 6)) return 1;
+        if (run<FORM, PLACE, 7>(waves, out, d_st, spin_s, c + 7)) return 1;
+        if (run<FORM, PLACE, 8>(waves, out, d_st, spin_s, c + 8)) return 1;
+        fit(FORM, PLACE, waves, c);
+    }
+    return 0;
+}
+
+template <int FORM> int form(uint32_t* out, stamp* d_st, double spin_s) {
+    for (int w : {2, 3, 4}) {
+        if (sweep<FORM, 0>(w, out, d_st, spin_s)) return 1;
+        if (sweep<FORM, 1>(w, out, d_st, spin_s)) return 1;
+    }
+    return 0;
 }
 
 int main(int argc, char** argv) {
     const double spin_s = argc > 1 ? atof(argv[1]) : 0.5;
     uint32_t* out; CK(hipMalloc(&out, (size_t)NCU * MAXW * 256 * 4));
     stamp* d_st; CK(hipMalloc(&d_st, (size_t)NCU * MAXW * 4 * sizeof(stamp)));
-    for (int w : {1, 2, 4}) {
-        if (sweep<0>(w, out, d_st, spin_s)) return 1;
-        if (sweep<1>(w, out, d_st, spin_s)) return 1;
-        if (w > 1 && sweep<2>(w, out, d_st, spin_s)) return 1;
-    }
+    if (form<0>(out, d_st, spin_s) || form<1>(out, d_st, spin_s) || form<2>(out, d_st, spin_s) || form<3>(out, d_st, spin_s)) return 1;
+    // the shipped form alone on its SIMD, and beside waves that issue only fillers
+    if (sweep<0, 0>(1, out, d_st, spin_s) || sweep<0, 1>(1, out, d_st, spin_s)) return 1;
+    if (sweep<0, 2>(2, out, d_st, spin_s) || sweep<0, 2>(4, out, d_st, spin_s)) return 1;
     return 0;
 }
