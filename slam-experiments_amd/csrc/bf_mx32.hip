@@ -35,13 +35,19 @@
 //         TESTED against c0: a tie against a key from a later row can win), and the same with the first row of the stage to come
 //         at the early exchanges (SLAM_MX_EARLY).  bound[] holds 2nd-best keys below SLAM_MX_BOUND_LIMIT, as in bf_mx.hip.
 //     A candidate is dropped only if some known 2nd-best key K has dist(K) < dist, or dist(K) == dist and row(K) < row.
-//   * row gates: a fired tile keys and merges, of a lane's 16 rows, only those at which SOME lane of the tile passes (one
-//     compare and one wave-uniform branch per row).  A skipped row is below the threshold of every lane of the tile.
-//   * scan loop: a whole stage is one trip of four groups; the A operand of K-quarter q of group g + 1 is read into the
-//     registers that the two MFMAs of quarter q of group g have just freed, so the LDS latency runs behind six MFMAs.  A stage
-//     that another follows expands and stores the thread's four source words of the next stage (ONE 16-byte load at the trip's
-//     start) in groups 1 to 3, between MFMAs.  The last stage of the train set, if short, runs group by group with the test
-//     for rows past the chunk.
+//   * row gates: a fired tile keys and merges, of a lane's 16 rows, only those at which SOME lane of the tile passes.  The 16
+//     compares are issued back to back into 16 SGPR pairs, the 16 wave-uniform branches test those on the scalar side: no
+//     branch waits on the compare in front of it.  A skipped row is below the threshold of every lane of the tile.
+//   * scan loop: a whole stage is one trip of four groups in which a tile's four MFMAs run together and the folds stand between
+//     the runs: t0k0 .. t0k3 [fold of tile 1, previous group] t1k0 .. t1k3 [fold of tile 0].  A tile's fold, and its update path
+//     where it fires, stands behind four MFMAs of the OTHER tile and behind the other tile's fold, so the wave keeps the matrix
+//     pipe fed while it folds and the compiler owes no wait states in front of a fold (a vector read of an MFMA result is not
+//     interlocked: 11 states after the MFMA).  Each tile sees its own MFMAs, fold and update in the order they always had;
+//     the tiles share only the wave-uniform `fired`.  The A operand of K-quarter q of group g + 1 is read once tile 1's MFMA of
+//     quarter q of group g has issued, into the registers it frees, three MFMAs ahead of its use.  A stage that another follows
+//     expands and stores the thread's four source words of the next stage (ONE 16-byte load at the trip's start) in groups 1 to
+//     3, between MFMAs.  The last stage of the train set, if short, runs group by group, both folds behind the eight MFMAs, with
+//     the test for rows past the chunk.
 //   * plan, tickets, bound exchange, epilogue: those of bf_top2_mx_kernel; bf_mx.hip plans and launches both kernels.
 #include "internal.h"
 #include <type_traits>
@@ -174,41 +180,42 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             if (!more && tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const uint4* tp = tile[buf];
             u32 fired = 0;                                       // wave-uniform: the tiles that took the update path in this stage
-            // fold the 2 x 16 results of group g and, where some lane passes, take the update path
-            auto fold = [&](int g, const mx_v16f (&acc)[2], auto rag) {
-                int m[2];
+            // fold the 16 results of tile tt of group g and, where some lane of the tile passes, take the update path.  A tile's
+            // fold and update path touch that tile's accumulators and state only (and the wave-uniform `fired`), so where the
+            // folds of the two tiles stand relative to each other and to the other tile's MFMAs does not matter to the result
+            auto fold_tile = [&](int tt, int g, const mx_v16f& acc, auto rag) {
+                int p = max(max(__float_as_int(acc[0]), __float_as_int(acc[1])), __float_as_int(acc[2]));
 #pragma unroll
-                for (int tt = 0; tt < 2; tt++) {
-                    int p = max(max(__float_as_int(acc[tt][0]), __float_as_int(acc[tt][1])), __float_as_int(acc[tt][2]));
+                for (int i = 3; i < 15; i += 2) p = max(max(p, __float_as_int(acc[i])), __float_as_int(acc[i + 1]));
+                const int m = max(p, __float_as_int(acc[15]));
+                if (__builtin_expect(__ballot(m >= thr[tt]) == 0ull, 1)) return;
+                fired |= 1u << tt;
+                // the group's first row is taken from the scalar side here: as a per-lane value it would be carried through
+                // every group that does not fire.  g is the group that is FOLDED, whichever group's MFMAs stand around the fold
+                int row0 = s0 + g * MX32_GROUP;
+                asm("" : "+s"(row0));
+                const u32 rowk = (u32)row0 + (u32)(4 * hk);
+                // key = (128 - D / 2) << 23 | row: base + (-D << 22), exact modulo 2^32 (D is an even integer)
+                const u32 base = (128u << SLAM_KEY_IDX_BITS) + rowk;
+                // the 16 row gates: the compares back to back, each into an SGPR pair of its own (the threshold moves only
+                // behind the rows), then scalar tests alone, so that no branch waits on the compare in front of it
+                unsigned long long gate[16];
 #pragma unroll
-                    for (int i = 3; i < 15; i += 2) p = max(max(p, __float_as_int(acc[tt][i])), __float_as_int(acc[tt][i + 1]));
-                    m[tt] = max(p, __float_as_int(acc[tt][15]));
+                for (int i = 0; i < 16; i++) gate[i] = __ballot(__float_as_int(acc[i]) >= thr[tt]);
+                asm volatile("" ::"s"(gate[0]), "s"(gate[1]), "s"(gate[2]), "s"(gate[3]), "s"(gate[4]), "s"(gate[5]), "s"(gate[6]),
+                             "s"(gate[7]), "s"(gate[8]), "s"(gate[9]), "s"(gate[10]), "s"(gate[11]), "s"(gate[12]), "s"(gate[13]),
+                             "s"(gate[14]), "s"(gate[15]));
+#pragma unroll
+                for (int i = 0; i < 16; i++) {
+                    if (gate[i] == 0ull) continue;
+                    const int off = 8 * (i >> 2) + (i & 3);
+                    u32 key = base + (u32)off + ((u32)(int)(-acc[i]) << (SLAM_KEY_IDX_BITS - 1));
+                    if constexpr (decltype(rag)::value)   // the rows past the end of a short stage never enter
+                        key = (int)rowk + off < c1 ? key : SLAM_KEY_NONE;
+                    b2[tt] = umed3(b1[tt], b2[tt], key);
+                    b1[tt] = min(b1[tt], key);
                 }
-                if (__builtin_expect(__ballot(m[0] >= thr[0] || m[1] >= thr[1]) != 0ull, 0)) {
-                    // the group's first row is taken from the scalar side here: as a per-lane value it would be carried through
-                    // every group that does not fire
-                    int row0 = s0 + g * MX32_GROUP;
-                    asm("" : "+s"(row0));
-                    const u32 rowk = (u32)row0 + (u32)(4 * hk);
-#pragma unroll
-                    for (int tt = 0; tt < 2; tt++) {
-                        if (__ballot(m[tt] >= thr[tt]) == 0ull) continue;
-                        fired |= 1u << tt;
-                        // key = (128 - D / 2) << 23 | row: base + (-D << 22), exact modulo 2^32 (D is an even integer)
-                        const u32 base = (128u << SLAM_KEY_IDX_BITS) + rowk;
-#pragma unroll
-                        for (int i = 0; i < 16; i++) {
-                            if (__ballot(__float_as_int(acc[tt][i]) >= thr[tt]) == 0ull) continue;
-                            const int off = 8 * (i >> 2) + (i & 3);
-                            u32 key = base + (u32)off + ((u32)(int)(-acc[tt][i]) << (SLAM_KEY_IDX_BITS - 1));
-                            if constexpr (decltype(rag)::value)   // the rows past the end of a short stage never enter
-                                key = (int)rowk + off < c1 ? key : SLAM_KEY_NONE;
-                            b2[tt] = umed3(b1[tt], b2[tt], key);
-                            b1[tt] = min(b1[tt], key);
-                        }
-                        set_threshold(tt, min(xs[tt], b2[tt] >> SLAM_KEY_IDX_BITS));
-                    }
-                }
+                set_threshold(tt, min(xs[tt], b2[tt] >> SLAM_KEY_IDX_BITS));
             };
             const mx_v16f zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             auto group = [&](int g, auto rag) {
@@ -219,10 +226,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
                     for (int tt = 0; tt < 2; tt++) acc[tt] = mx32_dot(a, qb[tt][kq], kq ? acc[tt] : zero);
                 }
-                fold(g, acc, rag);
+#pragma unroll
+                for (int tt = 0; tt < 2; tt++) fold_tile(tt, g, acc[tt], rag);
             };
-            // A whole stage: one trip of four groups.  The A operand of K-quarter kq of group k + 1 is read once the two MFMAs of
-            // quarter kq of group k have issued, into the registers they free; the last group reads nothing ahead, so no read
+            // A whole stage: one trip of four groups.  Group k issues, in this order,
+            //     t0k0 t0k1 t0k2 t0k3 [fold of tile 1, group k - 1] t1k0 t1k1 t1k2 t1k3 [fold of tile 0, group k]
+            // (t<tile>k<K-quarter>), so a fold - and the update path where the tile fires - runs while the last of four MFMAs of
+            // the OTHER tile is in the pipe, and between the last MFMA that wrote its accumulators and its first read stand those
+            // four and the other fold: more than the 11 wait states the compiler owes there, so it pads nothing (measured against
+            // the alternating orders in tools/ubench/mx_issue.hip).  Each tile still sees its own MFMAs, fold and
+            // update path in the same order, before its next C = 0 MFMA; tile 1 of the last group folds bare, behind tile 0's
+            // fold, so the stage end sees both tiles folded.
+            // The A operand of K-quarter kq of group k + 1 is read once tile 1's MFMA of quarter kq of group k has issued, into the
+            // registers it frees (three MFMAs before its first use); the last group reads nothing ahead, so no read
             // leaves the stage's own buffer.  With `shadow`, groups 1 to 3 also expand and store the thread's four source words
             // of the NEXT stage (into buffer buf ^ 1, free since the barrier that opened this stage) between their MFMAs.
             auto trip = [&](auto shadow) {
@@ -240,24 +256,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 uint4 a[4];
 #pragma unroll
                 for (int kq = 0; kq < 4; kq++) a[kq] = ap[kq * 64];
+                mx_v16f acc[2];
+                auto dot = [&](int tt, int kq) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    acc[tt] = mx32_dot(a[kq], qb[tt][kq], kq ? acc[tt] : zero);
+                    __builtin_amdgcn_sched_barrier(0);
+                };
 #pragma unroll
                 for (int k = 0; k < MX32_GROUPS; k++) {
-                    mx_v16f acc[2];
-#pragma unroll
-                    for (int kq = 0; kq < 4; kq++) {
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int tt = 0; tt < 2; tt++) acc[tt] = mx32_dot(a[kq], qb[tt][kq], kq ? acc[tt] : zero);
-                        __builtin_amdgcn_sched_barrier(0);
+                    auto ahead = [&](int kq) {                   // both MFMAs of quarter kq of this group have issued (tile 1's last)
                         if (k + 1 < MX32_GROUPS) a[kq] = ap[(k + 1) * 256 + kq * 64];
-                        // the next stage's words: word 0 in group 1, word 1 in group 2, words 2 and 3 in group 3
-                        if (SH && k >= 1 && kq == 1) store_word(dst, k - 1, nx[k - 1]);
-                        if (SH && k == 3 && kq == 2) store_word(dst, 3, nx[3]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    fold(k, acc, std::false_type{});
-                    __builtin_amdgcn_sched_barrier(0);
+                        __builtin_amdgcn_sched_barrier(0);
+                    };
+                    dot(0, 0);
+                    dot(0, 1);
+                    dot(0, 2);
+                    dot(0, 3);
+                    if (k) fold_tile(1, k - 1, acc[1], std::false_type{});
+                    dot(1, 0);
+                    ahead(0);
+                    dot(1, 1);
+                    ahead(1);
+                    // the next stage's words: word 0 in group 1, word 1 in group 2, words 2 and 3 in group 3
+                    if (SH && k >= 1) store_word(dst, k - 1, nx[k - 1]);
+                    dot(1, 2);
+                    ahead(2);
+                    if (SH && k == 3) store_word(dst, 3, nx[3]);
+                    dot(1, 3);
+                    ahead(3);
+                    fold_tile(0, k, acc[0], std::false_type{});
                 }
+                __builtin_amdgcn_sched_barrier(0);
+                fold_tile(1, MX32_GROUPS - 1, acc[1], std::false_type{});
             };
             if (more) {                                          // then this stage is whole
                 trip(std::true_type{});

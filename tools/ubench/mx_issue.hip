@@ -23,11 +23,22 @@
 // 25.8 plain instructions is max(n T, n H + 4 x 25.8) with n = 8 or 4 MFMAs.
 // It answers: how long an FP4 MFMA of either shape and spelling holds the vector issue, how many plain instructions per MFMA
 // are free in-wave and cross-wave, and what the issue floor of the shipped mix is in each form.
+// `mx_issue group [spin seconds]` runs instead the REAL group body of the 32x32x64 kernel (bf_mx32.hip) - the eight unscaled
+// MFMAs on two accumulator sets, the two eight-instruction integer folds and one compare per tile, with the wait states the
+// compiler puts between an MFMA and the first vector read of its result (11 after an 8-pass MFMA, every instruction between
+// counting as one) - in four orders, at 1, 2, 3 and 4 waves per SIMD, and prints cycles per group and the share of the
+// matrix pipe that is fed (8 x 32 cycles per group and wave):
+//   (a) bunched:    t0k0 t1k0 t0k1 t1k1 t0k2 t1k2 t0k3 t1k3 | both folds                      (the order before the pipelined trip)
+//   (b) pipelined:  t0k0 t0k1 [fold t1 of g - 1] t1k0 t1k1 t0k2 t1k2 t0k3 t1k3 [fold t0 of g]
+//   (c) tile-major: t0k0 t0k1 [fold t1 of g - 1] t0k2 t0k3 t1k0 t1k1 [fold t0 of g] t1k2 t1k3 (four dependent MFMAs back to back)
+//   (d) tile runs:  t0k0 t0k1 t0k2 t0k3 [fold t1 of g - 1] t1k0 t1k1 t1k2 t1k3 [fold t0 of g]  (each fold behind four MFMAs of the
+//                   other tile and the other fold: the compiler owes no wait states; the order the kernel takes)
 // build: hipcc --offload-arch=gfx950 -O3 mx_issue.hip -o mx_issue
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 #include <map>
 #include <vector>
@@ -90,6 +101,17 @@
 #define D5 WU("66:81", "42:45", "26:29", "v[66:81]")
 #define D6 WU("50:65", "46:49", "14:17", "v[50:65]")
 #define D7 WU("66:81", "46:49", "30:33", "v[66:81]")
+// the real group body: folds of tile 0 (v[50:65] -> v100, compare into s[20:21]) and tile 1 (v[66:81] -> v101, s[22:23])
+#define FD0 "v_max_i32 v100, v50, v51\n v_max3_i32 v100, v100, v52, v53\n v_max3_i32 v100, v100, v54, v55\n v_max3_i32 v100, v100, v56, v57\n" \
+            "v_max3_i32 v100, v100, v58, v59\n v_max3_i32 v100, v100, v60, v61\n v_max3_i32 v100, v100, v62, v63\n v_max3_i32 v100, v100, v64, v65\n" \
+            "v_cmp_ge_i32_e64 s[20:21], v100, v108\n"
+#define FD1 "v_max_i32 v101, v66, v67\n v_max3_i32 v101, v101, v68, v69\n v_max3_i32 v101, v101, v70, v71\n v_max3_i32 v101, v101, v72, v73\n" \
+            "v_max3_i32 v101, v101, v74, v75\n v_max3_i32 v101, v101, v76, v77\n v_max3_i32 v101, v101, v78, v79\n v_max3_i32 v101, v101, v80, v81\n" \
+            "v_cmp_ge_i32_e64 s[22:23], v101, v109\n"
+#define GROUP_A D0 D1 D2 D3 D4 D5 D6 D7 "s_nop 10\n" FD0 FD1
+#define GROUP_B D0 D2 FD1 D1 D3 D4 D5 D6 D7 "s_nop 9\n" FD0
+#define GROUP_C D0 D2 "s_nop 8\n" FD1 D4 D6 D1 D3 "s_nop 8\n" FD0 D5 D7
+#define GROUP_D D0 D2 D4 D6 FD1 D1 D3 D5 D7 FD0
 #define INTER_(P, F) P##0 F P##1 F P##2 F P##3 F P##4 F P##5 F P##6 F P##7 F
 #define BUNCH_(P, F) P##0 P##1 P##2 P##3 P##4 P##5 P##6 P##7 F F F F F F F F
 #define INTER_A(F) INTER_(A, F)
@@ -100,13 +122,15 @@
 #define BUNCH_B(F) BUNCH_(B, F)
 #define BUNCH_C(F) BUNCH_(C, F)
 #define BUNCH_D(F) BUNCH_(D, F)
+#define CLOBS CLOB, "s20", "s21", "s22", "s23"
 #define NOP16 "s_nop 15\n"
 #define X4(a) a a a a
 #define FILL_CYCLES 1500000ull
 
 struct stamp { unsigned long long c0, r0, c1, r1; unsigned role, hwid, xcc, count; };
 
-// FORM 0 16x16x128 scaled (shipped) | 1 16x16x128 unscaled | 2 32x32x64 scaled | 3 32x32x64 unscaled;
+// FORM 0 16x16x128 scaled (shipped) | 1 16x16x128 unscaled | 2 32x32x64 scaled | 3 32x32x64 unscaled | 4, 5, 6, 7 the real group
+// body of the 32x32x64 kernel in the orders (a), (b), (c), (d) (PLACE 0, K 0);
 // PLACE 0 interleaved | 1 bunched | 2 cross-wave; K fillers per MFMA
 #define PICK(BODY)                                            \
     {                                                         \
@@ -159,6 +183,10 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, stamp* st, int iters) {
             else if (FORM == 2 && PLACE == 1) PICK(BUNCH_C)
             else if (FORM == 3 && PLACE == 0) PICK(INTER_D)
             else if (FORM == 3 && PLACE == 1) PICK(BUNCH_D)
+            else if (FORM == 4) asm volatile(X4(GROUP_A) ::: CLOBS);
+            else if (FORM == 5) asm volatile(X4(GROUP_B) ::: CLOBS);
+            else if (FORM == 6) asm volatile(X4(GROUP_C) ::: CLOBS);
+            else if (FORM == 7) asm volatile(X4(GROUP_D) ::: CLOBS);
         }
     } else {
         // bursts of 8 K fillers for FILL_CYCLES of the shader clock (looked at once per four bursts); count = bursts issued
@@ -189,7 +217,8 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, stamp* st, int iters) {
 static double median(std::vector<double>& v) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[v.size() / 2]; }
 
 static const int MAXW = 4, NCU = 256;
-static const char* const FORM_NAME[] = {"16x16x128 scaled", "16x16x128 plain ", "32x32x64 scaled ", "32x32x64 plain  "};
+static const char* const FORM_NAME[] = {"16x16x128 scaled", "16x16x128 plain ", "32x32x64 scaled ", "32x32x64 plain  ",
+                                        "group (a) bunched", "group (b) pipelined", "group (c) tile-major", "group (d) tile runs"};
 
 // one row; *cyc = the SIMD's cycles per MFMA (median over SIMDs)
 template <int FORM, int PLACE, int K> int run(int waves, uint32_t* out, stamp* d_st, double spin_s, double* cyc) {
@@ -298,10 +327,24 @@ template <int FORM> int form(uint32_t* out, stamp* d_st, double spin_s) {
     return 0;
 }
 
+// the real group body in one order at 1 .. 4 waves per SIMD: cycles per group and SIMD, and the share of the pipe that is fed
+template <int FORM> int group_rows(uint32_t* out, stamp* d_st, double spin_s) {
+    for (int w : {1, 2, 3, 4}) {
+        double c = 0;
+        if (run<FORM, 0, 0>(w, out, d_st, spin_s, &c)) return 1;
+        printf("  %s, %d waves per SIMD: %6.1f cycles per group and SIMD, pipe fed %5.1f %%\n", FORM_NAME[FORM], w, 8 * c, 100.0 * 32.0 / c);
+        fflush(stdout);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
-    const double spin_s = argc > 1 ? atof(argv[1]) : 0.5;
+    const bool group = argc > 1 && !strcmp(argv[1], "group");
+    const double spin_s = argc > 1 + group ? atof(argv[1 + group]) : 0.5;
     uint32_t* out; CK(hipMalloc(&out, (size_t)NCU * MAXW * 256 * 4));
     stamp* d_st; CK(hipMalloc(&d_st, (size_t)NCU * MAXW * 4 * sizeof(stamp)));
+    if (group) return group_rows<4>(out, d_st, spin_s) || group_rows<5>(out, d_st, spin_s) || group_rows<6>(out, d_st, spin_s) ||
+                      group_rows<7>(out, d_st, spin_s);
     if (form<0>(out, d_st, spin_s) || form<1>(out, d_st, spin_s) || form<2>(out, d_st, spin_s) || form<3>(out, d_st, spin_s)) return 1;
     // the shipped form alone on its SIMD, and beside waves that issue only fillers
     if (sweep<0, 0>(1, out, d_st, spin_s) || sweep<0, 1>(1, out, d_st, spin_s)) return 1;
