@@ -1064,6 +1064,68 @@ SLAM_API int slam_bas_candidate_f64(slam_ctx* ctx, int64_t K, int64_t L, const u
                                     const double* d_bl, double lambda, double* d_poses_out, double* d_points_out, double* d_part,
                                     double* d_denominator);
 
+/* ---- bag-of-words place recognition (bow.hip) --------------------------------------------------------------
+ * DBoW2's vocabulary tree, BoW vectors and inverted-file database for 256-bit descriptors, as ORB-SLAM's KeyFrameDatabase
+ * uses them; no call site in the reference (it detects no loops).  PARITY UNPINNED: no DBoW2 exists here.  The tree is flat:
+ * d_node_desc u8 [n_nodes,32], d_child int32 [n_nodes,2] = (first child, child count; 0 = leaf, children contiguous),
+ * d_word_of_node int32 [n_nodes] (-1 for inner nodes), node 0 the root.  All buffers are the caller's; nothing is kept
+ * between launches, and no call takes the context's call lock. */
+/* h_limits [7] = {largest k, largest depth, descriptors per image, results per query, database entries per LDS pass of the
+ * query, node rows the transform stages in LDS, descriptors up to which lanes = 0 means sixteen lanes}; needs no GPU */
+SLAM_API int slam_bow_limits(int32_t* h_limits);
+/* TemplatedVocabulary::transform(feature, word id, node id, levelsup) for n descriptors u8 [n,32]: at every inner node to
+ * the child at the smallest Hamming distance (lowest child on ties), d_words [n] the leaf's word, d_nodes [n] the node of
+ * the path at depth min(leaf depth, max(0, depth - levels_up)).  lanes: 1 = one lane per descriptor (the tree's first 1152
+ * rows staged in LDS), 16 = sixteen lanes per descriptor (one child per lane), 0 = chosen by n; the same results either way */
+SLAM_API int slam_bow_transform(slam_ctx* ctx, const void* d_desc, int64_t n, const void* d_node_desc, const int32_t* d_child,
+                                const int32_t* d_word_of_node, int64_t n_nodes, int depth, int levels_up, int lanes,
+                                int32_t* d_words, int32_t* d_nodes);
+/* TemplatedVocabulary::transform(features, BowVector) under TF_IDF + L1_NORM for B images: image b owns the word ids
+ * d_words_in[d_offsets[b] .. d_offsets[b+1]) (at most 8192).  Output rows compressed: d_out_offsets int64 [B+1], and per kept
+ * word (ascending id) its id, value f64 and q = floor(value * 2^31); the three output arrays hold n slots (the worst case).
+ * d_ws: slam_bow_vectors_workspace(B, n) bytes. */
+SLAM_API int slam_bow_vectors(slam_ctx* ctx, const int32_t* d_words_in, const int64_t* d_offsets, int64_t B, int64_t n,
+                              const double* d_idf, int64_t n_words, void* d_ws, uint64_t ws_bytes, int64_t* d_out_offsets,
+                              int32_t* d_out_words, double* d_out_values, uint32_t* d_out_q);
+SLAM_API int slam_bow_vectors_workspace(int64_t B, int64_t n, uint64_t* h_bytes);
+/* counting sort: d_perm lists the items i with 0 <= d_keys[i] < n_keys grouped by key, d_key_off int32 [n_keys+1] where each
+ * group starts (the order inside a group is unspecified); d_cursor int32 [n_keys] is scratch */
+SLAM_API int slam_bow_group_keys(slam_ctx* ctx, const int32_t* d_keys, int64_t n, int64_t n_keys, int32_t* d_key_off,
+                                 int32_t* d_cursor, int32_t* d_perm);
+/* the inverted file of TemplatedDatabase (m_ifile) from the forward store: T (word, entry id, q) triples -> d_word_off int32
+ * [n_words+1] and d_postings [T] of (entry id, q) u32 pairs grouped by word; d_cursor [n_words] and d_perm [T] are scratch */
+SLAM_API int slam_bow_index_build(slam_ctx* ctx, const int32_t* d_words, const int32_t* d_entry, const uint32_t* d_q, int64_t T,
+                                  int64_t n_words, int32_t* d_word_off, int32_t* d_cursor, int32_t* d_perm, void* d_postings);
+/* TemplatedDatabase::queryL1 in fixed point for Q vectors (rows as slam_bow_vectors writes them): s_int = sum over the shared
+ * words of min(q, p), common = their number.  Top form (d_dense_s null): per query the entries with id < max_id that share a
+ * word, by (s_int descending, id ascending), the first max_results (<= 64) into d_ids / d_s_int / d_common [Q,max_results],
+ * fillers (-1, 0, 0).  Dense form (both d_dense_* given): s_int and common of every entry, [Q,E]; max_id, max_results and the
+ * three top tables are ignored. */
+SLAM_API int slam_bow_query(slam_ctx* ctx, const int64_t* d_q_offsets, const int32_t* d_q_words, const uint32_t* d_q_q, int64_t Q,
+                            const int32_t* d_word_off, const void* d_postings, int64_t n_words, int64_t E, int64_t max_id,
+                            int max_results, int32_t* d_ids, uint32_t* d_s_int, int32_t* d_common, uint32_t* d_dense_s,
+                            int32_t* d_dense_common);
+/* Training, one depth of the tree per round (TemplatedVocabulary::HKmeansStep for all nodes of a depth at once; maximin
+ * seeding instead of k-means++).  d_row_node int32 [n]: the node (index within the depth, < F) of each row, -1 = at a leaf;
+ * node f owns the centre rows d_cent u8 [F,k,32], d_cent_count [F] of them in use.
+ * seed: centre 0 = the node's first row, each further one the row farthest from the centres so far (first row on ties),
+ * until k centres or distance 0.  d_ws: slam_bow_train_seed_workspace(n, F) bytes. */
+SLAM_API int slam_bow_train_seed(slam_ctx* ctx, const void* d_desc, int64_t n, const int32_t* d_row_node, int64_t F, int k,
+                                 void* d_cent, int32_t* d_cent_count, void* d_ws, uint64_t ws_bytes);
+SLAM_API int slam_bow_train_seed_workspace(int64_t n, int64_t F, uint64_t* h_bytes);
+/* step: d_assign [n] = nearest centre of each live row (lowest index on ties), *h_changed = rows whose assignment changed
+ * (waits for the stream); with `update` and *h_changed > 0 every centre that has rows becomes their bitwise majority (a bit is
+ * set iff 2 * count >= rows, DBoW2's meanValue).  d_perm: the n_live live rows grouped by node (slam_bow_group_keys on
+ * d_row_node); d_bits u32 [F,k,256], d_rows_of u32 [F,k] and d_changed u32 [1] are scratch. */
+SLAM_API int slam_bow_train_step(slam_ctx* ctx, const void* d_desc, int64_t n, const int32_t* d_row_node, int64_t F, int k,
+                                 void* d_cent, const int32_t* d_cent_count, int32_t* d_assign, const int32_t* d_perm,
+                                 int64_t n_live, uint32_t* d_bits, uint32_t* d_rows_of, uint32_t* d_changed, int update,
+                                 int64_t* h_changed);
+/* descend: with d_own (u32 [F,k]) the rows each centre owns; with d_next_of (int32 [F,k]) d_row_node[i] becomes
+ * d_next_of[node, assignment], the row's node of the next depth (-1 = at a leaf).  Exactly one of the two. */
+SLAM_API int slam_bow_train_descend(slam_ctx* ctx, int32_t* d_row_node, const int32_t* d_assign, int64_t n, int64_t F, int k,
+                                    uint32_t* d_own, const int32_t* d_next_of);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

@@ -23,6 +23,7 @@ import numpy as np
 
 from slamhip import ba as _ba
 from slamhip import ba_sparse as _bas
+from slamhip import bow as _bow
 from slamhip import pnp as _pnp
 from slamhip import pose_graph as _pg
 from slamhip import sim3_graph as _s3g
@@ -158,6 +159,14 @@ class Backend:
         poses = np.tile(np.eye(4), (len(T), 1, 1))
         poses[:, :3, :] = T
         return poses, counts, masks
+
+    def detect_loop_candidates(self, db, vector, connected=(), min_score: float = 0.0):
+        """The first stage of ORB-SLAM's ``DetectLoopCandidates`` on a ``slamhip.BowDatabase`` (the reference detects no
+        loops): dense scores and shared-word counts of ``vector`` against every entry come from the device; the ``connected``
+        ids are dropped, and the entries with more than 0.8 of the largest shared-word count and a score of at least
+        ``min_score`` are returned as (ids, scores) by (score descending, id ascending) - the candidates ``relocalize`` and
+        ``estimate_sim3_batch`` take."""
+        return _bow.detect_loop_candidates(db, vector, connected, min_score)
 
     def triangulate(self, pose1, pose2, px1, px2, fx, fy, cx, cy, reference_projection: bool = False):
         """``triangulation`` (``utils.py:32-55``) on arrays: the poses (4x4 or 3x4 Tcw) of the source and the query frame

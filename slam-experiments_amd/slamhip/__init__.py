@@ -61,6 +61,17 @@ from .pnp import (  # noqa: F401
     solve_pnp_ransac_offsets,
 )
 from .ba_sparse import SparseBAProblem, bundle_adjust_sparse, covisibility  # noqa: F401
+from .bow import (  # noqa: F401
+    BowDatabase,
+    BowVectors,
+    Vocabulary,
+    bow_transform,
+    bow_vectors,
+    detect_loop_candidates,
+    read_dbow2_text,
+    train_vocabulary,
+    write_dbow2_text,
+)
 from .pose_graph import (  # noqa: F401
     loop_edges_from_two_view,
     optimize_pose_graph,

@@ -182,6 +182,20 @@ SIGNATURES = {
     "slam_bas_reduce_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64] + [c_void_p] * 12 + [c_double] + [c_void_p] * 5),
     "slam_bas_backsub_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64] + [c_void_p] * 8),
     "slam_bas_candidate_f64": (c_int, [c_void_p, c_int64, c_int64] + [c_void_p] * 7 + [c_double] + [c_void_p] * 4),
+    "slam_bow_limits": (c_int, [POINTER(c_int32)]),
+    "slam_bow_transform": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "slam_bow_vectors": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_uint64, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "slam_bow_vectors_workspace": (c_int, [c_int64, c_int64, POINTER(c_uint64)]),
+    "slam_bow_group_keys": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "slam_bow_index_build": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_bow_query": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_bow_train_seed": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_uint64]),
+    "slam_bow_train_seed_workspace": (c_int, [c_int64, c_int64, POINTER(c_uint64)]),
+    "slam_bow_train_step": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                    c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int64)]),
+    "slam_bow_train_descend": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "slam_comm_version": (c_int, [POINTER(c_int)]),
     "slam_comm_unique_id": (c_int, [c_void_p]),
     "slam_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),

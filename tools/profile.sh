@@ -54,6 +54,7 @@ $PY tools/size_probe.py > $OUT/sizes.log 2>&1
 $PY tools/latency.py > $OUT/latency_small_calls.log 2>&1
 $PY tools/fire_probe.py > $OUT/update_path_share.log 2>&1
 $PY tools/ba_time.py > $OUT/ba_timing.log 2>&1
+$PY tools/bow_time.py > $OUT/bow_time.log 2>&1
 $PY tools/pose_lm_probe.py > $OUT/pose_lm_probe.log 2>&1
 $PY bench.py --full --pipelined --no-reproj --no-cpu-baseline > $OUT/bench_pipelined.json 2> $OUT/bench_pipelined.err
 find $OUT -name "*kernel_stats.csv" | head
