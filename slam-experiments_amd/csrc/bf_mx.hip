@@ -22,13 +22,13 @@
 //     tiles whose own maximum passes, and is the VALU kernel's on packed keys (dist << 23 | row: med3 / min); a key is
 //     (e << 23 | row) - (D << 22), exact modulo 2^32 for every lane of a fired tile, also a lane whose e is -1.  The
 //     accumulators and C live in VGPRs (the Makefile's -amdgpu-mfma-vgpr-form for this file): no AGPR round trip.  Each lane
-//     keeps the top-2 of ITS rows; the four lanes of a query are united (two xor shuffles) once per stage that fired, at each
-//     chunk start for the bound exchange, and at the end, where lane l takes query 64 wave + l - the layout of bf_top2_kernel's
+//     keeps the top-2 of ITS rows; the four lanes of a query are united (two xor shuffles) at each chunk start and early
+//     exchange, for the bound exchange, and at the end, where lane l takes query 64 wave + l - the layout of bf_top2_kernel's
 //     epilogue, shared.
 //   * distance ties stay out of the update path where they cannot win.  e only ever falls, to one of:
-//       - dist(own 2nd-best) - 1 after a fire, dist(2nd-best of the query's four lanes) - 1 after a stage that fired and at a
-//         chunk start: a worker's chunks ascend (tickets), and so do stages, groups and a lane's rows, hence every row the lane
-//         has still to see has a higher index than every row in those pairs;
+//       - dist(own 2nd-best) - 1 after a fire, dist(2nd-best of the query's four lanes) - 1 at a chunk start and at an early
+//         exchange (not at a stage end): a worker's chunks ascend (tickets), and so do stages, groups and a lane's rows, hence
+//         every row the lane has still to see has a higher index than every row in those pairs;
 //       - dist(g) - (row(g) < c0 ? 1 : 0) for the key g read from bound[] at the start of the chunk that begins at row c0.
 //         bound[] holds the 2nd-best KEY some worker of the query block has published (this kernel's own exchange: bound[] is
 //         only read and written by the blocks of one launch, so the encoding is private to it; keys below 0x7F000000 only - at
@@ -82,18 +82,12 @@
 
 #define SLAM_MX_UNROLL 4         // groups of 16 rows per trip of the scan loop
 
-// The phase probe (tools/mx_phase_probe.py): an experiment build (-DSLAM_MX_PROBE) in which every wave sums the shader clock
-// over the phases of its life and leaves the sums in a buffer of the tool's.  The shipped build executes no stamp.
+// The phase probe (tools/mx_phase_probe.py; MX_STAMP and the phases are in bf_mx_common.h): this kernel's buffer
 #ifdef SLAM_MX_PROBE
 __device__ unsigned long long* g_mx_probe = nullptr;
 extern "C" __attribute__((visibility("default"))) int slam_exp_set_mx_probe(void* p) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mx_probe), &p, sizeof(p));
 }
-// phases: 0 prologue, 1 chunk start, 2 quiet scan, 3 update paths, 4 stage end (unions, early exchange), 5 stage barrier
-// (arrival to release), 6 epilogue, 7 stage head (the ticket's draw and its wait)
-#define MX_STAMP(ph) do { const unsigned long long now_ = __builtin_readcyclecounter(); pacc[ph] += now_ - plast; plast = now_; } while (0)
-#else
-#define MX_STAMP(ph) do {} while (0)
 #endif
 
 typedef float mx_v4f __attribute__((ext_vector_type(4)));
@@ -248,7 +242,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             MX_STAMP(7);
             const int ng = __builtin_amdgcn_readfirstlane(min(SLAM_MX_STAGE / 16, (c1 - s0 + 15) >> 4));
             const uint4* tp = tile[buf];
-            u32 fired = 0;                                       // wave-uniform: the tiles that took the update path in this stage
             auto dots0 = [&](const uint4& a, mx_v4f (&acc)[4]) {
 #pragma unroll
                 for (int tt = 0; tt < 4; tt++) acc[tt] = mx_dot(a, qb[tt][0], cth[tt]);
@@ -279,7 +272,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
                     for (int tt = 0; tt < 4; tt++) {
                         if (__ballot(max(p[tt], __float_as_int(acc[tt][3])) >= 0) == 0ull) continue;
-                        fired |= 1u << tt;
                         // key = (e - D / 2) << 23 | row with e = x - 1: base + r + (-D << 22), exact modulo 2^32 also for x = 0
                         const u32 xt = threshold_x(tt);
                         const u32 base = (xt << SLAM_KEY_IDX_BITS) + rowk;
@@ -384,15 +376,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             for (; g + SLAM_MX_UNROLL <= nwhole; g += SLAM_MX_UNROLL) trip(g, std::integral_constant<int, SLAM_MX_UNROLL>{}, std::false_type{});
             for (; g < ng; g++) group(g, std::true_type{});
             MX_STAMP(2);
-            // once per stage in which a key changed, for the tiles it changed in: the threshold of the query's four lanes together
-            // (their rows lie in this stage or before it, below every row still to come)
-#pragma unroll
-            for (int tt = 0; tt < 4; tt++) {
-                if (!(fired >> tt & 1u)) continue;
-                u32 u1, u2;
-                unite_tile(tt, u1, u2);
-                set_threshold(tt, min(threshold_x(tt), u2 >> SLAM_KEY_IDX_BITS));
-            }
+            // No union of a query's four lanes here: a stage ends with each lane's threshold at its own 2nd-best.  The united
+            // threshold spared 5 % of the fired tiles and cost four LDS round trips in front of the barrier in 27 % of the
+            // tile-stages (tools/mx_fire_model.py; DESIGN.md 3c "The stage tail"); the exchanges and the epilogue still unite.
             // an early exchange (SLAM_MX_EARLY): per wave, no barrier; every row still to come is at or above s1.  Not after a
             // chunk's last stage: the chunk-start exchange follows anyway
             scanned += min(s1, c1) - s0;

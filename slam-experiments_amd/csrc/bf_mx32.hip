@@ -28,9 +28,10 @@
 //     The compare is per tile, so the fire test per tile is free, and a threshold move is one conversion.
 //   * the tie rules of bf_mx.hip's header carry over unchanged, with two lanes per query where that kernel has four.  x only
 //     ever falls, to one of:
-//       - dist(own 2nd-best) after a fire, dist(2nd-best of the query's two lanes) after a stage that fired and at a chunk
-//         start: chunks, stages, groups and a lane's rows ascend, so every row the lane has still to see has a higher index
-//         than every row in those pairs, and a tie against them loses;
+//       - dist(own 2nd-best) after a fire, dist(2nd-best of the query's two lanes) at a chunk start and at an early exchange
+//         (not at a stage end: that union spared 2 % of the fires and stood in front of every other barrier): chunks, stages,
+//         groups and a lane's rows ascend, so every row the lane has still to see has a higher index than every row in those
+//         pairs, and a tie against them loses;
 //       - mx_bound_x(g, c0) for the key g read from bound[] at the start of the chunk that begins at row c0 (the row of g is
 //         TESTED against c0: a tie against a key from a later row can win), and the same with the first row of the stage to come
 //         at the early exchanges (SLAM_MX_EARLY).  bound[] holds 2nd-best keys below SLAM_MX_BOUND_LIMIT, as in bf_mx.hip.
@@ -43,7 +44,7 @@
 //     where it fires, stands behind four MFMAs of the OTHER tile and behind the other tile's fold, so the wave keeps the matrix
 //     pipe fed while it folds and the compiler owes no wait states in front of a fold (a vector read of an MFMA result is not
 //     interlocked: 11 states after the MFMA).  Each tile sees its own MFMAs, fold and update in the order they always had;
-//     the tiles share only the wave-uniform `fired`.  The A operand of K-quarter q of group g + 1 is read once tile 1's MFMA of
+//     the tiles share nothing.  The A operand of K-quarter q of group g + 1 is read once tile 1's MFMA of
 //     quarter q of group g has issued, into the registers it frees, three MFMAs ahead of its use.  A stage that another follows
 //     expands and stores the thread's four source words of the next stage (ONE 16-byte load at the trip's start) in groups 1 to
 //     3, between MFMAs.  The last stage of the train set, if short, runs group by group, both folds behind the eight MFMAs, with
@@ -56,6 +57,14 @@
 #include "bf_mx_common.h"
 
 typedef float mx_v16f __attribute__((ext_vector_type(16)));
+
+// The phase probe (tools/mx_phase_probe.py; MX_STAMP and the phases are in bf_mx_common.h): this kernel's buffer
+#ifdef SLAM_MX_PROBE
+__device__ unsigned long long* g_mx32_probe = nullptr;
+extern "C" __attribute__((visibility("default"))) int slam_exp_set_mx32_probe(void* p) {
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_mx32_probe), &p, sizeof(p));
+}
+#endif
 
 // c + A B over one K-quarter: A = 32 train rows, B = 32 queries, FP4 on both sides (format code 4).  Both scale operands are the
 // constant 0: the compiler then selects the unscaled v_mfma_f32_32x32x64_f8f6f4, which holds the vector issue for a shorter time
@@ -77,6 +86,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int hk = lane >> 5, col = lane & 31;
+#ifdef SLAM_MX_PROBE
+    unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, plast = __builtin_readcyclecounter();
+#endif
     const int bx = ((int)blockIdx.x + (int)blockIdx.y) % (int)gridDim.x;
     // the lane's query in the epilogue and in the bound exchange: worked out afresh at each of them (the empty asm hides that the
     // value repeats), or it and the addresses built on it hold registers through the scan
@@ -166,30 +178,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     __syncthreads();
     int ci = __builtin_amdgcn_readfirstlane((int)s_ticket);
     int scanned = 0;                                             // wave-uniform: the rows this block has scanned since launch
+    MX_STAMP(0);
     while (ci < nchunks) {
         const int c0 = tbl[ci], c1 = tbl[ci + 1];
         const uint4 first = load_stage(c0, c1);
         exchange(c0);
         store_stage(0, first);
         __syncthreads();
+        MX_STAMP(1);
         int buf = 0;
         for (int s0 = c0; s0 < c1; s0 += SLAM_MX_STAGE) {
             const int s1 = s0 + SLAM_MX_STAGE;
             const bool more = s1 < c1;
             // the next ticket is drawn while the chunk's last stage is scanned; read behind the stage's barrier
             if (!more && tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            MX_STAMP(7);
             const uint4* tp = tile[buf];
-            u32 fired = 0;                                       // wave-uniform: the tiles that took the update path in this stage
             // fold the 16 results of tile tt of group g and, where some lane of the tile passes, take the update path.  A tile's
-            // fold and update path touch that tile's accumulators and state only (and the wave-uniform `fired`), so where the
-            // folds of the two tiles stand relative to each other and to the other tile's MFMAs does not matter to the result
+            // fold and update path touch that tile's accumulators and state only, so where the folds of the two tiles stand
+            // relative to each other and to the other tile's MFMAs does not matter to the result
             auto fold_tile = [&](int tt, int g, const mx_v16f& acc, auto rag) {
                 int p = max(max(__float_as_int(acc[0]), __float_as_int(acc[1])), __float_as_int(acc[2]));
 #pragma unroll
                 for (int i = 3; i < 15; i += 2) p = max(max(p, __float_as_int(acc[i])), __float_as_int(acc[i + 1]));
                 const int m = max(p, __float_as_int(acc[15]));
                 if (__builtin_expect(__ballot(m >= thr[tt]) == 0ull, 1)) return;
-                fired |= 1u << tt;
+                MX_STAMP(2);
                 // the group's first row is taken from the scalar side here: as a per-lane value it would be carried through
                 // every group that does not fire.  g is the group that is FOLDED, whichever group's MFMAs stand around the fold
                 int row0 = s0 + g * MX32_GROUP;
@@ -216,6 +230,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                     b1[tt] = min(b1[tt], key);
                 }
                 set_threshold(tt, min(xs[tt], b2[tt] >> SLAM_KEY_IDX_BITS));
+                MX_STAMP(3);
             };
             const mx_v16f zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             auto group = [&](int g, auto rag) {
@@ -297,20 +312,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 const int ng = __builtin_amdgcn_readfirstlane((c1 - s0 + MX32_GROUP - 1) / MX32_GROUP);
                 for (int g = 0; g < ng; g++) group(g, std::true_type{});
             }
-            // once per stage in which a key changed, for the tiles it changed in: the threshold of the query's two lanes together
-            // (their rows lie in this stage or before it, below every row still to come)
-#pragma unroll
-            for (int tt = 0; tt < 2; tt++) {
-                if (!(fired >> tt & 1u)) continue;
-                u32 u1, u2;
-                unite_tile(tt, u1, u2);
-                set_threshold(tt, min(xs[tt], u2 >> SLAM_KEY_IDX_BITS));
-            }
+            MX_STAMP(2);
+            // No union of a query's two lanes here: a stage ends with each lane's threshold at its own 2nd-best.  The united
+            // threshold spared 2 % of the fired tiles and cost two LDS round trips in front of the barrier in 41 % of the
+            // tile-stages (tools/mx_fire_model.py; DESIGN.md 3c "The stage tail"); the exchanges and the epilogue still unite.
             // an early exchange (SLAM_MX_EARLY): per wave, no barrier; every row still to come is at or above s1.  Not after a
             // chunk's last stage: the chunk-start exchange follows anyway
             scanned += min(s1, c1) - s0;
             if (more && scanned < 32 * SLAM_MX_STAGE && (SLAM_MX_EARLY >> (scanned / SLAM_MX_STAGE) & 1u)) exchange(s1);
+            MX_STAMP(4);
             __syncthreads();
+            MX_STAMP(5);
             buf ^= 1;
         }
         ci = __builtin_amdgcn_readfirstlane((int)s_ticket);
@@ -324,4 +336,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const u32 gk[1] = {gkey < SLAM_MX_BOUND_LIMIT ? gkey >> SLAM_KEY_IDX_BITS : SLAM_BOUND_IDLE};
     bf_top2_epilogue<1, true>(st, bx, tid, lane, lane_query(), false, false, f1, f2, gk, pend, N, (int)gridDim.y, train_base, out_idx,
                               out_dist, sel, s_last);
+#ifdef SLAM_MX_PROBE
+    MX_STAMP(6);
+    if (g_mx32_probe && lane == 0) {
+        unsigned long long* o = g_mx32_probe + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8;
+        for (int i = 0; i < 8; i++) o[i] = pacc[i];
+    }
+#endif
 }

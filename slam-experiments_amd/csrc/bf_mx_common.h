@@ -13,6 +13,17 @@
 #define SLAM_MX_EARLY 0x16u      // after 128, 256 and 512 rows
 #define SLAM_MX_RESIDENT 4       // blocks of either kernel a CU holds at once (the plan describe counts on it; launches ask)
 
+// The phase probe (tools/mx_phase_probe.py): an experiment build (-DSLAM_MX_PROBE) in which every wave of either kernel sums the
+// shader clock over the phases of its life (pacc, plast: the kernel's locals) and leaves the sums in a buffer of the tool's.
+// The shipped build executes no stamp.
+// phases: 0 prologue, 1 chunk start, 2 quiet scan, 3 update paths, 4 stage end (unions, early exchange), 5 stage barrier
+// (arrival to release), 6 epilogue, 7 stage head (the ticket's draw and its wait)
+#ifdef SLAM_MX_PROBE
+#define MX_STAMP(ph) do { const unsigned long long now_ = __builtin_readcyclecounter(); pacc[ph] += now_ - plast; plast = now_; } while (0)
+#else
+#define MX_STAMP(ph) do {} while (0)
+#endif
+
 typedef int mx_v8i __attribute__((ext_vector_type(8)));
 
 // 32 descriptor bits -> 32 FP4 elements (-1.0 for a set bit, +1.0 for a clear one: the bit is the sign bit as it stands): nibble

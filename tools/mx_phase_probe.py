@@ -1,10 +1,11 @@
-"""Where a wave of the matrix-core top-2 search (bf_mx.hip) spends its life, by phase (development aid).
+"""Where a wave of a matrix-core top-2 search (bf_mx.hip, bf_mx32.hip) spends its life, by phase (development aid).
 
-    python tools/mx_phase_probe.py LIB [NxM ...] [--warm K]
+    python tools/mx_phase_probe.py LIB [NxM ...] [--warm K] [--engine 2|3]
 
-LIB is an experiment build of libslamhip.so with -DSLAM_MX_PROBE (tools/build_variant.sh bf_mx
-slam-experiments_amd/csrc/bf_mx.hip tools/exp/libslamhip_probe.so -mllvm -amdgpu-mfma-vgpr-form -DSLAM_MX_PROBE): every wave sums the shader clock (s_memtime) over its phases
-and lane 0 leaves the sums in a buffer of this tool's at the end.  The shipped build executes no stamp.  The stamps cost time
+LIB is an experiment build of libslamhip.so with -DSLAM_MX_PROBE in the kernel's file (tools/build_variant.sh bf_mx
+slam-experiments_amd/csrc/bf_mx.hip tools/exp/libslamhip_probe.so -mllvm -amdgpu-mfma-vgpr-form -DSLAM_MX_PROBE for the 16x16
+kernel, engine 2, the default; the same with bf_mx32 twice for the 32x32 kernel, engine 3): every wave sums the shader clock
+(s_memtime) over its phases and lane 0 leaves the sums in a buffer of this tool's at the end.  The shipped build executes no stamp.  The stamps cost time
 (about one scalar memory instruction and a wait per phase boundary, two boundaries per stage more in a stage that fires): read
 the SHARES, and the kernel time of the stamped build beside the shipped one's.
 
@@ -22,11 +23,19 @@ from slamhip._lib import SIGNATURES  # noqa: E402
 
 PHASES = ["prologue", "chunk start", "quiet scan", "update paths", "stage end", "stage barrier", "epilogue", "stage head"]
 
-warm = 50
-if "--warm" in sys.argv:
-    i = sys.argv.index("--warm")
-    warm = int(sys.argv[i + 1])
-    del sys.argv[i:i + 2]
+
+
+def opt(name, default):
+    if name in sys.argv:
+        i = sys.argv.index(name)
+        v = int(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
+        return v
+    return default
+
+
+warm, engine = opt("--warm", 50), opt("--engine", 2)
+assert engine in (2, 3), "--engine 2 (bf_top2_mx_kernel) or 3 (bf_top2_mx32_kernel)"
 path = sys.argv[1]
 sizes = [tuple(int(v) for v in a.split("x")) for a in sys.argv[2:]] or [(65536, 65536)]
 
@@ -35,10 +44,11 @@ for name, (res, args) in SIGNATURES.items():
     fn = getattr(lib, name, None)
     if fn is not None:
         fn.restype, fn.argtypes = res, args
-lib.slam_exp_set_mx_probe.argtypes = [ctypes.c_void_p]
+set_probe = lib.slam_exp_set_mx32_probe if engine == 3 else lib.slam_exp_set_mx_probe     # each kernel's file has its own buffer
+set_probe.argtypes = [ctypes.c_void_p]
 ctx = ctypes.c_void_p()
 assert lib.slam_ctx_create(0, ctypes.byref(ctx)) == 0
-assert lib.slam_bf_set_engine(ctx, 2) == 0
+assert lib.slam_bf_set_engine(ctx, engine) == 0
 
 
 def malloc(nbytes):
@@ -69,16 +79,16 @@ for n, m in sizes:
     for _ in range(20):
         lib.slam_bf_knn2_u256(ctx, dq, n, dt, m, 0, di, dd)
     lib.slam_timer_stop(ctx, ctypes.byref(ms))
-    assert lib.slam_exp_set_mx_probe(buf) == 0
+    assert set_probe(buf) == 0
     assert lib.slam_bf_knn2_u256(ctx, dq, n, dt, m, 0, di, dd) == 0
     lib.slam_sync(ctx)
-    assert lib.slam_exp_set_mx_probe(None) == 0
+    assert set_probe(None) == 0
     out = np.empty(nbytes // 8, np.uint64)
     assert lib.slam_download(ctx, out.ctypes.data, buf, nbytes) == 0
     s = out.reshape(-1, 4, 8).astype(np.float64)
     s = s[s.sum(axis=(1, 2)) > 0]                        # the blocks of the launch
     life = s.sum(axis=2, keepdims=True)
-    print(f"{n}x{m}: {len(s)} blocks, stamped build {ms.value / 20 * 1e3:.1f} us per launch; a wave's life: median {np.median(life):.0f} cycles "
+    print(f"{n}x{m} engine {engine}: {len(s)} blocks, stamped build {ms.value / 20 * 1e3:.1f} us per launch; a wave's life: median {np.median(life):.0f} cycles "
           f"(p5 {np.percentile(life, 5):.0f}, p95 {np.percentile(life, 95):.0f})")
     share = s / life
     for i in (0, 1, 7, 2, 3, 4, 5, 6):
