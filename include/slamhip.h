@@ -1126,6 +1126,60 @@ SLAM_API int slam_bow_train_step(slam_ctx* ctx, const void* d_desc, int64_t n, c
 SLAM_API int slam_bow_train_descend(slam_ctx* ctx, int32_t* d_row_node, const int32_t* d_assign, int64_t n, int64_t F, int k,
                                     uint32_t* d_own, const int32_t* d_next_of);
 
+/* ---- node-constrained matching over the BoW direct index (bow_match.hip) -----------------------------------
+ * ORBmatcher::SearchByBoW: the correspondences of candidate image pairs, comparing only the features that slam_bow_transform
+ * (bow_transform(..., levels_up)) put into the same vocabulary node; no call site in the reference.  PARITY UNPINNED: the
+ * one-to-one step and the rotation check are stated on integers (4k).  A pair is (side 1 = the keyframe, side 2 = the frame);
+ * row j of side 2 is a candidate for row i of side 1 iff their node ids are equal and >= 0 (a negative id takes a row out of
+ * the search on either side).  At most SLAM_BOW_MATCH_ROWS_MAX rows per image and SLAM_BOW_MATCH_PAIRS_MAX pairs per call. */
+#define SLAM_BOW_MATCH_ROWS_MAX 8192
+#define SLAM_BOW_MATCH_PAIRS_MAX 4096
+/* h_limits [6] = {rows per image, pairs per call, threads of a group workgroup, side-1 rows of a scan workgroup, orientation
+ * bins, the distance a missing second neighbour counts as in the ratio test}; needs no GPU */
+SLAM_API int slam_bow_match_limits(int32_t* h_limits);
+/* The launch plan for B images (group) or B pairs (search) of n rows per image; needs no GPU.  h_plan [8] = {length of the
+ * LDS sort (n padded to a power of two), LDS bytes of a group workgroup, group workgroups, scan workgroups, finish workgroups,
+ * workspace bytes of the search when the tables stay in the workspace, LDS bytes of a finish workgroup, workspace bytes of
+ * the group step} */
+SLAM_API int slam_bow_match_plan_describe(int64_t B, int64_t n, int64_t* h_plan);
+/* The group step - DBoW2's FeatureVector of B images at once, built once per image and reused by every search: image b owns the
+ * rows [h_offsets[b], h_offsets[b+1]) of d_desc u8 [n,32] and of d_nodes int32 [n] (slam_bow_transform's d_nodes; h_offsets
+ * is a HOST array and travels through the context's workspace).  Inside each image the rows are sorted by (node id as
+ * unsigned 32-bit, row), so masked rows go last: d_order [n] the row (local to its image) at each position, d_nodes_sorted
+ * [n] its node id, d_desc_sorted [n,32] its descriptor, d_inverse [n] the position of each row.  Asynchronous on the ctx
+ * stream. */
+SLAM_API int slam_bow_match_group(slam_ctx* ctx, const void* d_desc, const int32_t* d_nodes, const int64_t* h_offsets, int64_t B,
+                                  void* d_desc_sorted, int32_t* d_nodes_sorted, int32_t* d_order, int32_t* d_inverse);
+/* one set of grouped images, as slam_bow_match_group leaves it; d_bins: the orientation bin (0 .. 31, taken modulo 32) of each
+ * row in ROW order, or null; h_offsets is a HOST array */
+typedef struct slam_bow_groups {
+    const void* d_desc;
+    const int32_t* d_nodes;
+    const int32_t* d_order;
+    const int32_t* d_inverse;
+    const uint8_t* d_bins;
+    const int64_t* h_offsets;
+    int64_t B;
+} slam_bow_groups;
+/* The node top-2 of P pairs: h_pairs is a HOST array int32 [P,2] of (image of g1, image of g2); the pair table travels through
+ * the context's workspace.  Per side-1 row its two nearest candidates by (distance, side-2 row), rows local to the pair's
+ * images, missing neighbours (-1, INT32_MAX): d_idx / d_dist int32 [sum of the pairs' side-1 rows, 2], pair after pair in
+ * row order.  With all node ids equal this is slam_bf_knn2_u256.  scan_order: 0 = a lane per grouped position (shipped),
+ * 1 = a lane per row; the same results.  Asynchronous on the ctx stream (the table is copied from pageable host memory as
+ * slam_upload copies: the runtime may hold the caller until that copy has run; the launches behind it are not waited for). */
+SLAM_API int slam_bow_match_top2(slam_ctx* ctx, const slam_bow_groups* g1, const slam_bow_groups* g2, const int32_t* h_pairs, int64_t P,
+                                 int scan_order, int32_t* d_idx, int32_t* d_dist);
+/* ORBmatcher::SearchByBoW for P pairs: the node top-2, then row i is proposed iff d0 <= th_low and (double)d0 < ratio * (double)d1
+ * (a missing second neighbour counts as 256); among the proposed rows that name one side-2 row the smallest (d0, i) keeps it;
+ * and, when both sets carry bins, the rotation check: the histogram of (bin1[i] - bin2[j]) & 31, of which the first bin by
+ * (count descending, bin ascending) stays, and the second and third while their count c > 0 and 10 c >= the first's.
+ * d_matches12 int32 [sum of side-1 rows]: the side-2 row of each side-1 row or -1 (vpMatches12), d_count int32 [P] the matches
+ * of each pair; d_idx / d_dist: the top-2 tables as slam_bow_match_top2 writes them, or both null.  No host read-back between
+ * the steps; asynchronous on the ctx stream. */
+SLAM_API int slam_bow_match_search(slam_ctx* ctx, const slam_bow_groups* g1, const slam_bow_groups* g2, const int32_t* h_pairs, int64_t P,
+                                   int th_low, double ratio, int scan_order, int32_t* d_matches12, int32_t* d_count, int32_t* d_idx,
+                                   int32_t* d_dist);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

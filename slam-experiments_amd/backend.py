@@ -24,6 +24,7 @@ import numpy as np
 from slamhip import ba as _ba
 from slamhip import ba_sparse as _bas
 from slamhip import bow as _bow
+from slamhip import bow_match as _bm
 from slamhip import pnp as _pnp
 from slamhip import pose_graph as _pg
 from slamhip import sim3_graph as _s3g
@@ -167,6 +168,20 @@ class Backend:
         ``min_score`` are returned as (ids, scores) by (score descending, id ascending) - the candidates ``relocalize`` and
         ``estimate_sim3_batch`` take."""
         return _bow.detect_loop_candidates(db, vector, connected, min_score)
+
+    def match_by_bow(self, keyframes, frame, candidates, frame_index: int = 0, keyframe_bins=None, frame_bins=None,
+                     th_low: int = _bm.TH_LOW, ratio: float = _bm.RATIO):
+        """ORB-SLAM's ``ORBmatcher::SearchByBoW`` of one frame against its candidate keyframes, the step after
+        ``detect_loop_candidates``: ``keyframes`` and ``frame`` are ``slamhip.FeatureVectors`` (``bow_feature_vectors``),
+        ``candidates`` the keyframe ids, ``frame_index`` the image of ``frame``; the bins (``OrbResult.bin`` of every row of
+        the two sets) switch the rotation check on.  Returns per candidate ``(i1, i2)``: int32 arrays of the matched keyframe
+        rows (ascending) and frame rows, so that ``(map_points_of_keyframe[i1], frame_pixels[i2])`` is one entry of
+        ``relocalize``'s ``candidates`` and ``(points_of_keyframe[i1], points_of_frame[i2])`` one pair of
+        ``estimate_sim3_batch``."""
+        cand = np.asarray(list(candidates), np.int64).reshape(-1)
+        pairs = np.stack([cand, np.full(len(cand), int(frame_index), np.int64)], axis=1) if len(cand) else np.zeros((0, 2), np.int64)
+        matches, _ = _bm.search_by_bow(keyframes, frame, pairs, keyframe_bins, frame_bins, th_low, ratio, ctx=self._ctx)
+        return _bm.match_index_pairs(matches)
 
     def triangulate(self, pose1, pose2, px1, px2, fx, fy, cx, cy, reference_projection: bool = False):
         """``triangulation`` (``utils.py:32-55``) on arrays: the poses (4x4 or 3x4 Tcw) of the source and the query frame

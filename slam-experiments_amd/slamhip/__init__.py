@@ -72,6 +72,15 @@ from .bow import (  # noqa: F401
     train_vocabulary,
     write_dbow2_text,
 )
+from .bow_match import (  # noqa: F401
+    FeatureVectors,
+    bow_feature_vectors,
+    match_index_pairs,
+    node_match_arrays,
+    node_top2,
+    search_by_bow,
+    search_by_bow_descriptors,
+)
 from .pose_graph import (  # noqa: F401
     loop_edges_from_two_view,
     optimize_pose_graph,

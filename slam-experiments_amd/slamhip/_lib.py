@@ -196,6 +196,12 @@ SIGNATURES = {
     "slam_bow_train_step": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int64)]),
     "slam_bow_train_descend": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "slam_bow_match_limits": (c_int, [POINTER(c_int32)]),
+    "slam_bow_match_plan_describe": (c_int, [c_int64, c_int64, POINTER(c_int64)]),
+    "slam_bow_match_group": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_bow_match_top2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "slam_bow_match_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
     "slam_comm_version": (c_int, [POINTER(c_int)]),
     "slam_comm_unique_id": (c_int, [c_void_p]),
     "slam_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
@@ -215,6 +221,13 @@ class BfSearch(ctypes.Structure):
 
     _fields_ = [("d_query", c_void_p), ("N", c_int64), ("d_train", c_void_p), ("M", c_int64), ("train_base", c_int64),
                 ("d_idx", c_void_p), ("d_dist", c_void_p)]
+
+
+class BowGroups(ctypes.Structure):
+    """``slam_bow_groups`` of include/slamhip.h: one set of grouped images."""
+
+    _fields_ = [("d_desc", c_void_p), ("d_nodes", c_void_p), ("d_order", c_void_p), ("d_inverse", c_void_p), ("d_bins", c_void_p),
+                ("h_offsets", c_void_p), ("B", c_int64)]
 
 
 BF_BATCH_MAX = 32
