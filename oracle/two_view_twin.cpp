@@ -4,7 +4,8 @@
 // compiled for the host with contraction off and no FMA instructions available (x86-64 baseline), so a result here is
 // what the device must give bit for bit if "a pure function of its inputs whatever it is inlined into" holds.  The
 // "LDS" is a host array with the kernel's own lane stride (TV_LANES); lane 0 is used.  On top of the routines: a
-// restatement of the RANSAC (argmax by the same key, hypotheses in any order) and of the recoverPose vote.
+// restatement of the RANSAC (argmax by the kernel's own key, geo_key3 of geometry_common.h, hypotheses in any order) and
+// of the recoverPose vote.
 //
 // Built twice by oracle/Makefile: libtvtwin.so (bound in oracle.py) and tv_twin_san, a stand-alone program with
 // -fsanitize=undefined,address that reads a job file and writes a result file (TV_TWIN_MAIN).
@@ -34,11 +35,6 @@ double now_s() {
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
-// key of the kernel (tv_key), restated: more inliers, then the lower hypothesis, then the lower root; 0 = no model
-const int H_MAX = 1 << 20;
-unsigned long long key_of(int count, int h, int root) {
-    return ((unsigned long long)(unsigned)count << 32) | ((unsigned long long)(H_MAX - h) << 4) | (unsigned long long)(15 - root);
 }
 int solve_hypothesis(double* lds, const double* xn, int n, uint64_t seed, int h) {
     int idx[5];
@@ -120,7 +116,7 @@ void tvt_triangulate(int64_t N, const double* P1, const double* P2, const double
 // slam_tv_essential_ransac_f64 for one pair of n matches (pixels), every hypothesis 0 .. H-1 solved and scored in turn
 int tvt_ransac(int64_t n64, const double* px1, const double* px2, double fx, double fy, double cx, double cy, int H,
                double threshold_px, uint64_t seed, double* E_out, uint8_t* inlier, int32_t* stats) {
-    if (H < 1 || H > H_MAX || n64 < 0 || n64 > (1 << 28)) return -1;
+    if (H < 1 || H > GEO_H_MAX || n64 < 0 || n64 > (1 << 28)) return -1;
     const int n = (int)n64;
     for (int t = 0; t < 9; t++) E_out[t] = 0.0;
     for (int i = 0; i < n; i++) inlier[i] = 0;
@@ -149,7 +145,7 @@ int tvt_ransac(int64_t n64, const double* px1, const double* px2, double fx, dou
                 for (int t = 0; t < 9; t++) E[t] = TVL(TV_EOUT + 9 * r + t);
                 int count = 0;
                 for (int i = 0; i < n; i++) count += tv_sampson_sq(E, xn[4 * i], xn[4 * i + 1], xn[4 * i + 2], xn[4 * i + 3]) < thr2 ? 1 : 0;
-                const unsigned long long k = key_of(count, h, r);
+                const unsigned long long k = geo_key3(count, h, r);
                 if (k > mine) mine = k;
             }
         }
@@ -161,7 +157,7 @@ int tvt_ransac(int64_t n64, const double* px1, const double* px2, double fx, dou
     }
     stats[3] = (int32_t)models;
     if (!best) return 0;
-    const int count = (int)(best >> 32), h = H_MAX - (int)((best >> 4) & 0xFFFFFFFull), root = 15 - (int)(best & 15);
+    const int count = geo_key_count(best), h = geo_key3_h(best), root = geo_key3_sub(best);
     Lds l(g_fill);
     double* lds = l.lane0();
     solve_hypothesis(lds, xn.data(), n, seed, h);

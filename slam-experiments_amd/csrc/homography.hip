@@ -28,21 +28,24 @@
 // One sample per lane, straight-line code in registers: no run-time-indexed array, so nothing goes to scratch.
 //
 // The decomposition (Ma, Soatto, Kosecka, Sastry, "An Invitation to 3-D Vision", 5.3.3), through the eigenvectors of
-// Hn^T Hn by cyclic Jacobi: see hg_candidates.  hg_jacobi, hg_triangulate_point and hg_cheirality are PRIVATE COPIES of
-// tv_jacobi, tv_triangulate_point and tv_cheirality of two_view.hip (the kernel files share no geometry code); they must
-// stay operation for operation what those are, since the vote is defined as "triangulated as slam_tv_triangulate_f64".
+// Hn^T Hn by cyclic Jacobi: see hg_candidates.  The Jacobi sweeps, the triangulation and the cheirality test are
+// geometry_common.h's, the ones two_view.hip runs: the vote is defined as "triangulated as slam_tv_triangulate_f64".
 #ifndef HG_HOST_ONLY                 // a host build of the routines alone (the test suite's twin) defines it
 #include "internal.h"
 #endif
 #include <math.h>
 #include <stdint.h>
+#include "geometry_common.h"         // sampler, Jacobi, triangulation, cheirality, range clamp, intrinsics, model key, three-vectors
 
 #pragma clang fp contract(off)
 
 #define HG_HD __host__ __device__ __forceinline__
-#define HG_H_MAX (1 << 20)
-#define HG_BIG 1e200                 // a sample whose squared coordinates sum to this or more (or to NaN) has no model
-#define HG_FLAT 1e-20                // sin^2 of the smallest angle of a triangle that is still solved
+// the shared routines, key and intrinsics under this file's names, as its host twin calls them (four matches per sample)
+#define hg_draw_sample geo_draw_sample<4>
+#define hg_cheirality geo_cheirality
+#define hg_key geo_key2
+#define HG_H_MAX GEO_H_MAX
+typedef geo_cam hg_cam;
 #define HG_ROTATION_ONLY 1e-9        // (s1 - s3) / s2 below this: H is a rotation, no translation is reported.  The numpy
                                      // reference measures 2.4e-16 on pure_rotation/t0 (this file's Jacobi: 8.4e-16) and 1.25e-6
                                      // on pure_rotation/b1e-6 (profiles/homography_edges.log); the bound lies between the two
@@ -52,12 +55,12 @@
 
 // ---- the minimal solver -------------------------------------------------------------------------------------------------------
 HG_HD double hg_min(double a, double b) { return a < b ? a : b; }
-// twice the signed area of the triangle (a, b, c); *flat: sin^2 of one of its angles is below HG_FLAT (or a vertex repeats)
+// twice the signed area of the triangle (a, b, c); *flat: sin^2 of one of its angles is below GEO_FLAT (or a vertex repeats)
 HG_HD double hg_area2(double ax, double ay, double bx, double by, double cx, double cy, bool* flat) {
     const double ux = bx - ax, uy = by - ay, vx = cx - ax, vy = cy - ay, wx = cx - bx, wy = cy - by;
     const double cr = ux * vy - uy * vx, c2 = cr * cr;
     const double lu = ux * ux + uy * uy, lv = vx * vx + vy * vy, lw = wx * wx + wy * wy;
-    *flat = !(c2 > HG_FLAT * (lu * lv)) || !(c2 > HG_FLAT * (lu * lw)) || !(c2 > HG_FLAT * (lv * lw));
+    *flat = !(c2 > GEO_FLAT * (lu * lv)) || !(c2 > GEO_FLAT * (lu * lw)) || !(c2 > GEO_FLAT * (lv * lw));
     return cr;
 }
 // Hartley normalisation of four points p [8]: n [8] = s (p - c); returns false if the mean distance is not a positive finite double
@@ -86,7 +89,7 @@ HG_HD bool hg_fourpoint(const double* p1, const double* p2, double* H) {
     for (int i = 0; i < 8; i++) big += p1[i] * p1[i];
 #pragma unroll
     for (int i = 0; i < 8; i++) big += p2[i] * p2[i];
-    if (!(big < HG_BIG)) return false;                           // NaN, inf, coordinates beyond 1e100
+    if (!(big < GEO_BIG)) return false;                           // NaN, inf, coordinates beyond 1e100
     double p[8], q[8], s1, c1x, c1y, s2, c2x, c2y;
     if (!hg_hartley(p1, p, &s1, &c1x, &c1y) || !hg_hartley(p2, q, &s2, &c2x, &c2y)) return false;
     bool f0, f1, f2, f3, g0, g1, g2, g3;
@@ -178,34 +181,10 @@ HG_HD bool hg_inlier(const double* H, double x, double y, double u, double v, do
     const double dv = ((H[3] * x + H[4] * y) + H[5]) / w - v;
     return (w > 0.0) & ((du * du + dv * dv) < thr2);
 }
-HG_HD uint64_t hg_splitmix(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-HG_HD uint64_t hg_draw_word(uint64_t seed, uint64_t h, uint64_t d) {
-    return hg_splitmix(hg_splitmix(seed ^ (h * 0xD1B54A32D192ED03ull)) ^ (d * 0x8CB92BA72F3D8DD7ull));
-}
-HG_HD void hg_draw_sample(uint64_t seed, int h, int n, int* idx) {      // n >= 4
-    uint64_t d = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        int i;
-        bool dup;
-        do {
-            i = (int)(((hg_draw_word(seed, (uint64_t)h, d++) >> 32) * (uint64_t)n) >> 32);
-            dup = false;
-#pragma unroll
-            for (int j = 0; j < 4; j++) dup = dup || (j < k && idx[j] == i);
-        } while (dup);
-        idx[k] = i;
-    }
-}
 // hypothesis h of a pair of n matches px1 / px2 [n,2]: its sample drawn and solved
 HG_HD bool hg_solve_hypothesis(const double* px1, const double* px2, int n, uint64_t seed, int h, double* H) {
     int idx[4] = {0, 0, 0, 0};
-    hg_draw_sample(seed, h, n, idx);
+    geo_draw_sample<4>(seed, h, n, idx);
     double a[8], b[8];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -214,94 +193,8 @@ HG_HD bool hg_solve_hypothesis(const double* px1, const double* px2, int n, uint
     }
     return hg_fourpoint(a, b, H);
 }
-// key of a scored model: more inliers first, then the lower hypothesis; 0 = no model
-HG_HD unsigned long long hg_key(int count, int h) {
-    return ((unsigned long long)(unsigned)count << 32) | (unsigned long long)(HG_H_MAX - h);
-}
-
-// ---- small symmetric eigenproblems, triangulation, cheirality: private copies of two_view.hip's ------------------------------
-template <int N, int SWEEPS>
-HG_HD void hg_jacobi(double (&A)[N][N], double (&V)[N][N]) {
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < N; j++) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < SWEEPS; sweep++) {
-#pragma unroll
-        for (int p = 0; p < N - 1; p++)
-#pragma unroll
-            for (int q = p + 1; q < N; q++) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                A[p][p] -= t * apq;
-                A[q][q] += t * apq;
-                A[p][q] = A[q][p] = 0.0;
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    if (k != p && k != q) {
-                        const double akp = A[k][p], akq = A[k][q];
-                        A[k][p] = A[p][k] = c * akp - s * akq;
-                        A[k][q] = A[q][k] = s * akp + c * akq;
-                    }
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
-HG_HD void hg_triangulate_point(const double* P1, const double* P2, double a, double b, double c, double d, double* v) {
-    double A[4][4], S[4][4], V[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        A[0][j] = a * P1[8 + j] - P1[j];
-        A[1][j] = b * P1[8 + j] - P1[4 + j];
-        A[2][j] = c * P2[8 + j] - P2[j];
-        A[3][j] = d * P2[8 + j] - P2[4 + j];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = i; j < 4; j++) S[i][j] = S[j][i] = ((A[0][i] * A[0][j] + A[1][i] * A[1][j]) + A[2][i] * A[2][j]) + A[3][i] * A[3][j];
-    hg_jacobi<4, 10>(S, V);
-    double best = S[0][0];
-#pragma unroll
-    for (int k = 0; k < 4; k++) v[k] = V[k][0];
-#pragma unroll
-    for (int j = 1; j < 4; j++)
-        if (S[j][j] < best) {
-            best = S[j][j];
-#pragma unroll
-            for (int k = 0; k < 4; k++) v[k] = V[k][j];
-        }
-    const double inv = 1.0 / sqrt(((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + v[3] * v[3]);
-    const double sg = v[3] < 0.0 ? -inv : inv;
-#pragma unroll
-    for (int k = 0; k < 4; k++) v[k] *= sg;
-}
-// good under the pose T [12] = [R | t]: depth in (0, dist) in both cameras (cv2.recoverPose)
-HG_HD bool hg_cheirality(const double* T, double a, double b, double c, double d, double dist) {
-    const double P1[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    double v[4];
-    hg_triangulate_point(P1, T, a, b, c, d, v);
-    const double X = v[0] / v[3], Y = v[1] / v[3], Z = v[2] / v[3];
-    const double Z2 = ((T[8] * X + T[9] * Y) + T[10] * Z) + T[11];
-    return Z > 0.0 && Z < dist && Z2 > 0.0 && Z2 < dist;
-}
 
 // ---- the decomposition ---------------------------------------------------------------------------------------------------------
-struct hg_cam { double fx, fy, cx, cy; };
-HG_HD double hg_dot(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-HG_HD void hg_cross(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
-HG_HD void hg_unit(double* a) {
-    const double inv = 1.0 / sqrt(hg_dot(a, a));
-    a[0] *= inv; a[1] *= inv; a[2] *= inv;
-}
 HG_HD void hg_mv(const double* M, const double* v, double* r) {
 #pragma unroll
     for (int i = 0; i < 3; i++) r[i] = (M[3 * i] * v[0] + M[3 * i + 1] * v[1]) + M[3 * i + 2] * v[2];
@@ -316,7 +209,7 @@ HG_HD double hg_fix_sign(double* a) {
     return sg;
 }
 // Hn = K^-1 H K, operation by operation as the header states it
-HG_HD void hg_to_normalised(const double* H, const hg_cam& cam, double* Hn) {
+HG_HD void hg_to_normalised(const double* H, const geo_cam& cam, double* Hn) {
     double G[9];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -334,7 +227,7 @@ HG_HD void hg_to_normalised(const double* H, const hg_cam& cam, double* Hn) {
 // Singular values of Hn, descending, in sv [3] and its right singular vectors v1, v3 (of s1, s3) from the eigenvectors of
 // Hn^T Hn; each of v1, v3 with its largest-magnitude component positive.  false: H or Hn has a sum of squares that is not a
 // positive finite double, or s2 is not one (sv is then zero).
-HG_HD bool hg_singular(const double* H, const hg_cam& cam, double* Hn, double* sv, double* v1, double* v3) {
+HG_HD bool hg_singular(const double* H, const geo_cam& cam, double* Hn, double* sv, double* v1, double* v3) {
     sv[0] = sv[1] = sv[2] = 0.0;
     double nrm = 0.0;
 #pragma unroll
@@ -350,7 +243,7 @@ HG_HD bool hg_singular(const double* H, const hg_cam& cam, double* Hn, double* s
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = i; j < 3; j++) S[i][j] = S[j][i] = (Hn[i] * Hn[j] + Hn[3 + i] * Hn[3 + j]) + Hn[6 + i] * Hn[6 + j];
-    hg_jacobi<3, 8>(S, V);
+    geo_jacobi<3, 8>(S, V);
     const double e0 = S[0][0], e1 = S[1][1], e2 = S[2][2];
     // hi: the largest (first of equals), lo: the smallest (last of equals), mid: the remaining one
     int hi = 0, lo = 2;
@@ -376,17 +269,17 @@ HG_HD bool hg_singular(const double* H, const hg_cam& cam, double* Hn, double* s
 // v2 = v3 x v1, u1 = unit(Hs v1), u2 = unit(Hs v2 - (u1 . Hs v2) u1), u3 = u1 x u2: orthonormal with det +1 to rounding.
 HG_HD void hg_nearest_rotation(const double* Hs, const double* v1, const double* v3, double* R) {
     double v2[3], u1[3], u2[3], u3[3], w3[3];
-    hg_cross(v3, v1, v2);
-    hg_unit(v2);
-    hg_cross(v1, v2, w3);                                        // v3 again, exactly orthogonal to v1 and v2
+    geo_cross(v3, v1, v2);
+    geo_unit(v2);
+    geo_cross(v1, v2, w3);                                        // v3 again, exactly orthogonal to v1 and v2
     hg_mv(Hs, v1, u1);
     hg_mv(Hs, v2, u2);
-    hg_unit(u1);
-    const double dp = hg_dot(u1, u2);
+    geo_unit(u1);
+    const double dp = geo_dot(u1, u2);
 #pragma unroll
     for (int i = 0; i < 3; i++) u2[i] -= dp * u1[i];
-    hg_unit(u2);
-    hg_cross(u1, u2, u3);
+    geo_unit(u2);
+    geo_cross(u1, u2, u3);
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -401,10 +294,10 @@ HG_HD void hg_nearest_rotation(const double* Hs, const double* v1, const double*
 // pose [48]: (Ra, ta), (Ra, -ta), (Rb, tb), (Rb, -tb) as row-major 3x4; normal [12]: na, -na, nb, -nb.
 HG_HD void hg_candidates(const double* Hs, double sg1, double sg3, const double* v1, const double* v3, double* pose, double* normal) {
     double v2[3], w1[3];
-    hg_cross(v3, v1, v2);
-    hg_unit(v2);
+    geo_cross(v3, v1, v2);
+    geo_unit(v2);
     hg_mv(Hs, v2, w1);
-    hg_unit(w1);
+    geo_unit(w1);
     const double ra = 1.0 - sg3 * sg3, rb = sg1 * sg1 - 1.0;
     const double a = sqrt(ra > 0.0 ? ra : 0.0), b = sqrt(rb > 0.0 ? rb : 0.0);
 #pragma unroll
@@ -413,14 +306,14 @@ HG_HD void hg_candidates(const double* Hs, double sg1, double sg3, const double*
         double u[3], n[3], hu[3], w2[3], w3[3], R[9], Rn[3], Hsn[3], t[3];
 #pragma unroll
         for (int i = 0; i < 3; i++) u[i] = a * v1[i] + bs * v3[i];
-        hg_unit(u);
-        hg_cross(v2, u, n);
+        geo_unit(u);
+        geo_cross(v2, u, n);
         hg_mv(Hs, u, hu);
-        const double dp = hg_dot(w1, hu);
+        const double dp = geo_dot(w1, hu);
 #pragma unroll
         for (int i = 0; i < 3; i++) w2[i] = hu[i] - dp * w1[i];
-        hg_unit(w2);
-        hg_cross(w1, w2, w3);
+        geo_unit(w2);
+        geo_cross(w1, w2, w3);
 #pragma unroll
         for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -429,7 +322,7 @@ HG_HD void hg_candidates(const double* Hs, double sg1, double sg3, const double*
         hg_mv(Hs, n, Hsn);
 #pragma unroll
         for (int i = 0; i < 3; i++) t[i] = Hsn[i] - Rn[i];
-        const double len = sqrt(hg_dot(t, t));
+        const double len = sqrt(geo_dot(t, t));
         const bool has = len > 0.0 && isfinite(len);
         const double sg = hg_fix_sign(n);
 #pragma unroll
@@ -462,7 +355,7 @@ HG_HD void hg_adjugate(const double* h, double* a) {
     a[6] = h[3] * h[7] - h[4] * h[6]; a[7] = h[1] * h[6] - h[0] * h[7]; a[8] = h[0] * h[4] - h[1] * h[3];
 }
 // F = K^-T E K^-1, operation by operation as the header states it
-HG_HD void hg_fundamental(const double* E, const hg_cam& cam, double* F) {
+HG_HD void hg_fundamental(const double* E, const geo_cam& cam, double* F) {
     double A[9];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -519,14 +412,6 @@ __global__ __launch_bounds__(HG_LANES) void hg_fourpoint_kernel(int S, const dou
     for (int i = 0; i < 9; i++) H[(size_t)s * 9 + i] = T[i];
 }
 
-// pair b's slice of the concatenated arrays, never outside [0, M)
-__device__ __forceinline__ void hg_range(const int* offsets, int b, int M, int* first, int* last, bool* bad) {
-    const int lo = offsets[b], hi = offsets[b + 1];
-    *first = min(max(lo, 0), M);
-    *last = min(max(hi, *first), M);
-    *bad = *first != lo || *last != hi;
-}
-
 // grid (ceil(H / 256), B): lane = one hypothesis of pair blockIdx.y; the pair's matches pass through LDS in chunks and are
 // read as broadcasts (a wave's 64 hypotheses score the same match at the same time)
 __global__ __launch_bounds__(HG_THREADS) void hg_ransac_kernel(const int* __restrict__ offsets, int M, const double* __restrict__ px1_all,
@@ -537,7 +422,7 @@ __global__ __launch_bounds__(HG_THREADS) void hg_ransac_kernel(const int* __rest
     __shared__ int s_models;
     const int b = blockIdx.y, tid = threadIdx.x, h = blockIdx.x * HG_THREADS + tid;
     int first, last; bool bad;
-    hg_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     const int n = last - first;
     if (n < 4) return;                                  // block-uniform
     if (tid == 0) { s_key = 0ull; s_models = 0; }
@@ -565,7 +450,7 @@ __global__ __launch_bounds__(HG_THREADS) void hg_ransac_kernel(const int* __rest
         }
     }
     if (h < H && has) {
-        atomicMax(&s_key, hg_key(count, h));
+        atomicMax(&s_key, geo_key2(count, h));
         atomicAdd(&s_models, 1);
     }
     __syncthreads();
@@ -584,7 +469,7 @@ __global__ __launch_bounds__(HG_LANES) void hg_ransac_result_kernel(const int* _
                                                                     unsigned int* __restrict__ index_errors) {
     const int b = blockIdx.x, lane = threadIdx.x;
     int first, last; bool bad;
-    hg_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     if (bad && lane == 0) atomicAdd(index_errors, 1u);
     const int n = last - first;
     const unsigned long long key = n >= 4 ? keys[b] : 0ull;
@@ -594,7 +479,7 @@ __global__ __launch_bounds__(HG_LANES) void hg_ransac_result_kernel(const int* _
         if (lane == 0) { stats[4 * b] = 0; stats[4 * b + 1] = -1; stats[4 * b + 2] = -1; stats[4 * b + 3] = n >= 4 ? models[b] : 0; }
         return;
     }
-    const int count = (int)(key >> 32), h = HG_H_MAX - (int)(key & 0xFFFFFFFFull);
+    const int count = geo_key_count(key), h = geo_key2_h(key);
     const double* px1 = px1_all + 2 * (size_t)first;
     const double* px2 = px2_all + 2 * (size_t)first;
     double T[9];
@@ -611,7 +496,7 @@ __global__ __launch_bounds__(HG_LANES) void hg_ransac_result_kernel(const int* _
 // grid B, one block per pair: every thread decomposes the pair's H (the same arithmetic in every lane, so every branch on
 // its outcome is block-uniform), the matches are shared out for the two votes
 __global__ __launch_bounds__(HG_THREADS) void hg_decompose_kernel(const int* __restrict__ offsets, int M, const double* __restrict__ px1,
-                                                                  const double* __restrict__ px2, hg_cam cam, const double* __restrict__ H_all,
+                                                                  const double* __restrict__ px2, geo_cam cam, const double* __restrict__ H_all,
                                                                   const uint8_t* __restrict__ inlier_in, double dist,
                                                                   double* __restrict__ pose_all, double* __restrict__ normal_all,
                                                                   int* __restrict__ count_all, double* __restrict__ pose,
@@ -621,7 +506,7 @@ __global__ __launch_bounds__(HG_THREADS) void hg_decompose_kernel(const int* __r
     __shared__ int s_count[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     int first, last; bool bad;
-    hg_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     if (bad && tid == 0) atomicAdd(index_errors, 1u);
     const int n = last - first;
     double H[9], Hn[9], sv[3], v1[3], v3[3];
@@ -678,10 +563,10 @@ __global__ __launch_bounds__(HG_THREADS) void hg_decompose_kernel(const int* __r
         if (inlier_in && !inlier_in[first + i]) continue;
         const double a = (px1[2 * (size_t)(first + i)] - cam.cx) / cam.fx, bb = (px1[2 * (size_t)(first + i) + 1] - cam.cy) / cam.fy;
         const double c = (px2[2 * (size_t)(first + i)] - cam.cx) / cam.fx, d = (px2[2 * (size_t)(first + i) + 1] - cam.cy) / cam.fy;
-        c0 += hg_cheirality(P, a, bb, c, d, dist) ? 1 : 0;
-        c1 += hg_cheirality(P + 12, a, bb, c, d, dist) ? 1 : 0;
-        c2 += hg_cheirality(P + 24, a, bb, c, d, dist) ? 1 : 0;
-        c3 += hg_cheirality(P + 36, a, bb, c, d, dist) ? 1 : 0;
+        c0 += geo_cheirality(P, a, bb, c, d, dist) ? 1 : 0;
+        c1 += geo_cheirality(P + 12, a, bb, c, d, dist) ? 1 : 0;
+        c2 += geo_cheirality(P + 24, a, bb, c, d, dist) ? 1 : 0;
+        c3 += geo_cheirality(P + 36, a, bb, c, d, dist) ? 1 : 0;
     }
     if (c0) atomicAdd(&s_count[0], c0);
     if (c1) atomicAdd(&s_count[1], c1);
@@ -703,7 +588,7 @@ __global__ __launch_bounds__(HG_THREADS) void hg_decompose_kernel(const int* __r
         if (inlier_in && !inlier_in[first + i]) continue;
         const double a = (px1[2 * (size_t)(first + i)] - cam.cx) / cam.fx, bb = (px1[2 * (size_t)(first + i) + 1] - cam.cy) / cam.fy;
         const double c = (px2[2 * (size_t)(first + i)] - cam.cx) / cam.fx, d = (px2[2 * (size_t)(first + i) + 1] - cam.cy) / cam.fy;
-        inlier_out[first + i] = hg_cheirality(W, a, bb, c, d, dist) ? 1 : 0;
+        inlier_out[first + i] = geo_cheirality(W, a, bb, c, d, dist) ? 1 : 0;
     }
     if (tid == 0) {
 #pragma unroll
@@ -718,13 +603,13 @@ __global__ __launch_bounds__(HG_THREADS) void hg_decompose_kernel(const int* __r
 
 // grid B, one block per pair: the matches shared out, the terms summed as 64-bit integers (exact whatever the order)
 __global__ __launch_bounds__(HG_THREADS) void hg_score_kernel(const int* __restrict__ offsets, int M, const double* __restrict__ px1,
-                                                              const double* __restrict__ px2, hg_cam cam, const double* __restrict__ H_all,
+                                                              const double* __restrict__ px2, geo_cam cam, const double* __restrict__ H_all,
                                                               const double* __restrict__ E_all, double sigma2, long long* __restrict__ score,
                                                               double* __restrict__ ratio, unsigned int* __restrict__ index_errors) {
     __shared__ unsigned long long s_sum[2];
     const int b = blockIdx.x, tid = threadIdx.x;
     int first, last; bool bad;
-    hg_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     if (bad && tid == 0) atomicAdd(index_errors, 1u);
     const int n = last - first;
     if (tid < 2) s_sum[tid] = 0ull;
@@ -764,7 +649,7 @@ extern "C" int slam_hg_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_off
                                   int H, double threshold_px, uint64_t seed, double* d_H, uint8_t* d_inlier, int32_t* d_stats) {
     SLAM_REQUIRE(ctx, "slam_hg_ransac_f64: null ctx");
     SLAM_REQUIRE(B >= 0 && B <= 65535 && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld; B <= 65535)", (long long)B, (long long)M);
-    SLAM_REQUIRE(H >= 1 && H <= HG_H_MAX, "H=%d out of range [1, 2^20]", H);
+    SLAM_REQUIRE(H >= 1 && H <= GEO_H_MAX, "H=%d out of range [1, 2^20]", H);
     SLAM_REQUIRE(threshold_px > 0.0, "threshold must be positive");
     if (B == 0) return SLAM_OK;
     SLAM_REQUIRE(d_offsets && d_H && d_stats && (M == 0 || (d_px1 && d_px2 && d_inlier)), "slam_hg_ransac_f64: null device pointer");
@@ -799,7 +684,7 @@ extern "C" int slam_hg_decompose_f64(slam_ctx* ctx, int64_t B, const int32_t* d_
                      (M == 0 || (d_px1 && d_px2 && d_inlier_out)),
                  "slam_hg_decompose_f64: null device pointer");
     SLAM_HIP(hipSetDevice(ctx->device));
-    const hg_cam cam = {fx, fy, cx, cy};
+    const geo_cam cam = {fx, fy, cx, cy};
     if (M > 0) SLAM_HIP(hipMemsetAsync(d_inlier_out, 0, (size_t)M, ctx->stream));
     hg_decompose_kernel<<<(unsigned)B, HG_THREADS, 0, ctx->stream>>>(d_offsets, (int)M, d_px1, d_px2, cam, d_H, d_inlier_in, distance_thresh,
                                                                     d_pose_all, d_normal_all, d_count, d_pose, d_sv, d_inlier_out, d_stats,
@@ -813,12 +698,12 @@ extern "C" int slam_hg_model_score_f64(slam_ctx* ctx, int64_t B, const int32_t* 
                                        int64_t* d_score, double* d_ratio) {
     SLAM_REQUIRE(ctx, "slam_hg_model_score_f64: null ctx");
     SLAM_REQUIRE(B >= 0 && B <= (1 << 20) && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld)", (long long)B, (long long)M);
-    SLAM_REQUIRE(fx > 0.0 && fy > 0.0 && sigma > 0.0 && sigma * sigma > 0.0 && sigma * sigma < HG_BIG,
+    SLAM_REQUIRE(fx > 0.0 && fy > 0.0 && sigma > 0.0 && sigma * sigma > 0.0 && sigma * sigma < GEO_BIG,
                  "focal lengths and sigma must be positive (sigma^2 a positive finite double)");
     if (B == 0) return SLAM_OK;
     SLAM_REQUIRE(d_offsets && d_H && d_E && d_score && d_ratio && (M == 0 || (d_px1 && d_px2)), "slam_hg_model_score_f64: null device pointer");
     SLAM_HIP(hipSetDevice(ctx->device));
-    const hg_cam cam = {fx, fy, cx, cy};
+    const geo_cam cam = {fx, fy, cx, cy};
     hg_score_kernel<<<(unsigned)B, HG_THREADS, 0, ctx->stream>>>(d_offsets, (int)M, d_px1, d_px2, cam, d_H, d_E, sigma * sigma,
                                                                 (long long*)d_score, d_ratio, slam_index_error_counter(ctx));
     SLAM_HIP(hipGetLastError());

@@ -30,13 +30,14 @@
 #endif
 #include <math.h>
 #include <stdint.h>
+#include "geometry_common.h"         // sampler, range clamp, intrinsics, model key, three-vectors, GEO_BIG / GEO_FLAT
 
 #pragma clang fp contract(off)
 
 #define PNP_HD __host__ __device__ __forceinline__
-#define PNP_H_MAX (1 << 20)
-#define PNP_BIG 1e200                // a sample whose squared coordinates sum to this or more (or to NaN) has no solution
-#define PNP_FLAT 1e-20               // sin^2 of the smallest angle of a triangle / between two bearings that is still solved
+// the shared sampler and intrinsics under this file's names, as its host twin calls them (three correspondences per sample)
+#define pnp_draw_sample geo_draw_sample<3>
+typedef geo_cam pnp_cam;
 #define PNP_POLISH_STEPS 3
 
 // ---- real roots of a quartic ------------------------------------------------------------------------------------------------
@@ -138,23 +139,15 @@ PNP_HD int pnp_quartic_roots(const double* p, double* r) {      // p[5] ascendin
 }
 
 // ---- the minimal solver -------------------------------------------------------------------------------------------------------
-PNP_HD double pnp_dot(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-PNP_HD void pnp_cross(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
-PNP_HD void pnp_unit(double* a) {
-    const double inv = 1.0 / sqrt(pnp_dot(a, a));
-    a[0] *= inv; a[1] *= inv; a[2] *= inv;
-}
 // orthonormal frame of the triangle (p1, p2, p3): e1 along p2 - p1, e3 its normal, e2 = e3 x e1
 PNP_HD void pnp_frame(const double* p1, const double* p2, const double* p3, double* e1, double* e2, double* e3) {
     double d[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) { e1[i] = p2[i] - p1[i]; d[i] = p3[i] - p1[i]; }
-    pnp_cross(e1, d, e3);
-    pnp_unit(e1);
-    pnp_unit(e3);
-    pnp_cross(e3, e1, e2);
+    geo_cross(e1, d, e3);
+    geo_unit(e1);
+    geo_unit(e3);
+    geo_cross(e3, e1, e2);
 }
 // residuals of the three law-of-cosines equations at depths s; returns |F|^2
 PNP_HD double pnp_residual(const double* s, double ca, double cb, double cg, double a2, double b2, double c2, double* F) {
@@ -173,24 +166,24 @@ PNP_HD int pnp_p3p(const double* X, const double* x, double* pose) {
     for (int i = 0; i < 9; i++) big += X[i] * X[i];
 #pragma unroll
     for (int i = 0; i < 6; i++) big += x[i] * x[i];
-    if (!(big < PNP_BIG)) return 0;                              // NaN, inf, coordinates beyond 1e100
+    if (!(big < GEO_BIG)) return 0;                              // NaN, inf, coordinates beyond 1e100
     double f[3][3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         f[k][0] = x[2 * k]; f[k][1] = x[2 * k + 1]; f[k][2] = 1.0;
-        pnp_unit(f[k]);
+        geo_unit(f[k]);
     }
     double e12[3], e13[3], e23[3], nw[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) { e12[i] = X[3 + i] - X[i]; e13[i] = X[6 + i] - X[i]; e23[i] = X[6 + i] - X[3 + i]; }
-    const double a2 = pnp_dot(e23, e23), b2 = pnp_dot(e13, e13), c2 = pnp_dot(e12, e12);
-    pnp_cross(e12, e13, nw);
-    if (!(pnp_dot(nw, nw) > PNP_FLAT * (c2 * b2)) || !(a2 > 0.0)) return 0;          // repeated or collinear world points
-    const double ca = pnp_dot(f[1], f[2]), cb = pnp_dot(f[0], f[2]), cg = pnp_dot(f[0], f[1]);
+    const double a2 = geo_dot(e23, e23), b2 = geo_dot(e13, e13), c2 = geo_dot(e12, e12);
+    geo_cross(e12, e13, nw);
+    if (!(geo_dot(nw, nw) > GEO_FLAT * (c2 * b2)) || !(a2 > 0.0)) return 0;          // repeated or collinear world points
+    const double ca = geo_dot(f[1], f[2]), cb = geo_dot(f[0], f[2]), cg = geo_dot(f[0], f[1]);
     {
         double c01[3], c02[3], c12[3];
-        pnp_cross(f[0], f[1], c01); pnp_cross(f[0], f[2], c02); pnp_cross(f[1], f[2], c12);
-        if (!(pnp_dot(c01, c01) > PNP_FLAT && pnp_dot(c02, c02) > PNP_FLAT && pnp_dot(c12, c12) > PNP_FLAT)) return 0;   // repeated image points
+        geo_cross(f[0], f[1], c01); geo_cross(f[0], f[2], c02); geo_cross(f[1], f[2], c12);
+        if (!(geo_dot(c01, c01) > GEO_FLAT && geo_dot(c02, c02) > GEO_FLAT && geo_dot(c12, c12) > GEO_FLAT)) return 0;   // repeated image points
     }
     const double K = (a2 - c2) / b2, q = c2 / b2;
     const double Np[3] = {1.0 + K, -2.0 * (K * cb), K - 1.0};
@@ -281,42 +274,17 @@ PNP_HD int pnp_p3p(const double* X, const double* x, double* pose) {
 }
 
 // ---- scoring and sampling (stated in the header) ---------------------------------------------------------------------------
-struct pnp_cam { double fx, fy, cx, cy; };
-PNP_HD bool pnp_inlier(const double* T, double X, double Y, double Z, double u, double v, const pnp_cam& cam, double thr2) {
+PNP_HD bool pnp_inlier(const double* T, double X, double Y, double Z, double u, double v, const geo_cam& cam, double thr2) {
     const double xc = ((T[0] * X + T[1] * Y) + T[2] * Z) + T[3];
     const double yc = ((T[4] * X + T[5] * Y) + T[6] * Z) + T[7];
     const double zc = ((T[8] * X + T[9] * Y) + T[10] * Z) + T[11];
     const double du = (cam.fx * (xc / zc) + cam.cx) - u, dv = (cam.fy * (yc / zc) + cam.cy) - v;
     return zc > 0.0 && (du * du + dv * dv) < thr2;
 }
-PNP_HD uint64_t pnp_splitmix(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-PNP_HD uint64_t pnp_draw_word(uint64_t seed, uint64_t h, uint64_t d) {
-    return pnp_splitmix(pnp_splitmix(seed ^ (h * 0xD1B54A32D192ED03ull)) ^ (d * 0x8CB92BA72F3D8DD7ull));
-}
-PNP_HD void pnp_draw_sample(uint64_t seed, int h, int n, int* idx) {      // n >= 3
-    uint64_t d = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        int i;
-        bool dup;
-        do {
-            i = (int)(((pnp_draw_word(seed, (uint64_t)h, d++) >> 32) * (uint64_t)n) >> 32);
-            dup = false;
-#pragma unroll
-            for (int j = 0; j < 3; j++) dup = dup || (j < k && idx[j] == i);
-        } while (dup);
-        idx[k] = i;
-    }
-}
 // hypothesis h of a candidate of n correspondences X [n,3] / px [n,2]: its sample drawn, normalised and solved
-PNP_HD int pnp_solve_hypothesis(const double* X, const double* px, int n, const pnp_cam& cam, uint64_t seed, int h, double* pose) {
+PNP_HD int pnp_solve_hypothesis(const double* X, const double* px, int n, const geo_cam& cam, uint64_t seed, int h, double* pose) {
     int idx[3] = {0, 0, 0};
-    pnp_draw_sample(seed, h, n, idx);
+    geo_draw_sample<3>(seed, h, n, idx);
     double P[9], x[6];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -348,22 +316,10 @@ __global__ __launch_bounds__(PNP_LANES) void pnp_p3p_kernel(int S, const double*
     for (int i = 0; i < 48; i++) pose[(size_t)s * 48 + i] = T[i];
 }
 
-// candidate b's slice of the concatenated arrays, never outside [0, M)
-__device__ __forceinline__ void pnp_range(const int* offsets, int b, int M, int* first, int* last, bool* bad) {
-    const int lo = offsets[b], hi = offsets[b + 1];
-    *first = min(max(lo, 0), M);
-    *last = min(max(hi, *first), M);
-    *bad = *first != lo || *last != hi;
-}
-// key of a scored model: more inliers first, then the lower hypothesis, then the lower solution; 0 = no model
-__device__ __forceinline__ unsigned long long pnp_key(int count, int h, int sol) {
-    return ((unsigned long long)(unsigned)count << 32) | ((unsigned long long)(PNP_H_MAX - h) << 4) | (unsigned long long)(15 - sol);
-}
-
 // grid (ceil(H / 256), B): lane = one hypothesis of candidate blockIdx.y; the candidate's correspondences pass through LDS in
 // chunks and are read as broadcasts (a wave's 64 hypotheses score the same correspondence at the same time)
 __global__ __launch_bounds__(PNP_THREADS) void pnp_ransac_kernel(const int* __restrict__ offsets, int M, const double* __restrict__ X_all,
-                                                                 const double* __restrict__ px_all, pnp_cam cam, int H, double thr2,
+                                                                 const double* __restrict__ px_all, geo_cam cam, int H, double thr2,
                                                                  uint64_t seed, unsigned long long* __restrict__ keys,
                                                                  int* __restrict__ models) {
     __shared__ double s_pt[PNP_CHUNK * 5];
@@ -371,7 +327,7 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_ransac_kernel(const int* __re
     __shared__ int s_models;
     const int b = blockIdx.y, tid = threadIdx.x, h = blockIdx.x * PNP_THREADS + tid;
     int first, last; bool bad;
-    pnp_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     const int n = last - first;
     if (n < 3) return;                                  // block-uniform
     if (tid == 0) { s_key = 0ull; s_models = 0; }
@@ -401,7 +357,7 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_ransac_kernel(const int* __re
     const int cnt[4] = {c0, c1, c2, c3};
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-        const unsigned long long k = r < ns ? pnp_key(cnt[r], h, r) : 0ull;
+        const unsigned long long k = r < ns ? geo_key3(cnt[r], h, r) : 0ull;
         best = k > best ? k : best;
     }
     if (h < H) {
@@ -417,14 +373,14 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_ransac_kernel(const int* __re
 
 // grid B: the winner of candidate b solved again (every lane the same hypothesis), its pose, mask and stats written
 __global__ __launch_bounds__(PNP_LANES) void pnp_ransac_result_kernel(const int* __restrict__ offsets, int M, const double* __restrict__ X_all,
-                                                                      const double* __restrict__ px_all, pnp_cam cam, double thr2, uint64_t seed,
+                                                                      const double* __restrict__ px_all, geo_cam cam, double thr2, uint64_t seed,
                                                                       const unsigned long long* __restrict__ keys,
                                                                       const int* __restrict__ models, double* __restrict__ pose_out,
                                                                       uint8_t* __restrict__ inlier, int* __restrict__ stats,
                                                                       unsigned int* __restrict__ index_errors) {
     const int b = blockIdx.x, lane = threadIdx.x;
     int first, last; bool bad;
-    pnp_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     if (bad && lane == 0) atomicAdd(index_errors, 1u);
     const int n = last - first;
     const unsigned long long key = n >= 3 ? keys[b] : 0ull;
@@ -434,7 +390,9 @@ __global__ __launch_bounds__(PNP_LANES) void pnp_ransac_result_kernel(const int*
         if (lane == 0) { stats[4 * b] = 0; stats[4 * b + 1] = -1; stats[4 * b + 2] = -1; stats[4 * b + 3] = 0; }
         return;
     }
-    const int count = (int)(key >> 32), h = PNP_H_MAX - (int)((key >> 4) & 0xFFFFFFFull), sol = 15 - (int)(key & 15);
+    // geo_key3 unpacked in place, not through geo_key_count / geo_key3_h / geo_key3_sub: with the accessors this kernel's
+    // instruction stream changes (6658 -> 6626 instructions), every other result kernel's does not
+    const int count = (int)(key >> 32), h = GEO_H_MAX - (int)((key >> 4) & 0xFFFFFFFull), sol = 15 - (int)(key & 15);
     const double* X = X_all + 3 * (size_t)first;
     const double* px = px_all + 2 * (size_t)first;
     double T4[48], T[12];
@@ -468,7 +426,7 @@ extern "C" int slam_pnp_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_of
                                    uint8_t* d_inlier, int32_t* d_stats) {
     SLAM_REQUIRE(ctx, "slam_pnp_ransac_f64: null ctx");
     SLAM_REQUIRE(B >= 0 && B <= 65535 && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld; B <= 65535)", (long long)B, (long long)M);
-    SLAM_REQUIRE(H >= 1 && H <= PNP_H_MAX, "H=%d out of range [1, 2^20]", H);
+    SLAM_REQUIRE(H >= 1 && H <= GEO_H_MAX, "H=%d out of range [1, 2^20]", H);
     SLAM_REQUIRE(threshold_px > 0.0 && fx > 0.0 && fy > 0.0, "threshold and focal lengths must be positive");
     if (B == 0) return SLAM_OK;
     SLAM_REQUIRE(d_offsets && d_pose && d_stats && (M == 0 || (d_X && d_px && d_inlier)), "slam_pnp_ransac_f64: null device pointer");
@@ -479,7 +437,7 @@ extern "C" int slam_pnp_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_of
     if (int rc = slam_workspace(ctx, key_bytes + (uint64_t)B * 4, &ws)) return rc;
     unsigned long long* keys = (unsigned long long*)ws;
     int* models = (int*)((char*)ws + key_bytes);
-    const pnp_cam cam = {fx, fy, cx, cy};
+    const geo_cam cam = {fx, fy, cx, cy};
     const double thr2 = threshold_px * threshold_px;
     SLAM_HIP(hipMemsetAsync(ws, 0, (size_t)(key_bytes + (uint64_t)B * 4), ctx->stream));
     if (M > 0) SLAM_HIP(hipMemsetAsync(d_inlier, 0, (size_t)M, ctx->stream));

@@ -30,52 +30,19 @@
 #endif
 #include <math.h>
 #include <stdint.h>
+#include "geometry_common.h"         // sampler, Jacobi, range clamp, intrinsics, model key, dot, GEO_BIG / GEO_FLAT
 
 #pragma clang fp contract(off)
 
 #define S3_HD __host__ __device__ __forceinline__
-#define S3_H_MAX (1 << 20)
-#define S3_BIG 1e200                 // data whose squares sum to this or more (or to NaN) has no model
-#define S3_FLAT 1e-20                // sin^2 of the smallest angle of a triangle that is still solved (pnp.hip's rule)
+// the shared sampler and intrinsics under this file's names, as its host twin calls them (three correspondences per sample)
+#define s3_draw_sample geo_draw_sample<3>
+typedef geo_cam s3_cam;
 #define S3_GAP 1e-10                 // refit: (l1 - l2) / l1 of Horn's matrix below which the points count as collinear (sin, not sin^2)
 #define S3_SWEEPS 12                 // cyclic Jacobi sweeps of the 4x4 (converged after 5 - 7 in f64; the rest are no-ops)
 #define S3_REFIT_THREADS 256         // lanes of the refit's stated summation order (the host twin restates it)
 
 // ---- Horn's closed form from the sums -----------------------------------------------------------------------------------------
-// private copy of hg_jacobi (homography.hip): A symmetric, overwritten by its diagonal form; V its eigenvectors by columns
-template <int N, int SWEEPS>
-S3_HD void s3_jacobi(double (&A)[N][N], double (&V)[N][N]) {
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < N; j++) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < SWEEPS; sweep++) {
-#pragma unroll
-        for (int p = 0; p < N - 1; p++)
-#pragma unroll
-            for (int q = p + 1; q < N; q++) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                A[p][p] -= t * apq;
-                A[q][q] += t * apq;
-                A[p][q] = A[q][p] = 0.0;
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    if (k != p && k != q) {
-                        const double akp = A[k][p], akq = A[k][q];
-                        A[k][p] = A[p][k] = c * akp - s * akq;
-                        A[k][q] = A[q][k] = s * akp + c * akq;
-                    }
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
 S3_HD void s3_identity(double* model) {
 #pragma unroll
     for (int i = 0; i < 12; i++) model[i] = (i % 5 == 0) ? 1.0 : 0.0;
@@ -91,7 +58,7 @@ S3_HD bool s3_from_sums(const double* c1, const double* c2, const double (&M)[3]
     N[0][0] = (Sxx + Syy) + Szz; N[1][1] = (Sxx - Syy) - Szz; N[2][2] = (Syy - Sxx) - Szz; N[3][3] = (Szz - Sxx) - Syy;
     N[0][1] = N[1][0] = Syz - Szy; N[0][2] = N[2][0] = Szx - Sxz; N[0][3] = N[3][0] = Sxy - Syx;
     N[1][2] = N[2][1] = Sxy + Syx; N[1][3] = N[3][1] = Szx + Sxz; N[2][3] = N[3][2] = Syz + Szy;
-    s3_jacobi<4, S3_SWEEPS>(N, V);
+    geo_jacobi<4, S3_SWEEPS>(N, V);
     double best = N[0][0], q[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
     int arg = 0;
 #pragma unroll
@@ -116,14 +83,14 @@ S3_HD bool s3_from_sums(const double* c1, const double* c2, const double (&M)[3]
     const double r1 = (R[3] * M[1][0] + R[4] * M[1][1]) + R[5] * M[1][2];
     const double r2 = (R[6] * M[2][0] + R[7] * M[2][1]) + R[8] * M[2][2];
     const double s = fix_scale ? 1.0 : ((r0 + r1) + r2) / d1;
-    if (!(s > 0.0 && s < S3_BIG)) return false;
+    if (!(s > 0.0 && s < GEO_BIG)) return false;
     double T[3], chk = s;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         T[i] = c2[i] - s * ((R[3 * i] * c1[0] + R[3 * i + 1] * c1[1]) + R[3 * i + 2] * c1[2]);
         chk += ((fabs(R[3 * i]) + fabs(R[3 * i + 1])) + fabs(R[3 * i + 2])) + fabs(T[i]);
     }
-    if (!(chk < S3_BIG)) return false;
+    if (!(chk < GEO_BIG)) return false;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         model[4 * i] = R[3 * i]; model[4 * i + 1] = R[3 * i + 1]; model[4 * i + 2] = R[3 * i + 2]; model[4 * i + 3] = T[i];
@@ -133,15 +100,14 @@ S3_HD bool s3_from_sums(const double* c1, const double* c2, const double (&M)[3]
 }
 
 // ---- the minimal solver -------------------------------------------------------------------------------------------------------
-S3_HD double s3_dot(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 // a triangle that is neither repeated nor collinear (pnp.hip's rule on the world points)
 S3_HD bool s3_triangle(const double* P) {
     double e12[3], e13[3], e23[3], nw[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) { e12[i] = P[3 + i] - P[i]; e13[i] = P[6 + i] - P[i]; e23[i] = P[6 + i] - P[3 + i]; }
-    const double a2 = s3_dot(e23, e23), b2 = s3_dot(e13, e13), c2 = s3_dot(e12, e12);
-    nw[0] = e12[1] * e13[2] - e12[2] * e13[1]; nw[1] = e12[2] * e13[0] - e12[0] * e13[2]; nw[2] = e12[0] * e13[1] - e12[1] * e13[0];
-    return s3_dot(nw, nw) > S3_FLAT * (c2 * b2) && a2 > 0.0;
+    const double a2 = geo_dot(e23, e23), b2 = geo_dot(e13, e13), c2 = geo_dot(e12, e12);
+    geo_cross(e12, e13, nw);
+    return geo_dot(nw, nw) > GEO_FLAT * (c2 * b2) && a2 > 0.0;
 }
 // P1, P2 [9]: three points of each set; model [13] (the identity with s = 1 when there is none)
 S3_HD bool s3_threepoint(const double* P1, const double* P2, int fix_scale, double* model) {
@@ -151,7 +117,7 @@ S3_HD bool s3_threepoint(const double* P1, const double* P2, int fix_scale, doub
     for (int i = 0; i < 9; i++) big += P1[i] * P1[i];
 #pragma unroll
     for (int i = 0; i < 9; i++) big += P2[i] * P2[i];
-    if (!(big < S3_BIG)) return false;                           // NaN, inf, coordinates beyond 1e100
+    if (!(big < GEO_BIG)) return false;                           // NaN, inf, coordinates beyond 1e100
     if (!(s3_triangle(P1) && s3_triangle(P2))) return false;
     double c1[3], c2[3], a[3][3], b[3][3], M[3][3], l[2];
 #pragma unroll
@@ -165,15 +131,14 @@ S3_HD bool s3_threepoint(const double* P1, const double* P2, int fix_scale, doub
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) M[i][j] = (b[0][i] * a[0][j] + b[1][i] * a[1][j]) + b[2][i] * a[2][j];
-    const double d1 = (s3_dot(a[0], a[0]) + s3_dot(a[1], a[1])) + s3_dot(a[2], a[2]);
+    const double d1 = (geo_dot(a[0], a[0]) + geo_dot(a[1], a[1])) + geo_dot(a[2], a[2]);
     return s3_from_sums(c1, c2, M, d1, fix_scale, model, l);
 }
 
 // ---- scoring and sampling (stated in the header) ---------------------------------------------------------------------------
-struct s3_cam { double fx, fy, cx, cy; };
 // what a correspondence contributes whatever the hypothesis, c [12]: X1, X2, the projections (u1, v1), (u2, v2) of both and
 // the two gates g1, g2 (0 when one of the two points is not in front of its camera: no squared error is below 0)
-S3_HD void s3_stage(const double* x1, const double* x2, double sg1, double sg2, const s3_cam& cam, double chi2, double* c) {
+S3_HD void s3_stage(const double* x1, const double* x2, double sg1, double sg2, const geo_cam& cam, double chi2, double* c) {
     c[0] = x1[0]; c[1] = x1[1]; c[2] = x1[2]; c[3] = x2[0]; c[4] = x2[1]; c[5] = x2[2];
     c[6] = cam.fx * (x1[0] / x1[2]) + cam.cx; c[7] = cam.fy * (x1[1] / x1[2]) + cam.cy;
     c[8] = cam.fx * (x2[0] / x2[2]) + cam.cx; c[9] = cam.fy * (x2[1] / x2[2]) + cam.cy;
@@ -193,7 +158,7 @@ S3_HD void s3_scoring_form(const double* model, bool ok, double* m) {
         m[9 + i] = ok ? model[4 * i + 3] : 0.0;
     }
 }
-S3_HD bool s3_inlier(const double* m, const double* c, const s3_cam& cam) {
+S3_HD bool s3_inlier(const double* m, const double* c, const geo_cam& cam) {
     const double* A = m;
     const double* t = m + 9;
     const double* R = m + 12;
@@ -208,34 +173,10 @@ S3_HD bool s3_inlier(const double* m, const double* c, const s3_cam& cam) {
     const double du1 = (cam.fx * (wx / wz) + cam.cx) - c[6], dv1 = (cam.fy * (wy / wz) + cam.cy) - c[7];
     return z > 0.0 && wz > 0.0 && (du2 * du2 + dv2 * dv2) < c[11] && (du1 * du1 + dv1 * dv1) < c[10];
 }
-S3_HD uint64_t s3_splitmix(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-S3_HD uint64_t s3_draw_word(uint64_t seed, uint64_t h, uint64_t d) {
-    return s3_splitmix(s3_splitmix(seed ^ (h * 0xD1B54A32D192ED03ull)) ^ (d * 0x8CB92BA72F3D8DD7ull));
-}
-S3_HD void s3_draw_sample(uint64_t seed, int h, int n, int* idx) {      // n >= 3
-    uint64_t d = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        int i;
-        bool dup;
-        do {
-            i = (int)(((s3_draw_word(seed, (uint64_t)h, d++) >> 32) * (uint64_t)n) >> 32);
-            dup = false;
-#pragma unroll
-            for (int j = 0; j < 3; j++) dup = dup || (j < k && idx[j] == i);
-        } while (dup);
-        idx[k] = i;
-    }
-}
 // hypothesis h of a candidate of n correspondences X1 / X2 [n,3]: its sample drawn and solved
 S3_HD bool s3_solve_hypothesis(const double* X1, const double* X2, int n, int fix_scale, uint64_t seed, int h, double* model) {
     int idx[3] = {0, 0, 0};
-    s3_draw_sample(seed, h, n, idx);
+    geo_draw_sample<3>(seed, h, n, idx);
     double P1[9], P2[9];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -245,10 +186,6 @@ S3_HD bool s3_solve_hypothesis(const double* X1, const double* X2, int n, int fi
         P2[3 * k] = q[0]; P2[3 * k + 1] = q[1]; P2[3 * k + 2] = q[2];
     }
     return s3_threepoint(P1, P2, fix_scale, model);
-}
-// key of a scored model: more inliers first, then the lower hypothesis; 0 = no model
-S3_HD unsigned long long s3_key(int count, int h) {
-    return ((unsigned long long)(unsigned)count << 32) | (unsigned long long)(S3_H_MAX - h);
 }
 
 // ---- the refit's pieces: what one lane adds per correspondence, and the model from the combined sums ------------------------
@@ -264,15 +201,15 @@ S3_HD void s3_acc_centred(double* a, const double* x1, const double* x2, const d
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) a[3 * i + j] += q[i] * p[j];
-    a[9] += s3_dot(p, p);
-    a[10] += s3_dot(q, q);
+    a[9] += geo_dot(p, p);
+    a[10] += geo_dot(q, q);
 }
 // n selected points with centroids c [6] and centred sums a [11]; model [13] (the identity with s = 1 when not ok)
 S3_HD bool s3_refit_model(int n, const double* c, const double* a, int fix_scale, double* model) {
     s3_identity(model);
     if (n < 3) return false;
-    const double chk = ((s3_dot(c, c) + s3_dot(c + 3, c + 3)) + a[9]) + a[10];
-    if (!(chk < S3_BIG) || !(a[9] > 0.0 && a[10] > 0.0)) return false;        // NaN / inf / beyond 1e100; all points of a set equal
+    const double chk = ((geo_dot(c, c) + geo_dot(c + 3, c + 3)) + a[9]) + a[10];
+    if (!(chk < GEO_BIG) || !(a[9] > 0.0 && a[10] > 0.0)) return false;        // NaN / inf / beyond 1e100; all points of a set equal
     double M[3][3], l[2], out[13];
 #pragma unroll
     for (int i = 0; i < 3; i++)
@@ -303,19 +240,11 @@ __global__ __launch_bounds__(S3_LANES) void s3_threepoint_kernel(int S, const do
     for (int i = 0; i < 13; i++) model[(size_t)s * 13 + i] = m[i];
 }
 
-// candidate b's slice of the concatenated arrays, never outside [0, M)
-__device__ __forceinline__ void s3_range(const int* offsets, int b, int M, int* first, int* last, bool* bad) {
-    const int lo = offsets[b], hi = offsets[b + 1];
-    *first = min(max(lo, 0), M);
-    *last = min(max(hi, *first), M);
-    *bad = *first != lo || *last != hi;
-}
-
 // grid (ceil(H / 256), B): lane = one hypothesis of candidate blockIdx.y; the candidate's correspondences pass through LDS in
 // chunks (staged once per block: the four projections of the points themselves do not depend on the hypothesis) and are
 // read as broadcasts
 __global__ __launch_bounds__(S3_THREADS) void s3_ransac_kernel(const int* __restrict__ offsets, int M, const double* __restrict__ X1_all,
-                                                               const double* __restrict__ X2_all, const double* __restrict__ sigma2, s3_cam cam,
+                                                               const double* __restrict__ X2_all, const double* __restrict__ sigma2, geo_cam cam,
                                                                int H, double chi2, int fix_scale, uint64_t seed,
                                                                unsigned long long* __restrict__ keys, int* __restrict__ models) {
     __shared__ __attribute__((aligned(16))) double s_c[S3_CHUNK * 12];
@@ -323,7 +252,7 @@ __global__ __launch_bounds__(S3_THREADS) void s3_ransac_kernel(const int* __rest
     __shared__ int s_models;
     const int b = blockIdx.y, tid = threadIdx.x, h = blockIdx.x * S3_THREADS + tid;
     int first, last; bool bad;
-    s3_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     const int n = last - first;
     if (n < 3) return;                                  // block-uniform
     if (tid == 0) { s_key = 0ull; s_models = 0; }
@@ -348,7 +277,7 @@ __global__ __launch_bounds__(S3_THREADS) void s3_ransac_kernel(const int* __rest
         for (int i = 0; i < cm; i++) count += s3_inlier(m, s_c + 12 * i, cam) ? 1 : 0;
     }
     if (h < H && ok) {
-        atomicMax(&s_key, s3_key(count, h));
+        atomicMax(&s_key, geo_key2(count, h));
         atomicAdd(&s_models, 1);
     }
     __syncthreads();
@@ -361,13 +290,13 @@ __global__ __launch_bounds__(S3_THREADS) void s3_ransac_kernel(const int* __rest
 // grid B: the winner of candidate b solved again (every lane the same hypothesis), its model, mask and stats written
 __global__ __launch_bounds__(S3_LANES) void s3_ransac_result_kernel(const int* __restrict__ offsets, int M, const double* __restrict__ X1_all,
                                                                     const double* __restrict__ X2_all, const double* __restrict__ sigma2,
-                                                                    s3_cam cam, double chi2, int fix_scale, uint64_t seed,
+                                                                    geo_cam cam, double chi2, int fix_scale, uint64_t seed,
                                                                     const unsigned long long* __restrict__ keys, const int* __restrict__ models,
                                                                     double* __restrict__ model_out, uint8_t* __restrict__ inlier,
                                                                     int* __restrict__ stats, unsigned int* __restrict__ index_errors) {
     const int b = blockIdx.x, lane = threadIdx.x;
     int first, last; bool bad;
-    s3_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     if (bad && lane == 0) atomicAdd(index_errors, 1u);
     const int n = last - first;
     const unsigned long long key = n >= 3 ? keys[b] : 0ull;
@@ -382,7 +311,7 @@ __global__ __launch_bounds__(S3_LANES) void s3_ransac_result_kernel(const int* _
         for (int i = lane; i < n; i += S3_LANES) inlier[first + i] = 0;
         return;
     }
-    const int count = (int)(key >> 32), h = S3_H_MAX - (int)(key & 0xFFFFFFFFull);
+    const int count = geo_key_count(key), h = geo_key2_h(key);
     const double* X1 = X1_all + 3 * (size_t)first;
     const double* X2 = X2_all + 3 * (size_t)first;
     const double* sg = sigma2 ? sigma2 + 2 * (size_t)first : nullptr;
@@ -426,7 +355,7 @@ __global__ __launch_bounds__(S3_REFIT_THREADS) void s3_refit_kernel(const int* _
     __shared__ int s_cnt[S3_REFIT_THREADS];
     const int b = blockIdx.x, tid = threadIdx.x;
     int first, last; bool bad;
-    s3_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     if (bad && tid == 0) atomicAdd(index_errors, 1u);
     const int n = last - first;
     const double* X1 = X1_all + 3 * (size_t)first;
@@ -487,7 +416,7 @@ extern "C" int slam_sim3_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_o
                                     uint64_t seed, double* d_model, uint8_t* d_inlier, int32_t* d_stats) {
     SLAM_REQUIRE(ctx, "slam_sim3_ransac_f64: null ctx");
     SLAM_REQUIRE(B >= 0 && B <= 65535 && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld; B <= 65535)", (long long)B, (long long)M);
-    SLAM_REQUIRE(H >= 1 && H <= S3_H_MAX, "H=%d out of range [1, 2^20]", H);
+    SLAM_REQUIRE(H >= 1 && H <= GEO_H_MAX, "H=%d out of range [1, 2^20]", H);
     SLAM_REQUIRE(chi2_gate > 0.0 && fx > 0.0 && fy > 0.0, "chi2 gate and focal lengths must be positive");
     if (B == 0) return SLAM_OK;
     SLAM_REQUIRE(d_offsets && d_model && d_stats && (M == 0 || (d_X1 && d_X2 && d_inlier)), "slam_sim3_ransac_f64: null device pointer");
@@ -498,7 +427,7 @@ extern "C" int slam_sim3_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_o
     if (int rc = slam_workspace(ctx, key_bytes + (uint64_t)B * 4, &ws)) return rc;
     unsigned long long* keys = (unsigned long long*)ws;
     int* models = (int*)((char*)ws + key_bytes);
-    const s3_cam cam = {fx, fy, cx, cy};
+    const geo_cam cam = {fx, fy, cx, cy};
     SLAM_HIP(hipMemsetAsync(ws, 0, (size_t)(key_bytes + (uint64_t)B * 4), ctx->stream));
     if (M > 0) SLAM_HIP(hipMemsetAsync(d_inlier, 0, (size_t)M, ctx->stream));
     s3_ransac_kernel<<<dim3((unsigned)((H + S3_THREADS - 1) / S3_THREADS), (unsigned)B), S3_THREADS, 0, ctx->stream>>>(

@@ -33,12 +33,16 @@
 #include "internal.h"
 #endif
 #include <math.h>
+#include "geometry_common.h"         // sampler, Jacobi, triangulation, cheirality, range clamp, intrinsics, model key
 
 #pragma clang fp contract(off)
 
 #define TV_LANES 64
 #define TV_LDS_PER_LANE 236          // doubles: 10x20 system (reused by the root finder and the result) + 4x9 null space
 #define TV_HD __host__ __device__ __forceinline__
+// the shared routines under this file's names, as its host twin calls them (the sample size is this file's: five matches)
+#define tv_draw_sample geo_draw_sample<5>
+#define tv_triangulate_point geo_triangulate_point
 #define TVL(i) lds[(i) * TV_LANES]
 // LDS layout per lane after the elimination (the system is dead by then)
 #define TV_DER 0                     // 66: coefficients of p and its ten derivatives (11 + 10 + ... + 1)
@@ -550,104 +554,7 @@ TV_HD double tv_sampson_sq(const double* E, double a, double b, double c, double
     const double r = c * l0 + d * l1 + l2;
     return r * r / (l0 * l0 + l1 * l1 + m0 * m0 + m1 * m1);
 }
-TV_HD uint64_t tv_splitmix(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-TV_HD uint64_t tv_draw_word(uint64_t seed, uint64_t h, uint64_t d) {
-    return tv_splitmix(tv_splitmix(seed ^ (h * 0xD1B54A32D192ED03ull)) ^ (d * 0x8CB92BA72F3D8DD7ull));
-}
-TV_HD void tv_draw_sample(uint64_t seed, int h, int n, int* idx) {      // n >= 5
-    uint64_t d = 0;
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        int i;
-        bool dup;
-        do {
-            i = (int)(((tv_draw_word(seed, (uint64_t)h, d++) >> 32) * (uint64_t)n) >> 32);
-            dup = false;
-#pragma unroll
-            for (int j = 0; j < 5; j++) dup = dup || (j < k && idx[j] == i);
-        } while (dup);
-        idx[k] = i;
-    }
-}
 
-// ---- small symmetric eigenproblems (cyclic Jacobi, fixed sweep count: deterministic) ------------------------------------------
-template <int N, int SWEEPS>
-TV_HD void tv_jacobi(double (&A)[N][N], double (&V)[N][N]) {
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < N; j++) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < SWEEPS; sweep++) {
-#pragma unroll
-        for (int p = 0; p < N - 1; p++)
-#pragma unroll
-            for (int q = p + 1; q < N; q++) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                A[p][p] -= t * apq;
-                A[q][q] += t * apq;
-                A[p][q] = A[q][p] = 0.0;
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    if (k != p && k != q) {
-                        const double akp = A[k][p], akq = A[k][q];
-                        A[k][p] = A[p][k] = c * akp - s * akq;
-                        A[k][q] = A[q][k] = s * akp + c * akq;
-                    }
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
-
-// DLT triangulation of one point (cv2.triangulatePoints): v = unit eigenvector of the smallest eigenvalue of A^T A, v[3] >= 0
-TV_HD void tv_triangulate_point(const double* P1, const double* P2, double a, double b, double c, double d, double* v) {
-    double A[4][4], S[4][4], V[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        A[0][j] = a * P1[8 + j] - P1[j];
-        A[1][j] = b * P1[8 + j] - P1[4 + j];
-        A[2][j] = c * P2[8 + j] - P2[j];
-        A[3][j] = d * P2[8 + j] - P2[4 + j];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = i; j < 4; j++) S[i][j] = S[j][i] = ((A[0][i] * A[0][j] + A[1][i] * A[1][j]) + A[2][i] * A[2][j]) + A[3][i] * A[3][j];
-    tv_jacobi<4, 10>(S, V);
-    double best = S[0][0];
-#pragma unroll
-    for (int k = 0; k < 4; k++) v[k] = V[k][0];
-#pragma unroll
-    for (int j = 1; j < 4; j++)
-        if (S[j][j] < best) {
-            best = S[j][j];
-#pragma unroll
-            for (int k = 0; k < 4; k++) v[k] = V[k][j];
-        }
-    const double inv = 1.0 / sqrt(((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + v[3] * v[3]);
-    const double sg = v[3] < 0.0 ? -inv : inv;
-#pragma unroll
-    for (int k = 0; k < 4; k++) v[k] *= sg;
-}
-
-TV_HD void tv_cross(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
-TV_HD void tv_unit(double* a) {
-    const double inv = 1.0 / sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
-    a[0] *= inv; a[1] *= inv; a[2] *= inv;
-}
 // cv2.decomposeEssentialMat: R1 = U W V^T, R2 = U W^T V^T (det U = det V = +1), t = the unit left null vector of E, its
 // largest component (the first of equals) positive.  The SVD through the eigenvectors of E^T E (singular values 1, 1, 0
 // up to scale: the squared condition does no harm here).
@@ -657,7 +564,7 @@ TV_HD void tv_decompose(const double* E, double* R1, double* R2, double* t) {
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = i; j < 3; j++) S[i][j] = S[j][i] = (E[i] * E[j] + E[3 + i] * E[3 + j]) + E[6 + i] * E[6 + j];
-    tv_jacobi<3, 8>(S, V);
+    geo_jacobi<3, 8>(S, V);
     int lo = 0;
     double lv = S[0][0];
     if (S[1][1] < lv) { lo = 1; lv = S[1][1]; }
@@ -668,18 +575,18 @@ TV_HD void tv_decompose(const double* E, double* R1, double* R2, double* t) {
         v1[k] = lo == 0 ? V[k][1] : V[k][0];
         v2[k] = lo == 2 ? V[k][1] : V[k][2];
     }
-    tv_cross(v1, v2, v3);
+    geo_cross(v1, v2, v3);
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         u1[i] = (E[3 * i] * v1[0] + E[3 * i + 1] * v1[1]) + E[3 * i + 2] * v1[2];
         u2[i] = (E[3 * i] * v2[0] + E[3 * i + 1] * v2[1]) + E[3 * i + 2] * v2[2];
     }
-    tv_unit(u1);
+    geo_unit(u1);
     const double dp = (u1[0] * u2[0] + u1[1] * u2[1]) + u1[2] * u2[2];
 #pragma unroll
     for (int i = 0; i < 3; i++) u2[i] -= dp * u1[i];
-    tv_unit(u2);
-    tv_cross(u1, u2, u3);
+    geo_unit(u2);
+    geo_cross(u1, u2, u3);
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -695,20 +602,14 @@ TV_HD void tv_decompose(const double* E, double* R1, double* R2, double* t) {
 #pragma unroll
     for (int i = 0; i < 3; i++) t[i] = sg * u3[i];
 }
-// good under [R | t]: depth in (0, dist) in both cameras (cv2.recoverPose)
+// good under [R | t]: geo_cheirality on the packed 3x4
 TV_HD bool tv_cheirality(const double* R, const double* t, double a, double b, double c, double d, double dist) {
-    const double P1[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     const double P2[12] = {R[0], R[1], R[2], t[0], R[3], R[4], R[5], t[1], R[6], R[7], R[8], t[2]};
-    double v[4];
-    tv_triangulate_point(P1, P2, a, b, c, d, v);
-    const double X = v[0] / v[3], Y = v[1] / v[3], Z = v[2] / v[3];
-    const double Z2 = ((R[6] * X + R[7] * Y) + R[8] * Z) + t[2];
-    return Z > 0.0 && Z < dist && Z2 > 0.0 && Z2 < dist;
+    return geo_cheirality(P2, a, b, c, d, dist);
 }
 
 #ifndef TV_HOST_ONLY
 // =============================================================== kernels =====================================================
-struct tv_cam { double fx, fy, cx, cy; };
 
 __global__ __launch_bounds__(TV_LANES) void tv_fivepoint_kernel(int S, const double* __restrict__ x1, const double* __restrict__ x2,
                                                                 double* __restrict__ E, int* __restrict__ nroots) {
@@ -726,15 +627,7 @@ __global__ __launch_bounds__(TV_LANES) void tv_fivepoint_kernel(int S, const dou
     }
 }
 
-// pair b's slice of the concatenated arrays, never outside [0, M)
-__device__ __forceinline__ void tv_pair_range(const int* offsets, int b, int M, int* first, int* last, bool* bad) {
-    const int lo = offsets[b], hi = offsets[b + 1];
-    *first = min(max(lo, 0), M);
-    *last = min(max(hi, *first), M);
-    *bad = *first != lo || *last != hi;
-}
-
-__global__ void tv_prepare_kernel(int M, int B, const double2* __restrict__ px1, const double2* __restrict__ px2, tv_cam cam,
+__global__ void tv_prepare_kernel(int M, int B, const double2* __restrict__ px1, const double2* __restrict__ px2, geo_cam cam,
                                   double4* __restrict__ xn, unsigned long long* __restrict__ keys, int* __restrict__ models) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < M) {
@@ -744,15 +637,9 @@ __global__ void tv_prepare_kernel(int M, int B, const double2* __restrict__ px1,
     if (i < B) { keys[i] = 0ull; models[i] = 0; }
 }
 
-// key of a scored model: more inliers first, then the lower hypothesis, then the lower root; 0 = no model
-#define TV_H_MAX (1 << 20)
-__device__ __forceinline__ unsigned long long tv_key(int count, int h, int root) {
-    return ((unsigned long long)(unsigned)count << 32) | ((unsigned long long)(TV_H_MAX - h) << 4) | (unsigned long long)(15 - root);
-}
-
 __device__ __forceinline__ int tv_solve_hypothesis(double* lds, const double4* xn, int n, uint64_t seed, int h) {
     int idx[5];
-    tv_draw_sample(seed, h, n, idx);
+    geo_draw_sample<5>(seed, h, n, idx);
     double p1[10], p2[10];
 #pragma unroll
     for (int k = 0; k < 5; k++) {
@@ -771,7 +658,7 @@ __global__ __launch_bounds__(TV_LANES) void tv_ransac_kernel(const int* __restri
     __shared__ int s_models;
     const int b = blockIdx.y, lane = threadIdx.x, h = blockIdx.x * TV_LANES + lane;
     int first, last; bool bad;
-    tv_pair_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     const int n = last - first;
     if (n < 5) return;                                  // block-uniform
     if (lane == 0) { s_key = 0ull; s_models = 0; }
@@ -789,7 +676,7 @@ __global__ __launch_bounds__(TV_LANES) void tv_ransac_kernel(const int* __restri
             const double4 v = xn[i];
             count += tv_sampson_sq(E, v.x, v.y, v.z, v.w) < thr2 ? 1 : 0;
         }
-        const unsigned long long k = tv_key(count, h, r);
+        const unsigned long long k = geo_key3(count, h, r);
         best = k > best ? k : best;
     }
     if (h < H) {
@@ -812,7 +699,7 @@ __global__ __launch_bounds__(TV_LANES) void tv_ransac_result_kernel(const int* _
     __shared__ double s_lds[TV_LDS_PER_LANE * TV_LANES];
     const int b = blockIdx.x, lane = threadIdx.x;
     int first, last; bool bad;
-    tv_pair_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     if (bad && lane == 0) atomicAdd(index_errors, 1u);
     const int n = last - first;
     const unsigned long long key = n >= 5 ? keys[b] : 0ull;
@@ -822,7 +709,7 @@ __global__ __launch_bounds__(TV_LANES) void tv_ransac_result_kernel(const int* _
         if (lane == 0) { stats[4 * b] = 0; stats[4 * b + 1] = -1; stats[4 * b + 2] = -1; stats[4 * b + 3] = n >= 5 ? models[b] : 0; }
         return;
     }
-    const int count = (int)(key >> 32), h = TV_H_MAX - (int)((key >> 4) & 0xFFFFFFFull), root = 15 - (int)(key & 15);
+    const int count = geo_key_count(key), h = geo_key3_h(key), root = geo_key3_sub(key);
     const double4* xn = xn_all + first;
     double* lds = s_lds + lane;
     tv_solve_hypothesis(lds, xn, n, seed, h);
@@ -842,14 +729,14 @@ __global__ __launch_bounds__(TV_LANES) void tv_ransac_result_kernel(const int* _
 
 #define TV_RP_THREADS 256
 __global__ __launch_bounds__(TV_RP_THREADS) void tv_recover_pose_kernel(const int* __restrict__ offsets, int M, const double2* __restrict__ px1,
-                                                                        const double2* __restrict__ px2, tv_cam cam,
+                                                                        const double2* __restrict__ px2, geo_cam cam,
                                                                         const double* __restrict__ E_all, const uint8_t* __restrict__ inlier_in,
                                                                         double dist, double* __restrict__ pose, uint8_t* __restrict__ inlier_out,
                                                                         int* __restrict__ stats, unsigned int* __restrict__ index_errors) {
     __shared__ int s_count[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     int first, last; bool bad;
-    tv_pair_range(offsets, b, M, &first, &last, &bad);
+    geo_range(offsets, b, M, &first, &last, &bad);
     if (bad && tid == 0) atomicAdd(index_errors, 1u);
     const int n = last - first;
     double E[9], nrm = 0.0;
@@ -908,7 +795,7 @@ __global__ void tv_triangulate_kernel(int N, const double* __restrict__ P1, cons
 #pragma unroll
     for (int k = 0; k < 12; k++) { p1[k] = P1[k]; p2[k] = P2[k]; }
     const double2 a = x1[i], c = x2[i];
-    tv_triangulate_point(p1, p2, a.x, a.y, c.x, c.y, v);
+    geo_triangulate_point(p1, p2, a.x, a.y, c.x, c.y, v);
     X[3 * (size_t)i] = v[0] / v[3];
     X[3 * (size_t)i + 1] = v[1] / v[3];
     X[3 * (size_t)i + 2] = v[2] / v[3];
@@ -932,7 +819,7 @@ extern "C" int slam_tv_essential_ransac_f64(slam_ctx* ctx, int64_t B, const int3
                                             double* d_E, uint8_t* d_inlier, int32_t* d_stats) {
     SLAM_REQUIRE(ctx, "slam_tv_essential_ransac_f64: null ctx");
     SLAM_REQUIRE(B >= 0 && B <= 65535 && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld; B <= 65535)", (long long)B, (long long)M);
-    SLAM_REQUIRE(H >= 1 && H <= TV_H_MAX, "H=%d out of range [1, 2^20]", H);
+    SLAM_REQUIRE(H >= 1 && H <= GEO_H_MAX, "H=%d out of range [1, 2^20]", H);
     SLAM_REQUIRE(threshold_px > 0.0 && fx > 0.0 && fy > 0.0, "threshold and focal lengths must be positive");
     if (B == 0) return SLAM_OK;
     SLAM_REQUIRE(d_offsets && d_E && d_stats && (M == 0 || (d_px1 && d_px2 && d_inlier)), "slam_tv_essential_ransac_f64: null device pointer");
@@ -945,7 +832,7 @@ extern "C" int slam_tv_essential_ransac_f64(slam_ctx* ctx, int64_t B, const int3
     double4* xn = (double4*)ws;
     unsigned long long* keys = (unsigned long long*)((char*)ws + xn_bytes);
     int* models = (int*)((char*)ws + xn_bytes + key_bytes);
-    const tv_cam cam = {fx, fy, cx, cy};
+    const geo_cam cam = {fx, fy, cx, cy};
     const double thr = threshold_px / ((fx + fy) / 2.0), thr2 = thr * thr;
     const int64_t cover = M > B ? M : B;
     tv_prepare_kernel<<<(unsigned)((cover + 255) / 256), 256, 0, ctx->stream>>>((int)M, (int)B, (const double2*)d_px1, (const double2*)d_px2,
@@ -973,7 +860,7 @@ extern "C" int slam_tv_recover_pose_f64(slam_ctx* ctx, int64_t B, const int32_t*
                  "slam_tv_recover_pose_f64: null device pointer");
     SLAM_REQUIRE((((uintptr_t)d_px1 | (uintptr_t)d_px2) & 15) == 0, "d_px1 / d_px2 must be 16-byte aligned");
     SLAM_HIP(hipSetDevice(ctx->device));
-    const tv_cam cam = {fx, fy, cx, cy};
+    const geo_cam cam = {fx, fy, cx, cy};
     if (M > 0) SLAM_HIP(hipMemsetAsync(d_inlier_out, 0, (size_t)M, ctx->stream));
     tv_recover_pose_kernel<<<(unsigned)B, TV_RP_THREADS, 0, ctx->stream>>>(d_offsets, (int)M, (const double2*)d_px1, (const double2*)d_px2, cam,
                                                                           d_E, d_inlier_in, distance_thresh, d_pose, d_inlier_out, d_stats,

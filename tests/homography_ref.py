@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
+import ransac_draws
 import two_view_ref as ref
 
 EUROC = ref.EUROC
@@ -112,14 +113,8 @@ def inlier_mask(H, px1, px2, threshold):
 
 
 def draw_sample(seed, h, n):
-    """The four distinct match indices of hypothesis h of a pair of n >= 4 matches (the generator of two_view_ref.draw_word)."""
-    out, d = [], 0
-    while len(out) < 4:
-        i = ((ref.draw_word(seed, h, d) >> 32) * n) >> 32
-        d += 1
-        if i not in out:
-            out.append(int(i))
-    return out
+    """The four distinct match indices of hypothesis h of a pair of n >= 4 matches."""
+    return ransac_draws.draw_sample(seed, h, n, 4)
 
 
 def ransac(px1, px2, hypotheses=256, threshold=3.0, seed=0):

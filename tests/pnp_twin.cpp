@@ -2,8 +2,8 @@
 //
 // Includes the kernel file itself with PNP_HOST_ONLY defined: every pnp_* routine below IS the device routine's source,
 // compiled for the host with contraction off and no FMA instructions available (x86-64 baseline), so a result here is what
-// the device must give bit for bit.  On top of the routines: a restatement of the RANSAC loop (argmax by the same key,
-// hypotheses one after the other) and one C entry per device call.
+// the device must give bit for bit.  On top of the routines: a restatement of the RANSAC loop (argmax by the kernel's own key,
+// geo_key3 of geometry_common.h, hypotheses one after the other) and one C entry per device call.
 //
 // Built twice by tests/pnp_twin.py: a shared library (loaded through ctypes) and, with PNP_TWIN_MAIN and
 // -fsanitize=address,undefined, a stand-alone program that reads a job file and writes a result file.
@@ -19,14 +19,6 @@
 #define __device__
 #define __forceinline__ inline
 #include "../slam-experiments_amd/csrc/pnp.hip"
-
-namespace {
-// key of the kernel (pnp_key), restated: more inliers, then the lower hypothesis, then the lower solution; 0 = no model
-const int H_MAX = 1 << 20;
-unsigned long long key_of(int count, int h, int sol) {
-    return ((unsigned long long)(unsigned)count << 32) | ((unsigned long long)(H_MAX - h) << 4) | (unsigned long long)(15 - sol);
-}
-}  // namespace
 
 extern "C" {
 
@@ -53,7 +45,7 @@ void pnpt_inlier(const double* T, int64_t n, const double* X, const double* px, 
 // counts (or null) int32 [H,4]: the exact inlier count of every (hypothesis, solution), -1 where there is no solution
 int pnpt_ransac(int64_t n64, const double* X, const double* px, double fx, double fy, double cx, double cy, int H, double threshold_px,
                 uint64_t seed, double* pose, uint8_t* inlier, int32_t* stats, int32_t* counts) {
-    if (H < 1 || H > H_MAX || n64 < 0 || n64 > (1 << 28)) return -1;
+    if (H < 1 || H > GEO_H_MAX || n64 < 0 || n64 > (1 << 28)) return -1;
     const int n = (int)n64;
     for (int k = 0; k < 12; k++) pose[k] = (k % 5 == 0) ? 1.0 : 0.0;
     for (int i = 0; i < n; i++) inlier[i] = 0;
@@ -72,12 +64,12 @@ int pnpt_ransac(int64_t n64, const double* X, const double* px, double fx, doubl
             int count = 0;
             for (int i = 0; i < n; i++) count += pnp_inlier(T + 12 * r, X[3 * i], X[3 * i + 1], X[3 * i + 2], px[2 * i], px[2 * i + 1], cam, thr2) ? 1 : 0;
             if (counts) counts[4 * h + r] = count;
-            const unsigned long long k = key_of(count, h, r);
+            const unsigned long long k = geo_key3(count, h, r);
             if (k > best) best = k;
         }
     }
     if (!best) return 0;
-    const int count = (int)(best >> 32), h = H_MAX - (int)((best >> 4) & 0xFFFFFFFull), sol = 15 - (int)(best & 15);
+    const int count = geo_key_count(best), h = geo_key3_h(best), sol = geo_key3_sub(best);
     double T[48];
     pnp_solve_hypothesis(X, px, n, cam, seed, h, T);
     for (int k = 0; k < 12; k++) pose[k] = T[12 * sol + k];

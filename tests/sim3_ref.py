@@ -14,11 +14,14 @@ from __future__ import annotations
 
 import numpy as np
 
+import ransac_draws
+
 EUROC = (458.654, 457.296, 367.215, 248.375)      # fx, fy, cx, cy
 IMAGE = (752, 480)
 CHI2 = 9.210
 SEED = 3107
-MASK64 = (1 << 64) - 1
+MASK64 = ransac_draws.MASK64
+splitmix = ransac_draws.splitmix
 FLAT = 1e-20
 BIG = 1e200
 MIN_ANGLE_DEG = 5.0
@@ -102,24 +105,9 @@ def refit(X1, X2, mask=None, fix_scale=False):
 
 
 # ---------------------------------------------------------------- draws, score, RANSAC (the header's statements)
-def splitmix(x):
-    x = (x + 0x9E3779B97F4A7C15) & MASK64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & MASK64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & MASK64
-    return x ^ (x >> 31)
-
-
 def draw_sample(seed, h, n):
     """Three distinct indices of hypothesis h among n correspondences."""
-    idx, d = [], 0
-    base = splitmix((seed ^ ((h * 0xD1B54A32D192ED03) & MASK64)) & MASK64)
-    while len(idx) < 3:
-        w = splitmix(base ^ ((d * 0x8CB92BA72F3D8DD7) & MASK64))
-        d += 1
-        i = ((w >> 32) * n) >> 32
-        if i not in idx:
-            idx.append(i)
-    return idx
+    return ransac_draws.draw_sample(seed, h, n, 3)
 
 
 def score(model, X1, X2, K, chi2=CHI2, sigma2=None):

@@ -22,9 +22,7 @@
 #include "../slam-experiments_amd/csrc/sim3.hip"
 
 namespace {
-const int H_MAX = 1 << 20;
 const int LANES = 256;               // S3_REFIT_THREADS, restated
-unsigned long long key_of(int count, int h) { return ((unsigned long long)(unsigned)count << 32) | (unsigned long long)(H_MAX - h); }
 
 // the tree of the header: for stride = 128, 64, ..., 1: lane l < stride adds lane l + stride to its own
 void tree(std::vector<double>& s, int K) {
@@ -66,7 +64,7 @@ void s3t_inlier(const double* model, int64_t n, const double* X1, const double* 
 // counts (or null) int32 [H]: the exact inlier count of every hypothesis, -1 where it has no model
 int s3t_ransac(int64_t n64, const double* X1, const double* X2, const double* sigma2, double fx, double fy, double cx, double cy, int H,
                double chi2, int fix_scale, uint64_t seed, double* model, uint8_t* inlier, int32_t* stats, int32_t* counts) {
-    if (H < 1 || H > H_MAX || n64 < 0 || n64 > (1 << 28)) return -1;
+    if (H < 1 || H > GEO_H_MAX || n64 < 0 || n64 > (1 << 28)) return -1;
     const int n = (int)n64;
     s3_identity(model);
     for (int i = 0; i < n; i++) inlier[i] = 0;
@@ -86,11 +84,11 @@ int s3t_ransac(int64_t n64, const double* X1, const double* X2, const double* si
         int count = 0;
         for (int i = 0; i < n; i++) count += s3_inlier(m, c.data() + 12 * (size_t)i, cam) ? 1 : 0;
         if (counts) counts[h] = count;
-        const unsigned long long k = key_of(count, h);
+        const unsigned long long k = geo_key2(count, h);
         if (k > best) best = k;
     }
     if (!best) return 0;
-    const int count = (int)(best >> 32), h = H_MAX - (int)(best & 0xFFFFFFFFull);
+    const int count = geo_key_count(best), h = geo_key2_h(best);
     s3_solve_hypothesis(X1, X2, n, fix_scale != 0, seed, h, model);
     s3_scoring_form(model, true, m);
     for (int i = 0; i < n; i++) inlier[i] = s3_inlier(m, c.data() + 12 * (size_t)i, cam) ? 1 : 0;

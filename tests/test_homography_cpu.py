@@ -19,6 +19,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import geometry_sources
 import hg_twin as tw
 import homography_ref as hr
 import two_view_ref as ref
@@ -258,8 +259,10 @@ def test_other_scenes_give_some_finite_orthonormal_answer_and_numpy_counts(scene
 
 
 def test_private_copies_match_two_view_vote(scenes):
-    """The vote is defined as 'triangulated as slam_tv_triangulate_f64': the private copies in homography.hip give the bits of
-    two_view.hip's routines (its host twin), and their text is the same up to the prefix."""
+    """The vote is defined as 'triangulated as slam_tv_triangulate_f64': homography.hip's vote gives the bits of two_view.hip's
+    routines (its host twin), and there are no private copies left to drift apart - the Jacobi sweeps, the triangulation and
+    the cheirality test (with the sampler and the range clamp) are defined once, in csrc/geometry_common.h, and in none of the
+    four kernel files."""
     from oracle import oracle
 
     s = scenes["general/clean"]
@@ -268,12 +271,7 @@ def test_private_copies_match_two_view_vote(scenes):
     for k in range(4):
         good = oracle.tv_twin_cheirality(d["pose_all"][k][:, :3], d["pose_all"][k][:, 3], x1, x2, 50.0)
         assert (good & s["mask"]).sum() == d["count"][k]
-    tv = open(os.path.join(ROOT, "slam-experiments_amd", "csrc", "two_view.hip")).read()
-    hg = open(os.path.join(ROOT, "slam-experiments_amd", "csrc", "homography.hip")).read()
-    for fn in ("jacobi", "triangulate_point"):
-        a = re.search(r"\n[^\n]*\btv_%s\(.*?\n}\n" % fn, tv, re.S).group(0)
-        b = re.search(r"\n[^\n]*\bhg_%s\(.*?\n}\n" % fn, hg, re.S).group(0)
-        assert a.replace("TV_HD", "HG_HD").replace("tv_", "hg_") == b, fn
+    geometry_sources.assert_one_copy()
 
 
 # ------------------------------------------------------------------------------------------------ the scores
@@ -508,8 +506,9 @@ def test_abi_table_header_and_kernel_file_agree(built):
             want = "c_void_p" if base.endswith("*") else ctype[base]
             assert t.__name__ == want, (n, a, t.__name__)
     assert "#pragma clang fp contract(off)" in src and "HG_HOST_ONLY" in src
-    for word in ("acos", "atan", "cbrt", "pow(", "exp(", "log(", "fma("):      # + - * / sqrt only
-        assert word not in re.sub(r"//[^\n]*", "", src), word
+    assert "#pragma clang fp contract(off)" in geometry_sources.HEADER
+    for word in ("acos", "atan", "cbrt", "pow(", "exp(", "log(", "fma("):      # + - * / sqrt only, in the file and in the header it includes
+        assert word not in re.sub(r"//[^\n]*", "", src + geometry_sources.HEADER), word
     lib = _lib.load()
     for n in names:
         assert hasattr(lib, n)

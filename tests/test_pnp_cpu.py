@@ -18,6 +18,7 @@ import re
 import numpy as np
 import pytest
 
+import geometry_sources
 import pnp_ref as ref
 import pnp_twin as tw
 
@@ -189,6 +190,7 @@ def test_sources_are_wired_in():
     assert re.search(r"^SRCS\s*:=.*\bpnp\.hip\b", make, re.M)
     src = open(os.path.join(ROOT, "slam-experiments_amd", "csrc", "pnp.hip")).read()
     assert "#pragma clang fp contract(off)" in src
-    code = re.sub(r"//.*", "", src)
+    assert "#pragma clang fp contract(off)" in geometry_sources.HEADER and '#include "geometry_common.h"' in src
+    code = re.sub(r"//.*", "", src + geometry_sources.HEADER)
     for fn in ("acos", "cos", "cbrt", "pow", "sin", "atan2", "exp", "log", "fma"):
-        assert not re.search(r"\b%s\s*\(" % fn, code), fn                 # + - * / sqrt only
+        assert not re.search(r"\b%s\s*\(" % fn, code), fn                 # + - * / sqrt only, in the file and in the header it includes

@@ -15,6 +15,8 @@ from __future__ import annotations
 
 import numpy as np
 
+import ransac_draws
+
 EUROC = (458.654, 457.296, 367.215, 248.375)      # fx, fy, cx, cy
 IMAGE = (752, 480)
 MIN_ROTATION_DEG, MAX_ROTATION_DEG = 1.0, 20.0
@@ -150,30 +152,13 @@ def threshold_sq(threshold_px, K):
 
 
 # ---------------------------------------------------------------- the draw generator (header comment of slam_tv_essential_ransac_f64)
-_M64 = (1 << 64) - 1
-
-
-def _splitmix(x):
-    x = (x + 0x9E3779B97F4A7C15) & _M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
-    return x ^ (x >> 31)
-
-
-def draw_word(seed, h, d):
-    return _splitmix(_splitmix((seed & _M64) ^ ((h * 0xD1B54A32D192ED03) & _M64)) ^ ((d * 0x8CB92BA72F3D8DD7) & _M64))
+draw_word = ransac_draws.draw_word
 
 
 def draw_sample(seed, b, h, n):
     """The five distinct match indices of hypothesis h of a pair of n >= 5 matches.  The pair index b is accepted and
     deliberately unused: a pair's draws, and so its result, do not depend on where in a batch it stands."""
-    out, d = [], 0
-    while len(out) < 5:
-        i = ((draw_word(seed, h, d) >> 32) * n) >> 32
-        d += 1
-        if i not in out:
-            out.append(int(i))
-    return out
+    return ransac_draws.draw_sample(seed, h, n, 5)
 
 
 # ---------------------------------------------------------------- RANSAC, pose, triangulation
