@@ -1180,6 +1180,88 @@ SLAM_API int slam_bow_match_search(slam_ctx* ctx, const slam_bow_groups* g1, con
                                    int th_low, double ratio, int scan_order, int32_t* d_matches12, int32_t* d_count, int32_t* d_idx,
                                    int32_t* d_dist);
 
+/* ---- map points matched into frames by projection (proj_match.hip) ------------------------------------------
+ * ORBmatcher::SearchByProjection (the forms TrackWithMotionModel, TrackLocalMap / SearchLocalPoints, Relocalization and
+ * ComputeSim3 call) for up to SLAM_PROJ_MATCH_PAIRS_MAX (point set, frame, pose) pairs a call; the reference tracks by a
+ * whole-image brute-force match instead (frontend.py:156-187).  PARITY UNPINNED: the gates are stated in f64 in a fixed
+ * operation order, the predicted level without log, the one-to-one step and the rotation check as in 4k. */
+#define SLAM_PROJ_MATCH_ROWS_MAX 8192
+#define SLAM_PROJ_MATCH_PAIRS_MAX 4096
+#define SLAM_PROJ_MATCH_LEVELS_MAX 16
+/* h_limits [6] = {rows per frame and points per set, pairs per call, points of a scan workgroup, pyramid levels, orientation
+ * bins, bytes of one pair record in the workspace}; needs no GPU */
+SLAM_API int slam_proj_match_limits(int32_t* h_limits);
+/* The launch plan for B frames (grid step) and P pairs (search) of n rows / points each; needs no GPU.  h_plan [8] = {cell
+ * workgroups, sort workgroups, gather workgroups, scan workgroups, finish workgroups, workspace bytes of the search when the
+ * top-2 tables stay in the workspace, LDS bytes of a finish workgroup, workspace bytes of the grid step} */
+SLAM_API int slam_proj_match_plan_describe(int64_t B, int64_t P, int64_t n, int64_t* h_plan);
+/* The grid step - Frame::AssignFeaturesToGrid for B frames at once, built once per frame and reused by every search: frame b
+ * owns the rows [h_offsets[b], h_offsets[b+1]) (h_offsets a HOST array) of d_desc u8 [n,32], d_xy f32 [n,2] (level-0 pixels),
+ * d_level int32 [n] and d_taken u8 [n] (non-zero: out of every search; may be null).  The rows fall into square cells of
+ * `cell` pixels over [0, W) x [0, H), indices clamped into the grid; d_cells [n] receives each row's cell id, and inside each
+ * frame the rows are sorted by (cell, row): d_order the row at each position, d_cells_sorted, d_desc_sorted, d_xy_sorted and
+ * d_meta_sorted (the level, -1 for a taken row) the same order, d_inverse the position of each row.  Asynchronous on the ctx
+ * stream. */
+SLAM_API int slam_proj_match_grid(slam_ctx* ctx, const void* d_desc, const float* d_xy, const int32_t* d_level, const uint8_t* d_taken,
+                                  const int64_t* h_offsets, int64_t B, int W, int H, int cell, int32_t* d_cells, void* d_desc_sorted,
+                                  int32_t* d_cells_sorted, int32_t* d_order, int32_t* d_inverse, float* d_xy_sorted,
+                                  int32_t* d_meta_sorted);
+/* one set of frames as slam_proj_match_grid leaves it; d_level and d_bins (orientation bins, or null) in ROW order */
+typedef struct slam_proj_frames {
+    const void* d_desc;
+    const int32_t* d_cells;
+    const int32_t* d_order;
+    const float* d_xy;
+    const int32_t* d_meta;
+    const int32_t* d_level;
+    const uint8_t* d_bins;
+    const int64_t* h_offsets;
+    int64_t B;
+    int32_t W, H, cell, pad;
+} slam_proj_frames;
+/* map points (MapPoint): set a owns the points [h_offsets[a], h_offsets[a+1]); d_xyz f64 [n,3] world positions, d_desc u8
+ * [n,32]; optional (null: the gate or rule is off): d_range f64 [n,2] = (dmin^2, dmax^2) of the scale-invariance distances
+ * (MapPoint::GetMinDistanceInvariance / GetMaxDistanceInvariance, squared), d_normal f64 [n,3] (GetNormal), d_level int32 [n]
+ * the level the point was last seen at (clamped into [0, n_levels)), d_bins u8 [n] */
+typedef struct slam_proj_points {
+    const double* d_xyz;
+    const void* d_desc;
+    const double* d_range;
+    const double* d_normal;
+    const int32_t* d_level;
+    const uint8_t* d_bins;
+    const int64_t* h_offsets;
+    int64_t B;
+} slam_proj_points;
+/* camera, bounds, scale tables (HOST arrays of n_levels doubles: s^l and their squares) and the rules of one call; level_rule
+ * non-zero: frame row j is a candidate only if lp + lo <= level_j <= lp + hi */
+typedef struct slam_proj_params {
+    double fx, fy, cx, cy;
+    double min_x, max_x, min_y, max_y;
+    double cos2_limit, ratio;
+    const double* h_scale;
+    const double* h_scale2;
+    int32_t n_levels, th_high, level_rule, lo, hi, pad;
+} slam_proj_params;
+/* The gates alone (Frame::isInFrustum / the head of every SearchByProjection): for pair p the points of set h_sets[p] under the
+ * pose h_poses[p] (f64 [P,3,4] row-major, world -> camera; a rigid pose or [sR | t]), the camera centre h_centres[p] and the
+ * radius factor h_th[p] -> d_status (0 searched, 1 not in front, 2 out of bounds, 3 out of range, 4 off the normal), d_u, d_v
+ * f64 (NaN where never computed) and d_lp (the predicted level, -1), pair after pair. */
+SLAM_API int slam_proj_match_project(slam_ctx* ctx, const slam_proj_points* points, const int32_t* h_sets, const double* h_poses,
+                                     const double* h_centres, const double* h_th, int64_t P, const slam_proj_params* params,
+                                     int32_t* d_status, double* d_u, double* d_v, int32_t* d_lp);
+/* ORBmatcher::SearchByProjection for P pairs h_pairs int32 [P,2] = (point set, frame): the gates; per surviving point its two
+ * nearest frame rows by (distance, row) among the rows that are not taken, lie strictly inside the window of radius
+ * h_th[p] * scale[lp] about (u, v) and pass the level rule; the selection d0 <= th_high and not (a second neighbour on the
+ * first one's level with (double)d0 > ratio * (double)d1); the one-to-one step and the rotation check of
+ * slam_bow_match_search.  d_matches12 int32 [sum of the pairs' points], d_count int32 [P]; the tables d_status / d_u / d_v /
+ * d_lp (all or none) and d_idx / d_dist int32 [., 2] (both or neither) are optional.  The pair table and the parameters
+ * travel through the context's workspace; one memset and two launches; no host read-back; asynchronous on the ctx stream. */
+SLAM_API int slam_proj_match_search(slam_ctx* ctx, const slam_proj_points* points, const slam_proj_frames* frames, const int32_t* h_pairs,
+                                    const double* h_poses, const double* h_centres, const double* h_th, int64_t P,
+                                    const slam_proj_params* params, int32_t* d_matches12, int32_t* d_count, int32_t* d_status, double* d_u,
+                                    double* d_v, int32_t* d_lp, int32_t* d_idx, int32_t* d_dist);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

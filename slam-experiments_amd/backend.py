@@ -25,6 +25,7 @@ from slamhip import ba as _ba
 from slamhip import ba_sparse as _bas
 from slamhip import bow as _bow
 from slamhip import bow_match as _bm
+from slamhip import proj_match as _pm
 from slamhip import pnp as _pnp
 from slamhip import pose_graph as _pg
 from slamhip import sim3_graph as _s3g
@@ -182,6 +183,22 @@ class Backend:
         pairs = np.stack([cand, np.full(len(cand), int(frame_index), np.int64)], axis=1) if len(cand) else np.zeros((0, 2), np.int64)
         matches, _ = _bm.search_by_bow(keyframes, frame, pairs, keyframe_bins, frame_bins, th_low, ratio, ctx=self._ctx)
         return _bm.match_index_pairs(matches)
+
+    def match_by_projection(self, points, frames, candidates, poses, fx, fy, cx, cy, frame_index: int = 0, th: float = 15.0,
+                            th_high: int = _pm.TH_HIGH, ratio: float = _pm.RATIO, scale=None, bounds=None, centres=None):
+        """ORB-SLAM's ``ORBmatcher::SearchByProjection`` of the map points of candidate keyframes into one frame under a
+        first pose each - the step after ``relocalize``'s PnP or a motion-model prediction: ``points`` is a
+        ``slamhip.PointSets`` (one set per keyframe), ``frames`` a ``slamhip.FrameGrids``, ``candidates`` the point-set ids,
+        ``poses`` [C,3,4] or [C,4,4] the world -> camera estimate of the frame for each candidate, ``frame_index`` the image of
+        ``frames``.  Returns per candidate ``(i1, i2)``: int32 arrays of the matched points (ascending) and frame rows, as
+        ``match_by_bow`` does: ``(xyz_of_set[i1], frame_pixels[i2])`` is one entry of ``relocalize``'s ``candidates`` or the
+        input of ``correct_frame_pose`` / ``optimize_pose``, ``(xyz_of_set[i1], points_of_frame[i2])`` one pair of
+        ``estimate_sim3_batch``."""
+        cand = np.asarray(list(candidates), np.int64).reshape(-1)
+        pairs = np.stack([cand, np.full(len(cand), int(frame_index), np.int64)], axis=1) if len(cand) else np.zeros((0, 2), np.int64)
+        matches, _ = _pm.search_by_projection(points, frames, pairs, poses, centres, (fx, fy, cx, cy), bounds, scale, th, th_high, ratio,
+                                              ctx=self._ctx)
+        return _pm.match_index_pairs(matches)
 
     def triangulate(self, pose1, pose2, px1, px2, fx, fy, cx, cy, reference_projection: bool = False):
         """``triangulation`` (``utils.py:32-55``) on arrays: the poses (4x4 or 3x4 Tcw) of the source and the query frame

@@ -9,26 +9,18 @@
 //           matches12 and the count.
 // Every comparison is between integers (or doubles that hold integers <= 256), the atomics are integer minima and LDS integer
 // adds, so the result is the same bits on every run and for every launch geometry.
-#include "bf_common.h"
+#include "match_finish.h"
 
-#define BM_ROWS_MAX 8192            // rows of one image: the row fits the 13-bit field of the claim key and the LDS sort
-#define BM_PAIRS_MAX 4096           // pairs of one call (the pair table: 48 bytes each in the context's workspace)
+#define BM_ROWS_MAX MF_ROWS_MAX     // rows of one image: the row fits the 13-bit field of the claim key and the LDS sort
+#define BM_PAIRS_MAX MF_PAIRS_MAX   // pairs of one call (the pair table: 48 bytes each in the context's workspace)
 #define BM_GROUP_THREADS 1024
 #define BM_SCAN_LANES 64            // side-1 rows of one scan workgroup: one wave, so a lone pair of 2000 rows still spreads over 32 CUs
-#define BM_FIN_THREADS 256
-#define BM_BINS 32
-#define BM_ROW_BITS 13
+#define BM_FIN_THREADS MF_FIN_THREADS
+#define BM_BINS MF_BINS
 #define BM_NO_SECOND 256            // ORB-SLAM's initial bestDist2: what a missing second neighbour counts as in the ratio test
 
 typedef unsigned long long u64;
-
-struct bm_pair {
-    int64_t base1, base2;           // first row of the two images in their sets
-    int64_t out1, own2;             // where the pair's side-1 results and side-2 claim words start
-    int n1, n2, blk0, pad;          // rows, and the pair's first scan workgroup
-};
-
-static_assert(sizeof(bm_pair) == 48, "the pair table is laid out by the host");
+typedef mf_pair bm_pair;
 
 struct bm_set {
     const uint4* desc;              // rows in grouped order
@@ -85,19 +77,6 @@ __device__ __forceinline__ bool bm_proposed(int i0, int d0, int i1, int d1, int 
     return i0 >= 0 && d0 <= th_low && (double)d0 < ratio * (double)(i1 >= 0 ? d1 : BM_NO_SECOND);
 }
 
-// first position in a[0 .. n) whose id, as u32, is >= v (STRICT: > v)
-template <bool STRICT>
-__device__ __forceinline__ int bm_bound(const int* __restrict__ a, int n, u32 v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const u32 x = (u32)a[mid];
-        if (STRICT ? x <= v : x < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // One lane per side-1 row.  scan_order 0: lane t takes the row at grouped position t, so the lanes of a wave hold a few
 // nodes and read the same side-2 segments (one address per node: a broadcast); 1: lane t takes row t, whatever its node
 // (the A/B of profiles/bow_match_time.log).  The tables are written in row order either way.
@@ -122,7 +101,7 @@ __global__ __launch_bounds__(BM_SCAN_LANES) void bm_scan_kernel(const bm_set s1,
         const int* nodes2 = s2.nodes + pr.base2;
         const int* order2 = s2.order + pr.base2;
         const uint4* rows2 = s2.desc + 2 * pr.base2;
-        const int j0 = bm_bound<false>(nodes2, pr.n2, (u32)node), j1 = bm_bound<true>(nodes2, pr.n2, (u32)node);
+        const int j0 = mf_bound<false>(nodes2, pr.n2, (u32)node), j1 = mf_bound<true>(nodes2, pr.n2, (u32)node);
         u32 q[8];
         bf_load_query(s1.desc + 2 * pr.base1, pos, q);
         for (int j = j0; j < j1; j += 4) {              // four rows requested before the first distance is formed
@@ -154,71 +133,23 @@ __global__ __launch_bounds__(BM_SCAN_LANES) void bm_scan_kernel(const bm_set s1,
     const int i0 = bf_key_idx(b1, 0), d0 = bf_key_dist(b1), i1 = bf_key_idx(b2, 0), d1 = bf_key_dist(b2);
     idx[pr.out1 + row] = make_int2(i0, i1);
     dist[pr.out1 + row] = make_int2(d0, d1);
-    if (SELECT && bm_proposed(i0, d0, i1, d1, th_low, ratio)) atomicMin(&owner[pr.own2 + i0], ((u32)d0 << BM_ROW_BITS) | (u32)row);
+    if (SELECT && bm_proposed(i0, d0, i1, d1, th_low, ratio)) atomicMin(&owner[pr.own2 + i0], mf_claim_key(d0, row));
 }
 
 // --------------------------------------------------------------------------------------------------------------- finish
-// One workgroup per pair.  A proposed row survives iff the claim word of its side-2 row holds its own key (the smallest
-// (d0, row) among the rows that named it; the others are dropped, they do not fall back to their second neighbour).
-__device__ __forceinline__ int bm_survivor(const bm_pair& pr, int i, const int2* idx, const int2* dist, const u32* owner, int th_low,
-                                           double ratio) {
-    const int2 ix = idx[pr.out1 + i], ds = dist[pr.out1 + i];
-    if (!bm_proposed(ix.x, ds.x, ix.y, ds.y, th_low, ratio)) return -1;
-    return owner[pr.own2 + ix.x] == (((u32)ds.x << BM_ROW_BITS) | (u32)i) ? ix.x : -1;
-}
+// One workgroup per pair: the claim check, the rotation histogram, matches12 and the count of match_finish.h under 4k (b)
+struct bm_select {
+    int th_low;
+    double ratio;
+    __device__ __forceinline__ bool proposed(const mf_pair&, int2 ix, int2 ds) const { return bm_proposed(ix.x, ds.x, ix.y, ds.y, th_low, ratio); }
+};
 
 __global__ __launch_bounds__(BM_FIN_THREADS) void bm_finish_kernel(const bm_set s1, const bm_set s2, const bm_pair* __restrict__ pairs,
                                                                   int th_low, double ratio, const int2* __restrict__ idx,
                                                                   const int2* __restrict__ dist, const u32* __restrict__ owner,
                                                                   int* __restrict__ matches12, int* __restrict__ count) {
-    __shared__ int s_hist[BM_BINS];
-    __shared__ u32 s_keep;
-    __shared__ int s_count;
-    const int tid = threadIdx.x;
     const bm_pair pr = pairs[blockIdx.x];
-    const bool rot = s1.bins && s2.bins;
-    if (tid < BM_BINS) s_hist[tid] = 0;
-    if (tid == 0) {
-        s_keep = 0xFFFFFFFFu;
-        s_count = 0;
-    }
-    __syncthreads();
-    if (rot) {
-        for (int i = tid; i < pr.n1; i += BM_FIN_THREADS) {
-            const int j = bm_survivor(pr, i, idx, dist, owner, th_low, ratio);
-            if (j >= 0) atomicAdd(&s_hist[((int)s1.bins[pr.base1 + i] - (int)s2.bins[pr.base2 + j]) & (BM_BINS - 1)], 1);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            // the first three bins by (count descending, bin ascending); ComputeThreeMaxima's 0.1 rule in integers
-            int b[3] = {-1, -1, -1};
-            for (int s = 0; s < 3; s++)
-                for (int v = 0; v < BM_BINS; v++) {
-                    bool taken = false;
-                    for (int t = 0; t < s; t++) taken |= v == b[t];
-                    if (!taken && (b[s] < 0 || s_hist[v] > s_hist[b[s]])) b[s] = v;      // (strict: a tie stays with the lower bin)
-                }
-            const int c1 = s_hist[b[0]];
-            u32 keep = 1u << b[0];
-            for (int s = 1; s < 3; s++)
-                if (s_hist[b[s]] > 0 && 10 * s_hist[b[s]] >= c1) keep |= 1u << b[s];
-            s_keep = keep;
-        }
-        __syncthreads();
-    }
-    const u32 keep = s_keep;
-    int mine = 0;
-    for (int i = tid; i < pr.n1; i += BM_FIN_THREADS) {
-        int j = bm_survivor(pr, i, idx, dist, owner, th_low, ratio);
-        if (rot && j >= 0 && !((keep >> (((int)s1.bins[pr.base1 + i] - (int)s2.bins[pr.base2 + j]) & (BM_BINS - 1))) & 1u)) j = -1;
-        matches12[pr.out1 + i] = j;
-        mine += j >= 0 ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-    if ((tid & 63) == 0 && mine) atomicAdd(&s_count, mine);
-    __syncthreads();
-    if (tid == 0) count[blockIdx.x] = s_count;
+    mf_finish(bm_select{th_low, ratio}, pr, s1.bins, s2.bins, idx, dist, owner, matches12, count + blockIdx.x);
 }
 
 // =============================================================== entry points ================================================

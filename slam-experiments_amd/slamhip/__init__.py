@@ -81,6 +81,15 @@ from .bow_match import (  # noqa: F401
     search_by_bow,
     search_by_bow_descriptors,
 )
+from .proj_match import (  # noqa: F401
+    FrameGrids,
+    PointSets,
+    proj_match_arrays,
+    project_points,
+    scale_tables,
+    search_by_projection,
+    search_by_sim3,
+)
 from .pose_graph import (  # noqa: F401
     loop_edges_from_two_view,
     optimize_pose_graph,

@@ -202,6 +202,14 @@ SIGNATURES = {
     "slam_bow_match_top2": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "slam_bow_match_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
+    "slam_proj_match_limits": (c_int, [POINTER(c_int32)]),
+    "slam_proj_match_plan_describe": (c_int, [c_int64, c_int64, c_int64, POINTER(c_int64)]),
+    "slam_proj_match_grid": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_proj_match_project": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
+    "slam_proj_match_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "slam_comm_version": (c_int, [POINTER(c_int)]),
     "slam_comm_unique_id": (c_int, [c_void_p]),
     "slam_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
@@ -228,6 +236,30 @@ class BowGroups(ctypes.Structure):
 
     _fields_ = [("d_desc", c_void_p), ("d_nodes", c_void_p), ("d_order", c_void_p), ("d_inverse", c_void_p), ("d_bins", c_void_p),
                 ("h_offsets", c_void_p), ("B", c_int64)]
+
+
+class ProjFrames(ctypes.Structure):
+    """``slam_proj_frames`` of include/slamhip.h: one set of frames in grid order."""
+
+    _fields_ = [("d_desc", c_void_p), ("d_cells", c_void_p), ("d_order", c_void_p), ("d_xy", c_void_p), ("d_meta", c_void_p),
+                ("d_level", c_void_p), ("d_bins", c_void_p), ("h_offsets", c_void_p), ("B", c_int64), ("W", c_int32), ("H", c_int32),
+                ("cell", c_int32), ("pad", c_int32)]
+
+
+class ProjPoints(ctypes.Structure):
+    """``slam_proj_points`` of include/slamhip.h: sets of map points."""
+
+    _fields_ = [("d_xyz", c_void_p), ("d_desc", c_void_p), ("d_range", c_void_p), ("d_normal", c_void_p), ("d_level", c_void_p),
+                ("d_bins", c_void_p), ("h_offsets", c_void_p), ("B", c_int64)]
+
+
+class ProjParams(ctypes.Structure):
+    """``slam_proj_params`` of include/slamhip.h: camera, bounds, scale tables and rules of one projection search."""
+
+    _fields_ = [("fx", c_double), ("fy", c_double), ("cx", c_double), ("cy", c_double), ("min_x", c_double), ("max_x", c_double),
+                ("min_y", c_double), ("max_y", c_double), ("cos2_limit", c_double), ("ratio", c_double), ("h_scale", c_void_p),
+                ("h_scale2", c_void_p), ("n_levels", c_int32), ("th_high", c_int32), ("level_rule", c_int32), ("lo", c_int32), ("hi", c_int32),
+                ("pad", c_int32)]
 
 
 BF_BATCH_MAX = 32
