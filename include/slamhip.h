@@ -1262,6 +1262,70 @@ SLAM_API int slam_proj_match_search(slam_ctx* ctx, const slam_proj_points* point
                                     const slam_proj_params* params, int32_t* d_matches12, int32_t* d_count, int32_t* d_status, double* d_u,
                                     double* d_v, int32_t* d_lp, int32_t* d_idx, int32_t* d_dist);
 
+/* ---- epipolar node search and new map points (tri_match.hip) -----------------------------------------------
+ * ORBmatcher::SearchForTriangulation and the per-match half of LocalMapping::CreateNewMapPoints for up to
+ * SLAM_TRI_MATCH_PAIRS_MAX keyframe pairs a call; the reference creates its points from a whole-image match and a bare
+ * triangulation (frontend.py).  PARITY UNPINNED: the gates are stated in f64 in a fixed operation order, the epipolar distance
+ * without its division, the DLT by Jacobi sweeps instead of an SVD, the one-to-one step and the rotation check as in 4k. */
+#define SLAM_TRI_MATCH_ROWS_MAX 8192
+#define SLAM_TRI_MATCH_PAIRS_MAX 4096
+#define SLAM_TRI_MATCH_LEVELS_MAX 16
+/* h_limits [8] = {rows per image, pairs per call, rows of a scan workgroup, pyramid levels, orientation bins, bytes of one pair
+ * record of the search, of the triangulation, bytes of the parameter block}; needs no GPU */
+SLAM_API int slam_tri_match_limits(int32_t* h_limits);
+/* The launch plan for P pairs of n rows per image; needs no GPU.  h_plan [6] = {scan workgroups, finish workgroups,
+ * triangulation workgroups (256 rows each), workspace bytes of the search when the top-2 tables stay in the workspace, workspace bytes of the
+ * triangulation, LDS bytes of a finish workgroup} */
+SLAM_API int slam_tri_match_plan_describe(int64_t P, int64_t n, int64_t* h_plan);
+/* what a keyframe's rows carry besides their descriptors, in ROW order over the whole set: d_xy f32 [n,2] level-0 pixels,
+ * d_level int32 [n] pyramid levels (clamped into [0, n_levels)), d_taken u8 [n] or null: non-zero = the row has a map point
+ * already and is out of the search (it is not the masking by a negative node id: the grouped set stays as it is) */
+typedef struct slam_tri_views {
+    const float* d_xy;
+    const int32_t* d_level;
+    const uint8_t* d_taken;
+} slam_tri_views;
+/* camera, gates and level tables (HOST arrays of n_levels doubles: scale[l] = s^l and sigma2[l] = scale[l]^2) of one call.
+ * The search reads th_low, chi2, epipole_r2 and the tables; the triangulation the camera, cos_max, chi2_px, ratio_factor and
+ * the tables. */
+typedef struct slam_tri_params {
+    double fx, fy, cx, cy;
+    double chi2, epipole_r2;
+    double cos_max, chi2_px, ratio_factor;
+    const double* h_scale;
+    const double* h_sigma2;
+    int32_t n_levels, th_low;
+} slam_tri_params;
+/* ORBmatcher::SearchForTriangulation for P pairs h_pairs int32 [P,2] = (image of g1, image of g2), the sets as
+ * slam_bow_match_search takes them.  h_F f64 [P,9]: F12 row-major, x1^T F12 x2 = 0; h_epipole f64 [P,2]: the epipole of camera 1
+ * in image 2 (a NaN component: no epipole gate); both HOST arrays that travel with the pair table through the context's
+ * workspace.  Row j of side 2 is a candidate for row i of side 1 iff node1[i] == node2[j] >= 0, neither row is taken, the
+ * Hamming distance d <= th_low, NOT (ex - x2)^2 + (ey - y2)^2 < epipole_r2 * scale[l] with l = level2[j] clamped (ORB-SLAM's
+ * 100 * scaleFactor: the scale, not its square), and with (a, b, c) = F12^T (x1, y1, 1), num = (a x2 + b y2) + c and
+ * den = a a + b b: den > 0 and num num < (chi2 sigma2[l]) den (CheckDistEpipolarLine; strict, so F = 0 or a NaN passes
+ * nothing).  Per side-1 row the two nearest candidates by (distance, side-2 row) -> d_idx / d_dist as slam_bow_match_top2
+ * lays them out (both or neither); a row with a first neighbour is proposed (no ratio test: ORB-SLAM has none here); then the
+ * one-to-one step and the rotation check of slam_bow_match_search -> d_matches12 int32 [sum of side-1 rows], d_count int32
+ * [P].  One copy, one memset, two launches; no host read-back; asynchronous on the ctx stream. */
+SLAM_API int slam_tri_match_search(slam_ctx* ctx, const slam_bow_groups* g1, const slam_bow_groups* g2, const slam_tri_views* views1,
+                                   const slam_tri_views* views2, const int32_t* h_pairs, int64_t P, const double* h_F,
+                                   const double* h_epipole, const slam_tri_params* params, int scan_order, int32_t* d_matches12,
+                                   int32_t* d_count, int32_t* d_idx, int32_t* d_dist);
+/* LocalMapping::CreateNewMapPoints behind its matching, for the same pairs over the same image offsets (HOST arrays): every
+ * side-1 row i with d_matches12[i] = j in [0, n2) is triangulated from the poses h_T1, h_T2 (f64 [P,3,4] world -> camera) with
+ * the camera centres h_O1, h_O2 (f64 [P,3]).  d_status int32: 0 created, 1 no match, 2 parallax (rays R^T xn: dot > 0 and
+ * dot^2 < cos_max^2 n1 n2 required), 3 at infinity (the DLT's w <= 0 or X not finite), 4 / 5 not in front of camera 1 / 2,
+ * 6 / 7 squared reprojection error > chi2_px sigma2[level] in image 1 / 2, 8 scale inconsistent (dist2 / dist1 against
+ * scale[l1] / scale[l2] within ratio_factor); the first failure wins.  d_X f64 [.,3], d_normal f64 [.,3] (MapPoint::
+ * UpdateNormalAndDepth with keyframe 1 as the reference) and d_range f64 [.,2] = (dmin^2, dmax^2) hold NaN wherever
+ * status != 0: a NaN position fails the first gate of slam_proj_match_search, so the arrays are a slam_proj_points as they
+ * stand, uncompacted.  d_created int32 [P]: the points of each pair.  One copy, one memset, one launch; asynchronous. */
+SLAM_API int slam_tri_match_triangulate(slam_ctx* ctx, const int64_t* h_offsets1, int64_t B1, const int64_t* h_offsets2, int64_t B2,
+                                        const slam_tri_views* views1, const slam_tri_views* views2, const int32_t* h_pairs, int64_t P,
+                                        const int32_t* d_matches12, const double* h_T1, const double* h_T2, const double* h_O1,
+                                        const double* h_O2, const slam_tri_params* params, double* d_X, double* d_normal,
+                                        double* d_range, int32_t* d_status, int32_t* d_created);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

@@ -26,6 +26,7 @@ from slamhip import ba_sparse as _bas
 from slamhip import bow as _bow
 from slamhip import bow_match as _bm
 from slamhip import proj_match as _pm
+from slamhip import tri_match as _tm
 from slamhip import pnp as _pnp
 from slamhip import pose_graph as _pg
 from slamhip import sim3_graph as _s3g
@@ -199,6 +200,28 @@ class Backend:
         matches, _ = _pm.search_by_projection(points, frames, pairs, poses, centres, (fx, fy, cx, cy), bounds, scale, th, th_high, ratio,
                                               ctx=self._ctx)
         return _pm.match_index_pairs(matches)
+
+    def create_new_map_points(self, keyframes, new: int, neighbours, poses, fx, fy, cx, cy, views=None, bins=None, scale=None,
+                              th_low: int = _tm.TH_LOW):
+        """ORB-SLAM's ``LocalMapping::CreateNewMapPoints`` for keyframe ``new`` against its covisible ``neighbours`` (the caller
+        passes the neighbours worth searching: the baseline-to-depth gate is not applied): ``keyframes`` is a
+        ``slamhip.FeatureVectors`` of all of them, ``views`` the ``slamhip.KeyframeViews`` of the same rows (pixels, levels and
+        the rows that already have a map point), ``poses`` [K,3,4] or [K,4,4] world -> camera per keyframe, ``bins`` the
+        orientation bins of every row (the rotation check) or None.  ``SearchForTriangulation`` and the per-match checks run as
+        one chain of launches.  Returns per neighbour ``(i1, i2, X)``: the rows of ``new`` (ascending) and of the neighbour of
+        every created point and its position f64 [.,3]."""
+        if views is None:
+            raise ValueError("create_new_map_points needs the KeyframeViews of the keyframes (views=)")
+        nb = np.asarray(list(neighbours), np.int64).reshape(-1)
+        pairs = np.stack([np.full(len(nb), int(new), np.int64), nb], axis=1) if len(nb) else np.zeros((0, 2), np.int64)
+        T = np.asarray(poses, np.float64)
+        pts, _, _ = _tm.create_new_map_points(keyframes, keyframes, pairs, views, views, T[np.full(len(nb), int(new), np.int64)], T[nb],
+                                              (fx, fy, cx, cy), scale, bins, bins, th_low, ctx=self._ctx)
+        out = []
+        for d in pts:
+            i1 = np.flatnonzero(d["status"] == 0).astype(np.int32)
+            out.append((i1, d["matches12"][i1], d["X"][i1]))
+        return out
 
     def triangulate(self, pose1, pose2, px1, px2, fx, fy, cx, cy, reference_projection: bool = False):
         """``triangulation`` (``utils.py:32-55``) on arrays: the poses (4x4 or 3x4 Tcw) of the source and the query frame

@@ -90,6 +90,15 @@ from .proj_match import (  # noqa: F401
     search_by_projection,
     search_by_sim3,
 )
+from .tri_match import (  # noqa: F401
+    KeyframeViews,
+    create_new_map_points,
+    epi_match_arrays,
+    epipole_in_second,
+    fundamental_from_poses,
+    search_for_triangulation,
+    triangulate_matches,
+)
 from .pose_graph import (  # noqa: F401
     loop_edges_from_two_view,
     optimize_pose_graph,

@@ -210,6 +210,13 @@ SIGNATURES = {
                                         c_void_p, c_void_p]),
     "slam_proj_match_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_tri_match_limits": (c_int, [POINTER(c_int32)]),
+    "slam_tri_match_plan_describe": (c_int, [c_int64, c_int64, POINTER(c_int64)]),
+    "slam_tri_match_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_tri_match_triangulate": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
     "slam_comm_version": (c_int, [POINTER(c_int)]),
     "slam_comm_unique_id": (c_int, [c_void_p]),
     "slam_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
@@ -260,6 +267,20 @@ class ProjParams(ctypes.Structure):
                 ("min_y", c_double), ("max_y", c_double), ("cos2_limit", c_double), ("ratio", c_double), ("h_scale", c_void_p),
                 ("h_scale2", c_void_p), ("n_levels", c_int32), ("th_high", c_int32), ("level_rule", c_int32), ("lo", c_int32), ("hi", c_int32),
                 ("pad", c_int32)]
+
+
+class TriViews(ctypes.Structure):
+    """``slam_tri_views`` of include/slamhip.h: pixels, levels and taken marks of a set's rows."""
+
+    _fields_ = [("d_xy", c_void_p), ("d_level", c_void_p), ("d_taken", c_void_p)]
+
+
+class TriParams(ctypes.Structure):
+    """``slam_tri_params`` of include/slamhip.h: camera, gates and level tables of the epipolar search and the triangulation."""
+
+    _fields_ = [("fx", c_double), ("fy", c_double), ("cx", c_double), ("cy", c_double), ("chi2", c_double), ("epipole_r2", c_double),
+                ("cos_max", c_double), ("chi2_px", c_double), ("ratio_factor", c_double), ("h_scale", c_void_p), ("h_sigma2", c_void_p),
+                ("n_levels", c_int32), ("th_low", c_int32)]
 
 
 BF_BATCH_MAX = 32
