@@ -16,6 +16,38 @@ TMP="$(mktemp -d)"
 mkdir -p "$OUT"
 make -C "$SRC" -j8 all >/dev/null
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$ROOT/include -I/opt/rocm/include -I$SRC -fvisibility=hidden -DSLAM_BUILD"
+
+# tools/build_exp.sh orb-mutants: six copies of the library, each with ONE deliberate mistake in a temporary copy of orb.hip
+# (comparisons and constants only: no index, bound or loop limit changes), to show that tests/test_orb_edges_gpu.py sees it:
+#     SLAMHIP_TEST_LIB=tools/exp/libslamhip_orbmut1.so python -m pytest -m gpu tests/test_orb_edges_gpu.py tests/test_orb_gpu.py
+# Mutant 3 makes the gather of the selection disagree with its radix select, so fewer keys than the quota can pass and the
+# rest of the selection keeps stale coordinates that the describe kernel follows: run it only on
+# test_selection_when_every_candidate_ties_on_R, which fails at a quota (1 or 50 of 144) where at least quota keys still pass.
+if [ "${1:-}" = "orb-mutants" ]; then
+    python3 - "$SRC/orb.hip" "$TMP" <<'EOF'
+import sys
+src = open(sys.argv[1]).read()
+mutants = {
+    1: ("s > c[-1] && s > c[1] &&", "s > c[-1] && s >= c[1] &&"),                      # NMS no longer strict towards the right
+    2: ("{~((unsigned long long)c.R ^ (1ull << 63)), c.xy}", "{~((unsigned long long)c.R), c.xy}"),      # no sign flip in the key
+    3: ("(a.hi == b.hi && a.lo < b.lo)", "(a.hi == b.hi && a.lo > b.lo)"),               # ties on R ordered backwards
+    4: ("(unsigned)(ring[i] < p - th) << i", "(unsigned)(ring[i] <= p - th) << i"),      # darker arc one threshold too far
+    5: ("(2ll * x * P.W + w) / (2ll * w)", "(2ll * x * P.W) / (2ll * w)"),               # mask x: floor instead of rint
+    6: ("        if (lane < 4) { d_kp[4 * slot + lane] = 0; d_desc[4 * slot + lane] = 0ull; }\n        if (lane == 0) d_resp[slot] = 0;\n", ""),
+}
+for k, (old, new) in mutants.items():
+    assert src.count(old) == 1, f"ORB mutant {k} did not apply: the kernel source changed"
+    open(f"{sys.argv[2]}/orb_mut{k}.hip", "w").write(src.replace(old, new))
+EOF
+    ORB_OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v "/orb.o")
+    for k in 1 2 3 4 5 6; do
+        /opt/rocm/bin/hipcc $FLAGS -x hip -c "$TMP/orb_mut$k.hip" -o "$TMP/orb_mut$k.o"
+        /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libslamhip_orbmut$k.so" "$TMP/orb_mut$k.o" $ORB_OBJS -ldl
+    done
+    rm -rf "$TMP"
+    ls -la "$OUT"/libslamhip_orbmut*.so
+    exit 0
+fi
 OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v bf_hamming)
 
 python3 - "$SRC/bf_hamming.hip" "$TMP/bf_trace.hip" "$TMP/bf_keep.hip" "$TMP/bf_count.hip" "$TMP/bf_cycles.hip" <<'EOF'
