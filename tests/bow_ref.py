@@ -1,6 +1,7 @@
 """Bag-of-words place recognition restated in numpy: the word and direct-index node of a descriptor, the
 tf-idf vector of an image, the fixed-point score and the query order of the database, and the hierarchical k-majority
-training.  A helper module of tests/test_bow_cpu.py and tests/test_bow_gpu.py, like sim3_ref.py.
+training.  A helper module of tests/test_bow_cpu.py, tests/test_bow_gpu.py and the edge tests (tests/bow_cases.py), like
+sim3_ref.py.
 
 Everything is vectorised over whole levels of the tree: all descriptors take one step of the descent together, all nodes of
 a depth are seeded and iterated together.  Nothing here follows one descriptor through a loop the way the kernels do."""
@@ -47,6 +48,40 @@ def transform(vocab, desc, levels_up=0):
     return vocab["word_of_node"][cur].astype(np.int32), node.astype(np.int32)
 
 
+def transform_raw(desc, rows, child, word_of_node, n_nodes, depth, levels_up=0):
+    """What ``slam_bow_transform`` promises for any tables, malformed ones included: ``rows`` uint8 [n_nodes, 32],
+    ``child`` int [n_nodes, 2] = (child_begin, child_count).  A descent stops at ``child_count <= 0``; otherwise the children are
+    the rows ``first .. first + count`` with ``first = clamp(child_begin, 0, n_nodes - 1)`` and ``count = min(child_count, 32,
+    n_nodes - first)``; it takes at most ``depth`` steps; the word is ``word_of_node[cur]``, whatever that holds.  Only the first
+    ``n_nodes`` rows of the three tables are read.  On a valid tree this is ``transform``."""
+    desc = np.asarray(desc, np.uint8).reshape(-1, 32)
+    n_nodes, depth = int(n_nodes), int(depth)
+    nd = np.asarray(rows, np.uint8).reshape(-1, 32)[:n_nodes]
+    ch = np.asarray(child, np.int64).reshape(-1, 2)[:n_nodes]
+    won = np.asarray(word_of_node, np.int64).reshape(-1)[:n_nodes]
+    n = len(desc)
+    cur = np.zeros(n, np.int64)
+    node = np.zeros(n, np.int64)
+    target = max(0, depth - int(levels_up))
+    for level in range(1, depth + 1):
+        moving = ch[cur, 1] > 0
+        first = np.clip(ch[cur, 0], 0, n_nodes - 1)
+        count = np.where(moving, np.minimum(np.minimum(ch[cur, 1], 32), n_nodes - first), 0)
+        best = np.full(n, 1 << 30, np.int64)
+        arg = cur.copy()
+        for c in range(int(count.max()) if n else 0):
+            ok = c < count
+            at = np.where(ok, first + c, 0)
+            d = np.where(ok, hamming(desc, nd[at]), 1 << 30)
+            better = d < best                                   # strict: a tie stays with the lower child
+            best = np.where(better, d, best)
+            arg = np.where(better, at, arg)
+        cur = arg
+        if level <= target:
+            node = np.where(moving, cur, node)
+    return won[cur].astype(np.int32), node.astype(np.int32)
+
+
 # ---- vectors ----------------------------------------------------------------------------------------------------------------
 
 def ordered_sum(t):
@@ -63,11 +98,14 @@ def ordered_sum(t):
     return s
 
 
-def vector(words, idf):
-    """(words int32, values f64, q uint32) of one image's word ids."""
+def vector(words, idf, n_words=None):
+    """(words int32, values f64, q uint32) of one image's word ids.  With ``n_words`` (what ``slam_bow_vectors`` is given) an id
+    outside ``[0, n_words)`` weighs nothing and leaves the list like a word of idf 0; it still counts towards the 8192."""
     words = np.asarray(words, np.int64).reshape(-1)
     if len(words) > MAX_IMAGE:
         raise ValueError("more than 8192 descriptors in one image")
+    if n_words is not None:
+        words = words[(words >= 0) & (words < int(n_words))]
     w, cnt = np.unique(words, return_counts=True)
     t = cnt.astype(np.float64) * np.asarray(idf, np.float64)[w]
     keep = t > 0
@@ -82,7 +120,12 @@ def vector(words, idf):
 def vectors(vocab, desc, offsets):
     """(offsets int64 [B+1], words, values, q) of a batch: image b owns rows [offsets[b], offsets[b+1])."""
     words, _ = transform(vocab, desc)
-    out = [vector(words[offsets[b]:offsets[b + 1]], vocab["idf"]) for b in range(len(offsets) - 1)]
+    return vectors_of_words(words, offsets, vocab["idf"])
+
+
+def vectors_of_words(words, offsets, idf, n_words=None):
+    """``vectors`` from the word ids themselves (what ``slam_bow_vectors`` takes): image b owns ids [offsets[b], offsets[b+1])."""
+    out = [vector(words[offsets[b]:offsets[b + 1]], idf, n_words) for b in range(len(offsets) - 1)]
     off = np.zeros(len(out) + 1, np.int64)
     np.cumsum([len(o[0]) for o in out], out=off[1:])
     cat = lambda i, dt: np.concatenate([o[i] for o in out]).astype(dt) if out else np.zeros(0, dt)

@@ -48,6 +48,40 @@ EOF
     ls -la "$OUT"/libslamhip_orbmut*.so
     exit 0
 fi
+# tools/build_exp.sh bow-mutants: seven copies of the library, each with ONE deliberate mistake in a temporary copy of bow.hip
+# (comparisons and arithmetic on values only: no index, bound, clamp or loop limit changes), to show that
+# tests/test_bow_edges_gpu.py sees it:
+#     SLAMHIP_TEST_LIB=tools/exp/libslamhip_bowmut1.so python -m pytest -m gpu tests/test_bow_edges_gpu.py tests/test_bow_gpu.py
+# Mutants 2 and 7 leave the scatter of the counting sort with offsets that restart at every tile of 4096 keys, so past one tile
+# some slots of the permutation are written twice and others never; the index build and the training read rows through that
+# permutation, and an unwritten slot of a fresh allocation is not a row: run them only where the permutation is the test's own
+# initialised buffer (-k test_group_keys) or where no key count passes one tile (tests/test_bow_gpu.py).
+if [ "${1:-}" = "bow-mutants" ]; then
+    python3 - "$SRC/bow.hip" "$TMP" <<'EOF'
+import sys
+src = open(sys.argv[1]).read()
+mutants = {
+    1: ("        if (i < B) out_off[i] = carry + ex;\n        carry += total;\n", "        if (i < B) out_off[i] = carry + ex;\n", 1),      # offsets: no running total across tiles of 256 images
+    2: ("            run += v[u];\n        }\n        carry += total;\n", "            run += v[u];\n        }\n", 1),                # key scan: none across tiles of 4096 keys
+    3: ("                if (s_cnt[j]) {\n", "                if (s_acc[j]) {\n", 1),                                              # query: a hit of score 0 is no hit
+    4: ("__ballot(2u * bits[(size_t)g * 256 + b] >= m)", "__ballot(2u * bits[(size_t)g * 256 + b] > m)", 1),                    # majority: an exact half clears the bit
+    5: ("if (key < bound && key > best) best = key;", "if (key <= bound && key > best) best = key;", 2),                        # query: the previous maximum is selected again
+    6: ("t > 0.0", "t >= 0.0", 2),                                                                                              # vectors: words of weight 0 stay
+    7: ("int run = carry + bf_block_excl_scan(sum, s_scan, &total);", "int run = bf_block_excl_scan(sum, s_scan, &total);", 1),    # key scan: as 2, but the total in the last slot stays right
+}
+for k, (old, new, times) in mutants.items():
+    assert src.count(old) == times, f"BoW mutant {k} did not apply: the kernel source changed"
+    open(f"{sys.argv[2]}/bow_mut{k}.hip", "w").write(src.replace(old, new))
+EOF
+    BOW_OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v "/bow.o")
+    for k in 1 2 3 4 5 6 7; do
+        /opt/rocm/bin/hipcc $FLAGS -x hip -c "$TMP/bow_mut$k.hip" -o "$TMP/bow_mut$k.o"
+        /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libslamhip_bowmut$k.so" "$TMP/bow_mut$k.o" $BOW_OBJS -ldl
+    done
+    rm -rf "$TMP"
+    ls -la "$OUT"/libslamhip_bowmut*.so
+    exit 0
+fi
 OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v bf_hamming)
 
 python3 - "$SRC/bf_hamming.hip" "$TMP/bf_trace.hip" "$TMP/bf_keep.hip" "$TMP/bf_count.hip" "$TMP/bf_cycles.hip" <<'EOF'
