@@ -1022,8 +1022,12 @@ SLAM_API int slam_s3g_optimize_host_f64(slam_ctx* ctx, int64_t V, int64_t E, con
  * and the same xor tree - a function of the pair count alone, for one pair or thousands.  f64 without contraction and
  * without floating-point atomics: results are pure functions of the inputs.  Every buffer is the caller's
  * (slam_bas_workspace: their total); no call here takes the context's call lock or waits; all are asynchronous on the
- * context's stream.  An index outside its range is counted (slam_index_errors) and never dereferenced; what it feeds
- * becomes NaN.  Limits: K <= 2^24, E <= 2^25 (the solver's), L, O <= 2^28, P <= 2^30. */
+ * context's stream.  No index outside its range is dereferenced.  Counted (slam_index_errors), once each, by the first
+ * phase that reads it: an entry of obs_pose / obs_point (slam_bas_linearize_f64) or of pair_a / pair_b outside its range, a
+ * slice of pt_ptr or ps_ptr (slam_bas_linearize_f64) or of pair_ptr that is negative, descending or ends past its table.
+ * Not counted: an entry of pt_obs / ps_obs outside [0, O).  A bad entry makes what it feeds NaN (Hpl_o, Hll_l, cost_k,
+ * Hdiag_k, dl_l, W_e); a bad slice of pt_ptr / ps_ptr is an empty list (its sums are 0), one of pair_ptr makes W_e NaN.
+ * Limits: K <= 2^24, E <= 2^25 (the solver's), L, O <= 2^28, P <= 2^30. */
 #define SLAM_BAS_MAX_POINTS (1 << 28)
 #define SLAM_BAS_MAX_OBS (1 << 28)
 #define SLAM_BAS_MAX_PAIRS (1 << 30)

@@ -17,7 +17,8 @@
 //   bas_obs_kernel      a thread per observation   Hpl_o; the two indices are checked here and counted (slam_index_errors)
 //   bas_point_kernel    a thread per point         Hll (6), bl (3) over its list pt_obs, in list order
 //   bas_pose_kernel     a workgroup per pose       Hpp (21), bp (6), cost: thread t takes entries t, t + 256, .. of ps_obs,
-//                                                  then ba_block_sum (xor tree inside a wave, the four waves in order)
+//                                                  then ba_block_sum (xor tree inside a wave, the four waves in order); a
+//                                                  ps_ptr slice outside the table is counted here, once per slice
 //   bas_inverse_kernel  a thread per point         E_l, E_l bl_l
 //   bas_edge_kernel     a WAVE per edge            lane i takes pairs i, i + 64, .. of the edge's pair list, the 64 lane sums
 //                                                  meet in the xor tree: the order is a function of the pair count alone, an
@@ -108,15 +109,17 @@ __global__ __launch_bounds__(BA_THREADS) void bas_point_kernel(const bas_obs_tab
     for (int i = 0; i < 3; i++) bl[(size_t)l * 3 + i] = b[i];
 }
 
-// the slice [a0, a1) of a pose's list, clamped into the table
-__device__ __forceinline__ void bas_pose_range(const int* __restrict__ ps_ptr, int k, int O, int& a0, int& a1) {
+// the slice [a0, a1) of a pose's list; a slice that does not lie in the table is taken as empty, and false comes back
+__device__ __forceinline__ bool bas_pose_range(const int* __restrict__ ps_ptr, int k, int O, int& a0, int& a1) {
     a0 = ps_ptr[k]; a1 = ps_ptr[k + 1];
-    if (a0 < 0 || a1 < a0 || a1 > O) a0 = a1 = 0;
+    if (a0 < 0 || a1 < a0 || a1 > O) { a0 = a1 = 0; return false; }
+    return true;
 }
 
 __global__ __launch_bounds__(BA_THREADS) void bas_pose_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
                                                                const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs, ba_cam cam,
-                                                               double delta, double* __restrict__ Hpp /*[K,21]*/, double* __restrict__ bp /*[K,6]*/,
+                                                               double delta, unsigned int* __restrict__ index_errors,
+                                                               double* __restrict__ Hpp /*[K,21]*/, double* __restrict__ bp /*[K,6]*/,
                                                                double* __restrict__ cost /*[K]*/) {
     __shared__ double sw[BAS_WAVES][28];
     __shared__ double out[28];
@@ -125,7 +128,8 @@ __global__ __launch_bounds__(BA_THREADS) void bas_pose_kernel(const bas_obs_tab 
 #pragma unroll
     for (int i = 0; i < 28; i++) acc[i] = 0.0;
     int a0, a1;
-    bas_pose_range(ps_ptr, k, t.O, a0, a1);
+    // the first phase to read ps_ptr reports a corrupt slice, once (bas_cost_kernel and bas_diag_kernel take it as empty too)
+    if (!bas_pose_range(ps_ptr, k, t.O, a0, a1) && threadIdx.x == 0) atomicAdd(index_errors, 1u);
     for (int i = a0 + (int)threadIdx.x; i < a1; i += BA_THREADS) {
         ba_lin q;
         int k2, l;
@@ -438,7 +442,7 @@ extern "C" int slam_bas_linearize_f64(slam_ctx* ctx, int64_t K, int64_t L, int64
     unsigned int* ie = slam_index_error_counter(ctx);
     if (O) bas_obs_kernel<<<bas_blocks(O), BA_THREADS, 0, st>>>(t, d_poses, d_points, cam, huber_delta, ie, d_Hpl);
     bas_point_kernel<<<bas_blocks(L), BA_THREADS, 0, st>>>(t, d_poses, d_points, d_pt_ptr, d_pt_obs, cam, huber_delta, ie, d_Hll, d_bl);
-    bas_pose_kernel<<<(unsigned)K, BA_THREADS, 0, st>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, huber_delta, d_Hpp, d_bp, d_cost);
+    bas_pose_kernel<<<(unsigned)K, BA_THREADS, 0, st>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, huber_delta, ie, d_Hpp, d_bp, d_cost);
     bas_finish_kernel<<<1, BA_THREADS, 0, st>>>(d_cost, (int)K, d_scal, d_Hpp, d_fixed, (int)K, d_Hll, (int)L);
     return slam_launch_check("slam_bas_linearize_f64");
 }

@@ -31,7 +31,7 @@ def brute_covisibility(op, ol, K, fixed):
 
 
 def linearize(T12, X, op, ol, meas, intr, delta):
-    """Blocks at a state: Hpp [K,6,6], bp [K,6], Hll [L,3,3], bl [L,3], Hpl [O,6,3], cost."""
+    """Blocks at a state: Hpp [K,6,6], bp [K,6], Hll [L,3,3], bl [L,3], Hpl [O,6,3], cost, cost_pose [K]."""
     T12 = np.ascontiguousarray(T12, np.float64).reshape(-1, 12)
     X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
     K, L = len(T12), len(X)
@@ -40,14 +40,16 @@ def linearize(T12, X, op, ol, meas, intr, delta):
     s = np.sqrt(c2)
     out = (delta > 0) & (s > delta)
     w = np.where(out, delta / np.where(out, s, 1.0), 1.0)
-    cost = float(np.where(out, 2.0 * delta * s - delta * delta, c2).sum())
+    rho = np.where(out, 2.0 * delta * s - delta * delta, c2)
+    cost, cost_pose = float(rho.sum()), np.zeros(K)
+    np.add.at(cost_pose, op, rho)
     Jpw, Jqw = Jp * w[:, None, None], Jq * w[:, None, None]
     Hpp, bp, Hll, bl = np.zeros((K, 6, 6)), np.zeros((K, 6)), np.zeros((L, 3, 3)), np.zeros((L, 3))
     np.add.at(Hpp, op, np.einsum("oia,oib->oab", Jpw, Jp))
     np.add.at(bp, op, np.einsum("oia,oi->oa", Jpw, e))
     np.add.at(Hll, ol, np.einsum("oia,oib->oab", Jqw, Jq))
     np.add.at(bl, ol, np.einsum("oia,oi->oa", Jqw, e))
-    return dict(Hpp=Hpp, bp=bp, Hll=Hll, bl=bl, Hpl=np.einsum("oia,oib->oab", Jpw, Jq), cost=cost, K=K, L=L)
+    return dict(Hpp=Hpp, bp=bp, Hll=Hll, bl=bl, Hpl=np.einsum("oia,oib->oab", Jpw, Jq), cost=cost, cost_pose=cost_pose, K=K, L=L)
 
 
 def reduce(lin, op, ol, fixed, lam, cov=None):

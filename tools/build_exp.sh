@@ -82,6 +82,52 @@ EOF
     ls -la "$OUT"/libslamhip_bowmut*.so
     exit 0
 fi
+# tools/build_exp.sh bas-mutants: ten copies of the library, each with ONE deliberate mistake in a temporary copy of
+# ba_sparse.hip or of the ba_common.h it includes (strides, skips, a comparison and an index that stays inside its array: no
+# mutant can leave an array), to show that tests/test_ba_sparse_edges_gpu.py sees it.  Each is run on the narrowest test
+# (profiles/ba_sparse_edges_mutants.log names it):
+#     SLAMHIP_TEST_LIB=tools/exp/libslamhip_basmut1.so python -m pytest -m gpu tests/test_ba_sparse_edges_gpu.py -k long-delta5
+if [ "${1:-}" = "bas-mutants" ]; then
+    python3 - "$SRC" "$TMP" <<'EOF'
+import os, sys
+src, tmp = sys.argv[1], sys.argv[2]
+hip, hdr = open(f"{src}/ba_sparse.hip").read(), open(f"{src}/ba_common.h").read()
+loop = "for (int i = a0 + (int)threadIdx.x; i < a1; i += BA_THREADS) {"
+once = "for (int i = a0 + (int)threadIdx.x; i < a1; i = a1) {"
+
+
+def nth(text, old, new, n, times):
+    assert text.count(old) == times, f"BA mutant did not apply ({old!r}): the kernel source changed"
+    parts = text.split(old)
+    return old.join(parts[:n + 1]) + new + old.join(parts[n + 1:])
+
+
+mutants = {
+    1: ("hip", lambda s: nth(s, loop, once, 0, 3)),                                               # bas_pose_kernel: one trip of its loop
+    2: ("hip", lambda s: nth(s, loop, once, 1, 3)),                                               # bas_cost_kernel: one trip
+    3: ("hip", lambda s: nth(s, loop, once, 2, 3)),                                               # bas_diag_kernel: one trip
+    4: ("hip", lambda s: nth(s, "p < p1; p += 64)", "p < p1; p += 32)", 0, 1)),                   # edge lanes stride 32: pairs taken twice
+    5: ("hdr", lambda s: nth(s, " + sw[2][threadIdx.x]) + sw[3][threadIdx.x];", " + sw[2][threadIdx.x]);", 0, 1)),   # ba_block_sum drops wave 3
+    6: ("hip", lambda s: nth(s, "        if (fixed[k]) continue;\n", "", 0, 1)),                  # finish: a fixed pose's diagonal in the maximum
+    7: ("hip", lambda s: nth(s, "            if (fixed[k]) {\n", "            if (false) {\n", 0, 1)),   # candidate: fixed poses move and count
+    8: ("hip", lambda s: nth(s, "step = (int64_t)gridDim.x * BA_THREADS;", "step = BA_THREADS;", 0, 1)),  # candidate: items taken again by other workgroups
+    9: ("hdr", lambda s: nth(s, "if (en > delta) {", "if (en >= delta) {", 0, 1)),                # Huber gate no longer strict
+    10: ("hip", lambda s: nth(s, "const int n = a * 6 - a * (a - 1) / 2 + (d - a);", "const int n = a * 6 - a * (a + 1) / 2 + (d - a);", 0, 1)),  # Hdiag from a wrong (in-range) packed index
+}
+for k, (which, f) in mutants.items():
+    os.makedirs(f"{tmp}/bas{k}")                       # ba_sparse.hip includes "ba_common.h": the copy beside it wins
+    open(f"{tmp}/bas{k}/ba_sparse.hip", "w").write(f(hip) if which == "hip" else hip)
+    open(f"{tmp}/bas{k}/ba_common.h", "w").write(f(hdr) if which == "hdr" else hdr)
+EOF
+    BAS_OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v "/ba_sparse.o")
+    for k in 1 2 3 4 5 6 7 8 9 10; do
+        /opt/rocm/bin/hipcc $FLAGS -x hip -c "$TMP/bas$k/ba_sparse.hip" -o "$TMP/bas$k.o"
+        /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libslamhip_basmut$k.so" "$TMP/bas$k.o" $BAS_OBJS -ldl
+    done
+    rm -rf "$TMP"
+    ls -la "$OUT"/libslamhip_basmut*.so
+    exit 0
+fi
 OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v bf_hamming)
 
 python3 - "$SRC/bf_hamming.hip" "$TMP/bf_trace.hip" "$TMP/bf_keep.hip" "$TMP/bf_count.hip" "$TMP/bf_cycles.hip" <<'EOF'
