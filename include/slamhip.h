@@ -1330,6 +1330,57 @@ SLAM_API int slam_tri_match_triangulate(slam_ctx* ctx, const int64_t* h_offsets1
                                         const double* h_O2, const slam_tri_params* params, double* d_X, double* d_normal,
                                         double* d_range, int32_t* d_status, int32_t* d_created);
 
+/* ---- map-point fusion and observation refresh (fuse.hip) ----------------------------------------------------
+ * ORBmatcher::Fuse (LocalMapping::SearchInNeighbors; LoopClosing::SearchAndFuse with [sR | t] poses) for up to
+ * SLAM_PROJ_MATCH_PAIRS_MAX (point set, frame, pose) pairs a call, and MapPoint::ComputeDistinctiveDescriptors with
+ * MapPoint::UpdateNormalAndDepth for the points it touched; the reference has neither.  PARITY UNPINNED: integers and f64 in a
+ * fixed operation order; deterministic one-to-one and merge rules instead of iteration order, a unit normal instead of the
+ * mean, the chi2 product instead of the division, at most SLAM_FUSE_OBS_MAX observations a point.
+ * The observations of the M map points are one table in compressed rows: offsets int64 [M+1] (a HOST array and its copy on the
+ * device) and d_obs int32 [nnz,2] = (frame, row inside that frame), the frames of one list strictly ascending. */
+#define SLAM_FUSE_OBS_MAX 256
+/* h_limits [8] = {rows per frame and points per set, pairs per call, points of a scan workgroup, pyramid levels, observations
+ * per point, bytes of one pair record, bytes of one refresh job, threads of a refresh workgroup}; needs no GPU */
+SLAM_API int slam_fuse_limits(int32_t* h_limits);
+/* what the search takes beside a slam_proj_params (whose ratio, th_high and level_rule it does not read: there is no ratio
+ * test, and the level rule is always on): the margins of the range gate, SQUARED (ORB-SLAM: 0.8^2, 1.2^2; both positive),
+ * the chi2 of the reprojection gate (5.99) and the largest accepted descriptor distance (ORBmatcher::TH_LOW = 50) */
+typedef struct slam_fuse_params {
+    double m_lo2, m_hi2, chi2;
+    int32_t th_low, pad;
+} slam_fuse_params;
+/* ORBmatcher::Fuse for P pairs h_pairs int32 [P,2] = (point set, frame).  d_id int32 [points]: the map point of each point
+ * (-1: none); frames: a frame set as slam_proj_match_grid leaves it, built WITHOUT taken marks; d_point int32 [rows], ROW
+ * order: the map point each frame row holds, or -1.  Per point, the first that applies: status 5 - its list (d_id >= 0) holds
+ * an observation in the pair's frame; 1 - 4 - the gates of slam_proj_match_project, the range gate as d2 < m_lo2 dmin2 ||
+ * d2 > m_hi2 dmax2, the level predicted from dmax2 itself; 6 - no candidate, a candidate being a frame row j strictly inside
+ * the window of radius h_th[p] * scale[lp] with lp + lo <= level_j <= lp + hi and NOT e2 > chi2 * h_scale2[level_j] for
+ * e2 = (u - x_j)^2 + (v - y_j)^2 in f64; 7 - the nearest candidate by (distance, row) is farther than th_low; 8 - another
+ * point of the pair proposed the same row with a smaller (distance, point); 0 - linked.  d_row (-1 unless status 0, 7, 8),
+ * d_dist (INT32_MAX where there is no row), d_status, d_other (status 0: d_point of the row - -1 = the point gains an
+ * observation there, q >= 0 = the same landmark as q; status 8: d_id of the winner; else -1) int32 [sum of the pairs' points],
+ * pair after pair; d_count int32 [P,3] = status-0 rows with other < 0, status-0 rows with other >= 0, status-8 rows; d_u,
+ * d_v f64 and d_lp int32 optional (all or none).  One copy, one memset, two launches; asynchronous on the ctx stream. */
+SLAM_API int slam_fuse_search(slam_ctx* ctx, const slam_proj_points* points, const int32_t* d_id, const slam_proj_frames* frames,
+                              const int32_t* d_point, const int64_t* h_obs_offsets, const int64_t* d_obs_offsets, const int32_t* d_obs,
+                              int64_t M, const int32_t* h_pairs, const double* h_poses, const double* h_centres, const double* h_th, int64_t P,
+                              const slam_proj_params* params, const slam_fuse_params* fuse, int32_t* d_row, int32_t* d_dist,
+                              int32_t* d_status, int32_t* d_other, int32_t* d_count, double* d_u, double* d_v, int32_t* d_lp);
+/* The refresh of K map points, h_select int32 [K] of the M (null: all M, K ignored), results in that order.  d_xyz f64 [M,3];
+ * the frames' descriptors d_desc u8 [n,32] and levels d_level int32 [n] in ROW order over the B frames of h_frame_offsets
+ * (d_inverse non-null: d_desc is in grid order and d_inverse the grid position of each row, as slam_proj_match_grid leaves
+ * them); d_centres f64 [B,3] the camera centres; d_ref int32 [M] the index inside its list of each point's reference
+ * observation (clamped into the list; null: 0); h_scale f64 [n_levels].  With N the length of a list: D[i][k] the Hamming
+ * distance of observations i and k, med_i the element of rank (N - 1) / 2 of row i ascending, d_best the smallest (med_i, i)
+ * and d_desc_out u8 [K,32] its descriptor; d_normal f64 [K,3] = unit(sum over the list, in list order, of (X - O) / |X - O|);
+ * d_range f64 [K,2] = (dmin^2, dmax^2), dmax = |X - O_ref| * scale[level_ref], dmin = dmax / scale[n_levels - 1].  N = 0: -1,
+ * zero bytes, NaN; a normal that is not finite: NaN normal and range, the descriptor still chosen.  Up to three launches by
+ * list length (16, 64, 256 lanes a point); asynchronous on the ctx stream. */
+SLAM_API int slam_fuse_refresh(slam_ctx* ctx, const double* d_xyz, const int64_t* h_obs_offsets, const int32_t* d_obs, int64_t M,
+                               const int32_t* h_select, int64_t K, const void* d_desc, const int32_t* d_inverse, const int32_t* d_level,
+                               const int64_t* h_frame_offsets, int64_t B, const double* d_centres, const int32_t* d_ref, const double* h_scale,
+                               int n_levels, int32_t* d_best, void* d_desc_out, double* d_normal, double* d_range);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

@@ -25,6 +25,7 @@ from slamhip import ba as _ba
 from slamhip import ba_sparse as _bas
 from slamhip import bow as _bow
 from slamhip import bow_match as _bm
+from slamhip import fuse as _fz
 from slamhip import proj_match as _pm
 from slamhip import tri_match as _tm
 from slamhip import pnp as _pnp
@@ -221,6 +222,34 @@ class Backend:
         for d in pts:
             i1 = np.flatnonzero(d["status"] == 0).astype(np.int32)
             out.append((i1, d["matches12"][i1], d["X"][i1]))
+        return out
+
+    def search_in_neighbors(self, points, ids, frames, frame_points, obs, xyz, new: int, neighbours, poses, fx, fy, cx, cy, scale=None,
+                            th: float = _fz.TH, th_low: int = _fz.TH_LOW, ref=None):
+        """ORB-SLAM's ``LocalMapping::SearchInNeighbors`` for keyframe ``new`` and its ``neighbours``: ``points`` is a
+        ``slamhip.PointSets`` with one set per keyframe (the map points it observes; ``ids`` their map-point ids), ``frames``
+        the ``slamhip.FrameGrids`` of the same keyframes built without taken marks, ``frame_points`` the map point of every
+        frame row (-1: none), ``obs`` the ``slamhip.MapObservations`` of the map, ``xyz`` f64 [M,3] its positions, ``poses``
+        [K,3,4] or [K,4,4] world -> camera per keyframe.  Both directions - the points of ``new`` into every neighbour and the
+        points of every neighbour into ``new`` - run as one ``fuse_points`` call; ``apply_fusion`` merges the links; the
+        survivors whose observations changed get a new descriptor, normal and distance range (``refresh_map_points``).
+        Returns a dict: ``observations`` (the new table), ``alias`` int32 [M], ``updates`` int32 [K,3] = (frame, row, id),
+        ``touched`` int32 (the refreshed map points), ``points`` (a ``PointSets`` of them: one set, in ``touched`` order, None
+        when nothing changed), ``refresh`` (the arrays ``refresh_map_points`` returned) and ``counts`` int32 [P,3]."""
+        nb = np.asarray(list(neighbours), np.int64).reshape(-1)
+        k = np.full(len(nb), int(new), np.int64)
+        pairs = np.concatenate([np.stack([k, nb], 1), np.stack([nb, k], 1)]) if len(nb) else np.zeros((0, 2), np.int64)
+        T = np.asarray(poses, np.float64)
+        res, counts = _fz.fuse_points(points, ids, frames, frame_points, obs, pairs, T[pairs[:, 1]], None, (fx, fy, cx, cy), None, scale, th,
+                                      th_low, ctx=self._ctx)
+        table, alias, updates = _fz.apply_fusion(obs, res)
+        touched = np.flatnonzero((table.nobs != obs.nobs) & (alias == np.arange(len(obs)))).astype(np.int32)
+        out = dict(observations=table, alias=alias, updates=updates, touched=touched, points=None, refresh=None, counts=counts)
+        if len(touched):
+            X = np.asarray(xyz, np.float64).reshape(-1, 3)
+            r = _fz.refresh_map_points(X, table, frames, _pm.camera_centres(T[:, :3, :]), ref, scale, touched, ctx=self._ctx)
+            out["refresh"] = r
+            out["points"] = _pm.PointSets(X[touched], r["descriptors"], dmin2=r["dmin2"], dmax2=r["dmax2"], normal=r["normal"], ctx=self._ctx)
         return out
 
     def triangulate(self, pose1, pose2, px1, px2, fx, fy, cx, cy, reference_projection: bool = False):

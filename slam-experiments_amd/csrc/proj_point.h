@@ -30,9 +30,11 @@ struct pp_result {
 
 #pragma clang fp contract(off)
 // A: world -> camera, 3x4 row-major; Ow: the camera centre; X: the point; range: {dmin2, dmax2} or null; normal: the unit
-// viewing normal or null; level: the level the point was last seen at, or null (read only when range is null).
+// viewing normal or null; level: the level the point was last seen at, or null (read only when range is null).  m_lo2, m_hi2:
+// the margins of the range gate (Fuse: 0.8^2 and 1.2^2, fuse_point.h); times 1.0 is exact, and the level is predicted from the
+// range as it stands.
 PP_HD pp_result pp_gates(const pp_camera& c, const double* A, const double* Ow, double th, const double* X, const double* range,
-                         const double* normal, const int32_t* level) {
+                         const double* normal, const int32_t* level, double m_lo2 = 1.0, double m_hi2 = 1.0) {
     pp_result o;
     o.u = o.v = o.r = __builtin_nan("");
     o.lp = -1;
@@ -51,7 +53,7 @@ PP_HD pp_result pp_gates(const pp_camera& c, const double* A, const double* Ow, 
     if (range) {
         d2 = (xc * xc + yc * yc) + zc * zc;
         o.status = 3;
-        if (d2 < range[0] || d2 > range[1]) return o;
+        if (d2 < m_lo2 * range[0] || d2 > m_hi2 * range[1]) return o;
     }
     if (normal) {
         const double p0 = X[0] - Ow[0], p1 = X[1] - Ow[1], p2 = X[2] - Ow[2];

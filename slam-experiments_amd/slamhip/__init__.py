@@ -99,6 +99,14 @@ from .tri_match import (  # noqa: F401
     search_for_triangulation,
     triangulate_matches,
 )
+from .fuse import (  # noqa: F401
+    MapObservations,
+    apply_fusion,
+    fuse_arrays,
+    fuse_by_sim3,
+    fuse_points,
+    refresh_map_points,
+)
 from .pose_graph import (  # noqa: F401
     loop_edges_from_two_view,
     optimize_pose_graph,

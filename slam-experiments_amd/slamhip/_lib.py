@@ -217,6 +217,10 @@ SIGNATURES = {
     "slam_tri_match_triangulate": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p]),
+    "slam_fuse_limits": (c_int, [POINTER(c_int32)]),
+    "slam_fuse_search": (c_int, [c_void_p] * 8 + [c_int64] + [c_void_p] * 4 + [c_int64] + [c_void_p] * 10),
+    "slam_fuse_refresh": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 4),
     "slam_comm_version": (c_int, [POINTER(c_int)]),
     "slam_comm_unique_id": (c_int, [c_void_p]),
     "slam_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
@@ -281,6 +285,12 @@ class TriParams(ctypes.Structure):
     _fields_ = [("fx", c_double), ("fy", c_double), ("cx", c_double), ("cy", c_double), ("chi2", c_double), ("epipole_r2", c_double),
                 ("cos_max", c_double), ("chi2_px", c_double), ("ratio_factor", c_double), ("h_scale", c_void_p), ("h_sigma2", c_void_p),
                 ("n_levels", c_int32), ("th_low", c_int32)]
+
+
+class FuseParams(ctypes.Structure):
+    """``slam_fuse_params`` of include/slamhip.h: the margins, the chi-square bound and the distance bound of one fusion search."""
+
+    _fields_ = [("m_lo2", c_double), ("m_hi2", c_double), ("chi2", c_double), ("th_low", c_int32), ("pad", c_int32)]
 
 
 BF_BATCH_MAX = 32
