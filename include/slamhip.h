@@ -1381,6 +1381,44 @@ SLAM_API int slam_fuse_refresh(slam_ctx* ctx, const double* d_xyz, const int64_t
                                const int64_t* h_frame_offsets, int64_t B, const double* d_centres, const int32_t* d_ref, const double* h_scale,
                                int n_levels, int32_t* d_best, void* d_desc_out, double* d_normal, double* d_range);
 
+/* ---- the covisibility graph (covis.hip) ----------------------------------------------------------------------
+ * slamhip.covisibility on the device, bit for bit (KeyFrame::UpdateConnections for the whole map at once; the reference has
+ * no covisibility graph).  From d_obs_pose / d_obs_point int32 [O] and a byte mask d_fixed [K] (null: every pose counts):
+ *   d_edges int32 [E,2], k1 < k2, every pair of free poses with a common point, ascending by (k1, k2); d_weights int32 [E];
+ *   d_pair_ptr int32 [E+1]; d_pair_a / d_pair_b int32 [P]: the observation indices of (k1, l) and (k2, l), ascending in l.
+ * Three phases, because the host sizes the tables of each from the scalars of the one before:
+ *   slam_covis_count   sorts the observations by (point, fixed, pose) and scans the pairs of every point; waits, and returns
+ *                      h_scalars [4] = {observations of free poses, (pose, point) pairs observed more than once (fixed poses
+ *                      included), P, entries of obs_pose / obs_point out of range (also in slam_index_errors; such an entry
+ *                      is never dereferenced and takes no part)}.  With duplicates the later phases must not run.
+ *   slam_covis_pairs   writes the P pairs in point order, sorts them by k1 K + k2 (stable, 8-bit digits over the bits of
+ *                      K^2 - 1; 64-bit keys above K = 65 536) into d_pair_a / d_pair_b, counts the edges; waits, returns *h_edges.
+ *   slam_covis_edges   writes d_edges, d_weights and d_pair_ptr (E as returned); asynchronous on the ctx stream.
+ * The two workspaces are the caller's (slam_covis_workspace); the count workspace must live until slam_covis_pairs returns, the
+ * pair workspace until slam_covis_edges has run.  Integers only; atomics only count, so every output is a function of the
+ * input alone.  Limits: K <= SLAM_PG_MAX_VERTICES, L <= SLAM_BAS_MAX_POINTS, O <= SLAM_BAS_MAX_OBS, P <= SLAM_BAS_MAX_PAIRS,
+ * E <= SLAM_PG_MAX_EDGES. */
+/* h_limits [8] = {threads of a workgroup, keys of a sort tile, bits of a sort digit, entries of a scan tile, lanes ranked by one
+ * ballot, the largest K with 32-bit pair keys, list lengths at which a kernel changes form (0: none), bytes of the scalar
+ * block}; needs no device */
+SLAM_API int slam_covis_limits(int32_t* h_limits);
+/* h_plan [8] = {bits, passes, key bytes and tiles of the observation sort; bits, passes, key bytes and tiles of the pair sort
+ * (P = 0: what is known without it)}; needs no device */
+SLAM_API int slam_covis_plan(int64_t K, int64_t L, int64_t O, int64_t P, int32_t* h_plan);
+/* h_bytes [2] = {the count workspace, the pair workspace for P pairs}; needs no device */
+SLAM_API int slam_covis_workspace(int64_t K, int64_t L, int64_t O, int64_t P, uint64_t* h_bytes);
+SLAM_API int slam_covis_count(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, const int32_t* d_obs_pose, const int32_t* d_obs_point,
+                              const uint8_t* d_fixed, void* d_count_ws, int64_t* h_scalars);
+SLAM_API int slam_covis_pairs(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, int64_t P, const void* d_count_ws, void* d_pair_ws,
+                              int32_t* d_pair_a, int32_t* d_pair_b, int64_t* h_edges);
+SLAM_API int slam_covis_edges(slam_ctx* ctx, int64_t K, int64_t P, int64_t E, const void* d_pair_ws, int32_t* d_edges, int32_t* d_weights,
+                              int32_t* d_pair_ptr);
+/* the observation table of slam_fuse_* (d_offsets int64 [M+1] ON THE DEVICE, d_obs int32 [nnz,2]) as d_obs_pose / d_obs_point
+ * int32 [nnz]: slot s holds (frame of s, point whose list s lies in), so the pairs of slam_covis_pairs are slots of d_obs.
+ * d_offsets must ascend from 0 to nnz.  Asynchronous on the ctx stream. */
+SLAM_API int slam_covis_rows(slam_ctx* ctx, int64_t M, int64_t nnz, const int64_t* d_offsets, const int32_t* d_obs, int32_t* d_obs_pose,
+                             int32_t* d_obs_point);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

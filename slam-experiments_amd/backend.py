@@ -24,6 +24,7 @@ import numpy as np
 from slamhip import ba as _ba
 from slamhip import ba_sparse as _bas
 from slamhip import bow as _bow
+from slamhip import covis as _cv
 from slamhip import bow_match as _bm
 from slamhip import fuse as _fz
 from slamhip import proj_match as _pm
@@ -312,14 +313,33 @@ class Backend:
 
     def global_bundle_adjust(self, poses, points, obs_pose_idx, obs_point_idx, meas, fx, fy, cx, cy, iterations: int = 10,
                              fixed_poses=(0,), huber_delta: float = 0.0, pcg_tol: float = _bas.DEFAULT_PCG_TOL,
-                             pcg_max_iter: int = _bas.DEFAULT_PCG_MAX_ITER):
+                             pcg_max_iter: int = _bas.DEFAULT_PCG_MAX_ITER, covisibility: str = "host"):
         """Bundle adjustment over a whole map (ORB-SLAM's step after a closed loop; the reference's ``Backend`` has no
         body, ``backend.py:101-103``): the arguments of ``optimize``, for thousands of keyframes.  The reduced camera
         system is kept as 6x6 blocks over the covisibility graph and solved by the pose-graph PCG on the device
-        (``slamhip.bundle_adjust_sparse``); ``optimize`` and its routing are not involved.
+        (``slamhip.bundle_adjust_sparse``); ``optimize`` and its routing are not involved.  ``covisibility="device"`` builds
+        the covisibility tables on the device too (``slamhip.covis``): the same tables and the same result, bit for bit.
         Returns (``slamhip.ba.BAResult``, stats dict)."""
         return _bas.bundle_adjust_sparse(poses, points, obs_pose_idx, obs_point_idx, meas, (fx, fy, cx, cy), iterations, fixed_poses,
-                                         huber_delta, pcg_tol, pcg_max_iter, ctx=self.ctx)
+                                         huber_delta, pcg_tol, pcg_max_iter, ctx=self.ctx, covisibility=covisibility)
+
+    def covisibility_graph(self, obs_pose_idx, obs_point_idx, K: int, fixed=None):
+        """ORB-SLAM's covisibility graph over ``K`` keyframes (``KeyFrame::UpdateConnections`` for the whole map; the reference
+        keeps none): an edge between two keyframes that observe a common point, weighted by the number of such points, built on
+        the device (``slamhip.covisibility_device``).  Returns ``slamhip.CovisibilityGraph``: ``best(k, n)`` are the neighbours
+        ``create_new_map_points`` / ``search_in_neighbors`` search, ``connected(k)`` the ids ``detect_loop_candidates`` skips,
+        ``essential_edges()`` the edges of ``optimize_essential_graph``.  ``fixed`` (a mask [K]) leaves poses out."""
+        tab = _cv.covisibility_device(obs_pose_idx, obs_point_idx, K, fixed, ctx=self.ctx)
+        try:
+            return tab.graph()
+        finally:
+            tab.free()
+
+    def essential_graph_edges(self, obs_pose_idx, obs_point_idx, K: int, min_weight: int = 100, loop_edges=()):
+        """The edges of ORB-SLAM's essential graph, int32 [.,2] with k1 < k2, ascending: the spanning tree of the covisibility
+        graph, its edges of at least ``min_weight`` common points and ``loop_edges``
+        (``covisibility_graph(...).essential_edges``)."""
+        return self.covisibility_graph(obs_pose_idx, obs_point_idx, K).essential_edges(min_weight, loop_edges)
 
     def optimize_pose_graph(self, poses, edges, meas, info, fixed=(0,), iterations: int = _pg.DEFAULT_ITERATIONS,
                             huber_delta: float = 0.0, pcg_tol: float = _pg.DEFAULT_PCG_TOL,

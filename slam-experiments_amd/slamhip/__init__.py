@@ -61,6 +61,7 @@ from .pnp import (  # noqa: F401
     solve_pnp_ransac_offsets,
 )
 from .ba_sparse import SparseBAProblem, bundle_adjust_sparse, covisibility  # noqa: F401
+from .covis import CovisibilityGraph, CovisibilityTables, covisibility_device  # noqa: F401
 from .bow import (  # noqa: F401
     BowDatabase,
     BowVectors,

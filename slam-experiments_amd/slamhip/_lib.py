@@ -221,6 +221,13 @@ SIGNATURES = {
     "slam_fuse_search": (c_int, [c_void_p] * 8 + [c_int64] + [c_void_p] * 4 + [c_int64] + [c_void_p] * 10),
     "slam_fuse_refresh": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 4),
+    "slam_covis_limits": (c_int, [POINTER(c_int32)]),
+    "slam_covis_plan": (c_int, [c_int64, c_int64, c_int64, c_int64, POINTER(c_int32)]),
+    "slam_covis_workspace": (c_int, [c_int64, c_int64, c_int64, c_int64, POINTER(c_uint64)]),
+    "slam_covis_count": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
+    "slam_covis_pairs": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
+    "slam_covis_edges": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_covis_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "slam_comm_version": (c_int, [POINTER(c_int)]),
     "slam_comm_unique_id": (c_int, [c_void_p]),
     "slam_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),

@@ -102,6 +102,11 @@ def covisibility(obs_pose, obs_point, K: int, fixed, L: Optional[int] = None):
     return edges, np.diff(pair_ptr).astype(np.int32), pair_ptr, pa.astype(np.int32), pb.astype(np.int32)
 
 
+def _covisibility_host(op, ol, K, fixed, L):
+    """``covisibility`` for SparseBAProblem, which has an argument of the function's name (looked up at the call, as before)."""
+    return covisibility(op, ol, K, fixed, L)
+
+
 def workspace_bytes(K: int, L: int, O: int, E: int, P: int) -> int:
     """Device memory one problem takes in all (``slam_bas_workspace``); needs no device."""
     n = ctypes.c_uint64(0)
@@ -121,37 +126,63 @@ def plan(K: int, L: int, O: int, E: int, P: int) -> dict:
 
 class SparseBAProblem:
     """Device-resident state, index tables, blocks and solver buffers of one sparse bundle adjustment.  The arguments are
-    checked on the host (``ValueError``) before anything is allocated or launched."""
+    checked on the host (``ValueError``) before anything is allocated or launched.  With ``covisibility="device"`` the
+    covisibility tables are built by ``slam_covis_*`` from the uploaded observation lists instead of by ``covisibility`` (the
+    same tables, bit for bit); a (pose, point) pair observed twice is then refused after that build's count phase, with
+    everything freed."""
 
-    def __init__(self, ctx: Context, K: int, L: int, obs_pose, obs_point, meas, intrinsics, fixed):
+    def __init__(self, ctx: Context, K: int, L: int, obs_pose, obs_point, meas, intrinsics, fixed, covisibility: str = "host"):
         self._check = check
         self.ctx = ctx
         K, L = int(K), int(L)
         if not 1 <= L <= MAX_POINTS:
             raise ValueError(f"L must be in [1, {MAX_POINTS}]")
+        if covisibility not in ("host", "device"):
+            raise ValueError(f"covisibility must be 'host' or 'device', got {covisibility!r}")
         op, ol = _index_arrays(obs_pose, obs_point, K, L)
         O = len(op)
         meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 2)
         if meas.shape[0] != O:
             raise ValueError("obs_pose, obs_point and meas must have one row per observation")
         self.fixed = _fixed_mask(fixed, K)
-        self.edges, self.weights, pair_ptr, pair_a, pair_b = covisibility(op, ol, K, self.fixed, L)
-        self.K, self.L, self.O, self.E, self.P = K, L, O, len(self.edges), len(pair_a)
+        pad = lambda a: a if a.size else np.zeros(4, a.dtype)
+        up, new = ctx.upload, ctx.malloc
+        if covisibility == "device":
+            self._device_covisibility(ctx, op, ol, K, L, pad)      # the pair tables never leave the device (slamhip.covis)
+        else:
+            self.edges, self.weights, pair_ptr, pair_a, pair_b = _covisibility_host(op, ol, K, self.fixed, L)
+            self.P = len(pair_a)
+        self.K, self.L, self.O, self.E = K, L, O, len(self.edges)
         self.fx, self.fy, self.cx, self.cy = (float(v) for v in intrinsics)
         pt_ptr, pt_obs, ps_ptr, ps_obs = observation_lists(op, ol, K, L)
         vtx_ptr, vtx_adj = vertex_lists(K, self.edges)
-        pad = lambda a: a if a.size else np.zeros(4, a.dtype)
-        up, new = ctx.upload, ctx.malloc
         o, e = max(O, 1), max(self.E, 1)
-        self.d_op, self.d_ol, self.d_meas = up(pad(op)), up(pad(ol)), up(meas if O else np.zeros((1, 2)))
+        if covisibility == "host":
+            self.d_op, self.d_ol, self.d_fixed = up(pad(op)), up(pad(ol)), up(self.fixed.astype(np.uint8))
+            self.d_edges, self.d_pair_ptr, self.d_pair_a, self.d_pair_b = up(pad(self.edges)), up(pair_ptr), up(pad(pair_a)), up(pad(pair_b))
+        self.d_meas = up(meas if O else np.zeros((1, 2)))
         self.d_pt_ptr, self.d_pt_obs, self.d_ps_ptr, self.d_ps_obs = up(pt_ptr), up(pad(pt_obs)), up(ps_ptr), up(pad(ps_obs))
-        self.d_edges, self.d_pair_ptr, self.d_pair_a, self.d_pair_b = up(pad(self.edges)), up(pair_ptr), up(pad(pair_a)), up(pad(pair_b))
-        self.d_vtx_ptr, self.d_vtx_adj, self.d_fixed = up(vtx_ptr), up(pad(vtx_adj)), up(self.fixed.astype(np.uint8))
+        self.d_vtx_ptr, self.d_vtx_adj = up(vtx_ptr), up(pad(vtx_adj))
         self.d_T, self.d_X = [new(K * 96), new(K * 96)], [new(L * 24), new(L * 24)]      # [0] the state, [1] the candidate
         self.d_Hpl, self.d_Hll, self.d_bl, self.d_E, self.d_Ebl = new(o * 144), new(L * 48), new(L * 24), new(L * 72), new(L * 24)
         self.d_Hpp, self.d_bp, self.d_cost, self.d_cost2 = new(K * 168), new(K * 48), new(K * 8), new(K * 8)
         self.d_Hdiag, self.d_W, self.d_b, self.d_dp, self.d_dl = new(K * 288), new(e * 288), new(K * 48), new(K * 48), new(L * 24)
         self.d_part, self.d_scal = new(1024 * 8), new(64)       # scalars: cost, largest diagonal, gain-ratio denominator, candidate cost
+
+    def _device_covisibility(self, ctx: Context, op, ol, K: int, L: int, pad) -> None:
+        """The observation tables go up first and ``slam_covis_*`` builds edges, weights and pair tables from them: the problem
+        adopts the resident buffers, only ``edges`` and ``weights`` come down."""
+        from .covis import build_tables
+
+        self.d_op, self.d_ol, self.d_fixed = ctx.upload(pad(op)), ctx.upload(pad(ol)), ctx.upload(self.fixed.astype(np.uint8))
+        try:
+            tab = build_tables(ctx, self.d_op, self.d_ol, self.d_fixed, K, L, len(op))
+        except BaseException:
+            self.free()
+            raise
+        self.edges, self.weights, self.P = tab.edges, tab.weights, tab.P
+        for name, buf in tab.release().items():
+            setattr(self, name, buf)
 
     def _buffers(self):
         for name, b in list(vars(self).items()):
@@ -241,7 +272,8 @@ class SparseBAProblem:
 
 def bundle_adjust_sparse(poses, points, obs_pose_idx, obs_point_idx, meas, intrinsics, iterations: int = 10,
                          fixed_poses: Sequence[int] = (0,), huber_delta: float = 0.0, pcg_tol: float = DEFAULT_PCG_TOL,
-                         pcg_max_iter: int = DEFAULT_PCG_MAX_ITER, ctx: Optional[Context] = None, on_trial=None):
+                         pcg_max_iter: int = DEFAULT_PCG_MAX_ITER, ctx: Optional[Context] = None, on_trial=None,
+                         covisibility: str = "host"):
     """``bundle_adjust_device`` for maps instead of windows: the reduced camera system as 6x6 blocks over the covisibility
     graph (``slam_bas_*``), solved by the pose-graph PCG (``slam_pg_pcg_f64``).  Same arguments, same Levenberg-Marquardt
     schedule; the state goes to the device once and comes back once, a trial moves a few scalars.
@@ -249,12 +281,14 @@ def bundle_adjust_sparse(poses, points, obs_pose_idx, obs_point_idx, meas, intri
     Returns ``(BAResult, stats)`` with stats = dict(trials, cg_iterations, lam, status (the OR of the solves'
     ``SLAM_PG_STATUS_*`` bits), unconverged (solves that stopped at ``pcg_max_iter`` or broke down: each counted as a failed
     trial, the damping grows), edges, pairs).  ``on_trial(dict)`` is called after every trial (timing tools).
+    ``covisibility``: "host" builds the covisibility tables with numpy (``covisibility``), "device" with ``slam_covis_*``
+    (``slamhip.covis``); the tables, and with them every result, are the same bit for bit.
     Raises ``ValueError`` for an index out of range, a (pose, point) pair observed twice or no fixed pose, before any launch."""
     T12, X, K, L = state_arrays(poses, points)
     _check_solver_args(iterations, huber_delta, pcg_tol, pcg_max_iter)
     fixed = fixed_pose_mask(fixed_poses, K)
     ctx = ctx or default_context()
-    prob = SparseBAProblem(ctx, K, L, obs_pose_idx, obs_point_idx, meas, intrinsics, fixed)
+    prob = SparseBAProblem(ctx, K, L, obs_pose_idx, obs_point_idx, meas, intrinsics, fixed, covisibility)
     st = dict(trials=0, cg_iterations=0, lam=0.0, status=0, unconverged=0, edges=prob.E, pairs=prob.P)
 
     def trial(lam, cost):
