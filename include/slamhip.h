@@ -95,6 +95,12 @@ SLAM_API int slam_sync(slam_ctx* ctx);
 /* current sizes of the ctx's grow-only blocks (for tests): h_bytes[0..count), count <= 6, of {workspace, merge state,
  * pinned completion / count block, staging arena (device), staging arena (pinned host), radius tables}; 0 = not yet taken */
 SLAM_API int slam_ctx_block_bytes(slam_ctx* ctx, int64_t* h_bytes, int count);
+/* fills one scratch block of the ctx with `byte` (for tests of the state contract, DESIGN.md: no call reads a byte of a
+ * block that the same call has not written).  block: index as in slam_ctx_block_bytes; 0 (workspace), 3 (staging arena,
+ * device), 4 (staging arena, pinned host) and 5 (radius tables) are filled over their whole current size once the stream has
+ * drained, and a block not yet taken is a no-op.  Blocks 1 and 2 hold state that survives between calls (idle pattern:
+ * slam_bf_state_dirty) and are refused with SLAM_ERR_INVALID, as is any other index. */
+SLAM_API int slam_ctx_block_fill(slam_ctx* ctx, int block, int byte);
 
 /* ---- device memory (caller keeps the pointer, library tracks it) ------- */
 SLAM_API int slam_malloc(slam_ctx* ctx, uint64_t bytes, void** d_ptr);

@@ -279,6 +279,26 @@ extern "C" int slam_ctx_block_bytes(slam_ctx* ctx, int64_t* h_bytes, int count) 
     return SLAM_OK;
 }
 
+// Test hook beside slam_ctx_block_bytes: one scratch block filled with `byte`.  Blocks 1 (merge state) and 2 (pinned completion
+// / count block) carry state between calls and are refused.
+extern "C" int slam_ctx_block_fill(slam_ctx* ctx, int block, int byte) {
+    SLAM_REQUIRE(ctx, "slam_ctx_block_fill: null ctx");
+    SLAM_REQUIRE(block == 0 || (block >= 3 && block <= 5), "slam_ctx_block_fill: block %d is not a scratch block (0, 3, 4, 5)", block);
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    SLAM_HIP(hipSetDevice(ctx->device));
+    SLAM_HIP(hipStreamSynchronize(ctx->stream));
+    if (block == 4) {
+        if (ctx->io_host) memset(ctx->io_host, byte, ctx->io_host_bytes);
+        return SLAM_OK;
+    }
+    void* p = block == 0 ? ctx->workspace : block == 3 ? ctx->io_dev : ctx->radius_mem;
+    const uint64_t n = block == 0 ? ctx->workspace_bytes : block == 3 ? ctx->io_dev_bytes : ctx->radius_mem_bytes;
+    if (!p || !n) return SLAM_OK;
+    SLAM_HIP(hipMemsetAsync(p, byte, n, ctx->stream));
+    SLAM_HIP(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
 extern "C" int slam_timer_start(slam_ctx* ctx) {
     SLAM_REQUIRE(ctx, "slam_timer_start: null ctx");
     SLAM_HIP(hipSetDevice(ctx->device));

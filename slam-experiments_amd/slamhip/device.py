@@ -105,6 +105,11 @@ class Context:
         check(self.lib.slam_ctx_block_bytes(self.handle, b, len(self.BLOCKS)))
         return dict(zip(self.BLOCKS, b))
 
+    def fill_block(self, name: str, byte: int) -> None:
+        """Fill one scratch block with ``byte`` (``slam_ctx_block_fill``, a hook for tests): "workspace", "io_dev", "io_host"
+        or "radius_tables".  The blocks that carry state between calls ("merge_state", "pinned_block") are refused."""
+        check(self.lib.slam_ctx_block_fill(self.handle, self.BLOCKS.index(name), int(byte) & 0xFF))
+
     def plan_info(self, n: int, m: int) -> dict:
         """The launch plan the top-2 search would use for n x m (``slam_bf_plan_info``)."""
         p = (ctypes.c_int32 * 10)()

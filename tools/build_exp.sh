@@ -128,6 +128,46 @@ EOF
     ls -la "$OUT"/libslamhip_basmut*.so
     exit 0
 fi
+# tools/build_exp.sh ctx-mutants: four copies of the library, each with ONE initialisation of a context block dropped or one
+# layout mistake, to show that tests/test_ctx_poison_gpu.py sees it.  Each is built only because reading the
+# code shows that the stale value is compared, added or or-ed and never used as an index, an address or a loop bound
+# (profiles/ctx_poison_mutants.log gives the argument per mutant):
+#     SLAMHIP_TEST_LIB=tools/exp/libslamhip_ctxmut1.so python -m pytest -m gpu tests/test_ctx_poison_gpu.py tests/test_proj_match_gpu.py
+if [ "${1:-}" = "ctx-mutants" ]; then
+    python3 - "$SRC" "$TMP" <<'EOF'
+import os, sys
+src, tmp = sys.argv[1], sys.argv[2]
+mutants = {
+    # 1: the claim words of SearchByProjection keep what the workspace held
+    1: ("proj_match.hip", "proj_match.hip", "    if (search && own2 > 0) SLAM_HIP(hipMemsetAsync(owner, 0xFF, (size_t)own2 * 4, ctx->stream));\n", ""),
+    # 2: the RANSAC keys and model counts of the absolute pose keep what the workspace held
+    2: ("pnp.hip", "pnp.hip", "    SLAM_HIP(hipMemsetAsync(ws, 0, (size_t)(key_bytes + (uint64_t)B * 4), ctx->stream));\n", ""),
+    # 3: the scalar block of the graph solver (status, n_fixed, done, iters) keeps what the workspace held (SE(3) solver only)
+    3: ("pose_graph.hip", "graph_lm.h", "    SLAM_HIP(hipMemsetAsync(G.sc, 0, sizeof(glm_scal), st));\n", ""),
+    # 4: a host-side layout mistake in SearchByBoW: the claim words start one aligned block early, inside the distance table
+    4: ("bow_match.hip", "bow_match.hip", "    p.o_owner = p.o_dist + (own_tables ? slam_align_up((uint64_t)n1_total * 8) : 0);\n",
+        "    p.o_owner = p.o_dist + (own_tables ? slam_align_up((uint64_t)n1_total * 8) - 256 : 0);\n"),
+}
+for k, (unit, patched, old, new) in mutants.items():
+    os.makedirs(f"{tmp}/ctx{k}")
+    for name in {unit, patched}:                       # a quoted include finds the copy beside the unit first
+        text = open(f"{src}/{name}").read()
+        if name == patched:
+            assert text.count(old) == 1, f"context mutant {k} did not apply: the source changed"
+            text = text.replace(old, new)
+        open(f"{tmp}/ctx{k}/{name}", "w").write(text)
+    open(f"{tmp}/ctx{k}/unit", "w").write(unit)
+EOF
+    for k in 1 2 3 4; do
+        unit=$(cat "$TMP/ctx$k/unit")
+        OTHER=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v "/${unit%.hip}.o")
+        /opt/rocm/bin/hipcc $FLAGS -x hip -c "$TMP/ctx$k/$unit" -o "$TMP/ctx$k.o"
+        /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libslamhip_ctxmut$k.so" "$TMP/ctx$k.o" $OTHER -ldl
+    done
+    rm -rf "$TMP"
+    ls -la "$OUT"/libslamhip_ctxmut*.so
+    exit 0
+fi
 OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v bf_hamming)
 
 python3 - "$SRC/bf_hamming.hip" "$TMP/bf_trace.hip" "$TMP/bf_keep.hip" "$TMP/bf_count.hip" "$TMP/bf_cycles.hip" <<'EOF'
