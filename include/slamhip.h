@@ -300,6 +300,18 @@ SLAM_API int slam_bf_mx_plan_describe(int num_cu, int64_t N, int64_t M, int32_t*
  * or 32 (32x32x64 tiles).  Both kernels run the plan of slam_bf_mx_plan_describe.  For engine 0 this is the choice on the
  * shapes that h_plan[7] sends to the matrix cores. */
 SLAM_API int slam_bf_mx_tile_describe(int engine, int64_t N, int64_t M, int32_t* h_tile);
+/* How the 32x32x64 matrix-core kernel gets its train rows on this context: 0 = auto (the shipped choice), 1 = every query
+ * block expands the compact rows it scans, 2 = the train set is expanded once per search into a prepared image (a buffer of
+ * the context, 128 bytes per row, rebuilt by every search in stream order in front of it: train buffers may be overwritten
+ * in place between searches) and the search copies its stages from there.  Same tables bit for bit.  The setting applies to
+ * the passes that kernel runs (slam_bf_mx_tile_describe: 32); every other pass keeps its feed.  Any other value is refused. */
+SLAM_API int slam_bf_set_mx_feed(slam_ctx* ctx, int feed);
+/* The feed a pass of N x M on the 32x32x64 kernel takes under `feed` (0, 1 or 2), WITHOUT a device: *h_feed = 1 or 2. */
+SLAM_API int slam_bf_mx_feed_describe(int feed, int64_t N, int64_t M, int32_t* h_feed);
+/* For tests: the current size of the context's image buffer (0 = not yet taken), and the buffer filled with `byte` once the
+ * stream has drained (no search reads a byte of the image that the same search has not written). */
+SLAM_API int slam_bf_mx_image_bytes(slam_ctx* ctx, int64_t* h_bytes);
+SLAM_API int slam_bf_mx_image_fill(slam_ctx* ctx, int byte);
 /* Restore the matcher's per-context merge state to its idle values.  Every search leaves it clean by itself;
  * call this after a search failed part-way (the library does so on a failed launch).  Stream-ordered. */
 SLAM_API int slam_bf_reset_state(slam_ctx* ctx);

@@ -490,6 +490,74 @@ extern "C" int slam_bf_mx_tile_describe(int engine, int64_t N, int64_t M, int32_
     return SLAM_OK;
 }
 
+// The feed of the 32x32x64 kernel under feed 0 (auto): true = from the prepared image (bf_mx_image_kernel, then
+// bf_mx32_image_top2_kernel), false = expanded in the kernel by every query block.  The image costs a launch of its own in
+// front of the search and removes the staging's vector work from every stage of every block; the rule is measured like
+// bf_mx32_auto's (tools/ab_time.py parent,lib --check, the whole range of five rounds below the parent's;
+// profiles/mx_feed_ab.log, DESIGN.md 3c "Feed"): a shape where the image is not faster keeps the feed it had.  Measured faster
+// (1.1 - 3.3 %): 65536 x 65536, 131072 x 65536, 65536 x 200000, 131072 x 200000 - the four corners of the box below - and
+// 98304 x 65536, 65536 x 131072, 131072 x 131072 inside it.  Measured slower, the image's launch (6 - 16 us) outweighing what
+// the search gains: every shape of the 32x32 routing box with fewer than 65536 queries or train rows that was tried (8192 x
+// 16384 .. 32768 x 65536, 65536 x 32768, 20000 x 100000), 49152 x 65536 and 40000 x 200000 excepted (0.4 % and 2.2 % faster),
+// which stay outside: the rule is the box whose corners were measured.
+static bool bf_mx_feed_auto(int64_t N, int64_t M) {
+    return N >= 65536 && N <= 131072 && M >= 65536 && M <= 200000;
+}
+
+// The feed a pass of N x M takes on the 32x32x64 kernel under `feed` (0, 1 or 2), WITHOUT a device: *h_feed = 1 or 2.
+extern "C" int slam_bf_mx_feed_describe(int feed, int64_t N, int64_t M, int32_t* h_feed) {
+    SLAM_REQUIRE(h_feed, "slam_bf_mx_feed_describe: null argument");
+    SLAM_REQUIRE(feed >= 0 && feed <= 2, "feed must be 0 (auto), 1 (expand in the kernel) or 2 (prepared image)");
+    SLAM_REQUIRE(N >= 1 && M >= 1, "bad sizes");
+    *h_feed = feed == 2 || (feed == 0 && bf_mx_feed_auto(N, M)) ? 2 : 1;
+    return SLAM_OK;
+}
+
+extern "C" int slam_bf_set_mx_feed(slam_ctx* ctx, int feed) {
+    SLAM_REQUIRE(ctx, "slam_bf_set_mx_feed: null ctx");
+    SLAM_REQUIRE(feed >= 0 && feed <= 2, "feed must be 0 (auto), 1 (expand in the kernel) or 2 (prepared image)");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ctx->bf_mx_feed = feed;
+    return SLAM_OK;
+}
+
+// The image buffer of the context, at least `bytes` long.  A member of its own and not slam_workspace: a forced engine with M
+// above SLAM_MAX_TRAIN_PER_PASS runs passes while slam_bf_knn2_keep holds the workspace for its per-pass tables.  Grows behind
+// a stream synchronisation, like bf_state_get (callers hold ctx->call_mu).  Never cached: every pass that reads it writes the
+// whole of what it reads first, in stream order (callers overwrite train buffers in place).
+static int bf_mx_image_get(slam_ctx* ctx, uint64_t bytes, void** out) {
+    if (bytes > ctx->bf_mx_img_bytes) {
+        SLAM_HIP(hipStreamSynchronize(ctx->stream));
+        if (ctx->bf_mx_img) SLAM_HIP(hipFree(ctx->bf_mx_img));
+        ctx->bf_mx_img = nullptr;
+        ctx->bf_mx_img_bytes = 0;
+        const uint64_t want = bytes + (bytes >> 2);               // headroom: slightly larger calls do not realloc
+        SLAM_HIP(hipMalloc(&ctx->bf_mx_img, want));
+        ctx->bf_mx_img_bytes = want;
+    }
+    *out = ctx->bf_mx_img;
+    return SLAM_OK;
+}
+
+// Test hooks beside slam_ctx_block_bytes / slam_ctx_block_fill: the image buffer's current size, and the buffer filled with
+// `byte` once the stream has drained (a buffer not yet taken is a no-op).
+extern "C" int slam_bf_mx_image_bytes(slam_ctx* ctx, int64_t* h_bytes) {
+    SLAM_REQUIRE(ctx && h_bytes, "slam_bf_mx_image_bytes: null argument");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    *h_bytes = (int64_t)ctx->bf_mx_img_bytes;
+    return SLAM_OK;
+}
+extern "C" int slam_bf_mx_image_fill(slam_ctx* ctx, int byte) {
+    SLAM_REQUIRE(ctx, "slam_bf_mx_image_fill: null ctx");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    SLAM_HIP(hipSetDevice(ctx->device));
+    SLAM_HIP(hipStreamSynchronize(ctx->stream));
+    if (!ctx->bf_mx_img || !ctx->bf_mx_img_bytes) return SLAM_OK;
+    SLAM_HIP(hipMemsetAsync(ctx->bf_mx_img, byte, ctx->bf_mx_img_bytes, ctx->stream));
+    SLAM_HIP(hipStreamSynchronize(ctx->stream));
+    return SLAM_OK;
+}
+
 extern "C" int slam_bf_set_engine(slam_ctx* ctx, int engine) {
     SLAM_REQUIRE(ctx, "slam_bf_set_engine: null ctx");
     SLAM_REQUIRE(engine >= 0 && engine <= 3,
@@ -511,21 +579,24 @@ bool bf_mx_route(slam_ctx* ctx, int64_t N, int64_t M, bool rows_on_host) {
 
 int bf_mx_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_train, int64_t M, int64_t train_base, int32_t* d_idx,
                int32_t* d_dist, void* d_keep, const bf_select& sel, int* qblocks_out) {
-    int num_cu, engine;
+    int num_cu, engine, feed;
     {
         std::lock_guard<std::mutex> g(ctx->mu);
         num_cu = ctx->num_cu;
         engine = ctx->bf_engine;
+        feed = ctx->bf_mx_feed;
     }
     const bool wide = engine == 3 || (engine == 0 && bf_mx32_auto(N, M));     // the 32x32x64 kernel
-    const auto kernel = wide ? bf_top2_mx32_kernel : bf_top2_mx_kernel;
-    static std::atomic<int> occ_once[2] = {{0}, {0}};     // a property of the kernel and the architecture: asked once per process
-    int occ = occ_once[wide].load(std::memory_order_relaxed);
+    const bool image = wide && (feed == 2 || (feed == 0 && bf_mx_feed_auto(N, M)));   // ... fed from the prepared image
+    const auto kernel = image ? bf_mx32_image_top2_kernel : wide ? bf_top2_mx32_kernel : bf_top2_mx_kernel;
+    const int which = image ? 2 : wide ? 1 : 0;
+    static std::atomic<int> occ_once[3] = {{0}, {0}, {0}};   // a property of the kernel and the architecture: asked once per process
+    int occ = occ_once[which].load(std::memory_order_relaxed);
     if (!occ) {
         int o = 0;
         SLAM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, 256, 0));
         occ = o > 0 ? o : SLAM_MX_RESIDENT;
-        occ_once[wide].store(occ, std::memory_order_relaxed);
+        occ_once[which].store(occ, std::memory_order_relaxed);
     }
     std::vector<int> tbl;
     const bf_mx_plan p = make_mx_plan_core(num_cu, occ, N, M, &tbl);
@@ -535,9 +606,22 @@ int bf_mx_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_trai
     if (int rc = bf_table_get(ctx, tbl, &d_tbl)) return rc;
     if (qblocks_out) *qblocks_out = p.qblocks;
     SLAM_HIP(hipGetLastError());
+    const void* d_rows = d_train;
+    if (image) {
+        // a stage of the image kernel is one 16 KiB block of the image: every stage, hence every chunk, starts on a whole stage
+        for (size_t i = 0; i + 1 < tbl.size(); i++)
+            SLAM_REQUIRE(tbl[i] % SLAM_MX_STAGE == 0, "MX plan: chunk %zu starts at row %d, not a multiple of the stage", i, tbl[i]);
+        const int64_t rows = (M + SLAM_MX_STAGE - 1) / SLAM_MX_STAGE * SLAM_MX_STAGE;
+        void* img = nullptr;
+        if (int rc = bf_mx_image_get(ctx, (uint64_t)rows * SLAM_MX_IMAGE_ROW_BYTES, &img)) return rc;
+        bf_mx_image_kernel<<<dim3((unsigned)(rows * 2 / 256)), dim3(256), 0, ctx->stream>>>((const u32*)d_train, (int)M, (uint4*)img,
+                                                                                            (int)rows);
+        if (int rc = slam_launch_check("train image kernel")) return rc;
+        d_rows = img;
+    }
     if (int rc = slam_prof_begin(ctx)) return rc;
     kernel<<<dim3(p.qblocks, p.workers), dim3(256), 0, ctx->stream>>>(
-        (const uint4*)d_query, (int)N, (const uint4*)d_train, d_tbl, st, (int)train_base, (int2*)d_idx, (int2*)d_dist,
+        (const uint4*)d_query, (int)N, (const uint4*)d_rows, d_tbl, st, (int)train_base, (int2*)d_idx, (int2*)d_dist,
         (uint4*)d_keep, p.S, sel);
     if (int rc = slam_prof_end(ctx)) return rc;
     const hipError_t e = hipGetLastError();

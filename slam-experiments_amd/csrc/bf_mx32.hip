@@ -50,6 +50,10 @@
 //     3, between MFMAs.  The last stage of the train set, if short, runs group by group, both folds behind the eight MFMAs, with
 //     the test for rows past the chunk.
 //   * plan, tickets, bound exchange, epilogue: those of bf_top2_mx_kernel; bf_mx.hip plans and launches both kernels.
+//   * two feeds (slam_bf_set_mx_feed; DESIGN.md 3c "Feed"): the kernel's text is bf_mx32_scan.inc, included twice.
+//     bf_top2_mx32_kernel stages as described above.  bf_mx32_image_top2_kernel reads an image of the train set that
+//     bf_mx_image_kernel (below) expands once per search into the exact bytes of the LDS stages, and stages with four
+//     direct-to-LDS copies per thread (mx32_copy_stage): no expand, no ds_write, nothing else differs.
 #include "internal.h"
 #include <type_traits>
 
@@ -77,270 +81,57 @@ __device__ __forceinline__ mx_v16f mx32_dot(uint4 a, uint4 b, mx_v16f c) {
 #define MX32_GROUP 32                                  // train rows per group
 #define MX32_GROUPS (SLAM_MX_STAGE / MX32_GROUP)       // groups per whole stage
 
-// grid = (query blocks, workers).  Block (x, y) works for query block (x + y) mod grid.x, as bf_top2_mx_kernel.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void bf_top2_mx32_kernel(
-    const uint4* __restrict__ q, int N, const uint4* __restrict__ t, const int* __restrict__ tbl, bf_state st, int train_base,
-    int2* __restrict__ out_idx, int2* __restrict__ out_dist, uint4* __restrict__ keep, int nchunks, bf_select sel) {
-    __shared__ uint4 tile[2][SLAM_MX_STAGE * 8];
-    __shared__ u32 s_ticket, s_last;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int hk = lane >> 5, col = lane & 31;
-#ifdef SLAM_MX_PROBE
-    unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, plast = __builtin_readcyclecounter();
-#endif
-    const int bx = ((int)blockIdx.x + (int)blockIdx.y) % (int)gridDim.x;
-    // the lane's query in the epilogue and in the bound exchange: worked out afresh at each of them (the empty asm hides that the
-    // value repeats), or it and the addresses built on it hold registers through the scan
-    auto lane_query = [&]() -> int {
-        int v = tid;
-        asm volatile("" : "+v"(v));
-        return bx * 256 + v;
-    };
+// One 16 KiB stage of the prepared image straight from device memory into LDS: four global_load_lds_dwordx4 per thread, piece
+// j = bytes 4096 j .. of the stage, there (scalar base src + 4096 j, plus the thread's fixed offset voff = 16 tid) and here
+// (M0 = lds + 4096 j, wave-uniform: the wave's lane l writes M0 + 16 l, so lds is the stage buffer + 1024 wave).  No vector ALU
+// work and no register holds the bytes.  Written as one asm statement because the compiler, which counts a direct-to-LDS load
+// it knows of against every later ds_read, drains it (vmcnt(0)) in front of the trip's first operand read; this way the copies
+// stay in flight behind the whole trip.  The compiler therefore does not count them: the caller waits (mx32_copies_done) in
+// front of the barrier that hands the buffer to its readers, and until then the buffer is read by nobody.  M0 is saved and
+// restored inside the statement (the compiler keeps it for itself); one wait state between a write of M0 and its use.
+__device__ __forceinline__ void mx32_copy_stage(const uint4* src, u32 voff, u32 lds) {
+    const char* p = (const char*)src;
+    u32 keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
+        "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
+        "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %4\n\t"
+        "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(voff), "s"(p), "s"(p + 4096), "s"(p + 8192), "s"(p + 12288), "s"(lds)
+        : "memory", "scc");
+}
+__device__ __forceinline__ void mx32_copies_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-    // the wave's 64 queries as B operands: tile tt, K-quarter kq = word 2 kq + (lane >> 5) of query 64 wave + 32 tt + (lane & 31)
-    uint4 qb[2][4];
-    const u32* qw = (const u32*)q;
-#pragma unroll
-    for (int tt = 0; tt < 2; tt++) {
-        int qi = bx * 256 + wave * 64 + tt * 32 + col;
-        qi = qi < N ? qi : N - 1;                                // tail columns compute a duplicate and are never stored
-#pragma unroll
-        for (int kq = 0; kq < 4; kq++) qb[tt][kq] = mx_expand(qw[(size_t)qi * 8 + kq * 2 + hk]);
-    }
-    if (const int qbase = lane_query(); keep && blockIdx.y == 0 && qbase < N) {   // the caller wants the query rows left in device memory
-        keep[2 * (size_t)qbase] = q[2 * (size_t)qbase];
-        keep[2 * (size_t)qbase + 1] = q[2 * (size_t)qbase + 1];
-    }
+// The shipped kernel, then the same search fed from the prepared image (t is the image), under a name of its own: the
+// listing tests of the shipped kernel find theirs by prefix
+#define MX32_KERNEL bf_top2_mx32_kernel
+#define MX32_IMAGE_FEED 0
+#include "bf_mx32_scan.inc"
+#undef MX32_KERNEL
+#undef MX32_IMAGE_FEED
+#define MX32_KERNEL bf_mx32_image_top2_kernel
+#define MX32_IMAGE_FEED 1
+#include "bf_mx32_scan.inc"
+#undef MX32_KERNEL
+#undef MX32_IMAGE_FEED
 
-    // per tile: the lane's own top-2 over its rows, the exclusive threshold distance x and the pattern the fold compares against
-    u32 b1[2], b2[2], xs[2];
-    int thr[2];
-    auto set_threshold = [&](int tt, u32 x) {
-        xs[tt] = x;
-        thr[tt] = x > 129u ? (int)0x80000000u : __float_as_int((float)(258 - 2 * (int)x));
-    };
-#pragma unroll
-    for (int tt = 0; tt < 2; tt++) {
-        b1[tt] = b2[tt] = SLAM_KEY_NONE;
-        set_threshold(tt, SLAM_KEY_NONE >> SLAM_KEY_IDX_BITS);   // 511: everything passes
-    }
-    // the top-2 of one tile's query over the rows of the two lanes that hold it
-    auto unite_tile = [&](int tt, u32& u1, u32& u2) {
-        u1 = b1[tt];
-        u2 = b2[tt];
-        const u32 c1 = (u32)__shfl_xor((int)u1, 32, 64), c2 = (u32)__shfl_xor((int)u2, 32, 64);
-        mx_unite(u1, u2, c1, c2);
-    };
-    // Exchange with the other workers of this query block through bound[], at the start of the chunk (or stage) that begins at
-    // row c0; lane l speaks for query 64 wave + l, which tile (l >> 5) holds.  As bf_top2_mx_kernel's.
-    u32 gkey = SLAM_BOUND_IDLE, pend[1] = {0u};
-    auto exchange = [&](int c0) {
-        u32 u1[2], u2[2];
-#pragma unroll
-        for (int tt = 0; tt < 2; tt++) unite_tile(tt, u1[tt], u2[tt]);
-        if (const int qbase = lane_query(); qbase < N) {
-            const u32 own = hk ? u2[1] : u2[0];
-            asm volatile("" ::"v"(pend[0]));
-            const u32 g = __hip_atomic_load(&st.bound[qbase], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (own < g && own < SLAM_MX_BOUND_LIMIT) pend[0] = atomicMin(&st.bound[qbase], own);
-            gkey = g;
-        }
-#pragma unroll
-        for (int tt = 0; tt < 2; tt++) {
-            // the united pair comes from rows below c0: ties against it lose.  Another worker's key: mx_bound_x tests its row
-            const u32 g = (u32)__shfl((int)gkey, tt * 32 + col, 64);
-            set_threshold(tt, min(xs[tt], min(mx_bound_x(g, c0), u2[tt] >> SLAM_KEY_IDX_BITS)));
-        }
-    };
-
-    // staging: thread tid carries half (tid & 1) of row (tid >> 1) of a stage, i.e. the source words 4 sh + j, j = 0 .. 3: word
-    // j is the operand piece of K-quarter 2 sh + (j >> 1), lane (row & 31) + 32 (j & 1), in the row's group of 32
-    const int srow = tid >> 1, sh = tid & 1;
-    auto load_stage = [&](int s, int c1) -> uint4 {
-        const uint4* ts = t + 2 * (size_t)s;
-        if (s + SLAM_MX_STAGE <= c1) return ts[(u32)tid];
-        return s + srow < c1 ? ts[(u32)tid] : make_uint4(0, 0, 0, 0);
-    };
-    const u32 fill = 0x22222222u;
-    uint4* const dst0 = tile[0] + (srow >> 5) * 256 + sh * 128 + (srow & 31);
-    auto store_word = [&](uint4* dst, int j, u32 v) { dst[(j >> 1) * 64 + (j & 1) * 32] = mx_expand_op(v, fill); };
-    auto store_stage = [&](int b, uint4 v) {
-        uint4* dst = dst0 + b * (SLAM_MX_STAGE * 8);
-        store_word(dst, 0, v.x);
-        store_word(dst, 1, v.y);
-        store_word(dst, 2, v.z);
-        store_word(dst, 3, v.w);
-    };
-
-    u32* const cursor = st.cursor + (size_t)(4 * bx) * SLAM_CURSOR_STRIDE;
-    if (tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    int ci = __builtin_amdgcn_readfirstlane((int)s_ticket);
-    int scanned = 0;                                             // wave-uniform: the rows this block has scanned since launch
-    MX_STAMP(0);
-    while (ci < nchunks) {
-        const int c0 = tbl[ci], c1 = tbl[ci + 1];
-        const uint4 first = load_stage(c0, c1);
-        exchange(c0);
-        store_stage(0, first);
-        __syncthreads();
-        MX_STAMP(1);
-        int buf = 0;
-        for (int s0 = c0; s0 < c1; s0 += SLAM_MX_STAGE) {
-            const int s1 = s0 + SLAM_MX_STAGE;
-            const bool more = s1 < c1;
-            // the next ticket is drawn while the chunk's last stage is scanned; read behind the stage's barrier
-            if (!more && tid == 0) s_ticket = __hip_atomic_fetch_add(cursor, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            MX_STAMP(7);
-            const uint4* tp = tile[buf];
-            // fold the 16 results of tile tt of group g and, where some lane of the tile passes, take the update path.  A tile's
-            // fold and update path touch that tile's accumulators and state only, so where the folds of the two tiles stand
-            // relative to each other and to the other tile's MFMAs does not matter to the result
-            auto fold_tile = [&](int tt, int g, const mx_v16f& acc, auto rag) {
-                int p = max(max(__float_as_int(acc[0]), __float_as_int(acc[1])), __float_as_int(acc[2]));
-#pragma unroll
-                for (int i = 3; i < 15; i += 2) p = max(max(p, __float_as_int(acc[i])), __float_as_int(acc[i + 1]));
-                const int m = max(p, __float_as_int(acc[15]));
-                if (__builtin_expect(__ballot(m >= thr[tt]) == 0ull, 1)) return;
-                MX_STAMP(2);
-                // the group's first row is taken from the scalar side here: as a per-lane value it would be carried through
-                // every group that does not fire.  g is the group that is FOLDED, whichever group's MFMAs stand around the fold
-                int row0 = s0 + g * MX32_GROUP;
-                asm("" : "+s"(row0));
-                const u32 rowk = (u32)row0 + (u32)(4 * hk);
-                // key = (128 - D / 2) << 23 | row: base + (-D << 22), exact modulo 2^32 (D is an even integer)
-                const u32 base = (128u << SLAM_KEY_IDX_BITS) + rowk;
-                // the 16 row gates: the compares back to back, each into an SGPR pair of its own (the threshold moves only
-                // behind the rows), then scalar tests alone, so that no branch waits on the compare in front of it
-                unsigned long long gate[16];
-#pragma unroll
-                for (int i = 0; i < 16; i++) gate[i] = __ballot(__float_as_int(acc[i]) >= thr[tt]);
-                asm volatile("" ::"s"(gate[0]), "s"(gate[1]), "s"(gate[2]), "s"(gate[3]), "s"(gate[4]), "s"(gate[5]), "s"(gate[6]),
-                             "s"(gate[7]), "s"(gate[8]), "s"(gate[9]), "s"(gate[10]), "s"(gate[11]), "s"(gate[12]), "s"(gate[13]),
-                             "s"(gate[14]), "s"(gate[15]));
-#pragma unroll
-                for (int i = 0; i < 16; i++) {
-                    if (gate[i] == 0ull) continue;
-                    const int off = 8 * (i >> 2) + (i & 3);
-                    u32 key = base + (u32)off + ((u32)(int)(-acc[i]) << (SLAM_KEY_IDX_BITS - 1));
-                    if constexpr (decltype(rag)::value)   // the rows past the end of a short stage never enter
-                        key = (int)rowk + off < c1 ? key : SLAM_KEY_NONE;
-                    b2[tt] = umed3(b1[tt], b2[tt], key);
-                    b1[tt] = min(b1[tt], key);
-                }
-                set_threshold(tt, min(xs[tt], b2[tt] >> SLAM_KEY_IDX_BITS));
-                MX_STAMP(3);
-            };
-            const mx_v16f zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            auto group = [&](int g, auto rag) {
-                mx_v16f acc[2];
-#pragma unroll
-                for (int kq = 0; kq < 4; kq++) {
-                    const uint4 a = tp[g * 256 + kq * 64 + lane];
-#pragma unroll
-                    for (int tt = 0; tt < 2; tt++) acc[tt] = mx32_dot(a, qb[tt][kq], kq ? acc[tt] : zero);
-                }
-#pragma unroll
-                for (int tt = 0; tt < 2; tt++) fold_tile(tt, g, acc[tt], rag);
-            };
-            // A whole stage: one trip of four groups.  Group k issues, in this order,
-            //     t0k0 t0k1 t0k2 t0k3 [fold of tile 1, group k - 1] t1k0 t1k1 t1k2 t1k3 [fold of tile 0, group k]
-            // (t<tile>k<K-quarter>), so a fold - and the update path where the tile fires - runs while the last of four MFMAs of
-            // the OTHER tile is in the pipe, and between the last MFMA that wrote its accumulators and its first read stand those
-            // four and the other fold: more than the 11 wait states the compiler owes there, so it pads nothing (measured against
-            // the alternating orders in tools/ubench/mx_issue.hip).  Each tile still sees its own MFMAs, fold and
-            // update path in the same order, before its next C = 0 MFMA; tile 1 of the last group folds bare, behind tile 0's
-            // fold, so the stage end sees both tiles folded.
-            // The A operand of K-quarter kq of group k + 1 is read once tile 1's MFMA of quarter kq of group k has issued, into the
-            // registers it frees (three MFMAs before its first use); the last group reads nothing ahead, so no read
-            // leaves the stage's own buffer.  With `shadow`, groups 1 to 3 also expand and store the thread's four source words
-            // of the NEXT stage (into buffer buf ^ 1, free since the barrier that opened this stage) between their MFMAs.
-            auto trip = [&](auto shadow) {
-                constexpr bool SH = decltype(shadow)::value;
-                const uint4* ap = tp + lane;
-                uint4* const dst = dst0 + (buf ^ 1) * (SLAM_MX_STAGE * 8);
-                // the thread's 16 bytes of the next stage, one load at the trip's start: its latency runs behind group 0.  Were
-                // the next stage not whole, the rows past the chunk end would read its last row instead (what such a row holds
-                // never matters, the scan tests its index); this keeps the load inside the train set whatever the table
-                u32 nx[4] = {0, 0, 0, 0};
-                if (SH) {
-                    const uint4 x = (t + 2 * (size_t)s1)[2 * min(srow, c1 - 1 - s1) + sh];
-                    nx[0] = x.x; nx[1] = x.y; nx[2] = x.z; nx[3] = x.w;
-                }
-                uint4 a[4];
-#pragma unroll
-                for (int kq = 0; kq < 4; kq++) a[kq] = ap[kq * 64];
-                mx_v16f acc[2];
-                auto dot = [&](int tt, int kq) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    acc[tt] = mx32_dot(a[kq], qb[tt][kq], kq ? acc[tt] : zero);
-                    __builtin_amdgcn_sched_barrier(0);
-                };
-#pragma unroll
-                for (int k = 0; k < MX32_GROUPS; k++) {
-                    auto ahead = [&](int kq) {                   // both MFMAs of quarter kq of this group have issued (tile 1's last)
-                        if (k + 1 < MX32_GROUPS) a[kq] = ap[(k + 1) * 256 + kq * 64];
-                        __builtin_amdgcn_sched_barrier(0);
-                    };
-                    dot(0, 0);
-                    dot(0, 1);
-                    dot(0, 2);
-                    dot(0, 3);
-                    if (k) fold_tile(1, k - 1, acc[1], std::false_type{});
-                    dot(1, 0);
-                    ahead(0);
-                    dot(1, 1);
-                    ahead(1);
-                    // the next stage's words: word 0 in group 1, word 1 in group 2, words 2 and 3 in group 3
-                    if (SH && k >= 1) store_word(dst, k - 1, nx[k - 1]);
-                    dot(1, 2);
-                    ahead(2);
-                    if (SH && k == 3) store_word(dst, 3, nx[3]);
-                    dot(1, 3);
-                    ahead(3);
-                    fold_tile(0, k, acc[0], std::false_type{});
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                fold_tile(1, MX32_GROUPS - 1, acc[1], std::false_type{});
-            };
-            if (more) {                                          // then this stage is whole
-                trip(std::true_type{});
-            } else if (s1 == c1) {
-                trip(std::false_type{});
-            } else {                                             // a short stage: the last of the train set
-                const int ng = __builtin_amdgcn_readfirstlane((c1 - s0 + MX32_GROUP - 1) / MX32_GROUP);
-                for (int g = 0; g < ng; g++) group(g, std::true_type{});
-            }
-            MX_STAMP(2);
-            // No union of a query's two lanes here: a stage ends with each lane's threshold at its own 2nd-best.  The united
-            // threshold spared 2 % of the fired tiles and cost two LDS round trips in front of the barrier in 41 % of the
-            // tile-stages (tools/mx_fire_model.py; DESIGN.md 3c "The stage tail"); the exchanges and the epilogue still unite.
-            // an early exchange (SLAM_MX_EARLY): per wave, no barrier; every row still to come is at or above s1.  Not after a
-            // chunk's last stage: the chunk-start exchange follows anyway
-            scanned += min(s1, c1) - s0;
-            if (more && scanned < 32 * SLAM_MX_STAGE && (SLAM_MX_EARLY >> (scanned / SLAM_MX_STAGE) & 1u)) exchange(s1);
-            MX_STAMP(4);
-            __syncthreads();
-            MX_STAMP(5);
-            buf ^= 1;
-        }
-        ci = __builtin_amdgcn_readfirstlane((int)s_ticket);
-    }
-
-    u32 u1[2], u2[2];
-#pragma unroll
-    for (int tt = 0; tt < 2; tt++) unite_tile(tt, u1[tt], u2[tt]);
-    const u32 f1[1] = {hk ? u1[1] : u1[0]}, f2[1] = {hk ? u2[1] : u2[0]};
-    // the epilogue's skip test takes a DISTANCE that bounds the final 2nd-best one, or the idle pattern when there is none
-    const u32 gk[1] = {gkey < SLAM_MX_BOUND_LIMIT ? gkey >> SLAM_KEY_IDX_BITS : SLAM_BOUND_IDLE};
-    bf_top2_epilogue<1, true>(st, bx, tid, lane, lane_query(), false, false, f1, f2, gk, pend, N, (int)gridDim.y, train_base, out_idx,
-                              out_dist, sel, s_last);
-#ifdef SLAM_MX_PROBE
-    MX_STAMP(6);
-    if (g_mx32_probe && lane == 0) {
-        unsigned long long* o = g_mx32_probe + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8;
-        for (int i = 0; i < 8; i++) o[i] = pacc[i];
-    }
-#endif
+// The prepared image: the M compact train rows expanded once, in the order of an LDS stage of the search - group of 32 rows =
+// [K-quarter][lane] x 16 bytes (4 KiB), groups consecutive, so the stage that begins at a multiple of 128 rows is one block of
+// 16 KiB.  Thread i carries half (i & 1) of row (i >> 1), one 16-byte load, as a thread of the in-kernel feed does: source word
+// 4 sh + j is the piece of K-quarter 2 sh + (j >> 1), lane (row & 31) + 32 (j & 1), of the row's group - the map of store_word
+// / dst0.  Rows from M up to `rows` (M rounded up to whole stages) are written as the row of zero bits, which is what the
+// in-kernel feed stores there: every launch writes the whole of what its search can read.
+__global__ __launch_bounds__(256) void bf_mx_image_kernel(const u32* __restrict__ t, int M, uint4* __restrict__ img, int rows) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    const int row = i >> 1, sh = i & 1;
+    if (row >= rows) return;
+    const uint4 v = row < M ? ((const uint4*)t)[i] : make_uint4(0, 0, 0, 0);
+    uint4* dst = img + (size_t)(row >> 5) * 256 + sh * 128 + (row & 31);
+    dst[0] = mx_expand(v.x);
+    dst[32] = mx_expand(v.y);
+    dst[64] = mx_expand(v.z);
+    dst[96] = mx_expand(v.w);
 }

@@ -1,6 +1,7 @@
 // bf_mx_common.h — what the two matrix-core top-2 kernels share: bf_top2_mx_kernel (bf_mx.hip, 16x16x128 tiles) and
 // bf_top2_mx32_kernel (bf_mx32.hip, 32x32x64 tiles).  One copy of the +-1 FP4 expand map, the pair union, the exchange limit
-// and the stage geometry; the planner, the routing and the launch stay in bf_mx.hip, which launches either kernel.
+// and the stage geometry; the planner, the routing and the launch stay in bf_mx.hip, which launches either kernel (and the
+// 32x32x64 kernel's sibling that is fed from a prepared image of the train set).
 #pragma once
 #include "internal.h"
 #include "bf_common.h"
@@ -69,3 +70,10 @@ __device__ __forceinline__ u32 mx_bound_x(u32 g, int c0) {
 __global__ void bf_top2_mx32_kernel(const uint4* __restrict__ q, int N, const uint4* __restrict__ t, const int* __restrict__ tbl,
                                     bf_state st, int train_base, int2* __restrict__ out_idx, int2* __restrict__ out_dist,
                                     uint4* __restrict__ keep, int nchunks, bf_select sel);
+// The 32x32x64 search fed from the prepared image of the train set (bf_mx32.hip): t is the image, not the compact rows.
+__global__ void bf_mx32_image_top2_kernel(const uint4* __restrict__ q, int N, const uint4* __restrict__ t, const int* __restrict__ tbl,
+                                          bf_state st, int train_base, int2* __restrict__ out_idx, int2* __restrict__ out_dist,
+                                          uint4* __restrict__ keep, int nchunks, bf_select sel);
+// The image: M compact rows -> `rows` expanded rows of 128 bytes (rows = M rounded up to whole stages), one thread per half row.
+__global__ void bf_mx_image_kernel(const u32* __restrict__ t, int M, uint4* __restrict__ img, int rows);
+#define SLAM_MX_IMAGE_ROW_BYTES 128   // an expanded row: 8 source words x 16 bytes

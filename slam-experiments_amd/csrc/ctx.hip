@@ -79,6 +79,7 @@ extern "C" int slam_ctx_destroy(slam_ctx* ctx) {
     if (ctx->sel_host) (void)hipHostFree(ctx->sel_host);
     for (void* old : ctx->sel_host_old) (void)hipHostFree(old);
     if (ctx->bf_state_mem) (void)hipFree(ctx->bf_state_mem);
+    if (ctx->bf_mx_img) (void)hipFree(ctx->bf_mx_img);
     if (ctx->bf_tbl_ready) {
         (void)hipFree(ctx->bf_tbl_dev);
         (void)hipHostFree(ctx->bf_tbl_host);

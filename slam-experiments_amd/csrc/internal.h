@@ -33,6 +33,9 @@ struct slam_ctx {
     int64_t bf_state_rows = 0;
     int bf_knob[SLAM_BF_KNOBS] = {};                 // matcher tuning overrides (slam_bf_set_tuning), 0 = heuristic
     int bf_engine = 0;                              // top-2 engine (slam_bf_set_engine): 0 = auto, 1 = VALU, 2 / 3 = the 16x16 / 32x32 matrix-core kernel
+    int bf_mx_feed = 0;                             // feed of the 32x32 matrix-core kernel (slam_bf_set_mx_feed): 0 = auto, 1 = expand in the kernel, 2 = prepared image
+    void* bf_mx_img = nullptr;                      // the prepared image of the train set of the search in flight (grow-only, bf_mx.hip);
+    uint64_t bf_mx_img_bytes = 0;                   // written whole by every call that reads it: scratch in the sense of the state contract
     // chunk boundary tables of the recent searches: a ring of small slots + one big slot, device and pinned host
     void* bf_tbl_dev = nullptr;
     void* bf_tbl_host = nullptr;

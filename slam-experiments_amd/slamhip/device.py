@@ -90,6 +90,22 @@ class Context:
         32x32x64 tiles wherever 2 would be eligible.  Every engine gives the same tables, bit for bit."""
         check(self.lib.slam_bf_set_engine(self.handle, int(engine)))
 
+    def set_mx_feed(self, feed: int = 0) -> None:
+        """How the 32x32x64 matrix-core kernel gets its train rows on this context (``slam_bf_set_mx_feed``): 0 = auto
+        (shipped), 1 = expanded in the kernel by every query block, 2 = from an image of the train set prepared once per
+        search.  Every feed gives the same tables, bit for bit."""
+        check(self.lib.slam_bf_set_mx_feed(self.handle, int(feed)))
+
+    def mx_image_bytes(self) -> int:
+        """Current size of the context's prepared-image buffer (``slam_bf_mx_image_bytes``), 0 before the first use."""
+        n = ctypes.c_int64(-1)
+        check(self.lib.slam_bf_mx_image_bytes(self.handle, ctypes.byref(n)))
+        return n.value
+
+    def fill_mx_image(self, byte: int) -> None:
+        """Fill the prepared-image buffer with ``byte`` (``slam_bf_mx_image_fill``, a hook for tests)."""
+        check(self.lib.slam_bf_mx_image_fill(self.handle, int(byte) & 0xFF))
+
     def state_dirty(self) -> int:
         """Words of the search's merge state that are not idle once the stream has drained (``slam_bf_state_dirty``):
         0 after every completed search."""
@@ -172,6 +188,14 @@ def mx_tile_describe(n: int, m: int, engine: int = 0) -> int:
     tile = ctypes.c_int32(0)
     check(_lib.load().slam_bf_mx_tile_describe(int(engine), n, m, ctypes.byref(tile)))
     return tile.value
+
+
+def mx_feed_describe(n: int, m: int, feed: int = 0) -> int:
+    """The feed a pass of n x m on the 32x32x64 kernel takes under ``feed`` (0, 1 or 2), WITHOUT a device
+    (``slam_bf_mx_feed_describe``): 1 = expanded in the kernel, 2 = from the prepared image."""
+    out = ctypes.c_int32(0)
+    check(_lib.load().slam_bf_mx_feed_describe(int(feed), n, m, ctypes.byref(out)))
+    return out.value
 
 
 def plan_describe(n: int, m: int, num_cu: int = 256, qb_all: int = 0, rows_on_host: bool = False, **knobs):

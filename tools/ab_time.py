@@ -4,7 +4,9 @@
     python tools/ab_time.py LIB[:k=v...][,LIB...] [NxM ...] [--rounds R] [--reps K] [--check]
 
 A library may carry tuning knobs of slam_bf_set_tuning, e.g. path/libslamhip.so:R=2:bpc=16 (R, bpc, lead, leadchunk, tail, feed, cold, chunk, queue),
-and the engine of slam_bf_set_engine, e.g. path/libslamhip.so:engine=1 (0 = auto, 1 = VALU, 2 / 3 = the 16x16x128 / 32x32x64 matrix-core kernel where eligible).
+and the engine of slam_bf_set_engine, e.g. path/libslamhip.so:engine=1 (0 = auto, 1 = VALU, 2 / 3 = the 16x16x128 / 32x32x64 matrix-core kernel where eligible),
+and the feed of the 32x32x64 kernel (slam_bf_set_mx_feed), e.g. path/libslamhip.so:engine=3:mxfeed=2 (0 = auto, 1 = expanded in the kernel, 2 = prepared
+image; `feed` is the SGPR-feed knob of slam_bf_set_tuning, and a forced tuning knob sends the search to the VALU kernel).
 
 Each library is dlopen'ed privately (RTLD_LOCAL; the builds export the same symbols), gets its own context and its
 own copy of the inputs.  Per round and library: K back-to-back searches between two HIP events.  --check compares
@@ -43,6 +45,7 @@ class Lib:
         path, *kv = spec.split(":")
         knobs = dict((k, int(v)) for k, v in (x.split("=") for x in kv))
         engine = knobs.pop("engine", None)
+        mxfeed = knobs.pop("mxfeed", None)
         self.name = (os.path.basename(path).replace("libslamhip", "").replace(".so", "") or "shipped") + "".join(":" + x for x in kv)
         self.lib = ctypes.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL | os.RTLD_NOW)
         for n, (res, args) in SIGNATURES.items():
@@ -58,6 +61,8 @@ class Lib:
             assert self.lib.slam_bf_set_tuning(self.ctx, k, nk) == 0, self.lib.slam_last_error()
         if engine is not None:
             assert self.lib.slam_bf_set_engine(self.ctx, engine) == 0, self.lib.slam_last_error()
+        if mxfeed is not None:
+            assert self.lib.slam_bf_set_mx_feed(self.ctx, mxfeed) == 0, self.lib.slam_last_error()
 
     def malloc(self, nbytes):
         p = ctypes.c_void_p()

@@ -2,7 +2,8 @@
 
     python tools/mx_counters.py [--kernel NAME] [--mfma-per-group K] LABEL=DIR[,DIR...] [LABEL=DIR[,DIR...] ...] > profiles/<name>.json
 
-NAME: a substring of the kernel's name (default bf_top2_mx_kernel; bf_top2_mx32_kernel for the 32x32x64 kernel).  K: the MFMAs
+NAME: a substring of the kernel's name (default bf_top2_mx_kernel; bf_top2_mx32_kernel for the 32x32x64 kernel,
+bf_mx32_image_top2_kernel for the same fed from the prepared image, bf_mx_image_kernel for the image's own launch).  K: the MFMAs
 of a group-equivalent of 16 rows x 64 queries x 256 bits (default 8; 4 for the 32x32x64 kernel).
 
 Each DIR is the output directory of one pass (`rocprofv3 --pmc <set> --output-format csv -d DIR -- python3

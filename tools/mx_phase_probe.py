@@ -1,6 +1,6 @@
 """Where a wave of a matrix-core top-2 search (bf_mx.hip, bf_mx32.hip) spends its life, by phase (development aid).
 
-    python tools/mx_phase_probe.py LIB [NxM ...] [--warm K] [--engine 2|3]
+    python tools/mx_phase_probe.py LIB [NxM ...] [--warm K] [--engine 2|3] [--feed 0|1|2]
 
 LIB is an experiment build of libslamhip.so with -DSLAM_MX_PROBE in the kernel's file (tools/build_variant.sh bf_mx
 slam-experiments_amd/csrc/bf_mx.hip tools/exp/libslamhip_probe.so -mllvm -amdgpu-mfma-vgpr-form -DSLAM_MX_PROBE for the 16x16
@@ -34,7 +34,7 @@ def opt(name, default):
     return default
 
 
-warm, engine = opt("--warm", 50), opt("--engine", 2)
+warm, engine, feed = opt("--warm", 50), opt("--engine", 2), opt("--feed", 0)     # --feed: slam_bf_set_mx_feed (builds that have it)
 assert engine in (2, 3), "--engine 2 (bf_top2_mx_kernel) or 3 (bf_top2_mx32_kernel)"
 path = sys.argv[1]
 sizes = [tuple(int(v) for v in a.split("x")) for a in sys.argv[2:]] or [(65536, 65536)]
@@ -49,6 +49,8 @@ set_probe.argtypes = [ctypes.c_void_p]
 ctx = ctypes.c_void_p()
 assert lib.slam_ctx_create(0, ctypes.byref(ctx)) == 0
 assert lib.slam_bf_set_engine(ctx, engine) == 0
+if feed:
+    assert lib.slam_bf_set_mx_feed(ctx, feed) == 0
 
 
 def malloc(nbytes):
