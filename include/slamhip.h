@@ -312,6 +312,32 @@ SLAM_API int slam_bf_mx_feed_describe(int feed, int64_t N, int64_t M, int32_t* h
  * stream has drained (no search reads a byte of the image that the same search has not written). */
 SLAM_API int slam_bf_mx_image_bytes(slam_ctx* ctx, int64_t* h_bytes);
 SLAM_API int slam_bf_mx_image_fill(slam_ctx* ctx, int byte);
+/* Pinned train sets: expand a train set that stays fixed once, not once per search.
+ * slam_bf_train_pin registers rows [0, M) at d_train (inside one slam_malloc allocation of this context) as fixed and, where
+ * some search of this M would take the prepared image (slam_bf_mx_feed_describe_pinned, or feed 2 forced on the context at the
+ * time of the call), builds an image of its own for it on the context's stream, behind whatever filled the rows.  A top-2
+ * search (slam_bf_knn2_u256, the select, keep and batch forms) whose d_train and M are EXACTLY those of a registration then reads
+ * that image where the pinned rule or a forced feed 2 says image, with no image launch of its own; every other search, on any
+ * other pointer or M, sub-ranges of a pinned set included, runs as if nothing were pinned.  Same tables bit for bit.
+ * The contract is the caller's: between a pin and its unpin the rows are written only directly in front of a
+ * slam_bf_train_refresh (which rebuilds the image in stream order, so searches queued earlier see the old rows and later
+ * ones the new); a search between the write and the refresh may see either.  Nothing is cached for a buffer that is not
+ * pinned: it may be overwritten in place between searches as before.
+ * Pinning a pointer that is pinned already replaces the registration (another M included).  A context holds at most 8
+ * registrations; one more is refused with SLAM_ERR_INVALID.  slam_bf_train_unpin drops the registration and frees the image
+ * behind a stream synchronisation; refresh and unpin of a pointer that is not pinned are refused.  slam_free of an allocation
+ * that a pinned set lies in drops the registration first, so a later allocation at the same address never meets a stale image,
+ * and slam_ctx_destroy frees every image. */
+SLAM_API int slam_bf_train_pin(slam_ctx* ctx, const void* d_train, int64_t M);
+SLAM_API int slam_bf_train_refresh(slam_ctx* ctx, const void* d_train);
+SLAM_API int slam_bf_train_unpin(slam_ctx* ctx, const void* d_train);
+/* The feed a pass of N x M on the 32x32x64 kernel takes under `feed` (0, 1 or 2) when its train set is pinned, WITHOUT a
+ * device: *h_feed = 1 or 2.  Never 1 where slam_bf_mx_feed_describe gives 2. */
+SLAM_API int slam_bf_mx_feed_describe_pinned(int feed, int64_t N, int64_t M, int32_t* h_feed);
+/* For tests: the launches of the image kernel this context has issued so far (one per search of an unpinned set fed from the
+ * image, one per pin or refresh that builds an image), and the registrations it holds. */
+SLAM_API int slam_bf_mx_image_launches(slam_ctx* ctx, int64_t* h_count);
+SLAM_API int slam_bf_train_pins(slam_ctx* ctx, int64_t* h_count);
 /* Restore the matcher's per-context merge state to its idle values.  Every search leaves it clean by itself;
  * call this after a search failed part-way (the library does so on a failed launch).  Stream-ordered. */
 SLAM_API int slam_bf_reset_state(slam_ctx* ctx);

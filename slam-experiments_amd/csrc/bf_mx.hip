@@ -558,6 +558,152 @@ extern "C" int slam_bf_mx_image_fill(slam_ctx* ctx, int byte) {
     return SLAM_OK;
 }
 
+// ---- pinned train sets ----------------------------------------------------
+// A caller that holds a train set fixed says so (slam_bf_train_pin), and the image is then built once per train set and not
+// once per search: DESIGN.md 3c "Pinned train sets".  Nothing is cached for a buffer that is not pinned.
+
+// The feed of the 32x32x64 kernel under feed 0 for a pinned train set with an image: the image costs such a search no launch, so
+// the box is bf_mx_feed_auto's, widened.  Measured like it (tools/ab_time.py parent,lib:pin=1 --check, 5 rounds x 30 launches,
+// the whole range below the parent's; profiles/mx_pin_ab.log, table in DESIGN.md 3c "Pinned train sets"): a shape that is not
+// faster from the pinned image keeps feed 1.  Measured faster (1.8 - 3.4 %): the new corners 40000 x 32768, 131072 x 32768 and
+// 40000 x 200000, and 40000 x 65536, 49152 x 65536, 65536 x 32768, 65535 x 65536 inside; 65536 x 65535 in two sessions of
+// three (ranges 0.14 us into each other in the third).  Not faster by that rule: every shape tried with fewer than 20000
+// queries (8192 x 16384 .. 500 x 200000: level or 0.3 - 1.3 us slower, the image is four times the bytes and few query blocks
+// share them) and 32768 x 65536 (median 1.2 - 1.6 % faster, ranges overlap in both sessions).  20000 x 32768 .. 200000
+// measured faster too (1.0 - 2.8 %) and stay outside with 32768 x 65536 between them and the box: the rule is the box whose
+// corners were measured and that adds no shape that failed twice.
+static bool bf_mx_feed_pinned(int64_t N, int64_t M) {
+    return N >= 40000 && N <= 131072 && M >= 32768 && M <= 200000;
+}
+// Whether some N takes the image of a pinned set of M rows under feed 0: the M range of bf_mx_feed_pinned
+static bool bf_mx_feed_pinned_rows(int64_t M) {
+    return M >= 32768 && M <= 200000;
+}
+
+// The feed a pass of N x M takes on the 32x32x64 kernel under `feed` (0, 1 or 2) when its train set is pinned, WITHOUT a device.
+extern "C" int slam_bf_mx_feed_describe_pinned(int feed, int64_t N, int64_t M, int32_t* h_feed) {
+    SLAM_REQUIRE(h_feed, "slam_bf_mx_feed_describe_pinned: null argument");
+    SLAM_REQUIRE(feed >= 0 && feed <= 2, "feed must be 0 (auto), 1 (expand in the kernel) or 2 (prepared image)");
+    SLAM_REQUIRE(N >= 1 && M >= 1, "bad sizes");
+    *h_feed = feed == 2 || (feed == 0 && bf_mx_feed_pinned(N, M)) ? 2 : 1;
+    return SLAM_OK;
+}
+
+static int64_t bf_mx_image_rows(int64_t M) { return (M + SLAM_MX_STAGE - 1) / SLAM_MX_STAGE * SLAM_MX_STAGE; }
+
+// bf_mx_image_kernel of M train rows into img (whole stages), on the context's stream; callers hold ctx->call_mu
+static int bf_mx_image_launch(slam_ctx* ctx, const void* d_train, int64_t M, void* img) {
+    const int64_t rows = bf_mx_image_rows(M);
+    bf_mx_image_kernel<<<dim3((unsigned)(rows * 2 / 256)), dim3(256), 0, ctx->stream>>>((const u32*)d_train, (int)M, (uint4*)img,
+                                                                                        (int)rows);
+    if (int rc = slam_launch_check("train image kernel")) return rc;
+    ctx->bf_mx_img_launches++;
+    return SLAM_OK;
+}
+
+// the registration of exactly (d_train, M), or null; callers hold ctx->call_mu
+static bf_train_pin* bf_train_pin_find(slam_ctx* ctx, const void* d_train, int64_t M) {
+    for (bf_train_pin& p : ctx->bf_pin)
+        if (p.rows == d_train && p.M == M) return &p;
+    return nullptr;
+}
+
+// Frees the slot's image behind a stream synchronisation (queued searches may still read it) and clears the slot
+static int bf_train_pin_drop(slam_ctx* ctx, bf_train_pin* p) {
+    if (p->img) {
+        SLAM_HIP(hipStreamSynchronize(ctx->stream));
+        SLAM_HIP(hipFree(p->img));
+    }
+    *p = bf_train_pin();
+    return SLAM_OK;
+}
+
+extern "C" int slam_bf_train_pin(slam_ctx* ctx, const void* d_train, int64_t M) {
+    SLAM_REQUIRE(ctx && d_train, "slam_bf_train_pin: null argument");
+    SLAM_REQUIRE(M >= 1 && M <= (1ll << 40), "slam_bf_train_pin: bad size");
+    int feed;
+    {
+        // slam_free drops a registration by the allocation it lies in, so the rows must lie in one of this context
+        std::lock_guard<std::mutex> g(ctx->mu);
+        feed = ctx->bf_mx_feed;
+        bool owned = false;
+        const uintptr_t a = (uintptr_t)d_train, b = a + (uint64_t)M * 32;
+        for (const auto& kv : ctx->allocs)
+            owned = owned || ((uintptr_t)kv.first <= a && b <= (uintptr_t)kv.first + (kv.second ? kv.second : 16));
+        SLAM_REQUIRE(owned, "slam_bf_train_pin: rows %p .. + 32 x %lld are not inside one slam_malloc allocation of this context", d_train,
+                     (long long)M);
+    }
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    SLAM_HIP(hipSetDevice(ctx->device));
+    bf_train_pin* slot = nullptr;
+    for (bf_train_pin& p : ctx->bf_pin)
+        if (p.rows == d_train) slot = &p;                        // pinned already: the new registration replaces it
+    if (slot) {
+        if (int rc = bf_train_pin_drop(ctx, slot)) return rc;
+    } else {
+        for (bf_train_pin& p : ctx->bf_pin)
+            if (!p.rows && !slot) slot = &p;
+        SLAM_REQUIRE(slot, "slam_bf_train_pin: this context already holds %d pinned train sets; unpin one first", SLAM_BF_PINS);
+    }
+    void* img = nullptr;
+    if (M <= SLAM_MAX_TRAIN_PER_PASS && (feed == 2 || bf_mx_feed_pinned_rows(M))) {
+        SLAM_HIP(hipMalloc(&img, (uint64_t)bf_mx_image_rows(M) * SLAM_MX_IMAGE_ROW_BYTES));
+        if (int rc = bf_mx_image_launch(ctx, d_train, M, img)) {
+            (void)hipFree(img);
+            return rc;
+        }
+    }
+    slot->rows = d_train;
+    slot->M = M;
+    slot->img = img;
+    return SLAM_OK;
+}
+
+extern "C" int slam_bf_train_refresh(slam_ctx* ctx, const void* d_train) {
+    SLAM_REQUIRE(ctx && d_train, "slam_bf_train_refresh: null argument");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    SLAM_HIP(hipSetDevice(ctx->device));
+    for (bf_train_pin& p : ctx->bf_pin)
+        if (p.rows == d_train) return p.img ? bf_mx_image_launch(ctx, p.rows, p.M, p.img) : SLAM_OK;
+    return slam_set_error(SLAM_ERR_INVALID, "slam_bf_train_refresh: %p is not a pinned train set of this context", d_train);
+}
+
+extern "C" int slam_bf_train_unpin(slam_ctx* ctx, const void* d_train) {
+    SLAM_REQUIRE(ctx && d_train, "slam_bf_train_unpin: null argument");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    SLAM_HIP(hipSetDevice(ctx->device));
+    for (bf_train_pin& p : ctx->bf_pin)
+        if (p.rows == d_train) return bf_train_pin_drop(ctx, &p);
+    return slam_set_error(SLAM_ERR_INVALID, "slam_bf_train_unpin: %p is not a pinned train set of this context", d_train);
+}
+
+void bf_train_unpin_range(slam_ctx* ctx, const void* d_ptr, uint64_t bytes, std::vector<void*>* imgs) {
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    const uintptr_t a = (uintptr_t)d_ptr, b = a + bytes;
+    for (bf_train_pin& p : ctx->bf_pin) {
+        if (!p.rows || (uintptr_t)p.rows >= b || (uintptr_t)p.rows + (uint64_t)p.M * 32 <= a) continue;
+        if (p.img) imgs->push_back(p.img);
+        p = bf_train_pin();
+    }
+}
+
+// Test hooks: the image-kernel launches this context has issued (searches of unpinned sets, pins and refreshes), and the
+// train sets it holds pinned.
+extern "C" int slam_bf_mx_image_launches(slam_ctx* ctx, int64_t* h_count) {
+    SLAM_REQUIRE(ctx && h_count, "slam_bf_mx_image_launches: null argument");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    *h_count = ctx->bf_mx_img_launches;
+    return SLAM_OK;
+}
+extern "C" int slam_bf_train_pins(slam_ctx* ctx, int64_t* h_count) {
+    SLAM_REQUIRE(ctx && h_count, "slam_bf_train_pins: null argument");
+    std::lock_guard<std::mutex> lk(ctx->call_mu);
+    int64_t n = 0;
+    for (const bf_train_pin& p : ctx->bf_pin) n += p.rows ? 1 : 0;
+    *h_count = n;
+    return SLAM_OK;
+}
+
 extern "C" int slam_bf_set_engine(slam_ctx* ctx, int engine) {
     SLAM_REQUIRE(ctx, "slam_bf_set_engine: null ctx");
     SLAM_REQUIRE(engine >= 0 && engine <= 3,
@@ -587,7 +733,10 @@ int bf_mx_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_trai
         feed = ctx->bf_mx_feed;
     }
     const bool wide = engine == 3 || (engine == 0 && bf_mx32_auto(N, M));     // the 32x32x64 kernel
-    const bool image = wide && (feed == 2 || (feed == 0 && bf_mx_feed_auto(N, M)));   // ... fed from the prepared image
+    // a train set pinned as exactly (d_train, M) brings its image along: such a pass takes it by the pinned rule, with no launch
+    const bf_train_pin* pin = wide ? bf_train_pin_find(ctx, d_train, M) : nullptr;
+    const bool pinned = pin && pin->img && (feed == 2 || (feed == 0 && bf_mx_feed_pinned(N, M)));
+    const bool image = pinned || (wide && (feed == 2 || (feed == 0 && bf_mx_feed_auto(N, M))));   // ... fed from the prepared image
     const auto kernel = image ? bf_mx32_image_top2_kernel : wide ? bf_top2_mx32_kernel : bf_top2_mx_kernel;
     const int which = image ? 2 : wide ? 1 : 0;
     static std::atomic<int> occ_once[3] = {{0}, {0}, {0}};   // a property of the kernel and the architecture: asked once per process
@@ -611,12 +760,11 @@ int bf_mx_pass(slam_ctx* ctx, const void* d_query, int64_t N, const void* d_trai
         // a stage of the image kernel is one 16 KiB block of the image: every stage, hence every chunk, starts on a whole stage
         for (size_t i = 0; i + 1 < tbl.size(); i++)
             SLAM_REQUIRE(tbl[i] % SLAM_MX_STAGE == 0, "MX plan: chunk %zu starts at row %d, not a multiple of the stage", i, tbl[i]);
-        const int64_t rows = (M + SLAM_MX_STAGE - 1) / SLAM_MX_STAGE * SLAM_MX_STAGE;
-        void* img = nullptr;
-        if (int rc = bf_mx_image_get(ctx, (uint64_t)rows * SLAM_MX_IMAGE_ROW_BYTES, &img)) return rc;
-        bf_mx_image_kernel<<<dim3((unsigned)(rows * 2 / 256)), dim3(256), 0, ctx->stream>>>((const u32*)d_train, (int)M, (uint4*)img,
-                                                                                            (int)rows);
-        if (int rc = slam_launch_check("train image kernel")) return rc;
+        void* img = pinned ? pin->img : nullptr;
+        if (!pinned) {
+            if (int rc = bf_mx_image_get(ctx, (uint64_t)bf_mx_image_rows(M) * SLAM_MX_IMAGE_ROW_BYTES, &img)) return rc;
+            if (int rc = bf_mx_image_launch(ctx, d_train, M, img)) return rc;
+        }
         d_rows = img;
     }
     if (int rc = slam_prof_begin(ctx)) return rc;

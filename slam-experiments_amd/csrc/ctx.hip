@@ -80,6 +80,8 @@ extern "C" int slam_ctx_destroy(slam_ctx* ctx) {
     for (void* old : ctx->sel_host_old) (void)hipHostFree(old);
     if (ctx->bf_state_mem) (void)hipFree(ctx->bf_state_mem);
     if (ctx->bf_mx_img) (void)hipFree(ctx->bf_mx_img);
+    for (bf_train_pin& p : ctx->bf_pin)
+        if (p.img) (void)hipFree(p.img);
     if (ctx->bf_tbl_ready) {
         (void)hipFree(ctx->bf_tbl_dev);
         (void)hipHostFree(ctx->bf_tbl_host);
@@ -125,15 +127,21 @@ extern "C" int slam_malloc(slam_ctx* ctx, uint64_t bytes, void** d_ptr) {
 extern "C" int slam_free(slam_ctx* ctx, void* d_ptr) {
     SLAM_REQUIRE(ctx, "slam_free: null ctx");
     if (!d_ptr) return SLAM_OK;
+    uint64_t bytes = 0;
     {
         std::lock_guard<std::mutex> g(ctx->mu);
         auto it = ctx->allocs.find(d_ptr);
         SLAM_REQUIRE(it != ctx->allocs.end(), "slam_free: pointer %p not owned by this context", d_ptr);
+        bytes = it->second;
         ctx->allocs.erase(it);
     }
+    // a train set pinned inside this allocation goes with it: a later allocation at the same address must not meet its image
+    std::vector<void*> imgs;
+    bf_train_unpin_range(ctx, d_ptr, bytes ? bytes : 16, &imgs);
     SLAM_HIP(hipSetDevice(ctx->device));
     SLAM_HIP(hipStreamSynchronize(ctx->stream));
     if (ctx->comm_stream) SLAM_HIP(hipStreamSynchronize(ctx->comm_stream));   // the buffer may be one side of a gather in flight
+    for (void* img : imgs) SLAM_HIP(hipFree(img));
     SLAM_HIP(hipFree(d_ptr));
     return SLAM_OK;
 }

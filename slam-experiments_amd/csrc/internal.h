@@ -12,6 +12,15 @@
 
 #define SLAM_BF_TBL_RING 8
 #define SLAM_BF_TBL_SLOT 4096
+#define SLAM_BF_PINS 8
+
+// A pinned train set (slam_bf_train_pin, bf_mx.hip): the caller's promise that rows [0, M) at `rows` change only in front of a
+// slam_bf_train_refresh, and the prepared image that promise lets the searches share.
+struct bf_train_pin {
+    const void* rows = nullptr;                     // the train buffer (null: the slot is free)
+    int64_t M = 0;
+    void* img = nullptr;                            // its image, exactly M padded to whole stages x 128 B; null where no search of this M takes one
+};
 
 struct slam_ctx {
     int device = -1;
@@ -36,6 +45,8 @@ struct slam_ctx {
     int bf_mx_feed = 0;                             // feed of the 32x32 matrix-core kernel (slam_bf_set_mx_feed): 0 = auto, 1 = expand in the kernel, 2 = prepared image
     void* bf_mx_img = nullptr;                      // the prepared image of the train set of the search in flight (grow-only, bf_mx.hip);
     uint64_t bf_mx_img_bytes = 0;                   // written whole by every call that reads it: scratch in the sense of the state contract
+    bf_train_pin bf_pin[SLAM_BF_PINS];              // pinned train sets and their images (blocks of their own), under call_mu
+    int64_t bf_mx_img_launches = 0;                 // bf_mx_image_kernel launches issued so far (slam_bf_mx_image_launches), under call_mu
     // chunk boundary tables of the recent searches: a ring of small slots + one big slot, device and pinned host
     void* bf_tbl_dev = nullptr;
     void* bf_tbl_host = nullptr;
@@ -130,6 +141,9 @@ int slam_filter_count(slam_ctx* ctx, const int32_t* d_idx, const int32_t* d_dist
                       uint8_t* d_keep, int64_t* h_count, int32_t* h_min_dist);
 // bytes of the merge state block for `rows` query rows (bf_hamming.hip)
 size_t bf_state_bytes(size_t rows);
+// Drops every pinned train set that overlaps [d_ptr, d_ptr + bytes) and hands its image to `imgs` (bf_mx.hip; takes the call
+// lock).  slam_free frees those images behind its stream synchronisation, and slam_ctx_destroy drops all of them.
+void bf_train_unpin_range(slam_ctx* ctx, const void* d_ptr, uint64_t bytes, std::vector<void*>* imgs);
 // slam_bf_reset_state without the call lock
 int bf_state_reset(slam_ctx* ctx);
 // the filter kernels of slam_bf_match_filter without the read-back (asynchronous on the ctx stream)

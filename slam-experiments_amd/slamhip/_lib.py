@@ -88,6 +88,12 @@ SIGNATURES = {
     "slam_bf_mx_feed_describe": (c_int, [c_int, c_int64, c_int64, POINTER(c_int32)]),
     "slam_bf_mx_image_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     "slam_bf_mx_image_fill": (c_int, [c_void_p, c_int]),
+    "slam_bf_train_pin": (c_int, [c_void_p, c_void_p, c_int64]),
+    "slam_bf_train_refresh": (c_int, [c_void_p, c_void_p]),
+    "slam_bf_train_unpin": (c_int, [c_void_p, c_void_p]),
+    "slam_bf_mx_feed_describe_pinned": (c_int, [c_int, c_int64, c_int64, POINTER(c_int32)]),
+    "slam_bf_mx_image_launches": (c_int, [c_void_p, POINTER(c_int64)]),
+    "slam_bf_train_pins": (c_int, [c_void_p, POINTER(c_int64)]),
     "slam_bf_reset_state": (c_int, [c_void_p]),
     "slam_bf_state_dirty": (c_int, [c_void_p, POINTER(c_int64)]),
     "slam_bf_match_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p,

@@ -106,6 +106,32 @@ class Context:
         """Fill the prepared-image buffer with ``byte`` (``slam_bf_mx_image_fill``, a hook for tests)."""
         check(self.lib.slam_bf_mx_image_fill(self.handle, int(byte) & 0xFF))
 
+    def pin_train(self, buf: DeviceBuffer, rows: int) -> None:
+        """Declare the ``rows`` train rows at ``buf`` fixed (``slam_bf_train_pin``): their FP4 image is built once, and the
+        top-2 searches over exactly (``buf``, ``rows``) read it instead of building one per call.  From here to
+        ``unpin_train`` the rows may be rewritten only in front of a ``refresh_train``.  At most 8 sets per context."""
+        check(self.lib.slam_bf_train_pin(self.handle, buf.ptr, int(rows)))
+
+    def refresh_train(self, buf: DeviceBuffer) -> None:
+        """Rebuild the image of a pinned train set after its rows were rewritten in place (``slam_bf_train_refresh``)."""
+        check(self.lib.slam_bf_train_refresh(self.handle, buf.ptr))
+
+    def unpin_train(self, buf: DeviceBuffer) -> None:
+        """Drop the registration of a pinned train set (``slam_bf_train_unpin``); freeing the buffer does so too."""
+        check(self.lib.slam_bf_train_unpin(self.handle, buf.ptr))
+
+    def mx_image_launches(self) -> int:
+        """Launches of the image kernel this context has issued so far (``slam_bf_mx_image_launches``, a hook for tests)."""
+        n = ctypes.c_int64(-1)
+        check(self.lib.slam_bf_mx_image_launches(self.handle, ctypes.byref(n)))
+        return n.value
+
+    def train_pins(self) -> int:
+        """Train sets this context holds pinned (``slam_bf_train_pins``, a hook for tests)."""
+        n = ctypes.c_int64(-1)
+        check(self.lib.slam_bf_train_pins(self.handle, ctypes.byref(n)))
+        return n.value
+
     def state_dirty(self) -> int:
         """Words of the search's merge state that are not idle once the stream has drained (``slam_bf_state_dirty``):
         0 after every completed search."""
@@ -195,6 +221,14 @@ def mx_feed_describe(n: int, m: int, feed: int = 0) -> int:
     (``slam_bf_mx_feed_describe``): 1 = expanded in the kernel, 2 = from the prepared image."""
     out = ctypes.c_int32(0)
     check(_lib.load().slam_bf_mx_feed_describe(int(feed), n, m, ctypes.byref(out)))
+    return out.value
+
+
+def mx_feed_describe_pinned(n: int, m: int, feed: int = 0) -> int:
+    """``mx_feed_describe`` for a pass whose train set is pinned (``slam_bf_mx_feed_describe_pinned``): the image costs such
+    a pass no launch, so it is taken at more shapes."""
+    out = ctypes.c_int32(0)
+    check(_lib.load().slam_bf_mx_feed_describe_pinned(int(feed), n, m, ctypes.byref(out)))
     return out.value
 
 

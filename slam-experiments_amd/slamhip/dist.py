@@ -226,8 +226,26 @@ class _Gathering:
                                    "launcher's barrier (all ranks synced, then a process barrier)")
             self.close_peers()
             barrier()
+        self._unpin_train()
         for b in buffers:
             b.free()
+
+    def _pin_train(self, rows: int, synchronise: bool = False) -> None:
+        """The matcher owns ``d_train`` and never rewrites it: pin it (``slam_bf_train_pin``), so that every ``step()`` searches
+        the FP4 image built here once.  ``synchronise``: the rows arrive on another stream, wait for them first."""
+        self._pinned = None
+        if not rows:
+            return
+        if synchronise:
+            self.ctx.sync()
+        ptr = getattr(self.d_train, "buf", self.d_train).ptr     # DeviceDescriptors, or a bare buffer
+        check(self.ctx.lib.slam_bf_train_pin(self.ctx.handle, ptr, rows))
+        self._pinned = ptr
+
+    def _unpin_train(self) -> None:
+        if self._pinned is not None:
+            check(self.ctx.lib.slam_bf_train_unpin(self.ctx.handle, self._pinned))
+            self._pinned = None
 
 
 class ShardedMatcher(_Gathering):
@@ -258,6 +276,7 @@ class ShardedMatcher(_Gathering):
             self.train_replication = "rccl broadcast from rank 0"
         else:
             self.d_train = DeviceDescriptors(ctx, train)   # replicated: 2 MiB at 64k rows
+        self._pin_train(self.n_train, synchronise=self.train_replication != "per-rank upload")
         self.image_rows = None
         self._img_out = None
         if image_rows is not None:
@@ -364,6 +383,7 @@ class TrainShardedMatcher(_Gathering):
         self.n, self.m_local, self.train_base = query.shape[0], train_shard.shape[0], int(train_base)
         self.d_query = DeviceDescriptors(ctx, query)
         self.d_train = DeviceDescriptors(ctx, train_shard)
+        self._pin_train(self.m_local)
         self.slot_bytes = max(self.n, 1) * 8
         self.gathered = [ctx.malloc(self.slot_bytes * world) for _ in range(2)]   # [0]: idx tables, [1]: dist tables
         for g in self.gathered:

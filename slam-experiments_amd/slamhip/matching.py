@@ -54,6 +54,22 @@ class DeviceDescriptors:
     def rows_view(self, start: int, stop: int) -> DeviceBuffer:
         return self.buf.view(start * DESC_BYTES, (stop - start) * DESC_BYTES)
 
+    def pin(self) -> "DeviceDescriptors":
+        """These rows stay as they are while they serve as a train set (``Context.pin_train``): the searches over all of them
+        share one FP4 image instead of building one each.  Rewrite them only in front of ``refresh()``; ``free()`` unpins."""
+        if self.rows:
+            self.ctx.pin_train(self.buf, self.rows)
+        return self
+
+    def refresh(self) -> None:
+        """After the pinned rows were rewritten in place (``Context.refresh_train``)."""
+        if self.rows:
+            self.ctx.refresh_train(self.buf)
+
+    def unpin(self) -> None:
+        if self.rows:
+            self.ctx.unpin_train(self.buf)
+
     def free(self) -> None:
         self.buf.free()
 

@@ -6,7 +6,9 @@
 A library may carry tuning knobs of slam_bf_set_tuning, e.g. path/libslamhip.so:R=2:bpc=16 (R, bpc, lead, leadchunk, tail, feed, cold, chunk, queue),
 and the engine of slam_bf_set_engine, e.g. path/libslamhip.so:engine=1 (0 = auto, 1 = VALU, 2 / 3 = the 16x16x128 / 32x32x64 matrix-core kernel where eligible),
 and the feed of the 32x32x64 kernel (slam_bf_set_mx_feed), e.g. path/libslamhip.so:engine=3:mxfeed=2 (0 = auto, 1 = expanded in the kernel, 2 = prepared
-image; `feed` is the SGPR-feed knob of slam_bf_set_tuning, and a forced tuning knob sends the search to the VALU kernel).
+image; `feed` is the SGPR-feed knob of slam_bf_set_tuning, and a forced tuning knob sends the search to the VALU kernel),
+and pin=1: the train buffer is pinned once after its upload (slam_bf_train_pin) and unpinned before it is freed, e.g.
+path/libslamhip.so:pin=1 - the form a caller with a fixed train set runs.
 
 Each library is dlopen'ed privately (RTLD_LOCAL; the builds export the same symbols), gets its own context and its
 own copy of the inputs.  Per round and library: K back-to-back searches between two HIP events.  --check compares
@@ -46,6 +48,7 @@ class Lib:
         knobs = dict((k, int(v)) for k, v in (x.split("=") for x in kv))
         engine = knobs.pop("engine", None)
         mxfeed = knobs.pop("mxfeed", None)
+        self.pin = knobs.pop("pin", 0)
         self.name = (os.path.basename(path).replace("libslamhip", "").replace(".so", "") or "shipped") + "".join(":" + x for x in kv)
         self.lib = ctypes.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL | os.RTLD_NOW)
         for n, (res, args) in SIGNATURES.items():
@@ -90,6 +93,8 @@ for n, m in sizes:
     for l in L:
         dq, dt, di, dd = l.upload(q), l.upload(t), l.malloc(n * 8), l.malloc(n * 8)
         st.append((dq, dt, di, dd))
+        if l.pin:
+            assert l.lib.slam_bf_train_pin(l.ctx, dt, m) == 0, l.lib.slam_last_error()
     times = [[] for _ in L]
     ms = ctypes.c_float(0)
     for r in range(rounds + 1):                       # round 0 = spin-up, dropped
@@ -115,5 +120,7 @@ for n, m in sizes:
             same = "  table == first library's: %s" % bool(np.array_equal(tab[0], ref[0]) and np.array_equal(tab[1], ref[1]))
         a = np.array(times[i])
         print(f"{n}x{m} {l.name:>22}: median {np.median(a):9.2f} us  min {a.min():9.2f}  max {a.max():9.2f}  ({rounds} rounds x {k} launches){same}", flush=True)
+        if l.pin:
+            assert l.lib.slam_bf_train_unpin(l.ctx, st[i][1]) == 0, l.lib.slam_last_error()
         for p in st[i]:
             l.lib.slam_free(l.ctx, p)
