@@ -1463,6 +1463,60 @@ SLAM_API int slam_covis_edges(slam_ctx* ctx, int64_t K, int64_t P, int64_t E, co
 SLAM_API int slam_covis_rows(slam_ctx* ctx, int64_t M, int64_t nnz, const int64_t* d_offsets, const int32_t* d_obs, int32_t* d_obs_pose,
                              int32_t* d_obs_point);
 
+/* ---- local-map selection and keyframe culling (local_map.hip) -------------------------------------------------
+ * Tracking::UpdateLocalKeyFrames' vote, UpdateLocalPoints and LocalMapping::KeyFrameCulling over tables that stay on the device
+ * (the reference keeps a sliding window and no observation counts).  The map, as slam_fuse_* and slam_covis_rows take it:
+ *   d_offsets int64 [M+1] ON THE DEVICE and d_obs int32 [nnz,2] = (frame, row), lists of at most 256 entries;
+ *   d_frame_offsets int64 [F+1] ON THE DEVICE (h_frame_offsets: the same table on the host), n_rows = frame_offsets[F];
+ *   d_frame_points int32 [n_rows] in row order (-1: none) and d_level int32 [n_rows] in row order;
+ *   byte masks, each may be null: d_frame_removed [F] (a removed keyframe observes nothing, gets no vote, gives no local point
+ *   and counts (0, 0) as a candidate) and d_point_bad [M] (a bad point takes no part anywhere).
+ * Integers only.  Atomics count, or, and, or take a maximum, so every output is a function of the input alone.  No index outside
+ * its range is dereferenced; what is met out of range is skipped and counted in slam_index_errors.  The workspaces are the
+ * caller's (slam_lmap_workspace).  Limits: B <= 65535, F <= 2^24, M <= 2^24, nnz and n_rows < 2^31. */
+/* h_limits [8] = {threads of a workgroup; frames whose vote counters take 16 KiB of LDS; frames whose vote counters fit the LDS
+ * of a CU - above, the counters are global memory; the three lane-group sizes of slam_lmap_cull_count = the longest list each
+ * takes in one step (16, 64, 256); bitmap words of a scan tile; bytes of the scalar block}; needs no device */
+SLAM_API int slam_lmap_limits(int32_t* h_limits);
+/* h_bytes [4] = {the workspace of slam_lmap_frame_points, of slam_lmap_vote for B queries, of slam_lmap_points_mark / _fill for B
+ * queries over M points, of slam_lmap_cull_count for C candidates}; needs no device */
+SLAM_API int slam_lmap_workspace(int64_t B, int64_t F, int64_t M, int64_t C, uint64_t* h_bytes);
+/* The inverse table: d_frame_points = -1, then [frame_offsets[f] + r] = m for every slot (f, r) of point m.  Waits, and returns
+ * h_scalars [2] = {slots whose frame or row is out of range (never dereferenced), claims of a row that already had a point}.
+ * With a row claimed twice the table holds the greatest claimant and must not be used. */
+SLAM_API int slam_lmap_frame_points(slam_ctx* ctx, int64_t M, int64_t nnz, const int64_t* d_offsets, const int32_t* d_obs, int64_t F,
+                                    const int64_t* d_frame_offsets, int64_t n_rows, int32_t* d_frame_points, void* d_ws, int64_t* h_scalars);
+/* The vote of B query frames: query b tracks the map points d_qpoints [h_qoffsets[b], h_qoffsets[b+1]) (-1 and bad points are
+ * skipped; other entries outside [0, M) are skipped and counted).  d_votes int32 [B,F]: for every occurrence of a point in the
+ * list, +1 for every frame of its observation list that is not removed.  d_best int32 [B,2] = (the frame with the most votes, the
+ * lowest on ties; its votes) or (-1, 0); d_nvoted int32 [B] frames with a vote.  form: 0 = by F, 1 / 2 = the counters of a
+ * query in 16 KiB / all the LDS of a CU (F must fit), 3 = in global memory; every form gives the same bytes.  h_skipped null:
+ * asynchronous on the ctx stream; else waits and returns the entries counted. */
+SLAM_API int slam_lmap_vote(slam_ctx* ctx, int64_t B, const int32_t* d_qpoints, const int64_t* h_qoffsets, int64_t M, int64_t nnz,
+                            const int64_t* d_offsets, const int32_t* d_obs, const uint8_t* d_point_bad, int64_t F, const uint8_t* d_frame_removed,
+                            int form, void* d_ws, int32_t* d_votes, int32_t* d_best, int32_t* d_nvoted, int64_t* h_skipped);
+/* The local points of B queries in two phases.  mark: d_bitmap uint32 [B, ceil(M / 32)] = 0, then bit m of row b is set for
+ * every row of the frames d_lkf [h_lkf_offsets[b], h_lkf_offsets[b+1]) that holds a point m that is not bad (a removed frame
+ * has no rows), then cleared for every point of the query's own list d_qpoints; waits, and returns h_counts int64 [B], the bits
+ * set per query.  fill: writes the points of query b, ascending, to d_lpoints [h_out_offsets[b], ...) and never past
+ * h_out_offsets[b+1]; asynchronous on the ctx stream.  The workspace and the bitmap must live from mark until fill has run. */
+SLAM_API int slam_lmap_points_mark(slam_ctx* ctx, int64_t B, const int32_t* d_lkf, const int64_t* h_lkf_offsets, const int32_t* d_qpoints,
+                                   const int64_t* h_qoffsets, int64_t M, const uint8_t* d_point_bad, int64_t F, const int64_t* d_frame_offsets,
+                                   int64_t n_rows, const int32_t* d_frame_points, const uint8_t* d_frame_removed, uint32_t* d_bitmap, void* d_ws,
+                                   int64_t* h_counts);
+SLAM_API int slam_lmap_points_fill(slam_ctx* ctx, int64_t B, int64_t M, const uint32_t* d_bitmap, void* d_ws, const int64_t* h_out_offsets,
+                                   int32_t* d_lpoints);
+/* KeyFrameCulling's count for the C candidate frames h_cand (null: all F frames, C is ignored).  For a row r of candidate c that
+ * holds a point m that is not bad, with N the observers of m that are not removed and l = d_level[r]: n_points += 1; if
+ * N > th_obs and at least th_obs observers (f, r') with f != c have d_level[frame_offsets[f] + r'] <= l + 1, n_redundant += 1.
+ * d_counts int32 [C,2] = (n_points, n_redundant), on 8 bytes; d_flags (may be null) u8 per candidate row, the candidates in
+ * order: 0 no point, 1 counted, 2 redundant.  max_list: no list is longer (a lower value costs time, never a verdict).
+ * C times the rows of the longest candidate must not exceed 2^24 (split the candidates).  Asynchronous on the ctx stream. */
+SLAM_API int slam_lmap_cull_count(slam_ctx* ctx, int64_t C, const int32_t* h_cand, int64_t M, int64_t nnz, const int64_t* d_offsets,
+                                  const int32_t* d_obs, const uint8_t* d_point_bad, int64_t F, const int64_t* h_frame_offsets,
+                                  const int64_t* d_frame_offsets, const int32_t* d_frame_points, const int32_t* d_level,
+                                  const uint8_t* d_frame_removed, int th_obs, int max_list, void* d_ws, int32_t* d_counts, uint8_t* d_flags);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

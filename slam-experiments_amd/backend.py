@@ -27,6 +27,7 @@ from slamhip import bow as _bow
 from slamhip import covis as _cv
 from slamhip import bow_match as _bm
 from slamhip import fuse as _fz
+from slamhip import local_map as _lm
 from slamhip import proj_match as _pm
 from slamhip import tri_match as _tm
 from slamhip import pnp as _pnp
@@ -340,6 +341,23 @@ class Backend:
         graph, its edges of at least ``min_weight`` common points and ``loop_edges``
         (``covisibility_graph(...).essential_edges``)."""
         return self.covisibility_graph(obs_pose_idx, obs_point_idx, K).essential_edges(min_weight, loop_edges)
+
+    def local_map(self, tables, graph, query_points, limit: int = 80, best: int = 10):
+        """ORB-SLAM's ``Tracking::UpdateLocalMap`` for one frame: ``tables`` a ``slamhip.MapTables``, ``graph`` the
+        ``slamhip.CovisibilityGraph`` of the same keyframes, ``query_points`` the map points the frame tracks (-1: none).  The
+        vote and the local points run on the device (``slamhip.local_keyframe_votes`` / ``local_points``), the expansion over
+        the graph on the host (``slamhip.local_keyframes``).  Returns (local keyframes int32, reference keyframe or -1, local
+        map points int32, ascending, without the tracked ones): the point set ``match_by_projection`` searches next."""
+        votes = _lm.local_keyframe_votes(tables, [np.asarray(query_points).reshape(-1)])
+        keyframes, reference = _lm.local_keyframes(votes, graph, limit, best, frame_removed=tables.frame_removed)
+        points = _lm.local_points(tables, [keyframes], [np.asarray(query_points).reshape(-1)])[0]
+        return keyframes, reference, points
+
+    def cull_keyframes(self, tables, graph, new_keyframe: int, ratio=(9, 10), th_obs: int = 3, protect=(0,)):
+        """ORB-SLAM's ``LocalMapping::KeyFrameCulling`` after ``new_keyframe`` was inserted: the candidates are its connected
+        keyframes (``graph.connected``), judged one after the other against the map as the earlier removals left it
+        (``slamhip.cull_keyframes``).  Returns the removed keyframes int32; ``tables.frame_removed`` holds them on both sides."""
+        return _lm.cull_keyframes(tables, graph.connected(new_keyframe), ratio, th_obs, True, protect)
 
     def optimize_pose_graph(self, poses, edges, meas, info, fixed=(0,), iterations: int = _pg.DEFAULT_ITERATIONS,
                             huber_delta: float = 0.0, pcg_tol: float = _pg.DEFAULT_PCG_TOL,

@@ -108,6 +108,21 @@ from .fuse import (  # noqa: F401
     fuse_points,
     refresh_map_points,
 )
+from .local_map import (  # noqa: F401
+    MapTables,
+    cull_keyframes,
+    cull_map_points,
+    frame_points_host,
+    keyframe_redundancy,
+    keyframe_redundancy_host,
+    local_keyframe_votes,
+    local_keyframes,
+    local_points,
+    local_points_host,
+    redundant_verdict,
+    remove_frames,
+    votes_host,
+)
 from .pose_graph import (  # noqa: F401
     loop_edges_from_two_view,
     optimize_pose_graph,
