@@ -28,6 +28,8 @@
  *                          site in the reference (nearest: euroc.py:63-66 compares unaligned translations)
  *   slam_orb_*             cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26),
  *                          called from Frontend._detect_features (frontend.py:245)
+ *   slam_orb_*dist*        the same call with ORB-SLAM's quadtree keypoint distribution and a second,
+ *                          lower FAST threshold for cells without a corner (feature_detectors.py:18-26)
  *   slam_comm_*            no reference counterpart (the reference is single
  *                          process); RCCL all-gather of per-shard top-2 rows
  *
@@ -786,6 +788,32 @@ SLAM_API int slam_orb_extract_u8_host(slam_ctx* ctx, const uint8_t* h_images, in
                                       const uint8_t* h_mask, int mask_batched, int L, const int32_t* h_level_w,
                                       const int32_t* h_level_h, const int32_t* h_quota, int fast_threshold,
                                       const int8_t* h_table, int32_t* h_count, int32_t* h_kp, int64_t* h_resp, uint8_t* h_desc);
+
+/* Quadtree keypoint distribution with an adaptive FAST threshold (ORB-SLAM's ORBextractor retries a cell at a
+ * lower threshold and spreads the survivors with DistributeOctTree): the second selection mode of the extraction above.
+ * Workspace size and layout for slam_orb_extract_dist_u8 (feature_detectors.py:18-26 / frontend.py:245), no device needed.
+ * It takes the quotas themselves (the node tables are sized by them).  h_layout (optional) uint64 [4 + 10 L]: the 4 + 6 L
+ * entries of slam_orb_workspace, then per level {int32 node index per candidate, node table (64 bytes per node), list of the
+ * nodes' best candidates (offsets inside an image block), node capacity = roots + quota + 2, or 0 on a level too small for a
+ * feature}.  Argument errors as slam_orb_workspace, and a null or out-of-range quota. */
+SLAM_API int slam_orb_dist_workspace(int64_t B, int64_t H, int64_t W, int L, const int32_t* h_level_w, const int32_t* h_level_h,
+                                     const int32_t* h_quota, uint64_t* bytes, uint64_t* h_layout);
+
+/* OrbFeatureDetector.detect_and_compute (feature_detectors.py:18-26 / frontend.py:245) with the quadtree selection: the
+ * arguments, outputs and row order of slam_orb_extract_u8, with two changes.  FAST and the suppression run at
+ * fast_threshold_min; a candidate is live if it scores >= fast_threshold or if its 32 x 32 cell ((x-16) >> 5, (y-16) >> 5)
+ * holds no candidate that does.  Per level the live candidates are spread over a quadtree whose fullest nodes are split
+ * until there are quota[l] of them; every node gives its best candidate under (R descending, y, x) and the best quota[l] of
+ * those are kept: min(quota[l], live candidates) rows.  With fast_threshold_min == fast_threshold and a quota above the
+ * candidate count the outputs equal those of slam_orb_extract_u8 bit for bit.  The result does not depend on the order in
+ * which the candidates were appended.  d_workspace: at least slam_orb_dist_workspace bytes.  Four launches.  Errors as
+ * slam_orb_extract_u8, and fast_threshold_min outside [1, fast_threshold]: SLAM_ERR_INVALID, nothing launched, no output
+ * written.  B = 0 does nothing.  There is no host-buffer form. */
+SLAM_API int slam_orb_extract_dist_u8(slam_ctx* ctx, const uint8_t* d_images, int64_t B, int64_t H, int64_t W, const uint8_t* d_mask,
+                                      int mask_batched, int L, const int32_t* h_level_w, const int32_t* h_level_h,
+                                      const int32_t* h_quota, int fast_threshold, int fast_threshold_min, const int8_t* d_table,
+                                      void* d_workspace, uint64_t workspace_bytes, int32_t* d_count, int32_t* d_kp, int64_t* d_resp,
+                                      uint8_t* d_desc);
 
 /* ---- per-frame calls on caller-owned host buffers: one upload, one download, one wait (frame-sized: zero-copy, polled) ---- */
 /* BruteForceFeatureMatcher.match (feature_matchers.py:36-44; cv2.BFMatcher.match + the min-distance filter) in

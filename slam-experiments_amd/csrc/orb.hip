@@ -15,6 +15,8 @@
 //                          is longer than the quota, then a rank by counting among the kept ones: the order of the append drops out
 //   4 orb_describe_kernel  one wave per output slot: moments over the radius-15 disc, the 32-way bin by cross-product signs,
 //                          256 steered comparisons on the blurred level gathered with four ballots; unused slots are zeroed
+// slam_orb_extract_dist_u8 runs the same four launches with orb_distribute_kernel in the place of 3: FAST at the
+// lower of two thresholds, candidates of cells without a strong corner kept, and the quota spread over the level by a quadtree.
 #include "internal.h"
 
 #define ORB_BORDER 16
@@ -35,6 +37,21 @@ struct orb_cand {           // 16 bytes: one FAST survivor of a level
     long long R;            // Harris response
     unsigned int xy;        // x | y << 16 (level coordinates)
     unsigned int pad;
+};
+
+struct orb_dist {           // what the quadtree selection adds to the plan (offsets inside an image block)
+    int t_ini, adaptive;    // the upper threshold; whether the lower one differs from it
+    int n_ini[SLAM_ORB_MAX_LEVELS], node_cap[SLAM_ORB_MAX_LEVELS];
+    unsigned long long cn[SLAM_ORB_MAX_LEVELS], node[SLAM_ORB_MAX_LEVELS], fin[SLAM_ORB_MAX_LEVELS];
+};
+
+struct orb_node {           // 64 bytes: one cell of a level's quadtree, [x0, x1) x [y0, y1) in level coordinates
+    unsigned long long best;    // the best R among its live candidates, sign bit flipped (atomicMax)
+    unsigned bxy;               // x | y << 16 of the first candidate with that R (atomicMin)
+    int count;                  // live candidates inside
+    short x0, y0, x1, y1;
+    int gain, split;            // this round: non-empty children - 1 (-1: not splittable); whether it is being split
+    int cc[4], cm[4];           // this round: live candidates per child; the slot each non-empty child takes
 };
 
 static inline uint64_t orb_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
@@ -292,24 +309,13 @@ __device__ __forceinline__ int orb_kept(const orb_plan& P, const int* counts, in
     return n < P.quota[l] ? n : P.quota[l];
 }
 
-__global__ __launch_bounds__(ORB_SEL_THREADS) void orb_select_kernel(orb_plan P, uint8_t* __restrict__ ws, int32_t* __restrict__ d_count,
-                                                                     int32_t* __restrict__ d_kp, long long* __restrict__ d_resp) {
+// The best m of the n candidates under the key, written to output rows slot0 .. slot0 + m - 1 in key order; sel holds m entries.
+__device__ __forceinline__ void orb_rank_best(const orb_cand* cand, int n, int m, orb_cand* sel, size_t slot0, int l, int32_t* __restrict__ d_kp,
+                                              long long* __restrict__ d_resp) {
     __shared__ int s_hist[256];
     __shared__ orb_key s_prefix;
     __shared__ int s_rank, s_taken;
-    const int tid = threadIdx.x, l = blockIdx.x, b = blockIdx.y;
-    const int* counts = (const int*)(ws + P.counts_off) + b * SLAM_ORB_MAX_LEVELS;
-    int offset = 0, total = 0;
-    for (int j = 0; j < P.L; j++) {
-        const int k = orb_kept(P, counts, j);
-        if (j < l) offset += k;
-        total += k;
-    }
-    if (l == 0 && tid == 0) d_count[b] = total;
-    const int n = counts[l] < P.cap[l] ? counts[l] : P.cap[l], m = orb_kept(P, counts, l);
-    if (m == 0) return;
-    const orb_cand* cand = (const orb_cand*)(ws + P.image_base + (size_t)b * P.image_stride + P.cand[l]);
-    orb_cand* sel = (orb_cand*)(ws + P.sel_off) + (size_t)b * P.n_max + offset;
+    const int tid = threadIdx.x;
     if (tid == 0) { s_prefix = {0ull, 0u}; s_rank = m; s_taken = 0; }
     if (n > m) {                                                        // the m-th smallest key, digit by digit
         for (int d = 0; d < 12; d++) {
@@ -347,12 +353,295 @@ __global__ __launch_bounds__(ORB_SEL_THREADS) void orb_select_kernel(orb_plan P,
         const orb_key k = orb_key_of(c);
         int rank = 0;
         for (int j = 0; j < m; j++) rank += orb_key_less(orb_key_of(sel[j]), k) ? 1 : 0;
-        const size_t slot = (size_t)b * P.n_max + offset + rank;
+        const size_t slot = slot0 + rank;
         d_kp[4 * slot] = (int)(c.xy & 0xFFFF);
         d_kp[4 * slot + 1] = (int)(c.xy >> 16);
         d_kp[4 * slot + 2] = l;
         d_resp[slot] = c.R;
     }
+}
+
+__global__ __launch_bounds__(ORB_SEL_THREADS) void orb_select_kernel(orb_plan P, uint8_t* __restrict__ ws, int32_t* __restrict__ d_count,
+                                                                     int32_t* __restrict__ d_kp, long long* __restrict__ d_resp) {
+    const int tid = threadIdx.x, l = blockIdx.x, b = blockIdx.y;
+    const int* counts = (const int*)(ws + P.counts_off) + b * SLAM_ORB_MAX_LEVELS;
+    int offset = 0, total = 0;
+    for (int j = 0; j < P.L; j++) {
+        const int k = orb_kept(P, counts, j);
+        if (j < l) offset += k;
+        total += k;
+    }
+    if (l == 0 && tid == 0) d_count[b] = total;
+    const int n = counts[l] < P.cap[l] ? counts[l] : P.cap[l], m = orb_kept(P, counts, l);
+    if (m == 0) return;
+    const orb_cand* cand = (const orb_cand*)(ws + P.image_base + (size_t)b * P.image_stride + P.cand[l]);
+    orb_cand* sel = (orb_cand*)(ws + P.sel_off) + (size_t)b * P.n_max + offset;
+    orb_rank_best(cand, n, m, sel, (size_t)b * P.n_max + offset, l, d_kp, d_resp);
+}
+
+// --------------------------------------------------- 3': adaptive threshold and quadtree distribution
+#define ORB_STRONG_WORDS 2048                                           // one bit per 32 x 32 cell: at most 255 x 255 cells on a level
+
+// values that atomics of this block have changed are read past the vector L1
+__device__ __forceinline__ int orb_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned long long orb_ld(const unsigned long long* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned orb_ld(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ int orb_root_x(int i, int w, int n_ini) { return ORB_BORDER + (int)((long long)i * w / n_ini); }
+
+// ascending key order of the nodes of a round = (count descending, y0 ascending, x0 ascending)
+__device__ __forceinline__ unsigned long long orb_node_key(int count, int x0, int y0) {
+    return ((unsigned long long)~(unsigned)count << 32) | ((unsigned long long)(unsigned)y0 << 16) | (unsigned)x0;
+}
+
+// the child of a node that holds (x, y): bit 0 = right half, bit 1 = lower half; the halves are cut at x0 + ceil(width / 2)
+__device__ __forceinline__ int orb_quadrant(const orb_node& nd, int x, int y) {
+    const int xm = nd.x0 + ((nd.x1 - nd.x0 + 1) >> 1), ym = nd.y0 + ((nd.y1 - nd.y0 + 1) >> 1);
+    return (x >= xm ? 1 : 0) + (y >= ym ? 2 : 0);
+}
+
+// The number of live candidates of level j of one image: those that score >= t_ini, and the weaker ones whose 32 x 32 cell holds no
+// such candidate.  Returns early, with a smaller number that is still >= enough, once the strong ones alone reach `enough`; the
+// strong count is read between two barriers, so that return is uniform across the block.
+// With cn (the block's own level) nothing returns early, every candidate gets its root (or -1 if it is not live) and the
+// roots count their live candidates.  All threads of the block call it and get the same value.
+__device__ int orb_live(const orb_plan& P, const orb_dist& D, uint8_t* base, int j, int n, int enough, unsigned* s_strong, int* s_cnt,
+                        int* cn, orb_node* nodes) {
+    const int tid = threadIdx.x, w = P.w[j] - 2 * ORB_BORDER, cells_x = ((w - 1) >> 5) + 1, pitch = P.pitch[j], n_ini = D.n_ini[j];
+    const orb_cand* cand = (const orb_cand*)(base + P.cand[j]);
+    const uint8_t* score = base + P.score[j];
+    __threadfence_block();
+    __syncthreads();                                                    // the value of the call before has been read by everyone
+    for (int i = tid; i < ORB_STRONG_WORDS; i += ORB_SEL_THREADS) s_strong[i] = 0u;
+    if (tid == 0) *s_cnt = D.adaptive ? 0 : n;
+    __syncthreads();
+    if (D.adaptive) {
+        int mine = 0;
+        for (int i = tid; i < n; i += ORB_SEL_THREADS) {
+            const unsigned xy = cand[i].xy;
+            const int x = (int)(xy & 0xFFFF), y = (int)(xy >> 16);
+            if (score[(size_t)y * pitch + x] >= D.t_ini) {
+                const int c = ((y - ORB_BORDER) >> 5) * cells_x + ((x - ORB_BORDER) >> 5);
+                atomicOr(&s_strong[c >> 5], 1u << (c & 31));
+                mine++;
+            }
+        }
+        if (mine) atomicAdd(s_cnt, mine);
+        __syncthreads();
+        const int strong = *s_cnt;                                      // read by everyone before pass two adds to it, so the
+        __syncthreads();                                                // return below is taken by the whole block or by nobody
+        if (!cn && strong >= enough) return strong;
+    }
+    if (D.adaptive || cn) {
+        int mine = 0;
+        for (int i = tid; i < n; i += ORB_SEL_THREADS) {
+            const unsigned xy = cand[i].xy;
+            const int x = (int)(xy & 0xFFFF), y = (int)(xy >> 16);
+            const int c = ((y - ORB_BORDER) >> 5) * cells_x + ((x - ORB_BORDER) >> 5);
+            const bool strong = !D.adaptive || score[(size_t)y * pitch + x] >= D.t_ini;
+            const bool live = strong || !((s_strong[c >> 5] >> (c & 31)) & 1u);
+            mine += !strong && live ? 1 : 0;
+            if (cn) {
+                int r = -1;
+                if (live) {
+                    r = (int)((long long)(x - ORB_BORDER) * n_ini / w);
+                    r = r > n_ini - 1 ? n_ini - 1 : r;
+                    while (r > 0 && orb_root_x(r, w, n_ini) > x) r--;
+                    while (r + 1 < n_ini && orb_root_x(r + 1, w, n_ini) <= x) r++;
+                    atomicAdd(&nodes[r].count, 1);
+                }
+                cn[i] = r;
+            }
+        }
+        if (mine) atomicAdd(s_cnt, mine);
+        __threadfence_block();
+        __syncthreads();
+    }
+    return *s_cnt;
+}
+
+__global__ __launch_bounds__(ORB_SEL_THREADS) void orb_distribute_kernel(orb_plan P, orb_dist D, uint8_t* __restrict__ ws,
+                                                                         int32_t* __restrict__ d_count, int32_t* __restrict__ d_kp,
+                                                                         long long* __restrict__ d_resp) {
+    __shared__ unsigned s_strong[ORB_STRONG_WORDS];
+    __shared__ int s_hist[256];
+    __shared__ unsigned long long s_cut;
+    __shared__ int s_cnt, s_n, s_slots, s_split, s_gain, s_want, s_fin;
+    const int tid = threadIdx.x, l = blockIdx.x, b = blockIdx.y;
+    const int* counts = (const int*)(ws + P.counts_off) + b * SLAM_ORB_MAX_LEVELS;
+    uint8_t* base = ws + P.image_base + (size_t)b * P.image_stride;
+    int offset = 0;
+    for (int j = 0; j < l; j++) {                                       // rows of the levels below: min(quota, live) each
+        const int n = counts[j] < P.cap[j] ? counts[j] : P.cap[j], q = P.quota[j];
+        int k = n < q ? n : q;
+        if (D.adaptive && k > 0) {
+            const int live = orb_live(P, D, base, j, n, q, s_strong, &s_cnt, nullptr, nullptr);
+            k = live < q ? live : q;
+        }
+        offset += k;
+    }
+    const int n = counts[l] < P.cap[l] ? counts[l] : P.cap[l], N = P.quota[l], n_ini = D.n_ini[l], cap = D.node_cap[l];
+    const int w = P.w[l] - 2 * ORB_BORDER, h = P.h[l] - 2 * ORB_BORDER;
+    const orb_cand* cand = (const orb_cand*)(base + P.cand[l]);
+    orb_node* nodes = (orb_node*)(base + D.node[l]);
+    orb_cand* fin = (orb_cand*)(base + D.fin[l]);
+    int* cn = (int*)(base + D.cn[l]);
+    int live = 0;
+    if (n > 0 && N > 0) {                                               // the roots: n_ini vertical strips of the scoreable rectangle
+        for (int i = tid; i < n_ini; i += ORB_SEL_THREADS) {
+            orb_node nd = {0ull, 0xFFFFFFFFu, 0, (short)orb_root_x(i, w, n_ini), (short)ORB_BORDER, (short)orb_root_x(i + 1, w, n_ini),
+                           (short)(ORB_BORDER + h), -1, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
+            nodes[i] = nd;
+        }
+        live = orb_live(P, D, base, l, n, 0, s_strong, &s_cnt, cn, nodes);
+    }
+    const int m = live < N ? live : N;
+    if (l == P.L - 1 && tid == 0) d_count[b] = offset + m;
+    if (m == 0) return;
+    if (tid == 0) { s_n = 0; s_slots = n_ini; }
+    __syncthreads();
+    for (int i = tid; i < n_ini; i += ORB_SEL_THREADS)
+        if (orb_ld(&nodes[i].count) > 0) atomicAdd(&s_n, 1);
+    __syncthreads();
+    for (int round = 0; round < 32; round++) {                          // split the fullest nodes until there are N; extents halve: <= 15 rounds
+        const int n_nodes = s_n, slots = s_slots < cap ? s_slots : cap;
+        if (n_nodes >= N) break;
+        __syncthreads();
+        if (tid == 0) { s_split = 0; s_gain = 0; s_cut = 0ull; s_want = N - n_nodes; }
+        const bool in_lds = 4 * slots <= ORB_STRONG_WORDS;              // few nodes, many adds on each: the child counts go to the LDS,
+        int* s_cc = (int*)s_strong;                                     // where the bitmap was, and are copied to the table below
+        if (in_lds)
+            for (int i = tid; i < 4 * slots; i += ORB_SEL_THREADS) s_cc[i] = 0;
+        for (int j = tid; j < slots; j += ORB_SEL_THREADS) {
+            if (orb_ld(&nodes[j].count) > 1) { nodes[j].cc[0] = 0; nodes[j].cc[1] = 0; nodes[j].cc[2] = 0; nodes[j].cc[3] = 0; }
+            nodes[j].gain = -1;
+            nodes[j].split = 0;
+        }
+        __threadfence_block();
+        __syncthreads();
+        for (int i = tid; i < n; i += ORB_SEL_THREADS) {                // live candidates per child of every splittable node
+            const int j = cn[i];
+            if (j >= 0 && orb_ld(&nodes[j].count) > 1) {
+                const unsigned xy = cand[i].xy;
+                const int q = orb_quadrant(nodes[j], (int)(xy & 0xFFFF), (int)(xy >> 16));
+                if (in_lds) atomicAdd(&s_cc[4 * j + q], 1);
+                else atomicAdd(&nodes[j].cc[q], 1);
+            }
+        }
+        __syncthreads();
+        for (int j = tid; j < slots; j += ORB_SEL_THREADS) {
+            if (orb_ld(&nodes[j].count) > 1) {
+                int g = -1;
+                for (int q = 0; q < 4; q++) {
+                    if (in_lds) nodes[j].cc[q] = s_cc[4 * j + q];
+                    g += (in_lds ? s_cc[4 * j + q] : orb_ld(&nodes[j].cc[q])) > 0 ? 1 : 0;
+                }
+                nodes[j].gain = g;
+                atomicAdd(&s_split, 1);
+                if (g) atomicAdd(&s_gain, g);
+            }
+        }
+        __threadfence_block();
+        __syncthreads();
+        if (s_split == 0) break;
+        if (s_gain >= N - n_nodes) {                                    // the key at which the running sum of gains reaches N - n_nodes
+            for (int d = 0; d < 8; d++) {
+                if (tid < 256) s_hist[tid] = 0;
+                __syncthreads();
+                const unsigned long long prefix = s_cut;
+                for (int j = tid; j < slots; j += ORB_SEL_THREADS) {
+                    const int g = nodes[j].gain;
+                    if (g > 0) {
+                        const unsigned long long k = orb_node_key(orb_ld(&nodes[j].count), nodes[j].x0, nodes[j].y0);
+                        if (d == 0 || (k >> (64 - 8 * d)) == (prefix >> (64 - 8 * d))) atomicAdd(&s_hist[(unsigned)(k >> (56 - 8 * d)) & 255u], g);
+                    }
+                }
+                __syncthreads();
+                if (tid == 0) {
+                    int want = s_want, g = 0;
+                    while (g < 255 && want > s_hist[g]) want -= s_hist[g++];
+                    s_want = want;
+                    s_cut |= (unsigned long long)g << (56 - 8 * d);
+                }
+                __syncthreads();
+            }
+        } else {
+            if (tid == 0) s_cut = ~0ull;                                // the gains never reach it: every splittable node is split
+            __syncthreads();
+        }
+        const unsigned long long cut = s_cut;
+        for (int j = tid; j < slots; j += ORB_SEL_THREADS) {            // slots of the children: the first stays where its parent is
+            if (nodes[j].gain < 0 || orb_node_key(orb_ld(&nodes[j].count), nodes[j].x0, nodes[j].y0) > cut) continue;
+            bool first = true;
+            for (int q = 0; q < 4; q++) {
+                int at = -1;
+                if (orb_ld(&nodes[j].cc[q]) > 0) {
+                    at = first ? j : atomicAdd(&s_slots, 1);
+                    first = false;
+                }
+                nodes[j].cm[q] = at < cap ? at : -1;                    // n_ini + N + 2 slots always suffice
+            }
+            nodes[j].split = 1;
+            atomicAdd(&s_n, nodes[j].gain);
+        }
+        __threadfence_block();
+        __syncthreads();
+        for (int i = tid; i < n; i += ORB_SEL_THREADS) {                // candidates move to the child they lie in
+            const int j = cn[i];
+            if (j >= 0 && nodes[j].split) {
+                const unsigned xy = cand[i].xy;
+                cn[i] = nodes[j].cm[orb_quadrant(nodes[j], (int)(xy & 0xFFFF), (int)(xy >> 16))];
+            }
+        }
+        __threadfence_block();
+        __syncthreads();
+        for (int j = tid; j < slots; j += ORB_SEL_THREADS) {            // the children are written over and behind the nodes of the round
+            if (!nodes[j].split) continue;
+            const orb_node nd = nodes[j];
+            const int xm = nd.x0 + ((nd.x1 - nd.x0 + 1) >> 1), ym = nd.y0 + ((nd.y1 - nd.y0 + 1) >> 1);
+            for (int q = 0; q < 4; q++) {
+                if (nd.cm[q] < 0) continue;
+                const int c = orb_ld(&nodes[j].cc[q]);                  // slot j itself is written last: child 0, or read before
+                orb_node ch = {0ull, 0xFFFFFFFFu, c, (short)(q & 1 ? xm : nd.x0), (short)(q & 2 ? ym : nd.y0), (short)(q & 1 ? nd.x1 : xm),
+                               (short)(q & 2 ? nd.y1 : ym), -1, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
+                if (nd.cm[q] != j) nodes[nd.cm[q]] = ch;
+            }
+            for (int q = 0; q < 4; q++) {
+                if (nd.cm[q] != j) continue;
+                orb_node ch = {0ull, 0xFFFFFFFFu, orb_ld(&nodes[j].cc[q]), (short)(q & 1 ? xm : nd.x0), (short)(q & 2 ? ym : nd.y0),
+                               (short)(q & 1 ? nd.x1 : xm), (short)(q & 2 ? nd.y1 : ym), -1, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
+                nodes[j] = ch;
+            }
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+    __syncthreads();
+    const int slots = s_slots < cap ? s_slots : cap;
+    if (tid == 0) s_fin = 0;
+    for (int i = tid; i < n; i += ORB_SEL_THREADS) {                    // the best live candidate of every node: R first ...
+        const int j = cn[i];
+        if (j >= 0) atomicMax(&nodes[j].best, (unsigned long long)cand[i].R ^ (1ull << 63));
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += ORB_SEL_THREADS) {                    // ... then the smallest y, x among those that have it
+        const int j = cn[i];
+        if (j >= 0 && orb_ld(&nodes[j].best) == ((unsigned long long)cand[i].R ^ (1ull << 63))) atomicMin(&nodes[j].bxy, cand[i].xy);
+    }
+    __syncthreads();
+    for (int j = tid; j < slots; j += ORB_SEL_THREADS) {
+        if (orb_ld(&nodes[j].count) > 0) {
+            const int at = atomicAdd(&s_fin, 1);
+            orb_cand c = {(long long)(orb_ld(&nodes[j].best) ^ (1ull << 63)), orb_ld(&nodes[j].bxy), 0u};
+            fin[at] = c;
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    orb_cand* sel = (orb_cand*)(ws + P.sel_off) + (size_t)b * P.n_max + offset;
+    orb_rank_best(fin, s_fin, m, sel, (size_t)b * P.n_max + offset, l, d_kp, d_resp);
 }
 
 // ------------------------------------------------------------------------------------------ 4: orientation + descriptor
@@ -431,15 +720,19 @@ extern "C" int slam_orb_workspace(int64_t B, int64_t H, int64_t W, int L, const 
 // everything after the argument checks; the caller holds whatever lock its buffers need
 static int orb_launch(slam_ctx* ctx, const orb_plan& P, int64_t B, const uint8_t* d_images, const uint8_t* d_mask, int mask_batched,
                       int fast_threshold, const int8_t* d_table, void* d_workspace, int32_t* d_count, int32_t* d_kp, int64_t* d_resp,
-                      uint8_t* d_desc) {
+                      uint8_t* d_desc, const orb_dist* dist = nullptr) {
     const dim3 tiles((unsigned)P.tile0[P.L], (unsigned)B);
     orb_pyramid_kernel<<<tiles, ORB_THREADS, 0, ctx->stream>>>(P, d_images, (uint8_t*)d_workspace);
     SLAM_HIP(hipGetLastError());
     orb_fast_kernel<<<tiles, ORB_THREADS, 0, ctx->stream>>>(P, d_mask, mask_batched ? (unsigned long long)P.H * P.W : 0ull, fast_threshold,
                                                             (uint8_t*)d_workspace);
     SLAM_HIP(hipGetLastError());
-    orb_select_kernel<<<dim3((unsigned)P.L, (unsigned)B), ORB_SEL_THREADS, 0, ctx->stream>>>(P, (uint8_t*)d_workspace, d_count, d_kp,
-                                                                                             (long long*)d_resp);
+    if (dist)
+        orb_distribute_kernel<<<dim3((unsigned)P.L, (unsigned)B), ORB_SEL_THREADS, 0, ctx->stream>>>(P, *dist, (uint8_t*)d_workspace, d_count,
+                                                                                                     d_kp, (long long*)d_resp);
+    else
+        orb_select_kernel<<<dim3((unsigned)P.L, (unsigned)B), ORB_SEL_THREADS, 0, ctx->stream>>>(P, (uint8_t*)d_workspace, d_count, d_kp,
+                                                                                                 (long long*)d_resp);
     SLAM_HIP(hipGetLastError());
     if (P.n_max > 0) {
         const int64_t slots = B * P.n_max;
@@ -483,6 +776,85 @@ extern "C" int slam_orb_extract_u8(slam_ctx* ctx, const uint8_t* d_images, int64
                  "slam_orb_extract_u8: d_workspace, d_table, d_kp, d_resp and d_desc must be 16-byte aligned");
     SLAM_HIP(hipSetDevice(ctx->device));
     return orb_launch(ctx, P, B, d_images, d_mask, mask_batched, fast_threshold, d_table, d_workspace, d_count, d_kp, d_resp, d_desc);
+}
+
+// Appends, to every image block of a finished plan, what the quadtree selection needs per level: a node index per candidate, the
+// node table (the roots and at most quota + 2 children) and the list of the nodes' best candidates.
+static void orb_extend_plan(orb_plan& P, orb_dist& D, int64_t B, uint64_t& total) {
+    memset(&D, 0, sizeof(D));
+    uint64_t off = P.image_stride;
+    for (int l = 0; l < P.L; l++) {
+        const int w = P.w[l] - 2 * ORB_BORDER, h = P.h[l] - 2 * ORB_BORDER;
+        if (P.cap[l] > 0) {
+            const long long roots = (2ll * w + h) / (2ll * h);
+            D.n_ini[l] = (int)(roots > 1 ? roots : 1);
+            D.node_cap[l] = D.n_ini[l] + P.quota[l] + 2;
+        }
+        D.cn[l] = off; off += orb_up((uint64_t)P.cap[l] * 4, 16);
+        D.node[l] = off; off += (uint64_t)D.node_cap[l] * sizeof(orb_node);
+        D.fin[l] = off; off += (uint64_t)D.node_cap[l] * sizeof(orb_cand);
+    }
+    P.image_stride = orb_up(off, 256);
+    total = P.image_base + (uint64_t)(B > 0 ? B : 1) * P.image_stride;
+}
+
+static int orb_dist_checks(const char* who, int fast_threshold, int fast_threshold_min, orb_plan& P, orb_dist& D, int64_t B, uint64_t& total) {
+    SLAM_REQUIRE(fast_threshold_min >= 1 && fast_threshold_min <= fast_threshold, "%s: fast_threshold_min=%d out of range [1, fast_threshold=%d]",
+                 who, fast_threshold_min, fast_threshold);
+    orb_extend_plan(P, D, B, total);
+    D.t_ini = fast_threshold;
+    D.adaptive = fast_threshold_min < fast_threshold;
+    return SLAM_OK;
+}
+
+extern "C" int slam_orb_dist_workspace(int64_t B, int64_t H, int64_t W, int L, const int32_t* h_level_w, const int32_t* h_level_h,
+                                       const int32_t* h_quota, uint64_t* bytes, uint64_t* h_layout) {
+    orb_plan P;
+    orb_dist D;
+    uint64_t total = 0;
+    SLAM_REQUIRE(L >= 1 && L <= SLAM_ORB_MAX_LEVELS, "slam_orb_dist_workspace: L=%d out of range [1, %d]", L, SLAM_ORB_MAX_LEVELS);
+    SLAM_REQUIRE(h_quota, "slam_orb_dist_workspace: null quota array");
+    int64_t n_max = 0;
+    for (int l = 0; l < L; l++) {
+        SLAM_REQUIRE(h_quota[l] >= 0 && h_quota[l] <= SLAM_ORB_MAX_FEATURES, "slam_orb_dist_workspace: quota[%d]=%d out of range [0, %d]", l,
+                     h_quota[l], SLAM_ORB_MAX_FEATURES);
+        n_max += h_quota[l];
+    }
+    if (int rc = orb_make_plan("slam_orb_dist_workspace", B, H, W, L, h_level_w, h_level_h, n_max, P, total)) return rc;
+    SLAM_REQUIRE(bytes, "slam_orb_dist_workspace: null bytes");
+    for (int l = 0; l < L; l++) P.quota[l] = h_quota[l];
+    orb_extend_plan(P, D, B, total);
+    *bytes = total;
+    if (h_layout) {
+        h_layout[0] = P.image_base; h_layout[1] = P.image_stride; h_layout[2] = P.counts_off; h_layout[3] = P.sel_off;
+        for (int l = 0; l < L; l++) {
+            uint64_t* e = h_layout + 4 + 6 * l;
+            e[0] = P.img[l]; e[1] = P.blur[l]; e[2] = P.score[l]; e[3] = P.cand[l]; e[4] = (uint64_t)P.pitch[l]; e[5] = (uint64_t)P.cap[l];
+            uint64_t* f = h_layout + 4 + 6 * L + 4 * l;
+            f[0] = D.cn[l]; f[1] = D.node[l]; f[2] = D.fin[l]; f[3] = (uint64_t)D.node_cap[l];
+        }
+    }
+    return SLAM_OK;
+}
+
+extern "C" int slam_orb_extract_dist_u8(slam_ctx* ctx, const uint8_t* d_images, int64_t B, int64_t H, int64_t W, const uint8_t* d_mask,
+                                        int mask_batched, int L, const int32_t* h_level_w, const int32_t* h_level_h, const int32_t* h_quota,
+                                        int fast_threshold, int fast_threshold_min, const int8_t* d_table, void* d_workspace,
+                                        uint64_t workspace_bytes, int32_t* d_count, int32_t* d_kp, int64_t* d_resp, uint8_t* d_desc) {
+    orb_plan P;
+    orb_dist D;
+    uint64_t total = 0;
+    if (int rc = orb_checks("slam_orb_extract_dist_u8", ctx, B, H, W, L, h_level_w, h_level_h, h_quota, fast_threshold, P, total)) return rc;
+    if (int rc = orb_dist_checks("slam_orb_extract_dist_u8", fast_threshold, fast_threshold_min, P, D, B, total)) return rc;
+    if (B == 0) return SLAM_OK;
+    SLAM_REQUIRE(d_images && d_table && d_workspace && d_count && (P.n_max == 0 || (d_kp && d_resp && d_desc)),
+                 "slam_orb_extract_dist_u8: null device pointer");
+    SLAM_REQUIRE(workspace_bytes >= total, "slam_orb_extract_dist_u8: workspace of %llu bytes, %llu needed (slam_orb_dist_workspace)",
+                 (unsigned long long)workspace_bytes, (unsigned long long)total);
+    SLAM_REQUIRE((((uintptr_t)d_workspace | (uintptr_t)d_table | (uintptr_t)d_desc | (uintptr_t)d_kp | (uintptr_t)d_resp) & 15) == 0,
+                 "slam_orb_extract_dist_u8: d_workspace, d_table, d_kp, d_resp and d_desc must be 16-byte aligned");
+    SLAM_HIP(hipSetDevice(ctx->device));
+    return orb_launch(ctx, P, B, d_images, d_mask, mask_batched, fast_threshold_min, d_table, d_workspace, d_count, d_kp, d_resp, d_desc, &D);
 }
 
 extern "C" int slam_orb_extract_u8_host(slam_ctx* ctx, const uint8_t* h_images, int64_t B, int64_t H, int64_t W, const uint8_t* h_mask,

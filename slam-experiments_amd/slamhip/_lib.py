@@ -159,6 +159,9 @@ SIGNATURES = {
     "slam_orb_workspace": (c_int, [c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, POINTER(c_uint64), c_void_p]),
     "slam_orb_extract_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_int, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_orb_dist_workspace": (c_int, [c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_uint64), c_void_p]),
+    "slam_orb_extract_dist_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_int, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "slam_orb_extract_u8_host": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                          c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "slam_bf_match_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_double,

@@ -4,6 +4,10 @@
 PARITY UNPINNED: cv2 is absent here and OpenCV's learned sampling pattern is not shipped, so this is ORB's algorithm (oFAST,
 Harris ranking, intensity-centroid orientation, steered BRIEF with a discretised angle) under the integer-exact specification
 of DESIGN.md 4d, not ``cv2.ORB``'s output.  The sampling pattern is an argument.  There is no CPU fallback.
+
+``distribution="quadtree"`` replaces the per-level Harris selection by ORB-SLAM's two remedies against features
+that crowd on one object: cells without a corner at ``fast_threshold`` keep their corners down to ``fast_threshold_min``, and
+the quota is spread over the level by a quadtree.  It runs through ``slam_orb_extract_dist_u8`` on device-resident buffers.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ N_BINS = 32                 # orientation bins of 11.25 degrees
 MAX_LEVELS = 16
 MAX_SIDE = 8192
 MAX_FEATURES = 65536
+DISTRIBUTIONS = ("harris", "quadtree")
 
 # The default 256 comparison pairs (ax, ay, bx, by), int8: drawn once from a seeded isotropic Gaussian (sigma 31/5, rounded,
 # points beyond radius 15 and pairs closer than 2 pixels redrawn) and committed as numbers, 64 pairs per line.
@@ -115,7 +120,8 @@ def to_gray(img: np.ndarray) -> np.ndarray:
 class OrbParams:
     """Everything the library is told about one problem shape: validated sizes, level sizes, quotas, the steered table."""
 
-    def __init__(self, H, W, n_features=500, n_levels=8, scale=1.2, fast_threshold=20, pattern=None):
+    def __init__(self, H, W, n_features=500, n_levels=8, scale=1.2, fast_threshold=20, pattern=None, distribution="harris",
+                 fast_threshold_min=None):
         for name, v in (("n_features", n_features), ("n_levels", n_levels), ("fast_threshold", fast_threshold)):
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
                 raise ValueError(f"{name} must be an integer")
@@ -127,6 +133,16 @@ class OrbParams:
             raise ValueError("fast_threshold must be in [1, 254]")
         if not (np.isfinite(scale) and 1.0 < scale <= 4.0):
             raise ValueError("scale must be in (1, 4]")
+        if distribution not in DISTRIBUTIONS:
+            raise ValueError(f"distribution must be one of {DISTRIBUTIONS}, got {distribution!r}")
+        if fast_threshold_min is None:
+            fast_threshold_min = fast_threshold
+        if not isinstance(fast_threshold_min, (int, np.integer)) or isinstance(fast_threshold_min, bool):
+            raise ValueError("fast_threshold_min must be an integer or None")
+        if not 1 <= fast_threshold_min <= fast_threshold:
+            raise ValueError("fast_threshold_min must be in [1, fast_threshold]")
+        if distribution == "harris" and fast_threshold_min != fast_threshold:
+            raise ValueError('fast_threshold_min below fast_threshold needs distribution="quadtree"')
         if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
             raise ValueError(f"image sides must be in [1, {MAX_SIDE}], got {H} x {W}")
         self.H, self.W, self.L, self.scale, self.t = int(H), int(W), int(n_levels), float(scale), int(fast_threshold)
@@ -134,10 +150,22 @@ class OrbParams:
         self.quota = level_quotas(int(n_features), n_levels, scale)
         self.n_max = int(self.quota.sum())
         self.table = steered_table(pattern)
+        self.distribution, self.t_min = distribution, int(fast_threshold_min)
 
     def workspace(self, B: int) -> Tuple[int, dict]:
-        """(bytes, layout) of ``slam_orb_workspace``: byte offsets of every stage buffer, so a test can download them."""
+        """(bytes, layout) of ``slam_orb_workspace``, or of ``slam_orb_dist_workspace`` for the quadtree mode: byte offsets of
+        every stage buffer, so a test can download them."""
         n = ctypes.c_uint64(0)
+        if self.distribution == "quadtree":
+            lay = np.zeros(4 + 10 * self.L, np.uint64)
+            check(load().slam_orb_dist_workspace(B, self.H, self.W, self.L, addr(self.lw), addr(self.lh), addr(self.quota), ctypes.byref(n),
+                                                 addr(lay)))
+            lv = lay[4:4 + 6 * self.L].reshape(self.L, 6).astype(np.int64)
+            tree = lay[4 + 6 * self.L:].reshape(self.L, 4).astype(np.int64)
+            return int(n.value), {"image_base": int(lay[0]), "image_stride": int(lay[1]), "counts": int(lay[2]), "selection": int(lay[3]),
+                                  "image": lv[:, 0], "blur": lv[:, 1], "score": lv[:, 2], "candidates": lv[:, 3], "pitch": lv[:, 4],
+                                  "capacity": lv[:, 5], "node_index": tree[:, 0], "nodes": tree[:, 1], "node_best": tree[:, 2],
+                                  "node_capacity": tree[:, 3]}
         lay = np.zeros(4 + 6 * self.L, np.uint64)
         check(load().slam_orb_workspace(B, self.H, self.W, self.L, addr(self.lw), addr(self.lh), self.n_max, ctypes.byref(n), addr(lay)))
         lv = lay[4:].reshape(self.L, 6).astype(np.int64)
@@ -210,20 +238,25 @@ def _check_images(images, mask):
 
 
 def orb_extract_arrays(images, mask=None, n_features: int = 500, n_levels: int = 8, scale: float = 1.2, fast_threshold: int = 20,
-                       pattern=None, ctx: Optional[Context] = None, keep_on_device: bool = False) -> OrbResult:
+                       pattern=None, ctx: Optional[Context] = None, keep_on_device: bool = False, distribution: str = "harris",
+                       fast_threshold_min: Optional[int] = None) -> OrbResult:
     """ORB keypoints and descriptors of a batch of grayscale images u8 [B,H,W] (or one [H,W]); ``mask`` u8 [H,W] or [B,H,W],
-    non-zero = allowed.  Arguments are validated here (ValueError) before the library is called."""
+    non-zero = allowed.  Arguments are validated here (ValueError) before the library is called.  ``distribution="quadtree"``
+    spreads each level's quota by a quadtree and keeps corners down to ``fast_threshold_min`` (default: ``fast_threshold``) in
+    cells that have none at ``fast_threshold``; it always runs on device-resident buffers."""
     a, m, batched = _check_images(images, mask)
     B, H, W = a.shape
     if H == 0 or W == 0:
         raise ValueError("images must not be empty")
-    P = OrbParams(H, W, n_features, n_levels, scale, fast_threshold, pattern)
-    count, kp = np.zeros(B, np.int32), np.zeros((B, P.n_max, 4), np.int32)
-    resp, desc = np.zeros((B, P.n_max), np.int64), np.zeros((B, P.n_max, 32), np.uint8)
+    P = OrbParams(H, W, n_features, n_levels, scale, fast_threshold, pattern, distribution, fast_threshold_min)
+    to_host = not keep_on_device and P.distribution == "harris"
+    if B == 0 or to_host:
+        count, kp = np.zeros(B, np.int32), np.zeros((B, P.n_max, 4), np.int32)
+        resp, desc = np.zeros((B, P.n_max), np.int64), np.zeros((B, P.n_max, 32), np.uint8)
     if B == 0:
         return OrbResult(P, count, kp, resp, desc)
     ctx = ctx or default_context()
-    if not keep_on_device:
+    if to_host:
         check(ctx.lib.slam_orb_extract_u8_host(ctx.handle, addr(a), B, H, W, addr(m) if m is not None else None, batched, P.L, addr(P.lw),
                                                addr(P.lh), addr(P.quota), P.t, addr(P.table), addr(count), addr(kp), addr(resp),
                                                addr(desc)))
@@ -233,14 +266,15 @@ def orb_extract_arrays(images, mask=None, n_features: int = 500, n_levels: int =
         ex.upload(a, m)
         ex.run()
         count, kp, resp, desc = ex.download()
-        return OrbResult(P, count, kp, resp, desc, device_block=ex.release_descriptors())
+        return OrbResult(P, count, kp, resp, desc, device_block=ex.release_descriptors() if keep_on_device else None)
     finally:
         ex.free()
 
 
 class OrbExtractor:
-    """Resident buffers for repeated extraction of one problem shape through ``slam_orb_extract_u8`` (the device entry):
-    images, optional mask, table, workspace and outputs stay on the device between calls."""
+    """Resident buffers for repeated extraction of one problem shape through ``slam_orb_extract_u8`` (the device entry), or
+    through ``slam_orb_extract_dist_u8`` when the parameters ask for the quadtree distribution: images, optional mask, table,
+    workspace and outputs stay on the device between calls."""
 
     def __init__(self, ctx: Context, B: int, params: OrbParams):
         self.ctx, self.B, self.P = ctx, int(B), params
@@ -259,8 +293,18 @@ class OrbExtractor:
             self.bufs["mask"] = self.ctx.upload(mask)
             self.mask_batched = int(mask.ndim == 3)
 
+    def drop_mask(self) -> None:
+        if "mask" in self.bufs:
+            self.bufs.pop("mask").free()
+
     def run(self) -> None:
         P, b = self.P, self.bufs
+        if P.distribution == "quadtree":
+            check(self.ctx.lib.slam_orb_extract_dist_u8(self.ctx.handle, b["images"].ptr, self.B, P.H, P.W,
+                                                        b["mask"].ptr if "mask" in b else None, self.mask_batched, P.L, addr(P.lw), addr(P.lh),
+                                                        addr(P.quota), P.t, P.t_min, b["table"].ptr, b["ws"].ptr, self.ws_bytes,
+                                                        b["count"].ptr, b["kp"].ptr, b["resp"].ptr, b["desc"].ptr))
+            return
         check(self.ctx.lib.slam_orb_extract_u8(self.ctx.handle, b["images"].ptr, self.B, P.H, P.W, b["mask"].ptr if "mask" in b else None,
                                                self.mask_batched, P.L, addr(P.lw), addr(P.lh), addr(P.quota), P.t, b["table"].ptr, b["ws"].ptr,
                                                self.ws_bytes, b["count"].ptr, b["kp"].ptr, b["resp"].ptr, b["desc"].ptr))
@@ -282,7 +326,10 @@ class OrbExtractor:
         planes = [self.bufs["ws"].view(base + int(lay[k][level]), pitch * h).download(np.uint8, (h, pitch))[:, :w] for k in ("image", "blur", "score")]
         n = int(self.bufs["ws"].view(lay["counts"] + 4 * (16 * b + level), 4).download(np.int32, (1,))[0])
         n = min(n, int(lay["capacity"][level]))
-        raw = self.bufs["ws"].view(base + int(lay["candidates"][level]), 16 * max(n, 1)).download(np.int64, (max(n, 1), 2))[:n]
+        if n == 0:                                            # an empty list may end the workspace: nothing to read
+            raw = np.zeros((0, 2), np.int64)
+        else:
+            raw = self.bufs["ws"].view(base + int(lay["candidates"][level]), 16 * n).download(np.int64, (n, 2))
         xy = raw[:, 1] & 0xFFFFFFFF
         return planes[0], planes[1], planes[2], (raw[:, 0].copy(), (xy >> 16).astype(np.int64), (xy & 0xFFFF).astype(np.int64))
 
@@ -324,14 +371,48 @@ def _keypoints(res: OrbResult, b: int = 0) -> list:
 class OrbFeatureDetector:
     """Drop-in for the reference's ``OrbFeatureDetector`` (``feature_detectors.py:18-26``), to be passed to ``Frontend`` explicitly
     (``frontend.py:55-69`` takes the detector by injection).  Same signatures; keypoints are ``cv2.KeyPoint`` when cv2 imports,
-    else the ``KeyPoint`` stand-in.  A 3-channel image is converted by ``to_gray``."""
+    else the ``KeyPoint`` stand-in.  A 3-channel image is converted by ``to_gray``.  ``OrbFeatureDetector.quadtree(...)`` makes
+    one that spreads its keypoints by a quadtree and keeps one resident extractor per image shape."""
+
+    distribution, fast_threshold_min = "harris", None          # the constructor keeps the reference's signature: see quadtree()
 
     def __init__(self, n_features: int = 500) -> None:
         self.n_features = n_features
+        self._extractors = {}                                  # quadtree mode: one resident extractor per image shape
+
+    @classmethod
+    def quadtree(cls, n_features: int = 500, fast_threshold_min: Optional[int] = None) -> "OrbFeatureDetector":
+        """A detector of the quadtree mode: the quota of every level spread by a quadtree, corners down to
+        ``fast_threshold_min`` (default: the FAST threshold itself) kept in cells that have none at the FAST threshold."""
+        OrbParams(64, 64, n_features, distribution="quadtree", fast_threshold_min=fast_threshold_min)     # ValueError before anything runs
+        det = cls(n_features)
+        det.distribution, det.fast_threshold_min = "quadtree", fast_threshold_min
+        return det
 
     def detect(self, img: np.ndarray, mask: np.ndarray = None) -> Sequence:
         return self.detect_and_compute(img, mask)[0]
 
     def detect_and_compute(self, img: np.ndarray, mask: np.ndarray = None) -> tuple:
-        res = orb_extract_arrays(to_gray(img), mask=mask, n_features=self.n_features)
+        if self.distribution == "quadtree":
+            res = self._quadtree(to_gray(img), mask)
+        else:
+            res = orb_extract_arrays(to_gray(img), mask=mask, n_features=self.n_features)
         return _keypoints(res, 0), res.descriptors[0]
+
+    def _quadtree(self, gray: np.ndarray, mask) -> OrbResult:
+        a, m, _ = _check_images(gray, mask)
+        ex = self._extractors.get(a.shape[1:])
+        if ex is None:
+            P = OrbParams(a.shape[1], a.shape[2], self.n_features, distribution="quadtree", fast_threshold_min=self.fast_threshold_min)
+            ex = self._extractors[a.shape[1:]] = OrbExtractor(default_context(), 1, P)
+        if m is None:
+            ex.drop_mask()
+        ex.upload(a, m)
+        ex.run()
+        return OrbResult(ex.P, *ex.download())
+
+    def free(self) -> None:
+        """Releases the resident extractors of the quadtree mode."""
+        for ex in self._extractors.values():
+            ex.free()
+        self._extractors = {}
