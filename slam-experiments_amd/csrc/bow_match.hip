@@ -153,21 +153,6 @@ __global__ __launch_bounds__(BM_FIN_THREADS) void bm_finish_kernel(const bm_set 
 }
 
 // =============================================================== entry points ================================================
-// the workspace of one search: the pair table, the top-2 tables when the caller keeps none, the claim words
-struct bm_plan {
-    uint64_t o_pairs, o_idx, o_dist, o_owner, bytes;
-};
-
-static bm_plan bm_layout(int64_t P, int64_t n1_total, int64_t n2_total, bool own_tables) {
-    bm_plan p;
-    p.o_pairs = 0;
-    p.o_idx = slam_align_up((uint64_t)(P > 0 ? P : 1) * sizeof(bm_pair));
-    p.o_dist = p.o_idx + (own_tables ? slam_align_up((uint64_t)n1_total * 8) : 0);
-    p.o_owner = p.o_dist + (own_tables ? slam_align_up((uint64_t)n1_total * 8) : 0);
-    p.bytes = p.o_owner + slam_align_up((uint64_t)n2_total * 4);
-    return p;
-}
-
 extern "C" int slam_bow_match_limits(int32_t* h_limits) {
     SLAM_REQUIRE(h_limits, "slam_bow_match_limits: null pointer");
     h_limits[0] = BM_ROWS_MAX;
@@ -186,28 +171,17 @@ extern "C" int slam_bow_match_plan_describe(int64_t B, int64_t n, int64_t* h_pla
     int64_t P2 = 2;
     while (P2 < n) P2 <<= 1;
     const int64_t per = (n + BM_SCAN_LANES - 1) / BM_SCAN_LANES;
-    const bm_plan p = bm_layout(B, B * n, B * n, true);
+    const mf_plan p = mf_layout(0, B, sizeof(bm_pair), B * n, B * n, true);
     const int64_t v[8] = {P2, (int64_t)(BM_ROWS_MAX * sizeof(u64)), B, B * per, B, (int64_t)p.bytes,
                           (int64_t)(BM_BINS * 4 + 8), (int64_t)slam_align_up((uint64_t)(B + 1) * 8)};
     memcpy(h_plan, v, sizeof(v));
     return SLAM_OK;
 }
 
-static int bm_check_offsets(const int64_t* off, int64_t B, const char* who) {
-    SLAM_REQUIRE(B >= 0 && B <= (1 << 24), "%s: B=%lld out of range [0, 2^24]", who, (long long)B);
-    SLAM_REQUIRE(off && off[0] == 0, "%s: null offsets, or offsets that do not start at 0", who);
-    for (int64_t b = 0; b < B; b++) {
-        const int64_t n = off[b + 1] - off[b];
-        SLAM_REQUIRE(n >= 0 && n <= BM_ROWS_MAX, "%s: image %lld has %lld rows (0 .. %d)", who, (long long)b, (long long)n, BM_ROWS_MAX);
-    }
-    SLAM_REQUIRE(off[B] < (1ll << 31), "%s: more than 2^31 rows", who);
-    return SLAM_OK;
-}
-
 extern "C" int slam_bow_match_group(slam_ctx* ctx, const void* d_desc, const int32_t* d_nodes, const int64_t* h_offsets, int64_t B,
                                     void* d_desc_sorted, int32_t* d_nodes_sorted, int32_t* d_order, int32_t* d_inverse) {
     SLAM_REQUIRE(ctx, "slam_bow_match_group: null ctx");
-    if (int rc = bm_check_offsets(h_offsets, B, "slam_bow_match_group")) return rc;
+    if (int rc = mf_check_offsets(h_offsets, B, "slam_bow_match_group", "image")) return rc;
     const int64_t n = h_offsets[B];
     if (n == 0) return SLAM_OK;
     SLAM_REQUIRE(d_desc && d_nodes && d_desc_sorted && d_nodes_sorted && d_order && d_inverse, "slam_bow_match_group: null device pointer");
@@ -224,8 +198,7 @@ extern "C" int slam_bow_match_group(slam_ctx* ctx, const void* d_desc, const int
 
 static int bm_check_groups(const slam_bow_groups* g, const char* who, bm_set* out) {
     SLAM_REQUIRE(g, "%s: null group set", who);
-    if (int rc = bm_check_offsets(g->h_offsets, g->B, who)) return rc;
-    SLAM_REQUIRE(g->h_offsets[g->B] == 0 || (g->d_desc && g->d_nodes && g->d_order && g->d_inverse), "%s: null device pointer in a group set", who);
+    if (int rc = mf_check_groups(g, who)) return rc;
     SLAM_REQUIRE(((uintptr_t)g->d_desc & 15) == 0, "%s: descriptor pointers must be 16-byte aligned", who);
     out->desc = (const uint4*)g->d_desc;
     out->nodes = g->d_nodes;
@@ -252,39 +225,26 @@ static int bm_run(slam_ctx* ctx, const slam_bow_groups* g1, const slam_bow_group
     if (P == 0) return SLAM_OK;
     SLAM_REQUIRE(h_pairs, "%s: null pairs", who);
     std::vector<bm_pair> table((size_t)P);
-    int64_t out1 = 0, own2 = 0, blocks = 0;
-    for (int64_t p = 0; p < P; p++) {
-        const int64_t a = h_pairs[2 * p], b = h_pairs[2 * p + 1];
-        SLAM_REQUIRE(a >= 0 && a < g1->B && b >= 0 && b < g2->B, "%s: pair %lld = (%lld, %lld) names an image outside the sets (%lld, %lld)", who,
-                     (long long)p, (long long)a, (long long)b, (long long)g1->B, (long long)g2->B);
-        bm_pair& e = table[(size_t)p];
-        e.base1 = g1->h_offsets[a];
-        e.base2 = g2->h_offsets[b];
-        e.n1 = (int)(g1->h_offsets[a + 1] - e.base1);
-        e.n2 = (int)(g2->h_offsets[b + 1] - e.base2);
-        e.out1 = out1;
-        e.own2 = own2;
-        e.blk0 = (int)blocks;
-        e.pad = 0;
-        out1 += e.n1;
-        own2 += e.n2;
-        blocks += (e.n1 + BM_SCAN_LANES - 1) / BM_SCAN_LANES;
-    }
+    mf_totals t{0, 0, 0};
+    for (int64_t p = 0; p < P; p++)
+        if (int rc = mf_pair_next(table[(size_t)p], g1->h_offsets, g1->B, h_pairs[2 * p], g2->h_offsets, g2->B, h_pairs[2 * p + 1], BM_SCAN_LANES,
+                                  t, who, p))
+            return rc;
+    const int64_t out1 = t.out1, own2 = select ? t.own2 : 0, blocks = t.blocks;     // (the top-2 alone claims nothing)
     SLAM_REQUIRE(!select || (d_count && (out1 == 0 || d_matches12)), "%s: null result pointer", who);
     SLAM_REQUIRE(select || out1 == 0 || d_idx, "%s: null result pointer", who);
     if (!select && out1 == 0) return SLAM_OK;
     std::lock_guard<std::mutex> lk(ctx->call_mu);       // the pair table, the claim words and the tables nobody asked for: the workspace
     SLAM_HIP(hipSetDevice(ctx->device));
-    const bm_plan pl = bm_layout(P, out1, select ? own2 : 0, d_idx == nullptr);
+    const mf_plan pl = mf_layout(0, P, sizeof(bm_pair), out1, own2, d_idx == nullptr);
     void* ws = nullptr;
     if (int rc = slam_workspace(ctx, pl.bytes, &ws)) return rc;
     char* w = (char*)ws;
+    if (int rc = mf_stage(ctx, pl, w, table.data(), own2)) return rc;
     const bm_pair* d_pairs = (const bm_pair*)(w + pl.o_pairs);
     int2* idx = d_idx ? (int2*)d_idx : (int2*)(w + pl.o_idx);
     int2* dist = d_dist ? (int2*)d_dist : (int2*)(w + pl.o_dist);
     u32* owner = (u32*)(w + pl.o_owner);
-    SLAM_HIP(hipMemcpyAsync(w + pl.o_pairs, table.data(), (size_t)P * sizeof(bm_pair), hipMemcpyHostToDevice, ctx->stream));
-    if (select && own2 > 0) SLAM_HIP(hipMemsetAsync(owner, 0xFF, (size_t)own2 * 4, ctx->stream));
     if (blocks > 0) {
         if (int rc = slam_prof_begin(ctx)) return rc;
         if (select)

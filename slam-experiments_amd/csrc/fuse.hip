@@ -308,42 +308,30 @@ extern "C" int slam_fuse_search(slam_ctx* ctx, const slam_proj_points* points, c
     std::vector<char> block(head + (size_t)P * sizeof(fz_pair));
     memcpy(block.data(), &prm, sizeof(prm));
     fz_pair* table = (fz_pair*)(block.data() + head);
-    int64_t out1 = 0, own2 = 0, blocks = 0;
+    mf_totals t{0, 0, 0};
     for (int64_t p = 0; p < P; p++) {
-        const int64_t a = h_pairs[2 * p], b = h_pairs[2 * p + 1];
-        SLAM_REQUIRE(a >= 0 && a < points->B && b >= 0 && b < frames->B, "%s: pair %lld = (%lld, %lld) lies outside the sets", who, (long long)p,
-                     (long long)a, (long long)b);
-        SLAM_REQUIRE(h_th[p] > 0.0, "%s: th[%lld] is not positive", who, (long long)p);
         fz_pair& e = table[(size_t)p];
-        e.m.base1 = points->h_offsets[a];
-        e.m.n1 = (int)(points->h_offsets[a + 1] - e.m.base1);
-        e.m.base2 = frames->h_offsets[b];
-        e.m.n2 = (int)(frames->h_offsets[b + 1] - e.m.base2);
-        e.m.out1 = out1;
-        e.m.own2 = own2;
-        e.m.blk0 = (int)blocks;
-        e.m.pad = 0;
+        if (int rc = mf_pair_next(e.m, points->h_offsets, points->B, h_pairs[2 * p], frames->h_offsets, frames->B, h_pairs[2 * p + 1],
+                                  PM_SCAN_LANES, t, who, p))
+            return rc;
+        SLAM_REQUIRE(h_th[p] > 0.0, "%s: th[%lld] is not positive", who, (long long)p);
         memcpy(e.A, h_poses + 12 * p, sizeof(e.A));
         memcpy(e.Ow, h_centres + 3 * p, sizeof(e.Ow));
         e.th = h_th[p];
-        e.frame = (int)b;
+        e.frame = h_pairs[2 * p + 1];
         e.pad = 0;
-        out1 += e.m.n1;
-        own2 += e.m.n2;
-        blocks += (e.m.n1 + PM_SCAN_LANES - 1) / PM_SCAN_LANES;
     }
-    SLAM_REQUIRE(out1 < (1ll << 31) && own2 < (1ll << 31), "%s: more than 2^31 rows over the pairs", who);
+    const int64_t out1 = t.out1, own2 = t.own2, blocks = t.blocks;
     SLAM_REQUIRE(d_count && (out1 == 0 || (d_row && d_dist && d_status && d_other)), "%s: null result pointer", who);
     std::lock_guard<std::mutex> lk(ctx->call_mu);       // the parameters, the pair table and the claim words
     SLAM_HIP(hipSetDevice(ctx->device));
-    const uint64_t o_pairs = head, o_owner = o_pairs + slam_align_up((uint64_t)P * sizeof(fz_pair));
+    const mf_plan pl = mf_layout(sizeof(fz_params), P, sizeof(fz_pair), 0, own2, false);    // (the scan keeps no top-2 tables)
     void* ws = nullptr;
-    if (int rc = slam_workspace(ctx, o_owner + slam_align_up((uint64_t)own2 * 4), &ws)) return rc;
+    if (int rc = slam_workspace(ctx, pl.bytes, &ws)) return rc;
     char* w = (char*)ws;
-    const fz_pair* d_pairs = (const fz_pair*)(w + o_pairs);
-    u32* owner = (u32*)(w + o_owner);
-    SLAM_HIP(hipMemcpyAsync(w, block.data(), block.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (own2 > 0) SLAM_HIP(hipMemsetAsync(owner, 0xFF, (size_t)own2 * 4, ctx->stream));
+    if (int rc = mf_stage(ctx, pl, w, block.data(), own2)) return rc;
+    const fz_pair* d_pairs = (const fz_pair*)(w + pl.o_pairs);
+    u32* owner = (u32*)(w + pl.o_owner);
     if (blocks > 0) {
         const fz_obs ob{d_obs_offsets, (const int2*)d_obs, h_obs_offsets[M], (int)M};
         if (int rc = slam_prof_begin(ctx)) return rc;
@@ -365,7 +353,7 @@ extern "C" int slam_fuse_refresh(slam_ctx* ctx, const double* d_xyz, const int64
     SLAM_REQUIRE(h_obs_offsets && h_obs_offsets[0] == 0, "%s: null observation offsets, or offsets that do not start at 0", who);
     SLAM_REQUIRE(n_levels >= 1 && n_levels <= FP_LEVELS_MAX && h_scale, "%s: n_levels=%d outside [1, %d], or a null scale table", who, n_levels,
                  FP_LEVELS_MAX);
-    if (int rc = pm_check_offsets(h_frame_offsets, B, who, "frame")) return rc;
+    if (int rc = mf_check_offsets(h_frame_offsets, B, who, "frame")) return rc;
     if (!h_select) K = M;
     SLAM_REQUIRE(K >= 0 && K <= FZ_POINTS_MAX, "%s: K=%lld selected points out of range", who, (long long)K);
     // the jobs by the length of their lists: G = 16, 64, 256 lanes a point

@@ -149,22 +149,6 @@ __global__ __launch_bounds__(MF_FIN_THREADS) void pm_finish_kernel(const uint8_t
 }
 
 // =============================================================== entry points ================================================
-// the workspace of one search: the pair table, the parameters, the top-2 tables when the caller keeps none, the claim words
-struct pm_plan {
-    uint64_t o_pairs, o_prm, o_idx, o_dist, o_owner, bytes;
-};
-
-static pm_plan pm_layout(int64_t P, int64_t n1_total, int64_t n2_total, bool own_tables) {
-    pm_plan p;
-    p.o_prm = 0;                                        // the parameters and the pair table are one block: one copy
-    p.o_pairs = slam_align_up(sizeof(pm_params));
-    p.o_idx = p.o_pairs + slam_align_up((uint64_t)(P > 0 ? P : 1) * sizeof(pm_pair));
-    p.o_dist = p.o_idx + (own_tables ? slam_align_up((uint64_t)n1_total * 8) : 0);
-    p.o_owner = p.o_dist + (own_tables ? slam_align_up((uint64_t)n1_total * 8) : 0);
-    p.bytes = p.o_owner + slam_align_up((uint64_t)n2_total * 4);
-    return p;
-}
-
 extern "C" int slam_proj_match_limits(int32_t* h_limits) {
     SLAM_REQUIRE(h_limits, "slam_proj_match_limits: null pointer");
     h_limits[0] = PM_ROWS_MAX;
@@ -181,7 +165,7 @@ extern "C" int slam_proj_match_plan_describe(int64_t B, int64_t P, int64_t n, in
     SLAM_REQUIRE(B >= 0 && P >= 0 && P <= PM_PAIRS_MAX, "B=%lld, P=%lld out of range", (long long)B, (long long)P);
     SLAM_REQUIRE(n >= 0 && n <= PM_ROWS_MAX, "n=%lld out of range [0, %d] rows per image", (long long)n, PM_ROWS_MAX);
     const int64_t per = (n + PM_SCAN_LANES - 1) / PM_SCAN_LANES, row_blocks = (B * n + PM_ROW_THREADS - 1) / PM_ROW_THREADS;
-    const pm_plan p = pm_layout(P, P * n, P * n, true);
+    const mf_plan p = mf_layout(sizeof(pm_params), P, sizeof(pm_pair), P * n, P * n, true);
     const int64_t v[8] = {row_blocks, B, B * ((n + PM_ROW_THREADS - 1) / PM_ROW_THREADS), P * per, P, (int64_t)p.bytes,
                           (int64_t)(MF_BINS * 4 + 8), (int64_t)slam_align_up((uint64_t)(B + 1) * 8)};
     memcpy(h_plan, v, sizeof(v));
@@ -193,7 +177,7 @@ extern "C" int slam_proj_match_grid(slam_ctx* ctx, const void* d_desc, const flo
                                     int32_t* d_cells_sorted, int32_t* d_order, int32_t* d_inverse, float* d_xy_sorted,
                                     int32_t* d_meta_sorted) {
     SLAM_REQUIRE(ctx, "slam_proj_match_grid: null ctx");
-    if (int rc = pm_check_offsets(h_offsets, B, "slam_proj_match_grid", "frame")) return rc;
+    if (int rc = mf_check_offsets(h_offsets, B, "slam_proj_match_grid", "frame")) return rc;
     int gw, gh;
     if (int rc = pm_check_grid(W, H, cell, "slam_proj_match_grid", &gw, &gh)) return rc;
     const int64_t n = h_offsets[B];
@@ -250,44 +234,32 @@ static int pm_run(slam_ctx* ctx, const slam_proj_points* pts, const slam_proj_fr
     std::vector<char> block(head + (size_t)P * sizeof(pm_pair));
     memcpy(block.data(), &prm, sizeof(prm));
     pm_pair* table = (pm_pair*)(block.data() + head);
-    int64_t out1 = 0, own2 = 0, blocks = 0;
+    mf_totals t{0, 0, 0};
     for (int64_t p = 0; p < P; p++) {
-        const int64_t a = h_a[stride * p], b = search ? h_b[stride * p] : 0;
-        SLAM_REQUIRE(a >= 0 && a < pts->B && (!search || (b >= 0 && b < frames->B)), "%s: pair %lld = (%lld, %lld) lies outside the sets", who,
-                     (long long)p, (long long)a, (long long)b);
-        SLAM_REQUIRE(h_th[p] > 0.0, "%s: th[%lld] is not positive", who, (long long)p);
         pm_pair& e = table[(size_t)p];
-        e.m.base1 = pts->h_offsets[a];
-        e.m.n1 = (int)(pts->h_offsets[a + 1] - e.m.base1);
-        e.m.base2 = search ? frames->h_offsets[b] : 0;
-        e.m.n2 = search ? (int)(frames->h_offsets[b + 1] - e.m.base2) : 0;
-        e.m.out1 = out1;
-        e.m.own2 = own2;
-        e.m.blk0 = (int)blocks;
-        e.m.pad = 0;
+        if (int rc = mf_pair_next(e.m, pts->h_offsets, pts->B, h_a[stride * p], search ? frames->h_offsets : nullptr, search ? frames->B : 0,
+                                  search ? h_b[stride * p] : 0, PM_SCAN_LANES, t, who, p))
+            return rc;
+        SLAM_REQUIRE(h_th[p] > 0.0, "%s: th[%lld] is not positive", who, (long long)p);
         memcpy(e.A, h_poses + 12 * p, sizeof(e.A));
         memcpy(e.Ow, h_centres + 3 * p, sizeof(e.Ow));
         e.th = h_th[p];
-        out1 += e.m.n1;
-        own2 += e.m.n2;
-        blocks += (e.m.n1 + PM_SCAN_LANES - 1) / PM_SCAN_LANES;
     }
-    SLAM_REQUIRE(out1 < (1ll << 31) && own2 < (1ll << 31), "%s: more than 2^31 rows over the pairs", who);
+    const int64_t out1 = t.out1, own2 = t.own2, blocks = t.blocks;      // (own2 = 0 without a side 2)
     SLAM_REQUIRE(!search || (d_count && (out1 == 0 || d_matches12)), "%s: null result pointer", who);
     if (!search && out1 == 0) return SLAM_OK;
     std::lock_guard<std::mutex> lk(ctx->call_mu);       // the pair table, the parameters, the claim words and the tables nobody asked for
     SLAM_HIP(hipSetDevice(ctx->device));
-    const pm_plan pl = pm_layout(P, search ? out1 : 0, search ? own2 : 0, search && d_idx == nullptr);
+    const mf_plan pl = mf_layout(sizeof(pm_params), P, sizeof(pm_pair), search ? out1 : 0, own2, search && d_idx == nullptr);
     void* ws = nullptr;
     if (int rc = slam_workspace(ctx, pl.bytes, &ws)) return rc;
     char* w = (char*)ws;
+    if (int rc = mf_stage(ctx, pl, w, block.data(), own2)) return rc;
     const pm_pair* d_pairs = (const pm_pair*)(w + pl.o_pairs);
-    const pm_params* d_prm = (const pm_params*)(w + pl.o_prm);
+    const pm_params* d_prm = (const pm_params*)w;
     int2* idx = d_idx ? (int2*)d_idx : (int2*)(w + pl.o_idx);
     int2* dist = d_dist ? (int2*)d_dist : (int2*)(w + pl.o_dist);
     u32* owner = (u32*)(w + pl.o_owner);
-    SLAM_HIP(hipMemcpyAsync(w + pl.o_prm, block.data(), block.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (search && own2 > 0) SLAM_HIP(hipMemsetAsync(owner, 0xFF, (size_t)own2 * 4, ctx->stream));
     if (blocks > 0) {
         if (int rc = slam_prof_begin(ctx)) return rc;
         if (search)

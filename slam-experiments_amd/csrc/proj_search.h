@@ -49,17 +49,6 @@ struct pm_points {
 __device__ __forceinline__ int pm_cell_of(double x, double cell, int g) { return (int)fmin(fmax(floor(x / cell), 0.0), (double)(g - 1)); }
 
 // ------------------------------------------------------------------------------------------------- argument checks (host)
-static int pm_check_offsets(const int64_t* off, int64_t B, const char* who, const char* what) {
-    SLAM_REQUIRE(B >= 0 && B <= (1 << 24), "%s: %lld %ss out of range [0, 2^24]", who, (long long)B, what);
-    SLAM_REQUIRE(off && off[0] == 0, "%s: null %s offsets, or offsets that do not start at 0", who, what);
-    for (int64_t b = 0; b < B; b++) {
-        const int64_t n = off[b + 1] - off[b];
-        SLAM_REQUIRE(n >= 0 && n <= PM_ROWS_MAX, "%s: %s %lld has %lld rows (0 .. %d)", who, what, (long long)b, (long long)n, PM_ROWS_MAX);
-    }
-    SLAM_REQUIRE(off[B] < (1ll << 31), "%s: more than 2^31 rows", who);
-    return SLAM_OK;
-}
-
 static int pm_check_grid(int W, int H, int cell, const char* who, int* gw, int* gh) {
     SLAM_REQUIRE(W > 0 && H > 0, "%s: the image is %d x %d", who, W, H);
     SLAM_REQUIRE(cell > 0, "%s: cell=%d is not positive", who, cell);
@@ -95,7 +84,7 @@ static int pm_check_params(const slam_proj_params* p, const char* who, bool sear
 
 static int pm_check_points(const slam_proj_points* s, const char* who, pm_points* out) {
     SLAM_REQUIRE(s, "%s: null point sets", who);
-    if (int rc = pm_check_offsets(s->h_offsets, s->B, who, "point set")) return rc;
+    if (int rc = mf_check_offsets(s->h_offsets, s->B, who, "point set")) return rc;
     SLAM_REQUIRE(s->h_offsets[s->B] == 0 || s->d_xyz, "%s: null positions", who);
     SLAM_REQUIRE(((uintptr_t)s->d_desc & 15) == 0, "%s: descriptor pointers must be 16-byte aligned", who);
     out->xyz = s->d_xyz;
@@ -109,7 +98,7 @@ static int pm_check_points(const slam_proj_points* s, const char* who, pm_points
 
 // a frame set of a search (points: the point sets searched in it, for their descriptors)
 static int pm_check_frames(const slam_proj_frames* frames, const slam_proj_points* pts, const char* who, pm_frames* s2) {
-    if (int rc = pm_check_offsets(frames->h_offsets, frames->B, who, "frame")) return rc;
+    if (int rc = mf_check_offsets(frames->h_offsets, frames->B, who, "frame")) return rc;
     if (int rc = pm_check_grid(frames->W, frames->H, frames->cell, who, &s2->gw, &s2->gh)) return rc;
     SLAM_REQUIRE(frames->h_offsets[frames->B] == 0 ||
                      (frames->d_desc && frames->d_cells && frames->d_order && frames->d_xy && frames->d_meta && frames->d_level),

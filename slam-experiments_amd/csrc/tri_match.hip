@@ -201,23 +201,6 @@ __global__ __launch_bounds__(TM_TRI_ROWS) void tm_triangulate_kernel(const tm_vi
 }
 
 // =============================================================== entry points ================================================
-// the workspace of one call: the parameters and the pair table (one block, one copy), the top-2 tables when the caller keeps
-// none, the claim words
-struct tm_plan {
-    uint64_t o_prm, o_pairs, o_idx, o_dist, o_owner, bytes;
-};
-
-static tm_plan tm_layout(int64_t P, size_t pair_bytes, int64_t n1_total, int64_t n2_total, bool own_tables) {
-    tm_plan p;
-    p.o_prm = 0;
-    p.o_pairs = slam_align_up(sizeof(tp_params));
-    p.o_idx = p.o_pairs + slam_align_up((uint64_t)(P > 0 ? P : 1) * pair_bytes);
-    p.o_dist = p.o_idx + (own_tables ? slam_align_up((uint64_t)n1_total * 8) : 0);
-    p.o_owner = p.o_dist + (own_tables ? slam_align_up((uint64_t)n1_total * 8) : 0);
-    p.bytes = p.o_owner + slam_align_up((uint64_t)n2_total * 4);
-    return p;
-}
-
 extern "C" int slam_tri_match_limits(int32_t* h_limits) {
     SLAM_REQUIRE(h_limits, "slam_tri_match_limits: null pointer");
     h_limits[0] = TM_ROWS_MAX;
@@ -236,30 +219,18 @@ extern "C" int slam_tri_match_plan_describe(int64_t P, int64_t n, int64_t* h_pla
     SLAM_REQUIRE(P >= 0 && P <= TM_PAIRS_MAX, "P=%lld out of range [0, %d]", (long long)P, TM_PAIRS_MAX);
     SLAM_REQUIRE(n >= 0 && n <= TM_ROWS_MAX, "n=%lld out of range [0, %d] rows per image", (long long)n, TM_ROWS_MAX);
     const int64_t per = (n + TM_SCAN_LANES - 1) / TM_SCAN_LANES;
-    const tm_plan s = tm_layout(P, sizeof(tm_pair), P * n, P * n, true), t = tm_layout(P, sizeof(tt_pair), 0, 0, false);
+    const mf_plan s = mf_layout(sizeof(tp_params), P, sizeof(tm_pair), P * n, P * n, true);
+    const mf_plan t = mf_layout(sizeof(tp_params), P, sizeof(tt_pair), 0, 0, false);
     const int64_t v[6] = {P * per, P, P * ((n + TM_TRI_ROWS - 1) / TM_TRI_ROWS), (int64_t)s.bytes, (int64_t)t.bytes, (int64_t)(MF_BINS * 4 + 8)};
     memcpy(h_plan, v, sizeof(v));
     return SLAM_OK;
 }
 
-static int tm_check_offsets(const int64_t* off, int64_t B, const char* who) {
-    SLAM_REQUIRE(B >= 0 && B <= (1 << 24), "%s: B=%lld out of range [0, 2^24]", who, (long long)B);
-    SLAM_REQUIRE(off && off[0] == 0, "%s: null offsets, or offsets that do not start at 0", who);
-    for (int64_t b = 0; b < B; b++) {
-        const int64_t n = off[b + 1] - off[b];
-        SLAM_REQUIRE(n >= 0 && n <= TM_ROWS_MAX, "%s: image %lld has %lld rows (0 .. %d)", who, (long long)b, (long long)n, TM_ROWS_MAX);
-    }
-    SLAM_REQUIRE(off[B] < (1ll << 31), "%s: more than 2^31 rows", who);
-    return SLAM_OK;
-}
-
-// the few lines of bow_match.hip that turn a slam_bow_groups into kernel arguments, with the side's pixels, levels and marks
+// a checked slam_bow_groups as kernel arguments, with the side's pixels, levels and marks
 static int tm_check_side(const slam_bow_groups* g, const slam_tri_views* v, const char* who, tm_set* out) {
     SLAM_REQUIRE(g && v, "%s: null group set or views", who);
-    if (int rc = tm_check_offsets(g->h_offsets, g->B, who)) return rc;
-    const bool rows = g->h_offsets[g->B] > 0;
-    SLAM_REQUIRE(!rows || (g->d_desc && g->d_nodes && g->d_order && g->d_inverse), "%s: null device pointer in a group set", who);
-    SLAM_REQUIRE(!rows || (v->d_xy && v->d_level), "%s: null pixels or levels", who);
+    if (int rc = mf_check_groups(g, who)) return rc;
+    SLAM_REQUIRE(g->h_offsets[g->B] == 0 || (v->d_xy && v->d_level), "%s: null pixels or levels", who);
     SLAM_REQUIRE(((uintptr_t)g->d_desc & 15) == 0 && ((uintptr_t)v->d_xy & 7) == 0, "%s: misaligned descriptors or pixels", who);
     out->desc = (const uint4*)g->d_desc;
     out->nodes = g->d_nodes;
@@ -294,35 +265,6 @@ static int tm_check_params(const slam_tri_params* p, const char* who, bool searc
     return SLAM_OK;
 }
 
-// the pair records' common head; block_rows: the side-1 rows one workgroup of the kernel that reads the table takes
-template <class REC>
-static int tm_fill_pairs(const int64_t* off1, int64_t B1, const int64_t* off2, int64_t B2, const int32_t* h_pairs, int64_t P, REC* table,
-                         int block_rows, const char* who, int64_t* out1_total, int64_t* own2_total, int64_t* blocks_total) {
-    int64_t out1 = 0, own2 = 0, blocks = 0;
-    for (int64_t p = 0; p < P; p++) {
-        const int64_t a = h_pairs[2 * p], b = h_pairs[2 * p + 1];
-        SLAM_REQUIRE(a >= 0 && a < B1 && b >= 0 && b < B2, "%s: pair %lld = (%lld, %lld) names an image outside the sets (%lld, %lld)", who,
-                     (long long)p, (long long)a, (long long)b, (long long)B1, (long long)B2);
-        mf_pair& e = table[(size_t)p].m;
-        e.base1 = off1[a];
-        e.base2 = off2[b];
-        e.n1 = (int)(off1[a + 1] - e.base1);
-        e.n2 = (int)(off2[b + 1] - e.base2);
-        e.out1 = out1;
-        e.own2 = own2;
-        e.blk0 = (int)blocks;
-        e.pad = 0;
-        out1 += e.n1;
-        own2 += e.n2;
-        blocks += (e.n1 + block_rows - 1) / block_rows;
-    }
-    SLAM_REQUIRE(out1 < (1ll << 31) && own2 < (1ll << 31), "%s: more than 2^31 rows over the pairs", who);
-    *out1_total = out1;
-    *own2_total = own2;
-    *blocks_total = blocks;
-    return SLAM_OK;
-}
-
 extern "C" int slam_tri_match_search(slam_ctx* ctx, const slam_bow_groups* g1, const slam_bow_groups* g2, const slam_tri_views* views1,
                                      const slam_tri_views* views2, const int32_t* h_pairs, int64_t P, const double* h_F,
                                      const double* h_epipole, const slam_tri_params* params, int scan_order, int32_t* d_matches12,
@@ -344,27 +286,29 @@ extern "C" int slam_tri_match_search(slam_ctx* ctx, const slam_bow_groups* g1, c
     std::vector<char> block(head + (size_t)P * sizeof(tm_pair));
     memcpy(block.data(), &prm, sizeof(prm));
     tm_pair* table = (tm_pair*)(block.data() + head);
-    int64_t out1, own2, blocks;
-    if (int rc = tm_fill_pairs(g1->h_offsets, g1->B, g2->h_offsets, g2->B, h_pairs, P, table, TM_SCAN_LANES, who, &out1, &own2, &blocks)) return rc;
+    mf_totals t{0, 0, 0};
     for (int64_t p = 0; p < P; p++) {
-        memcpy(table[(size_t)p].F, h_F + 9 * p, sizeof(table[0].F));
-        table[(size_t)p].ex = h_epipole[2 * p];
-        table[(size_t)p].ey = h_epipole[2 * p + 1];
+        tm_pair& e = table[(size_t)p];
+        if (int rc = mf_pair_next(e.m, g1->h_offsets, g1->B, h_pairs[2 * p], g2->h_offsets, g2->B, h_pairs[2 * p + 1], TM_SCAN_LANES, t, who, p))
+            return rc;
+        memcpy(e.F, h_F + 9 * p, sizeof(e.F));
+        e.ex = h_epipole[2 * p];
+        e.ey = h_epipole[2 * p + 1];
     }
+    const int64_t out1 = t.out1, own2 = t.own2, blocks = t.blocks;
     SLAM_REQUIRE(d_count && (out1 == 0 || d_matches12), "%s: null result pointer", who);
     std::lock_guard<std::mutex> lk(ctx->call_mu);       // the parameters, the pair table, the claim words and the tables nobody asked for
     SLAM_HIP(hipSetDevice(ctx->device));
-    const tm_plan pl = tm_layout(P, sizeof(tm_pair), out1, own2, d_idx == nullptr);
+    const mf_plan pl = mf_layout(sizeof(tp_params), P, sizeof(tm_pair), out1, own2, d_idx == nullptr);
     void* ws = nullptr;
     if (int rc = slam_workspace(ctx, pl.bytes, &ws)) return rc;
     char* w = (char*)ws;
+    if (int rc = mf_stage(ctx, pl, w, block.data(), own2)) return rc;
     const tm_pair* d_pairs = (const tm_pair*)(w + pl.o_pairs);
-    const tp_params* d_prm = (const tp_params*)(w + pl.o_prm);
+    const tp_params* d_prm = (const tp_params*)w;
     int2* idx = d_idx ? (int2*)d_idx : (int2*)(w + pl.o_idx);
     int2* dist = d_dist ? (int2*)d_dist : (int2*)(w + pl.o_dist);
     u32* owner = (u32*)(w + pl.o_owner);
-    SLAM_HIP(hipMemcpyAsync(w + pl.o_prm, block.data(), block.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (own2 > 0) SLAM_HIP(hipMemsetAsync(owner, 0xFF, (size_t)own2 * 4, ctx->stream));
     if (blocks > 0) {
         if (int rc = slam_prof_begin(ctx)) return rc;
         tm_scan_kernel<<<(unsigned)blocks, TM_SCAN_LANES, 0, ctx->stream>>>(s1, s2, d_pairs, (int)P, d_prm, scan_order, idx, dist, owner);
@@ -382,8 +326,8 @@ extern "C" int slam_tri_match_triangulate(slam_ctx* ctx, const int64_t* h_offset
                                           int32_t* d_status, int32_t* d_created) {
     const char* who = "slam_tri_match_triangulate";
     SLAM_REQUIRE(ctx, "%s: null ctx", who);
-    if (int rc = tm_check_offsets(h_offsets1, B1, who)) return rc;
-    if (int rc = tm_check_offsets(h_offsets2, B2, who)) return rc;
+    if (int rc = mf_check_offsets(h_offsets1, B1, who, "image")) return rc;
+    if (int rc = mf_check_offsets(h_offsets2, B2, who, "image")) return rc;
     SLAM_REQUIRE(views1 && views2, "%s: null views", who);
     SLAM_REQUIRE((h_offsets1[B1] == 0 || (views1->d_xy && views1->d_level)) && (h_offsets2[B2] == 0 || (views2->d_xy && views2->d_level)),
                  "%s: null pixels or levels", who);
@@ -397,29 +341,29 @@ extern "C" int slam_tri_match_triangulate(slam_ctx* ctx, const int64_t* h_offset
     std::vector<char> block(head + (size_t)P * sizeof(tt_pair));
     memcpy(block.data(), &prm, sizeof(prm));
     tt_pair* table = (tt_pair*)(block.data() + head);
-    int64_t out1, own2, blocks;
-    if (int rc = tm_fill_pairs(h_offsets1, B1, h_offsets2, B2, h_pairs, P, table, TM_TRI_ROWS, who, &out1, &own2, &blocks)) return rc;
+    mf_totals t{0, 0, 0};
     for (int64_t p = 0; p < P; p++) {
         tt_pair& e = table[(size_t)p];
+        if (int rc = mf_pair_next(e.m, h_offsets1, B1, h_pairs[2 * p], h_offsets2, B2, h_pairs[2 * p + 1], TM_TRI_ROWS, t, who, p)) return rc;
         memcpy(e.T1, h_T1 + 12 * p, sizeof(e.T1));
         memcpy(e.T2, h_T2 + 12 * p, sizeof(e.T2));
         memcpy(e.O1, h_O1 + 3 * p, sizeof(e.O1));
         memcpy(e.O2, h_O2 + 3 * p, sizeof(e.O2));
     }
-    SLAM_REQUIRE(d_created && (out1 == 0 || (d_matches12 && d_X && d_normal && d_range && d_status)), "%s: null device pointer", who);
+    SLAM_REQUIRE(d_created && (t.out1 == 0 || (d_matches12 && d_X && d_normal && d_range && d_status)), "%s: null device pointer", who);
     std::lock_guard<std::mutex> lk(ctx->call_mu);       // the parameters and the pair table travel through the workspace
     SLAM_HIP(hipSetDevice(ctx->device));
-    const tm_plan pl = tm_layout(P, sizeof(tt_pair), 0, 0, false);
+    const mf_plan pl = mf_layout(sizeof(tp_params), P, sizeof(tt_pair), 0, 0, false);     // (no tables, no claim words)
     void* ws = nullptr;
     if (int rc = slam_workspace(ctx, pl.bytes, &ws)) return rc;
     char* w = (char*)ws;
-    SLAM_HIP(hipMemcpyAsync(w + pl.o_prm, block.data(), block.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = mf_stage(ctx, pl, w, block.data(), 0)) return rc;
     SLAM_HIP(hipMemsetAsync(d_created, 0, (size_t)P * 4, ctx->stream));
-    if (blocks == 0) return SLAM_OK;
+    if (t.blocks == 0) return SLAM_OK;
     const tm_views v1{(const float2*)views1->d_xy, views1->d_level}, v2{(const float2*)views2->d_xy, views2->d_level};
     if (int rc = slam_prof_begin(ctx)) return rc;
-    tm_triangulate_kernel<<<(unsigned)blocks, TM_TRI_ROWS, 0, ctx->stream>>>(v1, v2, (const tt_pair*)(w + pl.o_pairs), (int)P,
-                                                                              (const tp_params*)(w + pl.o_prm), d_matches12, d_X, d_normal,
+    tm_triangulate_kernel<<<(unsigned)t.blocks, TM_TRI_ROWS, 0, ctx->stream>>>(v1, v2, (const tt_pair*)(w + pl.o_pairs), (int)P,
+                                                                              (const tp_params*)w, d_matches12, d_X, d_normal,
                                                                               d_range, d_status, d_created);
     if (int rc = slam_prof_end(ctx)) return rc;
     return slam_launch_check("tri match triangulate");

@@ -15,10 +15,10 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._args import _Buffers, _device_rows, _offsets, _rows_arg
 from ._lib import check, load
 from .device import Context, DeviceBuffer, default_context
 from .matching import as_descriptors
-from .two_view import _Buffers
 
 K_MAX, DEPTH_MAX, IMAGE_MAX, RESULTS_MAX = 32, 10, 8192, 64
 WORDS_MAX = 1 << 24
@@ -32,16 +32,6 @@ def limits() -> dict:
     check(load().slam_bow_limits(lim))
     assert (lim[0], lim[1], lim[2], lim[3]) == (K_MAX, DEPTH_MAX, IMAGE_MAX, RESULTS_MAX), "the library's limits are not this module's"
     return {"query_pass_entries": lim[4], "staged_nodes": lim[5], "lanes16_up_to": lim[6]}
-
-
-def _offsets(offsets, n: int, name: str = "offsets") -> np.ndarray:
-    off = np.asarray(offsets)
-    if off.dtype.kind not in "iu" or off.ndim != 1 or len(off) < 1:
-        raise ValueError(f"{name} must be integers of shape [B + 1]")
-    off = np.ascontiguousarray(off, np.int64)
-    if off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
-        raise ValueError(f"{name} must ascend from 0 to {n}")
-    return off
 
 
 # ----------------------------------------------------------------------------------------------------------------- vocabulary
@@ -232,26 +222,6 @@ def write_dbow2_text(vocab: Vocabulary, path) -> None:
 
 
 # ------------------------------------------------------------------------------------------------------------------ transform
-
-def _rows_arg(descriptors):
-    """(rows, n) of a descriptor argument, checked: host rows u8 [n,32], or a ``(DeviceBuffer, n)`` pair as it is."""
-    if isinstance(descriptors, tuple) and len(descriptors) == 2 and isinstance(descriptors[0], DeviceBuffer):
-        buf, n = descriptors[0], int(descriptors[1])
-        if n < 0 or n * 32 > buf.nbytes:
-            raise ValueError(f"{n} rows do not fit a device buffer of {buf.nbytes} bytes")
-        return buf, n
-    d = as_descriptors(descriptors)
-    return d, len(d)
-
-
-def _device_rows(ctx: Context, m: _Buffers, rows) -> DeviceBuffer:
-    """The rows of ``_rows_arg`` on the device of ``ctx``: host rows are uploaded."""
-    if isinstance(rows, DeviceBuffer):
-        if rows.ctx is not ctx:
-            raise ValueError("the device rows belong to another context")
-        return rows
-    return m.up(rows)
-
 
 def _transform_device(dv: DeviceVocabulary, m: _Buffers, rows: DeviceBuffer, n: int, levels_up: int, lanes: int = 0):
     ctx, v = dv.ctx, dv.vocab

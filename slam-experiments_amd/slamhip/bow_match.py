@@ -14,12 +14,13 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+from ._args import N_BINS, PAIRS_MAX, _Buffers, _bins_arg, _device_rows, _down_split, _offsets, _pairs_arg, _rows_arg
 from ._lib import BowGroups, addr, check, load
-from .bow import _Buffers, _device_rows, _levels_up, _offsets, _rows_arg, _transform_device
+from .bow import _levels_up, _transform_device
 from .device import Context, DeviceBuffer, default_context
 from .matching import as_descriptors
 
-ROWS_MAX, PAIRS_MAX, N_BINS, NO_SECOND = 8192, 4096, 32, 256
+ROWS_MAX, NO_SECOND = 8192, 256
 TH_LOW, RATIO = 50, 0.75           # ORBmatcher::TH_LOW and the nnratio of the loop-closing and relocalisation calls
 LEVELS_UP = 4
 
@@ -56,22 +57,6 @@ def _image_offsets(offsets, n: int) -> np.ndarray:
     if len(off) > 1 and np.diff(off).max() > ROWS_MAX:
         raise ValueError(f"at most {ROWS_MAX} rows per image")
     return off
-
-
-def _bins_arg(bins, n: int, name: str) -> Optional[np.ndarray]:
-    """Orientation bins of a whole set in row order as uint8 [n]: one array, or a list of one array per image."""
-    if bins is None:
-        return None
-    if isinstance(bins, (list, tuple)) and len(bins) and not np.isscalar(bins[0]):
-        bins = np.concatenate([np.asarray(b).reshape(-1) for b in bins])
-    a = np.asarray(bins)
-    if a.size == 0:
-        a = np.zeros(0, np.int64)
-    if a.dtype.kind not in "iu" or a.shape != (n,):
-        raise ValueError(f"{name} must be integers of shape [{n}], got {a.dtype} {a.shape}")
-    if n and (a.min() < 0 or a.max() >= N_BINS):
-        raise ValueError(f"{name} must lie in [0, {N_BINS})")
-    return np.ascontiguousarray(a, np.uint8)
 
 
 class FeatureVectors:
@@ -192,19 +177,6 @@ def bow_feature_vectors(vocab, descriptors, offsets, levels_up: int = LEVELS_UP,
         m.free()
 
 
-def _pairs_arg(pairs, B1: int, B2: int) -> np.ndarray:
-    p = np.asarray(pairs)
-    if p.size == 0:
-        return np.zeros((0, 2), np.int32)
-    if p.dtype.kind not in "iu" or p.ndim != 2 or p.shape[1] != 2:
-        raise ValueError(f"pairs must be integers of shape [P, 2], got {p.dtype} {p.shape}")
-    if len(p) > PAIRS_MAX:
-        raise ValueError(f"at most {PAIRS_MAX} pairs per call")
-    if p.min() < 0 or p[:, 0].max() >= B1 or p[:, 1].max() >= B2:
-        raise ValueError(f"pairs name images outside the two sets ({B1} and {B2} images)")
-    return np.ascontiguousarray(p, np.int32)
-
-
 def _scan_order(scan_order) -> int:
     if scan_order not in (0, 1):
         raise ValueError("scan_order must be 0 (a lane per grouped position) or 1 (a lane per row)")
@@ -213,11 +185,6 @@ def _scan_order(scan_order) -> int:
 
 def _groups(fv: FeatureVectors, dev, d_bins) -> BowGroups:
     return BowGroups(dev[0].ptr, dev[1].ptr, dev[2].ptr, dev[3].ptr, d_bins.ptr if d_bins is not None else None, addr(fv.offsets), len(fv))
-
-
-def _split(flat: np.ndarray, sizes: np.ndarray) -> List[np.ndarray]:
-    ends = np.cumsum(sizes)
-    return [flat[e - s:e].copy() for s, e in zip(sizes, ends)]
 
 
 def search_by_bow(fv1: FeatureVectors, fv2: FeatureVectors, pairs, bins1=None, bins2=None, th_low: int = TH_LOW, ratio: float = RATIO,
@@ -258,12 +225,10 @@ def search_by_bow(fv1: FeatureVectors, fv2: FeatureVectors, pairs, bins1=None, b
         check(ctx.lib.slam_bow_match_search(ctx.handle, ctypes.byref(g1), ctypes.byref(g2), addr(p), P, int(th_low), ratio, scan_order,
                                             d_m.ptr, d_c.ptr, d_i.ptr if d_i else None, d_d.ptr if d_d else None))
         counts = d_c.download(np.int32, (P,))
-        matches = _split(d_m.download(np.int32, (total,)) if total else np.zeros(0, np.int32), sizes)
+        matches = _down_split(d_m, np.int32, (), total, sizes)
         if not return_tables:
             return matches, counts
-        idx = d_i.download(np.int32, (total, 2)) if total else np.zeros((0, 2), np.int32)
-        dist = d_d.download(np.int32, (total, 2)) if total else np.zeros((0, 2), np.int32)
-        return matches, counts, list(zip(_split(idx, sizes), _split(dist, sizes)))
+        return matches, counts, list(zip(_down_split(d_i, np.int32, (2,), total, sizes), _down_split(d_d, np.int32, (2,), total, sizes)))
     finally:
         m.free()
 
@@ -283,9 +248,7 @@ def node_top2(fv1: FeatureVectors, fv2: FeatureVectors, pairs, ctx: Optional[Con
         g1, g2 = _groups(fv1, fv1._resident(ctx, m), None), _groups(fv2, fv2._resident(ctx, m), None)
         d_i, d_d = m.new(8 * total), m.new(8 * total)
         check(ctx.lib.slam_bow_match_top2(ctx.handle, ctypes.byref(g1), ctypes.byref(g2), addr(p), P, scan_order, d_i.ptr, d_d.ptr))
-        idx = d_i.download(np.int32, (total, 2)) if total else np.zeros((0, 2), np.int32)
-        dist = d_d.download(np.int32, (total, 2)) if total else np.zeros((0, 2), np.int32)
-        return list(zip(_split(idx, sizes), _split(dist, sizes)))
+        return list(zip(_down_split(d_i, np.int32, (2,), total, sizes), _down_split(d_d, np.int32, (2,), total, sizes)))
     finally:
         m.free()
 

@@ -14,12 +14,11 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._args import _Buffers, _down_split, _f64_rows, _int_rows, _pairs_arg
 from ._lib import FuseParams, addr, check, load
-from .bow import _Buffers
-from .bow_match import _pairs_arg, _split
 from .device import Context, default_context
 from .matching import as_descriptors
-from .proj_match import (CELL, COS2_LIMIT, LEVELS_MAX, PAIRS_MAX, ROWS_MAX, FrameGrids, PointSets, _default_bounds, _f64_rows, _pair_args,  # noqa: F401
+from .proj_match import (CELL, COS2_LIMIT, LEVELS_MAX, PAIRS_MAX, ROWS_MAX, FrameGrids, PointSets, _default_bounds, _pair_args,  # noqa: F401
                          _params, scale_tables)
 
 OBS_MAX = 256                                   # SLAM_FUSE_OBS_MAX
@@ -126,16 +125,7 @@ class MapObservations:
 
 
 def _ids_arg(a, n: int, name: str, M: int) -> np.ndarray:
-    if isinstance(a, (list, tuple)) and len(a) and not np.isscalar(a[0]):
-        a = np.concatenate([np.asarray(x).reshape(-1) for x in a])
-    a = np.asarray(a)
-    if a.size == 0:
-        a = np.zeros(0, np.int64)
-    if a.dtype.kind not in "iu" or a.shape != (n,):
-        raise ValueError(f"{name} must be integers of shape [{n}], got {a.dtype} {a.shape}")
-    if n and (a.min() < -1 or a.max() >= M):
-        raise ValueError(f"{name} must be -1 or a map point in [0, {M})")
-    return np.ascontiguousarray(a, np.int32)
+    return np.ascontiguousarray(_int_rows(a, n, name, -1, M, "iu", f"be -1 or a map point in [0, {M})"), np.int32)
 
 
 def _fuse_params(th_low, margins, chi2) -> FuseParams:
@@ -193,7 +183,7 @@ def fuse_points(points: PointSets, ids, frames: FrameGrids, frame_points, obs: M
                                        ob["obs"].ptr, len(obs), addr(p), addr(A), addr(Ow), addr(t), P, ctypes.byref(prm), ctypes.byref(fp),
                                        *(b.ptr for b in out), d_c.ptr, *(b.ptr if b else None for b in tabs)))
         counts = d_c.download(np.int32, (P, 3))
-        down = lambda b, dt: _split(b.download(dt, (total,)) if total else np.zeros(0, dt), sizes)  # noqa: E731
+        down = lambda b, dt: _down_split(b, dt, (), total, sizes)  # noqa: E731
         cols = dict(zip(("row", "dist", "status", "other"), (down(b, np.int32) for b in out)))
         if return_tables:
             cols.update(u=down(tabs[0], np.float64), v=down(tabs[1], np.float64), lp=down(tabs[2], np.int32))

@@ -18,10 +18,10 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from ._args import _Buffers
 from ._lib import check
 from .device import Context, default_context
-from .two_view import (DEFAULT_DISTANCE, DEFAULT_HYPOTHESES, MAX_PAIRS, _Buffers, _check_ransac_args, _intrinsics, _pair_arrays,
-                       _points)
+from .two_view import DEFAULT_DISTANCE, DEFAULT_HYPOTHESES, MAX_PAIRS, _check_ransac_args, _intrinsics, _pair_arrays, _points
 from .two_view import DEFAULT_THRESHOLD as DEFAULT_THRESHOLD_E
 
 DEFAULT_THRESHOLD_H = 3.0       # pixels: cv2.findHomography's default, and the value in the reference's comment

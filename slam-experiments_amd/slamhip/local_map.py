@@ -14,12 +14,12 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._args import _Buffers
 from ._lib import addr, check, load
 from .covis import CovisibilityGraph
 from .device import Context, default_context
 from .fuse import OBS_MAX, POINTS_MAX, MapObservations
 from .proj_match import FrameGrids
-from .two_view import _Buffers
 
 LIMIT_NAMES = ("threads", "vote_lds_small", "vote_lds_frames", "group16", "group64", "group256", "scan_tile_words", "scalar_bytes")
 WORKSPACE_NAMES = ("frame_points", "vote", "points", "cull")

@@ -17,10 +17,11 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from ._args import _Buffers
 from ._lib import check
 from .device import Context, default_context
 from .pose_opt import CHI2_THRESHOLD, HUBER_DELTA
-from .two_view import MAX_PAIRS, _Buffers, _check_ransac_args, _intrinsics, _points
+from .two_view import MAX_PAIRS, _check_ransac_args, _intrinsics, _points
 
 DEFAULT_HYPOTHESES = 256        # as the essential-matrix RANSAC; ln(0.001) / ln(1 - 0.5**3) = 52 would do at 50 % inliers
 DEFAULT_THRESHOLD = 8.0         # pixels, cv2.solvePnPRansac's reprojectionError default

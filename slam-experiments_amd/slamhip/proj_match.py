@@ -15,13 +15,14 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._args import (N_BINS, PAIRS_MAX, _Buffers, _bins_arg, _device_rows, _down_split, _f64_rows, _int_rows, _offsets, _pairs_arg, _poses_arg,
+                    _rows_arg)
 from ._lib import ProjFrames, ProjParams, ProjPoints, addr, check, load
-from .bow import _Buffers, _device_rows, _offsets, _rows_arg
-from .bow_match import _bins_arg, _split, match_index_pairs  # noqa: F401  (match_index_pairs: part of this module's interface)
+from .bow_match import match_index_pairs  # noqa: F401  (part of this module's interface)
 from .device import Context, DeviceBuffer, default_context
 from .matching import as_descriptors
 
-ROWS_MAX, PAIRS_MAX, LEVELS_MAX, N_BINS = 8192, 4096, 16, 32
+ROWS_MAX, LEVELS_MAX = 8192, 16
 TH_HIGH, RATIO, COS2_LIMIT, CELL = 100, 0.9, 0.25, 16     # ORBmatcher::TH_HIGH, mfNNratio of the tracking calls, cos^2 60 deg
 
 
@@ -58,28 +59,6 @@ def _set_offsets(offsets, n: int, what: str) -> np.ndarray:
     if len(off) > 1 and np.diff(off).max() > ROWS_MAX:
         raise ValueError(f"at most {ROWS_MAX} {what}")
     return off
-
-
-def _int_rows(a, n: int, name: str, lo: int, hi: int) -> np.ndarray:
-    if isinstance(a, (list, tuple)) and len(a) and not np.isscalar(a[0]):
-        a = np.concatenate([np.asarray(x).reshape(-1) for x in a])
-    a = np.asarray(a)
-    if a.size == 0:
-        a = np.zeros(0, np.int64)
-    if a.dtype.kind not in "iub" or a.shape != (n,):
-        raise ValueError(f"{name} must be integers of shape [{n}], got {a.dtype} {a.shape}")
-    if n and (a.min() < lo or a.max() >= hi):
-        raise ValueError(f"{name} must lie in [{lo}, {hi})")
-    return a
-
-
-def _f64_rows(a, n: int, k: int, name: str) -> np.ndarray:
-    a = np.asarray(a, np.float64)
-    if a.size == 0 and n == 0:
-        return np.zeros((0, k))
-    if a.shape != (n, k) and not (k == 1 and a.shape == (n,)):
-        raise ValueError(f"{name} must have shape [{n}, {k}], got {a.shape}")
-    return np.ascontiguousarray(a.reshape(n, k))
 
 
 class FrameGrids:
@@ -266,17 +245,6 @@ class PointSets:
         return ProjPoints(p("xyz"), p("desc"), p("range"), p("normal"), p("level"), p("bins"), addr(self.offsets), len(self))
 
 
-def _poses_arg(poses, P: int) -> np.ndarray:
-    a = np.asarray(poses, np.float64)
-    if P == 0:
-        return np.zeros((0, 3, 4))
-    if a.ndim == 2:
-        a = a[None]
-    if a.ndim != 3 or a.shape[0] != P or a.shape[1:] not in ((3, 4), (4, 4)):
-        raise ValueError(f"poses must have shape [{P},3,4] or [{P},4,4], got {a.shape}")
-    return np.ascontiguousarray(a[:, :3, :])
-
-
 def camera_centres(poses) -> np.ndarray:
     """The camera centres ``-M^-1 t`` of poses ``[M | t]`` f64 [P,3,4] (M = R, or sR for a Sim(3))."""
     A = np.asarray(poses, np.float64).reshape(-1, 3, 4)
@@ -346,7 +314,6 @@ def search_by_projection(points: PointSets, frames: FrameGrids, pairs, poses, ce
     of dicts ``status, u, v, lp, idx, dist`` per pair."""
     if not isinstance(points, PointSets) or not isinstance(frames, FrameGrids):
         raise ValueError("search_by_projection takes PointSets and FrameGrids")
-    from .bow_match import _pairs_arg
     p = _pairs_arg(pairs, len(points), len(frames))
     P = len(p)
     A, Ow, t = _pair_args(P, poses, centres, th)
@@ -366,7 +333,7 @@ def search_by_projection(points: PointSets, frames: FrameGrids, pairs, poses, ce
         check(ctx.lib.slam_proj_match_search(ctx.handle, ctypes.byref(sp), ctypes.byref(sf), addr(p), addr(A), addr(Ow), addr(t), P,
                                              ctypes.byref(prm), d_m.ptr, d_c.ptr, *(b.ptr if b else None for b in tabs)))
         counts = d_c.download(np.int32, (P,))
-        matches = _split(d_m.download(np.int32, (total,)) if total else np.zeros(0, np.int32), sizes)
+        matches = _down_split(d_m, np.int32, (), total, sizes)
         if not return_tables:
             return matches, counts
         return matches, counts, _tables(tabs, total, sizes, True)
@@ -378,7 +345,7 @@ def search_by_projection(points: PointSets, frames: FrameGrids, pairs, poses, ce
 def _tables(tabs, total: int, sizes, search: bool) -> List[dict]:
     spec = (("status", np.int32, ()), ("u", np.float64, ()), ("v", np.float64, ()), ("lp", np.int32, ()), ("idx", np.int32, (2,)),
             ("dist", np.int32, (2,)))[:6 if search else 4]
-    cols = {name: _split(b.download(dt, (total,) + sh) if total else np.zeros((0,) + sh, dt), sizes) for (name, dt, sh), b in zip(spec, tabs)}
+    cols = {name: _down_split(b, dt, sh, total, sizes) for (name, dt, sh), b in zip(spec, tabs)}
     return [{name: cols[name][i] for name in cols} for i in range(len(sizes))]
 
 
@@ -462,7 +429,6 @@ def search_by_sim3(points1: PointSets, frames1: FrameGrids, rows1: Sequence, poi
     ``S12^-1 poses1`` and the points of b in frame a under ``S12 poses2`` (two calls of ``search_by_projection``; no ratio
     test by default, as in ORB-SLAM); on the host the matches both directions agree on are kept.  Returns per pair
     ``(i1, i2)``: int32 indices into the two point sets, i1 ascending - one pair of ``estimate_sim3_batch``."""
-    from .bow_match import _pairs_arg
     p = _pairs_arg(pairs, len(points1), len(points2))
     P = len(p)
     if len(frames1) != len(points1) or len(frames2) != len(points2) or len(rows1) != len(points1) or len(rows2) != len(points2):

@@ -17,10 +17,11 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from ._args import _Buffers
 from ._lib import check
 from .device import Context, default_context
 from .pnp import _points3
-from .two_view import MAX_PAIRS, _Buffers, _check_ransac_args, _intrinsics
+from .two_view import MAX_PAIRS, _check_ransac_args, _intrinsics
 
 DEFAULT_HYPOTHESES = 256        # as the other RANSAC calls; ORB-SLAM's Sim3Solver: at most 300 iterations
 DEFAULT_CHI2_GATE = 9.210       # chi-square of 2 degrees of freedom at 99 %, ORB-SLAM's Sim3Solver

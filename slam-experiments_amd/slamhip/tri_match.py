@@ -16,14 +16,14 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+from ._args import N_BINS, PAIRS_MAX, _Buffers, _bins_arg, _down, _down_split, _int_rows, _pairs_arg, _poses_arg, _split
 from ._lib import TriParams, TriViews, addr, check, load
-from .bow import _Buffers
-from .bow_match import FeatureVectors, _bins_arg, _groups, _pairs_arg, _scan_order, _split
+from .bow_match import FeatureVectors, _groups, _scan_order
 from .device import Context, default_context
 from .matching import as_descriptors
-from .proj_match import _int_rows, _poses_arg, camera_centres, scale_tables
+from .proj_match import camera_centres, scale_tables
 
-ROWS_MAX, PAIRS_MAX, LEVELS_MAX, N_BINS = 8192, 4096, 16, 32
+ROWS_MAX, LEVELS_MAX = 8192, 16
 TH_LOW, CHI2, EPIPOLE_R2 = 50, 3.84, 100.0          # ORBmatcher::TH_LOW, CheckDistEpipolarLine's 3.84, the 100 of 100 * scaleFactor
 COS_MAX, CHI2_PX, RATIO = 0.9998, 5.991, 1.5        # CreateNewMapPoints: cosParallaxRays, the reprojection chi2, ratioFactor's 1.5
 
@@ -195,10 +195,6 @@ def _triangulate(ctx, m, fv1, fv2, v1, v2, p, d_m, T1, T2, prm, total):
     return out
 
 
-def _down(buf, dtype, shape, total: int) -> np.ndarray:
-    return buf.download(dtype, (total,) + shape) if total else np.zeros((0,) + shape, dtype)
-
-
 def _sizes(fv1, p):
     sizes = np.diff(fv1.offsets)[p[:, 0]]
     return sizes, int(sizes.sum())
@@ -242,10 +238,10 @@ def search_for_triangulation(fv1: FeatureVectors, fv2: FeatureVectors, pairs, vi
     try:
         d_m, d_c, d_i, d_d, _ = _search(ctx, m, fv1, fv2, views1, views2, p, Fm, epi, prm, b1, b2, scan_order, total, return_tables)
         counts = d_c.download(np.int32, (P,))
-        matches = _split(_down(d_m, np.int32, (), total), sizes)
+        matches = _down_split(d_m, np.int32, (), total, sizes)
         if not return_tables:
             return matches, counts
-        return matches, counts, list(zip(_split(_down(d_i, np.int32, (2,), total), sizes), _split(_down(d_d, np.int32, (2,), total), sizes)))
+        return matches, counts, list(zip(_down_split(d_i, np.int32, (2,), total, sizes), _down_split(d_d, np.int32, (2,), total, sizes)))
     finally:
         m.free()
         del keep
@@ -315,7 +311,7 @@ def create_new_map_points(fv1: FeatureVectors, fv2: FeatureVectors, pairs, views
         d_m, d_c, _, _, (v1, v2) = _search(ctx, m, fv1, fv2, views1, views2, p, F, epi, prm, b1, b2, 0, total, False)
         out = _triangulate(ctx, m, fv1, fv2, v1, v2, p, d_m, T1, T2, prm, total)
         pts = _points(out, P, total, sizes)
-        for d, m12 in zip(pts, _split(_down(d_m, np.int32, (), total), sizes)):
+        for d, m12 in zip(pts, _down_split(d_m, np.int32, (), total, sizes)):
             d["matches12"] = m12
         return pts, d_c.download(np.int32, (P,)), out[4].download(np.int32, (P,))
     finally:

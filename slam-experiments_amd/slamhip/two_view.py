@@ -17,6 +17,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._args import _Buffers
 from ._lib import check
 from .device import Context, default_context
 
@@ -81,25 +82,6 @@ def _check_ransac_args(hypotheses, threshold, seed):
     if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool):
         raise TypeError("seed must be an integer")
     return int(hypotheses), float(threshold), int(seed) & ((1 << 64) - 1)
-
-
-class _Buffers:
-    def __init__(self, ctx):
-        self.ctx, self.bufs = ctx, []
-
-    def up(self, a):
-        b = self.ctx.upload(a if a.size else np.zeros(2, a.dtype))
-        self.bufs.append(b)
-        return b
-
-    def new(self, nbytes):
-        b = self.ctx.malloc(max(int(nbytes), 16))
-        self.bufs.append(b)
-        return b
-
-    def free(self):
-        for b in self.bufs:
-            b.free()
 
 
 def fivepoint_arrays(x1, x2, ctx: Optional[Context] = None):
