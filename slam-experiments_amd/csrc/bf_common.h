@@ -108,6 +108,18 @@ __device__ __forceinline__ void bf_load_query(const uint4* q, int qi, u32 (&qr)[
     qr[4] = y.x; qr[5] = y.y; qr[6] = y.z; qr[7] = y.w;
 }
 
+// the Hamming distance of the eight words q to the row (a, b): one accumulating v_bcnt per word
+__device__ __forceinline__ u32 bf_hamming256(const u32 (&q)[8], uint4 a, uint4 b) {
+    u32 d = bcnt_acc(q[0] ^ a.x, 0);
+    d = bcnt_acc(q[1] ^ a.y, d);
+    d = bcnt_acc(q[2] ^ a.z, d);
+    d = bcnt_acc(q[3] ^ a.w, d);
+    d = bcnt_acc(q[4] ^ b.x, d);
+    d = bcnt_acc(q[5] ^ b.y, d);
+    d = bcnt_acc(q[6] ^ b.z, d);
+    return bcnt_acc(q[7] ^ b.w, d);
+}
+
 // One group of U rows of the LDS tile tp from row j, read rolling one row ahead through one LDS address + immediate
 // offsets (bf_top2_block): a0 / c0 hold row j on entry and row j + U on return.
 template <int U>

@@ -43,14 +43,7 @@ __device__ __forceinline__ int bow_nearest(const u32 (&q)[8], const uint4* rows,
         }
 #pragma unroll
         for (int u = 0; u < 8; u++) {
-            u32 d = bcnt_acc(q[0] ^ a[u].x, 0);
-            d = bcnt_acc(q[1] ^ a[u].y, d);
-            d = bcnt_acc(q[2] ^ a[u].z, d);
-            d = bcnt_acc(q[3] ^ a[u].w, d);
-            d = bcnt_acc(q[4] ^ b[u].x, d);
-            d = bcnt_acc(q[5] ^ b[u].y, d);
-            d = bcnt_acc(q[6] ^ b[u].z, d);
-            d = bcnt_acc(q[7] ^ b[u].w, d);
+            const u32 d = bf_hamming256(q, a[u], b[u]);
             if (c0 + u < count && d < best) {
                 best = d;
                 arg = c0 + u;
@@ -62,14 +55,7 @@ __device__ __forceinline__ int bow_nearest(const u32 (&q)[8], const uint4* rows,
 
 __device__ __forceinline__ u32 bow_distance(const u32 (&q)[8], const uint4* rows, size_t r) {
     const uint4 a = rows[2 * r], b = rows[2 * r + 1];
-    u32 d = bcnt_acc(q[0] ^ a.x, 0);
-    d = bcnt_acc(q[1] ^ a.y, d);
-    d = bcnt_acc(q[2] ^ a.z, d);
-    d = bcnt_acc(q[3] ^ a.w, d);
-    d = bcnt_acc(q[4] ^ b.x, d);
-    d = bcnt_acc(q[5] ^ b.y, d);
-    d = bcnt_acc(q[6] ^ b.z, d);
-    return bcnt_acc(q[7] ^ b.w, d);
+    return bf_hamming256(q, a, b);
 }
 
 // ------------------------------------------------------------------------------------------------------------ transform

@@ -9,7 +9,7 @@
 //           matches12 and the count.
 // Every comparison is between integers (or doubles that hold integers <= 256), the atomics are integer minima and LDS integer
 // adds, so the result is the same bits on every run and for every launch geometry.
-#include "match_finish.h"
+#include "node_walk.h"
 
 #define BM_ROWS_MAX MF_ROWS_MAX     // rows of one image: the row fits the 13-bit field of the claim key and the LDS sort
 #define BM_PAIRS_MAX MF_PAIRS_MAX   // pairs of one call (the pair table: 48 bytes each in the context's workspace)
@@ -85,55 +85,24 @@ __global__ __launch_bounds__(BM_SCAN_LANES) void bm_scan_kernel(const bm_set s1,
                                                                int scan_order, int th_low, double ratio, int2* __restrict__ idx,
                                                                int2* __restrict__ dist, u32* __restrict__ owner) {
     const int bx = (int)blockIdx.x;
-    int lo = 0, hi = P - 1;
-    while (lo < hi) {                                   // the last pair whose first workgroup is not behind this one
-        const int mid = (lo + hi + 1) >> 1;
-        if (pairs[mid].blk0 <= bx) lo = mid;
-        else hi = mid - 1;
-    }
-    const bm_pair pr = pairs[lo];
+    const bm_pair pr = pairs[mf_pair_of(pairs, P, bx)];
     const int t = (bx - pr.blk0) * BM_SCAN_LANES + (int)threadIdx.x;
     if (t >= pr.n1) return;
     const int pos = scan_order == 0 ? t : s1.inverse[pr.base1 + t];
     const int node = s1.nodes[pr.base1 + pos], row = scan_order == 0 ? s1.order[pr.base1 + pos] : t;
-    u32 b1 = SLAM_KEY_NONE, b2 = SLAM_KEY_NONE;
+    mf_top2 top;
     if (node >= 0 && pr.n2 > 0) {
         const int* nodes2 = s2.nodes + pr.base2;
-        const int* order2 = s2.order + pr.base2;
-        const uint4* rows2 = s2.desc + 2 * pr.base2;
-        const int j0 = mf_bound<false>(nodes2, pr.n2, (u32)node), j1 = mf_bound<true>(nodes2, pr.n2, (u32)node);
+        const int2 seg = make_int2(mf_bound<false>(nodes2, pr.n2, (u32)node), mf_bound<true>(nodes2, pr.n2, (u32)node));
         u32 q[8];
         bf_load_query(s1.desc + 2 * pr.base1, pos, q);
-        for (int j = j0; j < j1; j += 4) {              // four rows requested before the first distance is formed
-            uint4 a[4], b[4];
-            int r[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int jj = min(j + u, j1 - 1);
-                a[u] = rows2[2 * (size_t)jj];
-                b[u] = rows2[2 * (size_t)jj + 1];
-                r[u] = order2[jj];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                u32 d = bcnt_acc(q[0] ^ a[u].x, 0);
-                d = bcnt_acc(q[1] ^ a[u].y, d);
-                d = bcnt_acc(q[2] ^ a[u].z, d);
-                d = bcnt_acc(q[3] ^ a[u].w, d);
-                d = bcnt_acc(q[4] ^ b[u].x, d);
-                d = bcnt_acc(q[5] ^ b[u].y, d);
-                d = bcnt_acc(q[6] ^ b[u].z, d);
-                d = bcnt_acc(q[7] ^ b[u].w, d);
-                const u32 key = j + u < j1 ? (d << SLAM_KEY_IDX_BITS) | (u32)r[u] : SLAM_KEY_NONE;
-                b2 = min(b2, max(b1, key));
-                b1 = min(b1, key);
-            }
-        }
+        nw_walk(s2.order + pr.base2, s2.desc + 2 * pr.base2, seg, q,
+                [&](u32 d, int r, bool inside) { top.take(inside ? (d << SLAM_KEY_IDX_BITS) | (u32)r : SLAM_KEY_NONE); });
     }
-    const int i0 = bf_key_idx(b1, 0), d0 = bf_key_dist(b1), i1 = bf_key_idx(b2, 0), d1 = bf_key_dist(b2);
-    idx[pr.out1 + row] = make_int2(i0, i1);
-    dist[pr.out1 + row] = make_int2(d0, d1);
-    if (SELECT && bm_proposed(i0, d0, i1, d1, th_low, ratio)) atomicMin(&owner[pr.own2 + i0], mf_claim_key(d0, row));
+    const int2 ix = top.idx(), ds = top.dist();
+    idx[pr.out1 + row] = ix;
+    dist[pr.out1 + row] = ds;
+    if (SELECT && bm_proposed(ix.x, ds.x, ix.y, ds.y, th_low, ratio)) atomicMin(&owner[pr.own2 + ix.x], mf_claim_key(ds.x, row));
 }
 
 // --------------------------------------------------------------------------------------------------------------- finish

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(PM_SCAN_LANES) void fz_scan_kernel(const pm_points 
                                                                u32* __restrict__ owner, double* __restrict__ tu, double* __restrict__ tv,
                                                                int* __restrict__ tlp) {
     const int bx = (int)blockIdx.x;
-    const fz_pair* pp = pm_pair_of(pairs, P, bx);
+    const fz_pair* pp = pairs + mf_pair_of(pairs, P, bx);
     const mf_pair pr = pp->m;
     const int i = (bx - pr.blk0) * PM_SCAN_LANES + (int)threadIdx.x;
     if (i >= pr.n1) return;

@@ -1,13 +1,16 @@
-// grid_walk.h - the scan of a search by projection in shareable form: the pair of a scan workgroup and the
-// walk over the grid rows a point's window touches, as a template over the test a row inside the window still has to pass and
-// over what is kept of the keys dist << 23 | row.  fuse.hip (Fuse) is built on it.  pm_scan_kernel of proj_match.hip
-// (SearchByProjection) still carries the text the walk was lifted from: built on this template it computes the same but comes
-// out with another register allocation and scalar schedule, and the times of 4l were measured on the code object it has
-// (DESIGN.md 4n and 7 say what moving it over takes).  Everything else the two files share is in proj_search.h.
+// grid_walk.h - the scan of a search by projection in shareable form: the walk over the grid rows a point's
+// window touches, as a template over the test a row inside the window still has to pass and over what is kept of the keys
+// dist << 23 | row.  fuse.hip (Fuse) is built on it.  The walk's text exists twice: pm_scan_kernel of proj_match.hip
+// (SearchByProjection) carries the text it was lifted from.  Built on this template, with either form of the Hamming distance,
+// pm_scan_kernel was timed against itself and missed one line of the rule it was held to (has the figures;
+// profiles/pair_scan_time_ab.log all of them).  Everything else the two files share is in proj_search.h, the pair of a scan
+// workgroup in match_finish.h.
 #pragma once
 #include "proj_search.h"
 
-// the Hamming distance of the eight words q and the row (a, b), in plain C++
+// The Hamming distance of the eight words q and the row (a, b), in plain C++.  It stays beside bf_hamming256 (bf_common.h): on
+// the v_bcnt chain fz_refresh_kernel took 372.8 us against 336.3 for 1000 points of 256 observations, and fz_scan_kernel 19.0
+// against 18.8 for one pair of 2000 points (profiles/pair_scan_time_ab.log, session 1).
 __device__ __forceinline__ u32 gw_hamming(const u32* q, const uint4& a, const uint4& b) {
     return (u32)(((__popc(q[0] ^ a.x) + __popc(q[1] ^ a.y)) + (__popc(q[2] ^ a.z) + __popc(q[3] ^ a.w))) +
                  ((__popc(q[4] ^ b.x) + __popc(q[5] ^ b.y)) + (__popc(q[6] ^ b.z) + __popc(q[7] ^ b.w))));
@@ -66,16 +69,4 @@ __device__ __forceinline__ void pm_walk(const pm_frames& s2, const mf_pair& pr, 
             }
         }
     }
-}
-
-// the pair of a scan workgroup: the last pair whose first workgroup is not behind it (REC: a record that starts with an mf_pair m)
-template <class REC>
-__device__ __forceinline__ const REC* pm_pair_of(const REC* __restrict__ pairs, int P, int bx) {
-    int lo = 0, hi = P - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pairs[mid].m.blk0 <= bx) lo = mid;
-        else hi = mid - 1;
-    }
-    return pairs + lo;
 }

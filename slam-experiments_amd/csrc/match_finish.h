@@ -1,6 +1,6 @@
 // match_finish.h - what the four pair-table searches share around their scans (bow_match.hip: SearchByBoW, proj_match.hip:
-// SearchByProjection, tri_match.hip: SearchForTriangulation, fuse.hip: Fuse).  Device: the pair record, the claim key of the
-// one-to-one step, and the finish step - the winners of the claims, the 32-bin rotation histogram with its three maxima,
+// SearchByProjection, tri_match.hip: SearchForTriangulation, fuse.hip: Fuse).  Device: the pair record, the pair of a workgroup,
+// the register top-2 of a lane, the claim key of the one-to-one step, and the finish step - the winners of the claims, the 32-bin rotation histogram with its three maxima,
 // matches12 and the count; the searches differ in which rows their selection proposes:
 // SEL::proposed(pr, top-2 rows, top-2 distances).  Host (at the end): the offsets and group-set checks, the head of a pair
 // record, the workspace layout and the staging of the host block ("The host side").
@@ -20,6 +20,34 @@ struct mf_pair {
 };
 
 static_assert(sizeof(mf_pair) == 48, "the pair table is laid out by the host");
+
+// the head of a pair record: the record itself, or the mf_pair m it starts with
+__device__ __forceinline__ const mf_pair& mf_head(const mf_pair& r) { return r; }
+template <class REC>
+__device__ __forceinline__ const mf_pair& mf_head(const REC& r) { return r.m; }
+
+// the pair of workgroup bx of a kernel launched over the table of P pairs: the last one whose first workgroup is not behind it
+template <class REC>
+__device__ __forceinline__ int mf_pair_of(const REC* __restrict__ pairs, int P, int bx) {
+    int lo = 0, hi = P - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (mf_head(pairs[mid]).blk0 <= bx) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// the two smallest of the keys dist << 23 | row a lane has taken, in registers, and what they say: rows and distances
+struct mf_top2 {
+    u32 b1 = SLAM_KEY_NONE, b2 = SLAM_KEY_NONE;
+    __device__ __forceinline__ void take(u32 key) {
+        b2 = min(b2, max(b1, key));
+        b1 = min(b1, key);
+    }
+    __device__ __forceinline__ int2 idx() const { return make_int2(bf_key_idx(b1, 0), bf_key_idx(b2, 0)); }
+    __device__ __forceinline__ int2 dist() const { return make_int2(bf_key_dist(b1), bf_key_dist(b2)); }
+};
 
 // first position in a[0 .. n) whose id, as u32, is >= v (STRICT: > v): the ends of an id's segment in a grouped image
 template <bool STRICT>

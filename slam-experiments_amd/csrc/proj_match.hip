@@ -45,7 +45,9 @@ struct pm_select {
     }
 };
 
-// One lane per map point.  SEARCH false: the gates alone (project_points).
+// One lane per map point.  SEARCH false: the gates alone (project_points).  (The grid walk below is the second copy of pm_walk
+// of grid_walk.h, kept because the kernel built on the template missed one line of its timing rule; grid_walk.h and DESIGN.md
+// 7, item 6, say which.)
 template <bool SEARCH>
 __global__ __launch_bounds__(PM_SCAN_LANES) void pm_scan_kernel(const pm_points s1, const pm_frames s2, const pm_pair* __restrict__ pairs, int P,
                                                                const pm_params* __restrict__ prm, int2* __restrict__ idx,

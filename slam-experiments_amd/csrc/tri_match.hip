@@ -47,6 +47,8 @@ struct tm_views {
 };
 
 // ----------------------------------------------------------------------------------------------------------------- scan
+// (The segment walk below is the second copy of nw_walk of node_walk.h, kept because the kernel built on the template missed
+// two lines of its timing rule; node_walk.h and DESIGN.md 7, item 7, say which.)
 __global__ __launch_bounds__(TM_SCAN_LANES) void tm_scan_kernel(const tm_set s1, const tm_set s2, const tm_pair* __restrict__ pairs, int P,
                                                                const tp_params* __restrict__ prm, int scan_order, int2* __restrict__ idx,
                                                                int2* __restrict__ dist, u32* __restrict__ owner) {
@@ -142,13 +144,8 @@ __global__ __launch_bounds__(TM_TRI_ROWS) void tm_triangulate_kernel(const tm_vi
                                                                     int* __restrict__ created) {
     __shared__ int s_row[TM_TRI_ROWS], s_match[TM_TRI_ROWS], s_wave[TM_TRI_ROWS / 64];
     const int bx = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int lo = 0, hi = P - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pairs[mid].m.blk0 <= bx) lo = mid;
-        else hi = mid - 1;
-    }
-    const tt_pair* pp = pairs + lo;
+    const int p = mf_pair_of(pairs, P, bx);
+    const tt_pair* pp = pairs + p;
     const mf_pair pr = pp->m;
     const int first = (bx - pr.blk0) * TM_TRI_ROWS, i = first + tid;
     const double nan = __builtin_nan("");
@@ -197,7 +194,7 @@ __global__ __launch_bounds__(TM_TRI_ROWS) void tm_triangulate_kernel(const tm_vi
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) made += __shfl_xor(made, off, 64);
-    if (lane == 0 && made) atomicAdd(&created[lo], made);
+    if (lane == 0 && made) atomicAdd(&created[p], made);
 }
 
 // =============================================================== entry points ================================================
