@@ -740,6 +740,83 @@ SLAM_API int slam_sim3_refit_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offs
                                  const double* d_X2, int64_t M, const uint8_t* d_mask, int fix_scale, double* d_model,
                                  int32_t* d_stats);
 
+/* ---- Sim(3) refinement by reprojection error (sim3_opt.hip): ORB-SLAM's Optimizer::OptimizeSim3, batched -------------------
+ * The step between the Sim3Solver above and the fusion: a 7-DoF Levenberg-Marquardt refinement of the similarity between two
+ * keyframes on the reprojection error of the matched map points in BOTH images against the MEASURED keypoints, with a Huber
+ * kernel, a chi-square gate and a second refinement on the survivors; the number of survivors is what a loop is accepted on.
+ * The reference has no call site.  PARITY UNPINNED against ORB-SLAM and g2o (both absent here): the chart below is not g2o's
+ * Sim3::log / exp, and the map points are constants, not vertices.  f64, only + - * / sqrt, none of them fused: a host build
+ * of the same source gives the same bits.  B candidates a call (B <= 65535), one workgroup each; candidate b owns the
+ * correspondences [d_offsets[b], d_offsets[b+1]) under the contract of slam_pose_optimize_batch_f64 (clamped, counted by
+ * slam_index_errors; the slices of two candidates must not overlap).  The call is asynchronous on the ctx stream and takes
+ * no workspace from the ctx block.
+ *
+ * Inputs per correspondence i: X1 = (a0, a1, a2) and X2 = (b0, b1, b2) of d_X1 / d_X2 [M,3] as above; d_px1 / d_px2 [M,2] the
+ * measured keypoints (u1, v1), (u2, v2) in image 1 and image 2 (NOT the projections of the points); d_sigma2 [M,2] = (g1, g2)
+ * the squared keypoint sigmas (NULL: all 1).  d_model_in [B,13]: the start, X2 = s R X1 + t (r0..r8 row-major, t0..t2, s).
+ *
+ * Residuals at a model, in the operation order of the RANSAC score (A_k = s * r_k):
+ *     x = ((A0*a0 + A1*a1) + A2*a2) + t0;  y = ((A3*a0 + A4*a1) + A5*a2) + t1;  z = ((A6*a0 + A7*a1) + A8*a2) + t2;   (Y)
+ *     e2 = (u2 - (fx * (x / z) + cx), v2 - (fy * (y / z) + cy));
+ *     y0 = b0 - t0;  y1 = b1 - t1;  y2 = b2 - t2;
+ *     wx = (r0*y0 + r3*y1) + r6*y2;  wy = (r1*y0 + r4*y1) + r7*y2;  wz = (r2*y0 + r5*y1) + r8*y2;                   (W, not / s)
+ *     e1 = (u1 - (fx * (wx / wz) + cx), v1 - (fy * (wy / wz) + cy));
+ *     c2 = (e2[0]*e2[0] + e2[1]*e2[1]) / g2;  c1 = (e1[0]*e1[0] + e1[1]*e1[1]) / g1.
+ *   Each edge k has its own Huber kernel of width delta on q = sqrt(c_k): q <= delta (or delta = 0): w_k = 1, rho_k = c_k;
+ *   else w_k = delta / q, rho_k = (2 * delta) * q - delta * delta.  The cost of a model is the sum of rho2 + rho1 over the
+ *   active pairs.
+ * Chart (tangent order [omega (3), upsilon (3), sigma], a left update): a = omega / 2, n = (a0*a0 + a1*a1) + a2*a2,
+ *     R_d = ((1 - n) I + 2 a a^T + 2 [a]x) / (1 + n)     (Cayley: an exact rotation, equal to Exp(omega) to first order),
+ *     s_d = (1 + sigma) + (sigma * sigma) / 2             (positive for every sigma, equal to e^sigma to second order),
+ *     S <- (s_d * s, R_d R, s_d * (R_d t) + upsilon).
+ *   Jacobians at 0: dY = [-[Y]x, I, Y], dW = R^T [[X2]x, -I, -X2], J_k = -Jpi(P) d(P) with Jpi(P) = [[fx / P2, 0,
+ *   -(fx * P0) / P2^2], [0, fy / P2, -(fy * P1) / P2^2]], formed as zi = 1 / P2, J[0][c] = -((fx * zi) * d[0][c] - ((fx * P0) *
+ *   (zi * zi)) * d[2][c]), J[1][c] likewise with fy, P1, d[1][c]; dW[i][c] = (r_i * G[0][c] + r_(3+i) * G[1][c]) + r_(6+i) * G[2][c]
+ *   for G = [[X2]x, -I, -X2]; the update entry by entry: Q = R_d with Q_ii = ((1 - n) + 2 (a_i a_i)) * (1 / (1 + n)), Q_ij =
+ *   (2 (a_i a_j) -+ 2 a_k) * (1 / (1 + n)), (R_d R)_ij = (Q_i0 r_0j + Q_i1 r_1j) + Q_i2 r_2j, t_i' = s_d * ((Q_i0 t0 + Q_i1 t1) +
+ *   Q_i2 t2) + upsilon_i.  fix_scale != 0: the sigma column of both is zero, the sigma
+ *   component of every step is exactly 0 and s comes back bit for bit.
+ * Normal equations: H = sum (w_k / g_k) J_k^T J_k (upper triangle, row by row: 28 terms), b = sum (w_k / g_k) J_k^T e_k
+ *   (7 terms) and the cost (1 term): per pair edge 2 is added first, then edge 1.
+ * Sums: lane l of 256 starts from 0 and adds the active pairs at the positions l, l + 256, l + 512, ... of the candidate,
+ *   ascending; within each group of 64 consecutive lanes the tree "for stride = 32, 16, ..., 1: lane l < stride adds lane
+ *   l + stride to its own"; the four group sums are combined as (g0 + g1) + (g2 + g3).  No floating-point atomics: the
+ *   bits depend on the candidate's data alone, not on B or on the order in which workgroups finish.
+ * Levenberg-Marquardt (g2o's schedule), per stage: linearise at the stage's start, lambda = 1e-5 * max(largest diagonal
+ *   entry of H, 1e-12), ni = 2.  Each iteration linearises at the current model (the first one uses the stage's) and makes
+ *   up to ten trials: solve (H + lambda I) x = -b by LDL^T; candidate = the update of the model by x; its cost F' over the
+ *   active pairs; gain = (F - F') / (sum_i x_i * (lambda * x_i - b_i) + 1e-3).  A trial FAILS when a pivot of the LDL^T is
+ *   not finite and positive, when the candidate is not finite with s > 0, when F' is not finite, when an active pair has
+ *   z <= 0 or wz <= 0 at the candidate, or when gain is not > 0: then lambda *= ni, ni *= 2.  Otherwise the candidate
+ *   becomes the model, lambda *= max(1/3, min(1 - (2 gain - 1)^3, 2/3)), ni = 2, and the iteration ends.  Ten failures in
+ *   one iteration end the stage (status bit 4).
+ * Schedule (ORB-SLAM: th2 = 10, it0 / it_bad / it_clean = 5 / 10 / 5, at least 10 survivors):
+ *   1. inactive from the start and never an inlier: a pair with a non-finite coordinate, pixel or sigma, a2 <= 0 or b2 <= 0,
+ *      a sigma that is not positive, or z <= 0 or wz <= 0 at the input model;
+ *   2. stage 1: it0 iterations with delta = sqrt(th2) on the active pairs;
+ *   3. an active pair stays iff c1 <= th2 and c2 <= th2 and z > 0 and wz > 0 at the current model; nBad = how many left;
+ *   4. fewer than min_pairs staying: the candidate is REJECTED (status bit 1);
+ *   5. stage 2 from the stage-1 model with delta = 0: it_bad iterations if nBad > 0, else it_clean;
+ *   6. the rule of 3. again on the pairs that stayed: this is the mask and the count.
+ * Outputs: d_model_out [B,13] (a rejected candidate: its input model bit for bit); d_inlier uint8 [M] (0 for a rejected
+ * candidate and outside every candidate); d_chi2 [M,2] = (c1, c2) at the output model for every pair that was active at the
+ * start, NaN for the others and for every pair of a rejected candidate (entries outside every candidate are not written);
+ * d_stats int32 [B,4] = {inliers, accepted steps, nBad, status}.  Finite data whose squares overflow (coordinates of 1e200, a
+ * sigma of 1e-300) stay active by rule 1: the sums are then not finite, every trial of the stage fails on its pivots, and the
+ * pairs are judged at the model the stage started from.  An input model that is not finite or has s <= 0 is data:
+ * status 1 | 2, the identity with s = 1, mask 0, stats {0, 0, 0, 3}.  d_model_out is always finite and one candidate's data
+ * never changes another's result.  Candidates of up to SLAM_SIM3_OPT_STAGE pairs are kept in LDS, larger ones run the same
+ * code on the global arrays (d_inlier holds their flags meanwhile).  Returns SLAM_ERR_INVALID before any device call for a
+ * null pointer (d_sigma2 excepted; the [M,...] arrays only when M > 0), B < 0 or > 65535, M outside [0, 2^28], th2 not positive and finite, an iteration count
+ * outside [0, 1000], min_pairs < 1, focal lengths that are not positive or intrinsics that are not finite. */
+#define SLAM_SIM3_OPT_STAGE 512
+SLAM_API int slam_sim3_optimize_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_X1,
+                                    const double* d_X2, const double* d_px1, const double* d_px2, int64_t M,
+                                    const double* d_sigma2, const double* d_model_in, double fx, double fy, double cx,
+                                    double cy, double th2, int it0, int it_bad, int it_clean, int min_pairs,
+                                    int fix_scale, double* d_model_out, uint8_t* d_inlier, double* d_chi2,
+                                    int32_t* d_stats);
+
 /* ---- ORB feature extraction (orb.hip): cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26), which
  * Frontend._detect_features calls on every frame with a mask (frontend.py:245) -------------------------------------------
  * A batch of B grayscale u8 images [B,H,W] (any W) goes through the integer-exact specification of DESIGN.md 4d: an L-level

@@ -33,6 +33,7 @@ from slamhip import tri_match as _tm
 from slamhip import pnp as _pnp
 from slamhip import pose_graph as _pg
 from slamhip import sim3_graph as _s3g
+from slamhip import sim3_opt as _s3o
 from slamhip import pose_opt as _po
 from slamhip import reproj as _r
 from slamhip import two_view as _tv
@@ -173,6 +174,17 @@ class Backend:
         ``min_score`` are returned as (ids, scores) by (score descending, id ascending) - the candidates ``relocalize`` and
         ``estimate_sim3_batch`` take."""
         return _bow.detect_loop_candidates(db, vector, connected, min_score)
+
+    def compute_sim3(self, cands, K, min_inliers: int = _s3o.DEFAULT_MIN_INLIERS, **kw):
+        """The estimation half of ORB-SLAM's ``LoopClosing::ComputeSim3`` (the reference closes no loops): ``cands`` = list of
+        ``(X1 [N_b,3], X2 [N_b,3], px1 [N_b,2], px2 [N_b,2][, sigma2 [N_b,2]])``, the matched map points of a loop candidate
+        in their own camera frames and their measured keypoints -> ``estimate_sim3_batch`` (RANSAC + refit), then
+        ``optimize_sim3_batch`` (the reprojection refinement, ``Optimizer::OptimizeSim3``) on the RANSAC inliers.  Returns
+        (models = (s, R, t) with ``X2 = s R X1 + t``, what ``sim3_edges_from_sim3`` takes; masks over each candidate's own
+        indexing; counts [B]; accepted bool [B] = count >= ``min_inliers``, ORB-SLAM's 20).  ``slamhip.sim3_to_s12`` turns a
+        model into what ``search_by_sim3`` and ``fuse_by_sim3`` take."""
+        models, masks, counts, accepted, _ = _s3o.compute_sim3(cands, K, min_inliers, ctx=self._ctx, **kw)
+        return models, masks, counts, accepted
 
     def match_by_bow(self, keyframes, frame, candidates, frame_index: int = 0, keyframe_bins=None, frame_bins=None,
                      th_low: int = _bm.TH_LOW, ratio: float = _bm.RATIO):

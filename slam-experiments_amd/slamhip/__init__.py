@@ -143,6 +143,13 @@ from .sim3 import (  # noqa: F401
     loop_edges_from_sim3,
     sim3_threepoint_arrays,
 )
+from .sim3_opt import (  # noqa: F401
+    compute_sim3,
+    optimize_sim3,
+    optimize_sim3_batch,
+    optimize_sim3_offsets,
+    sim3_to_s12,
+)
 from .sim3_graph import (  # noqa: F401
     correct_points,
     lift_se3_graph,
