@@ -168,6 +168,60 @@ EOF
     ls -la "$OUT"/libslamhip_ctxmut*.so
     exit 0
 fi
+# tools/build_exp.sh covis-mutants: ten copies of the library, each with ONE deliberate mistake in a temporary copy of
+# covis.hip, to show what tests/test_covis_edges_gpu.py sees that tests/test_covis_gpu.py does not.  No mutant touches a guard:
+# every store of the file stays behind its bound (cv_scatter `pos < n`, cv_emit `j >= s + n`, cv_edges `r >= E`, the point
+# field checked against L), so a wrong order or a wrong rank yields wrong values, never an address.  Mutants 1 to 3 leave an
+# observation sort of 64-bit keys unsorted, after which the pair count P is arbitrary (it sizes the tables): run them only on
+# the tests profiles/covis_edges_mutants.log names, where the mistake is met before P is used or only the pair sort is hit.
+if [ "${1:-}" = "covis-mutants" ]; then
+    python3 - "$SRC/covis.hip" "$TMP" <<'EOF'
+import sys
+src = open(sys.argv[1]).read()
+mutants = {
+    # 1: 64-bit observation keys only past 33 bits: the keys of the 33-bit forms are cut to 32
+    1: [("y.o64 = y.obits > 32;", "y.o64 = y.obits > 33;")],
+    # 2: the digit of a sort pass from the low word of the key (both readers of the digit, so the ranks stay a permutation)
+    2: [("(unsigned)(keys[i] >> shift) & (CV_DIGITS - 1)", "((unsigned)keys[i] >> shift) & (CV_DIGITS - 1)"),
+        ("(unsigned)(key >> shift) & (CV_DIGITS - 1)", "((unsigned)key >> shift) & (CV_DIGITS - 1)")],
+    # 3: no sixth pass
+    3: [("static inline int cv_passes(int bits) { return (bits + CV_DIGIT_BITS - 1) / CV_DIGIT_BITS; }",
+         "static inline int cv_passes(int bits) { const int p = (bits + CV_DIGIT_BITS - 1) / CV_DIGIT_BITS; return p > 5 ? 5 : p; }")],
+    # 4: cv_scan hands its `total` to the first level only
+    4: [("    cv_scan(st, scratch, nb, scratch + slam_align_up((uint64_t)nb, 32), total);", "    cv_scan(st, scratch, nb, scratch + slam_align_up((uint64_t)nb, 32), (T*)nullptr);")],
+    # 5: ... to the first two levels only
+    5: [("    cv_scan(st, scratch, nb, scratch + slam_align_up((uint64_t)nb, 32), total);",
+         "    cv_scan(st, scratch, nb, scratch + slam_align_up((uint64_t)nb, 32), nb > CV_SCAN_TILE ? (T*)nullptr : total);")],
+    # 6: cv_scan_add skipped for the inner level of a scan of three
+    6: [("static void cv_scan(hipStream_t st, T* d, int64_t n, T* scratch, T* total) {", "static void cv_scan(hipStream_t st, T* d, int64_t n, T* scratch, T* total, int depth = 0) {"),
+        ("    cv_scan(st, scratch, nb, scratch + slam_align_up((uint64_t)nb, 32), total);", "    cv_scan(st, scratch, nb, scratch + slam_align_up((uint64_t)nb, 32), total, depth + 1);"),
+        ("    cv_scan_add<T><<<(unsigned)nb, CV_THREADS, 0, st>>>(d, n, scratch);", "    if (depth == 0) cv_scan_add<T><<<(unsigned)nb, CV_THREADS, 0, st>>>(d, n, scratch);")],
+    # 7: cv_row_start in 32 bits
+    7: [("cv_row_start(cv_u64 i, cv_u64 n) { return i * (2 * n - i - 1) / 2; }",
+         "cv_row_start(cv_u64 i, cv_u64 n) { return (uint32_t)i * (2 * (uint32_t)n - (uint32_t)i - 1) / 2; }")],
+    # 8: the bisection of the row starts stops after ten steps (rows of up to 1 024)
+    8: [("    while (ihi - ilo > 1) {\n", "    for (int step = 0; step < 10 && ihi - ilo > 1; ++step) {\n")],
+    # 9: cv_rows: the upper end of the bisection one point short
+    9: [("    int64_t lo = 0, hi = M;\n", "    int64_t lo = 0, hi = M - 1;\n")],
+    # 10: cv_rows: the bisection stops after sixteen steps (65 536 points)
+    10: [("    int64_t lo = 0, hi = M;\n    while (hi - lo > 1) {\n", "    int64_t lo = 0, hi = M;\n    for (int step = 0; step < 16 && hi - lo > 1; ++step) {\n")],
+}
+for k, edits in mutants.items():
+    text = src
+    for old, new in edits:
+        assert text.count(old) == 1, f"covis mutant {k} did not apply: the kernel source changed"
+        text = text.replace(old, new)
+    open(f"{sys.argv[2]}/covis_mut{k}.hip", "w").write(text)
+EOF
+    CV_OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v "/covis.o")
+    for k in 1 2 3 4 5 6 7 8 9 10; do
+        /opt/rocm/bin/hipcc $FLAGS -x hip -c "$TMP/covis_mut$k.hip" -o "$TMP/covis_mut$k.o"
+        /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libslamhip_covismut$k.so" "$TMP/covis_mut$k.o" $CV_OBJS -ldl
+    done
+    rm -rf "$TMP"
+    ls -la "$OUT"/libslamhip_covismut*.so
+    exit 0
+fi
 OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v bf_hamming)
 
 python3 - "$SRC/bf_hamming.hip" "$TMP/bf_trace.hip" "$TMP/bf_keep.hip" "$TMP/bf_count.hip" "$TMP/bf_cycles.hip" <<'EOF'
