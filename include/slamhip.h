@@ -817,6 +817,92 @@ SLAM_API int slam_sim3_optimize_f64(slam_ctx* ctx, int64_t B, const int32_t* d_o
                                     int fix_scale, double* d_model_out, uint8_t* d_inlier, double* d_chi2,
                                     int32_t* d_stats);
 
+/* ---- Lens distortion (camera.hip, cam_model.h): Frame::UndistortKeyPoints / ComputeImageBounds of ORB-SLAM, and
+ * cv2.initUndistortRectifyMap + cv2.remap ------------------------------------------------------------------------------------
+ * Every geometric call of this header takes a pinhole camera (fx, fy, cx, cy).  These four bring the pixels of a real lens to
+ * that camera: the keypoints after extraction, or the image before it.  PARITY UNPINNED against OpenCV (absent here): the
+ * inverse is Newton's method, not OpenCV's five-step fixed-point iteration, and every point carries a status.  f64, no fused
+ * operation, + - * / and sqrt only: a host build of cam_model.h gives the device's bits for every model.  atan and tan below
+ * are cam_atan and cam_tan of cam_model.h (argument reduction and Taylor series in the four operations, within about 2 ulp of
+ * the true value), not the math library's, which differs by a few ulp between the two builds.
+ *
+ * A camera record is f64 [SLAM_CAM_RECORD = 16]: {fx, fy, cx, cy, model, k[0..7], 0, 0, 0}; the model code is an exact small
+ * double.  Records are HOST arrays and are checked before any launch: every value finite, fx, fy > 0, model in {0, 1, 2}.
+ *   model 0, pinhole:      no coefficients.
+ *   model 1, radtan:       OpenCV / Brown-Conrady, k = (k1, k2, p1, p2, k3).
+ *   model 2, equidistant:  Kannala-Brandt with four coefficients, k = (k1, k2, k3, k4) (cv2.fisheye, Kalibr "equidistant").
+ * Forward, normalised (x, y) -> raw pixel (u, v), in this operation order:
+ *   radtan:       r2 = x*x + y*y;  rad = 1 + r2*(k1 + r2*(k2 + r2*k3));
+ *                 xd = (x*rad + ((2*p1)*x)*y) + p2*(r2 + (2*x)*x);  yd = (y*rad + p1*(r2 + (2*y)*y)) + ((2*p2)*x)*y;
+ *   equidistant:  r = sqrt(x*x + y*y);  th = atan(r);  t2 = th*th;  thd = th*(1 + t2*(k1 + t2*(k2 + t2*(k3 + t2*k4))));
+ *                 s = thd / r (1 when r == 0);  xd = x*s;  yd = y*s;
+ *   pinhole:      xd = x;  yd = y;
+ *   all:          u = fx*xd + cx;  v = fy*yd + cy.
+ * Inverse, raw pixel (u, v) -> normalised (x, y) and the pinhole pixel (fx*x + cx, fy*y + cy):  x0 = (u - cx)/fx, y0 = (v - cy)/fy;
+ *   radtan:       from (x, y) = (x0, y0), exactly `iterations` Newton steps on (xd, yd)(x, y) - (x0, y0) = 0, no early exit: with
+ *                 dr = k1 + r2*(2*k2 + r2*(3*k3)), c = ((2*x)*y)*dr + ((2*p1)*x + (2*p2)*y),
+ *                 a = (rad + ((2*x)*x)*dr) + ((2*p1)*y + (6*p2)*x),  d = (rad + ((2*y)*y)*dr) + ((6*p1)*y + (2*p2)*x),
+ *                 det = a*d - c*c,  x -= (d*ex - c*ey)/det,  y -= (a*ey - c*ex)/det   (the Jacobian is symmetric; adjugate);
+ *   equidistant:  rd = sqrt(x0*x0 + y0*y0); from th = rd, `iterations` Newton steps on thd(th) - rd = 0 with the derivative
+ *                 1 + t2*(3*k1 + t2*(5*k2 + t2*(7*k3 + t2*(9*k4))));  s = tan(th)/rd (1 when rd == 0);  x = x0*s;  y = y0*s;
+ *   pinhole:      x = x0;  y = y0.
+ * Status per point (uint8), the first that applies:
+ *   3  the input is not finite;
+ *   2  no pinhole image exists: radtan - the Jacobian is not positive definite (det > 0 and a + d > 0) at an iterate a step
+ *      is taken from (the point lies beyond the fold where the model stops being monotonic; det alone is positive again
+ *      where both eigenvalues are negative); equidistant - the derivative is not > 0 at an iterate, or th is not in [0, 1.5);
+ *   1  not converged: the residual at the result, max(|xd - x0|, |yd - y0|) (equidistant: |thd(th) - rd|, which bounds it),
+ *      is above 64 * 2^-52 * max(1, |x0|, |y0|);
+ *   0  converged.
+ * For a status other than 0 all four outputs of the point are NaN: no caller receives a plausible wrong number.
+ *
+ * slam_cam_undistort_f64 / slam_cam_distort_f64: B sets of points, set b owning [h_offsets[b], h_offsets[b+1]) of d_px f64 [n,2]
+ * (HOST offsets int64 [B+1], ascending from 0, n = h_offsets[B] <= 2^30); C <= SLAM_CAM_MAX cameras h_cameras [C,16]; set b uses
+ * camera h_cam_index[b] (HOST int32 [B]; NULL: camera 0).  d_px_out f64 [n,2], d_norm f64 [n,2] or NULL, d_status uint8 [n];
+ * nothing outside [0, n) is written; no output may overlap d_px (the calls do not work in place: SLAM_ERR_INVALID).
+ * undistort (replaces cv2.undistortPoints(..., P = K)): raw pixels in, pinhole pixels and
+ * normalised coordinates out; iterations in [0, SLAM_CAM_ITERATIONS_MAX], 10 is the default of the Python layer.  distort
+ * (replaces cv2.projectPoints on unit-depth points): pinhole pixels of the same fx..cy in, raw pixels and DISTORTED normalised
+ * coordinates out; status 3 for an input that is not finite, else 0.  One lane per point; the workgroups of a launch are
+ * mapped to sets, so the record and the model are uniform.  Asynchronous on the ctx stream, no memory of the context is used.
+ *
+ * slam_cam_rectify_map (replaces cv2.initUndistortRectifyMap with CV_16SC2-like fixed point): the map of a Wd x Hd destination
+ * image of the pinhole camera h_new_K = (fx', fy', cx', cy') turned by h_R (HOST row-major [9], NULL = identity; taken as a
+ * rotation, checked for finiteness only) into the raw image of h_camera: d_map int32 [Hd, Wd, 2], 8-byte aligned.  Entry (i, j):
+ *   xn = (j - cx')/fx';  yn = (i - cy')/fy';  X = (R0*xn + R3*yn) + R6;  Y = (R1*xn + R4*yn) + R7;  Z = (R2*xn + R5*yn) + R8
+ *   (that is R^T (xn, yn, 1));  (u, v) = forward(X/Z, Y/Z);  entry = (rint(32*u), rint(32*v)), ties to even;
+ *   the sentinel (INT32_MIN, INT32_MIN) when Z is not > 0 or |32*u| or |32*v| is not < 2^30 (not finite included).
+ *
+ * slam_cam_remap_u8 (replaces cv2.remap(..., INTER_LINEAR, BORDER_CONSTANT)): B source images u8 [Hs, Ws] at d_src + b*src_stride
+ * with rows src_pitch apart, one map [Hd, Wd, 2], B destination images at d_dst + b*dst_stride with rows dst_pitch apart and
+ * an optional validity mask d_mask of the destination's shape, pitch and stride.  Integers only; for the entry (U, V):
+ *   x0 = U >> 5, a = U & 31, y0 = V >> 5, b = V & 31;  taps (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1) with the weights
+ *   (32-a)(32-b), a(32-b), (32-a)b, ab;  a tap outside the source reads `border` (0..255);  dst = (sum + 512) >> 10;
+ *   mask = 255 when every tap with a non-zero weight lies inside the source, else 0;  a tap of weight 0 is never loaded;
+ *   an entry with U or V equal to INT32_MIN gives dst = border, mask = 0.
+ * Bytes of the pitch padding and between images are not written.  Source, destination and mask must not overlap
+ * (SLAM_ERR_INVALID): a destination pixel reads source pixels that other lanes may already have replaced.  Sides in [1, SLAM_CAM_SIDE_MAX], pitches >= widths, strides
+ * >= pitch*(H-1) + W.  Both outputs can be the image and mask blocks of slam_orb_extract_u8 (pitch W, stride H*W,
+ * mask_batched = 1).
+ *
+ * All four return SLAM_ERR_INVALID before any device call for a null pointer (the optional ones excepted; device pointers only
+ * when there is something to do), sizes outside the ranges above, and a record, K' or R that fails its check. */
+#define SLAM_CAM_RECORD 16
+#define SLAM_CAM_MAX 8
+#define SLAM_CAM_ITERATIONS_MAX 100
+#define SLAM_CAM_SIDE_MAX 32768
+SLAM_API int slam_cam_undistort_f64(slam_ctx* ctx, int64_t B, const int64_t* h_offsets, int64_t C, const double* h_cameras,
+                                    const int32_t* h_cam_index, int iterations, const double* d_px, double* d_px_out,
+                                    double* d_norm, uint8_t* d_status);
+SLAM_API int slam_cam_distort_f64(slam_ctx* ctx, int64_t B, const int64_t* h_offsets, int64_t C, const double* h_cameras,
+                                  const int32_t* h_cam_index, const double* d_px, double* d_px_out, double* d_norm,
+                                  uint8_t* d_status);
+SLAM_API int slam_cam_rectify_map(slam_ctx* ctx, const double* h_camera, const double* h_R, const double* h_new_K, int64_t Wd,
+                                  int64_t Hd, int32_t* d_map);
+SLAM_API int slam_cam_remap_u8(slam_ctx* ctx, const uint8_t* d_src, int64_t B, int64_t Hs, int64_t Ws, int64_t src_pitch,
+                               int64_t src_stride, const int32_t* d_map, int64_t Hd, int64_t Wd, int border, uint8_t* d_dst,
+                               int64_t dst_pitch, int64_t dst_stride, uint8_t* d_mask);
+
 /* ---- ORB feature extraction (orb.hip): cv2.ORB behind OrbFeatureDetector (feature_detectors.py:18-26), which
  * Frontend._detect_features calls on every frame with a mask (frontend.py:245) -------------------------------------------
  * A batch of B grayscale u8 images [B,H,W] (any W) goes through the integer-exact specification of DESIGN.md 4d: an L-level

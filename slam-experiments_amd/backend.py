@@ -26,6 +26,7 @@ from slamhip import ba_sparse as _bas
 from slamhip import bow as _bow
 from slamhip import covis as _cv
 from slamhip import bow_match as _bm
+from slamhip import camera as _cam
 from slamhip import fuse as _fz
 from slamhip import local_map as _lm
 from slamhip import proj_match as _pm
@@ -185,6 +186,18 @@ class Backend:
         model into what ``search_by_sim3`` and ``fuse_by_sim3`` take."""
         models, masks, counts, accepted, _ = _s3o.compute_sim3(cands, K, min_inliers, ctx=self._ctx, **kw)
         return models, masks, counts, accepted
+
+    def undistort_points(self, px, camera, offsets=None, camera_index=None, iterations: int = _cam.DEFAULT_ITERATIONS):
+        """``Frame::UndistortKeyPoints`` (the reference works on raw ``keypoint.pt`` and has no counterpart): raw pixels [n,2]
+        under a ``slamhip.CameraModel`` (or up to 8, selected per set) -> (pinhole pixels [n,2], status u8 [n]); NaN where
+        the status is not 0 (1 not converged, 2 beyond the fold of the model, 3 input not finite)."""
+        out, _, status = _cam.undistort_points(px, camera, offsets, camera_index, iterations, ctx=self._ctx)
+        return out, status
+
+    def image_bounds(self, camera, size, iterations: int = _cam.DEFAULT_ITERATIONS):
+        """``Frame::ComputeImageBounds``: (min_x, max_x, min_y, max_y) of the undistorted corners of a ``size = (W, H)`` image,
+        the ``bounds`` of ``match_by_projection``'s searches."""
+        return _cam.image_bounds(camera, size, iterations, ctx=self._ctx)
 
     def match_by_bow(self, keyframes, frame, candidates, frame_index: int = 0, keyframe_bins=None, frame_bins=None,
                      th_low: int = _bm.TH_LOW, ratio: float = _bm.RATIO):

@@ -150,6 +150,14 @@ from .sim3_opt import (  # noqa: F401
     optimize_sim3_offsets,
     sim3_to_s12,
 )
+from .camera import (  # noqa: F401
+    CameraModel,
+    RectifyMap,
+    distort_points,
+    image_bounds,
+    remap_images,
+    undistort_points,
+)
 from .sim3_graph import (  # noqa: F401
     correct_points,
     lift_se3_graph,

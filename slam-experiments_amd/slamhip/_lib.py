@@ -135,6 +135,11 @@ SIGNATURES = {
     "slam_sim3_optimize_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                        c_double, c_double, c_double, c_double, c_double, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
+    "slam_cam_undistort_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_cam_distort_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "slam_cam_rectify_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "slam_cam_remap_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p,
+                                  c_int64, c_int64, c_void_p]),
     "slam_pg_workspace": (c_int, [c_int64, c_int64, POINTER(c_uint64)]),
     "slam_pg_plan": (c_int, [c_int64, c_int64, POINTER(c_int32)]),
     "slam_pg_linearize_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -205,6 +205,13 @@ class OrbResult:
         n = int(self.counts[b])
         return self._block.view(b * self.params.n_max * 32, n * 32), n
 
+    def undistorted(self, camera, iterations: int = 10, ctx: Optional[Context] = None):
+        """``Frame::UndistortKeyPoints``: (list of f64 [n,2] pinhole pixels per image, list of u8 [n] status) of ``xy`` under a
+        ``CameraModel`` (``slamhip.camera``); NaN where the status is not 0."""
+        from .camera import undistort_keypoints
+
+        return undistort_keypoints(self, camera, iterations, ctx)
+
     def free(self) -> None:
         if self._block is not None:
             self._block.free()
@@ -292,6 +299,47 @@ class OrbExtractor:
                 self.bufs.pop("mask").free()
             self.bufs["mask"] = self.ctx.upload(mask)
             self.mask_batched = int(mask.ndim == 3)
+
+    def upload_raw(self, images: np.ndarray, rect_map, border: int = 0, mask: Optional[np.ndarray] = None) -> None:
+        """Raw (distorted) frames u8 [B, Hs, Ws] in, rectified frames in the resident image block: the frames are uploaded to a
+        scratch buffer and resampled through ``rect_map`` (a ``slamhip.camera.RectifyMap`` of this extractor's W x H) on the
+        device; the validity mask of the resampling becomes the detection mask.  The frames cross PCIe once.  With a caller's
+        ``mask`` ([H, W] or [B, H, W], in rectified coordinates, non-zero = allowed) the validity mask is downloaded, ANDed
+        with it on the host and uploaded again: one more round trip of B x H x W bytes."""
+        from .camera import _check_border, _check_frames, remap_device
+
+        a = _check_frames(images)
+        border = _check_border(border)
+        if rect_map.size != (self.P.W, self.P.H):
+            raise ValueError(f"the map is {rect_map.size[0]} x {rect_map.size[1]}, the extractor {self.P.W} x {self.P.H}")
+        if a.shape[0] != self.B:
+            raise ValueError(f"{a.shape[0]} frames for an extractor of {self.B}")
+        if rect_map.ctx is not self.ctx:
+            raise ValueError("the map belongs to another context")
+        m = None
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.dtype not in (np.uint8, np.bool_):
+                raise ValueError(f"mask must be uint8 or bool, got {m.dtype}")
+            if m.shape not in ((self.P.H, self.P.W), (self.B, self.P.H, self.P.W)):
+                raise ValueError(f"mask shape {m.shape} matches neither [H, W] nor [B, H, W] of the extractor")
+        if self.B == 0:
+            return
+        n = self.B * self.P.H * self.P.W
+        if "mask" in self.bufs and (self.bufs["mask"].nbytes < n or not self.mask_batched):
+            self.bufs.pop("mask").free()
+        if "mask" not in self.bufs:
+            self.bufs["mask"] = self.ctx.malloc(max(n, 16))
+        self.mask_batched = 1
+        raw = self.ctx.upload(a)
+        try:
+            remap_device(self.ctx, raw, self.B, a.shape[1], a.shape[2], rect_map, self.bufs["images"], self.bufs["mask"], border)
+            if m is not None:
+                valid = self.bufs["mask"].download(np.uint8, (self.B, self.P.H, self.P.W))
+                self.bufs["mask"].upload(np.where((valid != 0) & (m != 0), 255, 0).astype(np.uint8))
+            self.ctx.sync()
+        finally:
+            raw.free()
 
     def drop_mask(self) -> None:
         if "mask" in self.bufs:

@@ -175,10 +175,13 @@ class FrameGrids:
         return cls(ctx, off, (W, H), int(cell), dev)
 
     @classmethod
-    def from_orb(cls, result, taken=None, cell: int = CELL, ctx: Optional[Context] = None) -> "FrameGrids":
+    def from_orb(cls, result, taken=None, cell: int = CELL, ctx: Optional[Context] = None, xy=None) -> "FrameGrids":
         """The frames of an ``OrbResult``: pixels, levels and bins as it holds them.  A result kept on the device
         (``keep_on_device=True``) whose rows are contiguous - one image, or every image full - is grouped from its resident
-        descriptor block; otherwise the descriptors are uploaded."""
+        descriptor block; otherwise the descriptors are uploaded.  ``xy`` (one array [n,2] or a list of one per image)
+        overrides the pixels the grid is built from: the undistorted keypoints (``OrbResult.undistorted``), kept as float32
+        like ORB-SLAM's ``mvKeysUn``.  Pixels outside the image fall into the border cells; a row whose override is not
+        finite (a keypoint without an undistorted image) is taken out of every search."""
         counts = np.asarray(result.counts, np.int64)
         off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         n = int(off[-1])
@@ -186,7 +189,18 @@ class FrameGrids:
         desc = cat(result.descriptors, (-1, 32), np.uint8)
         if getattr(result, "_block", None) is not None and n and (len(counts) == 1 or (counts == result.params.n_max).all()):
             desc = (result._block.view(0, n * 32), n)
-        return cls.from_arrays(desc, cat(result.xy, (-1, 2), np.float32), cat(result.level, (-1,), np.int64), (result.params.W, result.params.H),
+        if xy is None:
+            pix = cat(result.xy, (-1, 2), np.float32)
+        else:
+            pix = cat(xy, (-1, 2), np.float32) if isinstance(xy, (list, tuple)) else np.asarray(xy, np.float32).reshape(-1, 2)
+            if pix.shape != (n, 2):
+                raise ValueError(f"xy must hold {n} pixels, got shape {pix.shape}")
+            lost = ~np.isfinite(pix).all(axis=1)
+            if lost.any():
+                pix = np.where(lost[:, None], np.float32(0), pix)
+                tk = np.zeros(n, np.uint8) if taken is None else (_int_rows(taken, n, "taken", 0, 256) != 0).astype(np.uint8)
+                taken = tk | lost.astype(np.uint8)
+        return cls.from_arrays(desc, pix, cat(result.level, (-1,), np.int64), (result.params.W, result.params.H),
                                off, cat(result.bin, (-1,), np.int64), taken, cell, ctx)
 
 

@@ -222,6 +222,56 @@ EOF
     ls -la "$OUT"/libslamhip_covismut*.so
     exit 0
 fi
+# tools/build_exp.sh camera-remap: libslamhip_camremap.so, the library with two knobs in a temporary copy of camera.hip that
+# tools/camera_remap_ab.py sets through the environment between calls (profiles/camera_remap_ab.log):
+#     SLAM_EXP_REMAP_WG      the workgroup target of slam_cam_remap_u8 (the product: 4096)
+#     SLAM_EXP_REMAP_PAIRED  set: the two taps of a source row come from one 16-bit load where both count and both lie inside
+#                            the source (tap by tap elsewhere); the loads stay inside the source rows the byte taps read
+if [ "${1:-}" = "camera-remap" ]; then
+    python3 - "$SRC/camera.hip" "$TMP/camera_exp.hip" <<'EOF'
+import sys
+src = open(sys.argv[1]).read()
+row = '''typedef unsigned short __attribute__((aligned(1))) cam_u16;
+__device__ __forceinline__ int cam_row(const uint8_t* __restrict__ img, int64_t pitch, int Ws, int Hs, int x, int y, int wl, int wr, int wy, int border,
+                                       bool* ok) {
+    if (wy != 0 && wr != 0 && x >= 0 && x + 1 < Ws && y >= 0 && y < Hs) {
+        const unsigned v = *reinterpret_cast<const cam_u16*>(img + (int64_t)y * pitch + x);
+        return wy * (wl * (int)(v & 255u) + wr * (int)(v >> 8));
+    }
+    return cam_tap(img, pitch, Ws, Hs, x, y, wl * wy, border, ok) + cam_tap(img, pitch, Ws, Hs, x + 1, y, wr * wy, border, ok);
+}
+
+template <bool PAIRED>
+'''
+edits = [
+    ("__global__ __launch_bounds__(CAM_LANES) void cam_remap_kernel(", row + "__global__ __launch_bounds__(CAM_LANES) void cam_remap_kernel("),
+    ("                int sum = cam_tap(img, src_pitch, Ws, Hs, x0, y0, (32 - a) * (32 - c), border, &ok);\n",
+     "                int sum = 0;\n"
+     "                if (PAIRED) sum = cam_row(img, src_pitch, Ws, Hs, x0, y0, 32 - a, a, 32 - c, border, &ok) + cam_row(img, src_pitch, Ws, Hs, x0, y0 + 1, 32 - a, a, c, border, &ok);\n"
+     "                else {\n                sum = cam_tap(img, src_pitch, Ws, Hs, x0, y0, (32 - a) * (32 - c), border, &ok);\n"),
+    ("                sum += cam_tap(img, src_pitch, Ws, Hs, x0 + 1, y0 + 1, a * c, border, &ok);\n",
+     "                sum += cam_tap(img, src_pitch, Ws, Hs, x0 + 1, y0 + 1, a * c, border, &ok);\n                }\n"),
+    ("    const int64_t target = 4096;\n",
+     '    const char* exp_wg = getenv("SLAM_EXP_REMAP_WG");\n    const int64_t target = exp_wg && atoll(exp_wg) > 0 ? atoll(exp_wg) : 4096;\n'),
+    ("    cam_remap_kernel<<<grid, dim3(64, 4), 0, ctx->stream>>>(d_src, (int)B, (int)Hs, (int)Ws, src_pitch, src_stride, d_map, (int)Hd, (int)Wd, border,\n"
+     "                                                           d_dst, dst_pitch, dst_stride, d_mask, words);\n",
+     '    if (getenv("SLAM_EXP_REMAP_PAIRED"))\n'
+     "        cam_remap_kernel<true><<<grid, dim3(64, 4), 0, ctx->stream>>>(d_src, (int)B, (int)Hs, (int)Ws, src_pitch, src_stride, d_map, (int)Hd, (int)Wd, border, d_dst, dst_pitch, dst_stride, d_mask, words);\n"
+     "    else\n"
+     "        cam_remap_kernel<false><<<grid, dim3(64, 4), 0, ctx->stream>>>(d_src, (int)B, (int)Hs, (int)Ws, src_pitch, src_stride, d_map, (int)Hd, (int)Wd, border, d_dst, dst_pitch, dst_stride, d_mask, words);\n"),
+]
+for old, new in edits:
+    assert src.count(old) == 1, "camera-remap knobs did not apply: the kernel source changed"
+    src = src.replace(old, new)
+open(sys.argv[2], "w").write(src)
+EOF
+    CAM_OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v "/camera.o")
+    /opt/rocm/bin/hipcc $FLAGS -x hip -c "$TMP/camera_exp.hip" -o "$TMP/camera_exp.o"
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libslamhip_camremap.so" "$TMP/camera_exp.o" $CAM_OBJS -ldl
+    rm -rf "$TMP"
+    ls -la "$OUT"/libslamhip_camremap.so
+    exit 0
+fi
 OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v bf_hamming)
 
 python3 - "$SRC/bf_hamming.hip" "$TMP/bf_trace.hip" "$TMP/bf_keep.hip" "$TMP/bf_count.hip" "$TMP/bf_cycles.hip" <<'EOF'
