@@ -978,6 +978,63 @@ SLAM_API int slam_orb_extract_dist_u8(slam_ctx* ctx, const uint8_t* d_images, in
                                       void* d_workspace, uint64_t workspace_bytes, int32_t* d_count, int32_t* d_kp, int64_t* d_resp,
                                       uint8_t* d_desc);
 
+/* ---- Stereo matching (stereo.hip, stereo_point.h): Frame::ComputeStereoMatches of ORB-SLAM (the reference opens one camera
+ * only) -------------------------------------------------------------------------------------------------------------------
+ * P pairs of rectified images, h_pairs HOST int32 [P,2] = (image of the left block, image of the right block).  A block is what
+ * slam_orb_extract_u8 or slam_orb_extract_dist_u8 left on the device for B images: d_count int32 [B], d_kp int32 [B,N_max,4] =
+ * (x, y, level, bin) in level coordinates, d_desc u8 [B,N_max,32] and the extractor's workspace, where the pyramids are.  Both
+ * blocks share N_max and one level layout, given as HOST values taken from slam_orb_workspace's layout: image_base and
+ * image_stride, and per level h_level_offset uint64 [L] (the level image inside an image block), h_level_pitch, h_level_w,
+ * h_level_h int32 [L].  The same block may be passed as left and right.  h_scale HOST f32 [L] = float32(s) ** arange(L) as
+ * OrbResult makes it, each in [1, 65536]: no pow runs on the device.  Keypoints must lie inside their level (the extractor's
+ * do); a row whose level is outside [0, L) neither has nor is a candidate.  A count is clamped to [0, N_max].
+ *
+ * The level-0 pixel of a row is the single f32 product (float)x * h_scale[l], promoted to f64; everything below is f64 or
+ * integer, unfused, in the order written (tests/stereo_ref.py is the numpy statement).  For a left row i with
+ * (uL, vL, lL):
+ *   1. a right row j with (uR, vR, lR) is a candidate when floor(vR - r) <= trunc(vL) <= ceil(vR + r) with r = 2 h_scale[lR],
+ *      lL - 1 <= lR <= lL + 1, and uL - max_d <= uR <= uL - min_d; a left row with uL - min_d < 0 has none;
+ *   2. the candidate of the smallest (Hamming distance, j) is taken, and the row goes on if that distance is < th_orb;
+ *   3. on level lL of both pyramids, on the row y = y_level of the left keypoint: left centre x = x_level, right centre
+ *      c0 = floor(uR / h_scale[lL] + 0.5).  Status "window" unless c0 - Ls - w >= 0, c0 + Ls + w + 1 < level_w, and the left
+ *      patch and the rows y +- w lie inside the level.  For inc in [-Ls, Ls]
+ *      SAD(inc) = sum over dy, dx in [-w, w] of |(IL(y+dy, x+dx) - IL(y, x)) - (IR(y+dy, c0+inc+dx) - IR(y, c0+inc))|;
+ *      the best is the smallest (SAD, inc); status "slide border" if that inc is -Ls or Ls;
+ *   4. d1, d2, d3 = SAD(inc-1), SAD(inc), SAD(inc+1); den = d1 + d3 - 2 d2 (>= 0); delta = 0 if den = 0, else
+ *      (double)(d1 - d3) / (double)(2 den), so |delta| <= 1/2;
+ *   5. u_right = h_scale[lL] * ((c0 + inc) + delta), disp = uL - u_right; accepted when min_d <= disp < max_d, else status
+ *      "disparity"; disp <= 0 becomes disp = 0.01 and u_right = uL - 0.01; depth = bf / disp;
+ * and once per pair, if `reject`:
+ *   6. with m the SAD at index n / 2 of the n accepted rows in ascending (SAD, i), a row is kept when 10 SAD < 21 m, else its
+ *      status is "median" (ORB-SLAM compares with 1.5f * 1.4f * m in float: the two differ at exact equality only).
+ * Outputs [P,N_max] each: d_right int32 = the row taken in step 2 (-1: no candidate); d_u_right, d_depth f64 (NaN unless the
+ * status is 0); d_orb_dist int32 (256: no candidate); d_sad int32 = the best SAD (-1 for status 1, 2 and 3); d_status u8:
+ *   0 matched, 1 no candidate, 2 descriptor distance >= th_orb, 3 window, 4 slide border, 5 disparity out of range,
+ *   6 rejected by the median;
+ * slots at or past the left image's count are status 1 rows.  d_counts int32 [P,2] = (rows of status 0, rows accepted before
+ * step 6).  The result is a pure function of the arguments.  d_workspace: slam_stereo_workspace bytes, 16-byte aligned like
+ * d_kp and d_desc; it holds the level table and the pair table.  Two copies and three launches whatever P is, asynchronous on
+ * the ctx stream, no memory of the context is used.  SLAM_ERR_INVALID with nothing launched: null pointers (device pointers
+ * only when P > 0 and N_max > 0), P outside [0, SLAM_STEREO_MAX_PAIRS], N_max outside [0, SLAM_STEREO_MAX_ROWS], L outside
+ * [1, SLAM_STEREO_MAX_LEVELS], a pair outside its block, th_orb outside [0, 256], w or Ls outside [1, SLAM_STEREO_HALF_MAX],
+ * bf not positive and finite, min_d not finite, max_d <= min_d (or NaN), a level side outside [1, SLAM_STEREO_MAX_SIDE] or a
+ * pitch below its width, a scale outside [1, 65536], a workspace that is too small or misaligned.  P = 0 does nothing. */
+#define SLAM_STEREO_MAX_PAIRS 4096
+#define SLAM_STEREO_MAX_ROWS 8192
+#define SLAM_STEREO_MAX_LEVELS 16
+#define SLAM_STEREO_MAX_SIDE 8192
+#define SLAM_STEREO_HALF_MAX 15
+SLAM_API int slam_stereo_workspace(int64_t P, int64_t n_max, uint64_t* bytes);
+SLAM_API int slam_stereo_match(slam_ctx* ctx, int64_t P, const int32_t* h_pairs, int64_t B_left, const int32_t* d_count_left,
+                               const int32_t* d_kp_left, const uint8_t* d_desc_left, const void* d_ws_left, int64_t B_right,
+                               const int32_t* d_count_right, const int32_t* d_kp_right, const uint8_t* d_desc_right,
+                               const void* d_ws_right, int64_t n_max, int L, uint64_t image_base, uint64_t image_stride,
+                               const uint64_t* h_level_offset, const int32_t* h_level_pitch, const int32_t* h_level_w,
+                               const int32_t* h_level_h, const float* h_scale, double bf, double min_d, double max_d, int th_orb,
+                               int w, int Ls, int reject, void* d_workspace, uint64_t workspace_bytes, int32_t* d_right,
+                               double* d_u_right, double* d_depth, int32_t* d_orb_dist, int32_t* d_sad, uint8_t* d_status,
+                               int32_t* d_counts);
+
 /* ---- per-frame calls on caller-owned host buffers: one upload, one download, one wait (frame-sized: zero-copy, polled) ---- */
 /* BruteForceFeatureMatcher.match (feature_matchers.py:36-44; cv2.BFMatcher.match + the min-distance filter) in
  * one call.  Query rows h_query [N,32]; train rows either h_train [M,32] (host) or d_train (device, e.g. the

@@ -35,6 +35,7 @@ from slamhip import pnp as _pnp
 from slamhip import pose_graph as _pg
 from slamhip import sim3_graph as _s3g
 from slamhip import sim3_opt as _s3o
+from slamhip import stereo as _st
 from slamhip import pose_opt as _po
 from slamhip import reproj as _r
 from slamhip import two_view as _tv
@@ -198,6 +199,14 @@ class Backend:
         """``Frame::ComputeImageBounds``: (min_x, max_x, min_y, max_y) of the undistorted corners of a ``size = (W, H)`` image,
         the ``bounds`` of ``match_by_projection``'s searches."""
         return _cam.image_bounds(camera, size, iterations, ctx=self._ctx)
+
+    def stereo_frame(self, left, right=None, pairs=None, *, bf, fx=None, **kw):
+        """ORB-SLAM's ``Frame::ComputeStereoMatches`` (the reference opens one camera and has no counterpart): ``left`` and
+        ``right`` are ``slamhip.OrbExtractor``s of the rectified images after ``run()`` - or one extractor and ``pairs`` =
+        (left image, right image) inside it - and ``bf`` the focal length times the baseline.  Returns a
+        ``slamhip.StereoResult``: per pair ``u_right``, ``depth`` and a status for every left keypoint; its ``points`` and
+        ``point_set`` turn the matched rows into camera-frame or world points."""
+        return _st.stereo_match(left, right, pairs, bf=bf, fx=fx, **kw)
 
     def match_by_bow(self, keyframes, frame, candidates, frame_index: int = 0, keyframe_bins=None, frame_bins=None,
                      th_low: int = _bm.TH_LOW, ratio: float = _bm.RATIO):

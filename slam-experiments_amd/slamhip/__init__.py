@@ -158,6 +158,11 @@ from .camera import (  # noqa: F401
     remap_images,
     undistort_points,
 )
+from .stereo import (  # noqa: F401
+    StereoResult,
+    stereo_match,
+    stereo_match_arrays,
+)
 from .sim3_graph import (  # noqa: F401
     correct_points,
     lift_se3_graph,

@@ -140,6 +140,11 @@ SIGNATURES = {
     "slam_cam_rectify_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "slam_cam_remap_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                   c_int64, c_int64, c_void_p]),
+    "slam_stereo_workspace": (c_int, [c_int64, c_int64, POINTER(c_uint64)]),
+    "slam_stereo_match": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int64, c_int, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double,
+                                  c_double, c_int, c_int, c_int, c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "slam_pg_workspace": (c_int, [c_int64, c_int64, POINTER(c_uint64)]),
     "slam_pg_plan": (c_int, [c_int64, c_int64, POINTER(c_int32)]),
     "slam_pg_linearize_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
