@@ -634,37 +634,30 @@ __global__ __launch_bounds__(HG_THREADS) void hg_score_kernel(const int* __restr
 }
 
 // =============================================================== entry points ================================================
+#include "geometry_host.h"           // the checks, the vote block and the launch shapes the four estimators' entry points share
+
 extern "C" int slam_hg_fourpoint_f64(slam_ctx* ctx, int64_t S, const double* d_p1, const double* d_p2, double* d_H, int32_t* d_ok) {
-    SLAM_REQUIRE(ctx, "slam_hg_fourpoint_f64: null ctx");
-    SLAM_REQUIRE(S >= 0 && S <= (1 << 24), "S=%lld out of range [0, 2^24]", (long long)S);
-    if (S == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_p1 && d_p2 && d_H && d_ok, "slam_hg_fourpoint_f64: null device pointer");
+    GEO_SAMPLE_SIZES(ctx, S);
+    GEO_POINTERS(S, d_p1 && d_p2 && d_H && d_ok);
     SLAM_HIP(hipSetDevice(ctx->device));
-    hg_fourpoint_kernel<<<(unsigned)((S + HG_LANES - 1) / HG_LANES), HG_LANES, 0, ctx->stream>>>((int)S, d_p1, d_p2, d_H, d_ok);
+    hg_fourpoint_kernel<<<geo_blocks(S, HG_LANES), HG_LANES, 0, ctx->stream>>>((int)S, d_p1, d_p2, d_H, d_ok);
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }
 
 extern "C" int slam_hg_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_px1, const double* d_px2, int64_t M,
                                   int H, double threshold_px, uint64_t seed, double* d_H, uint8_t* d_inlier, int32_t* d_stats) {
-    SLAM_REQUIRE(ctx, "slam_hg_ransac_f64: null ctx");
-    SLAM_REQUIRE(B >= 0 && B <= 65535 && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld; B <= 65535)", (long long)B, (long long)M);
-    SLAM_REQUIRE(H >= 1 && H <= GEO_H_MAX, "H=%d out of range [1, 2^20]", H);
+    GEO_RANSAC_SIZES(ctx, B, M, H);
     SLAM_REQUIRE(threshold_px > 0.0, "threshold must be positive");
-    if (B == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_offsets && d_H && d_stats && (M == 0 || (d_px1 && d_px2 && d_inlier)), "slam_hg_ransac_f64: null device pointer");
+    GEO_POINTERS(B, d_offsets && d_H && d_stats && (M == 0 || (d_px1 && d_px2 && d_inlier)));
     SLAM_HIP(hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> lk(ctx->call_mu);        // the workspace holds the keys and the model counts
-    const uint64_t key_bytes = (uint64_t)B * 8;
     void* ws = nullptr;
-    if (int rc = slam_workspace(ctx, key_bytes + (uint64_t)B * 4, &ws)) return rc;
-    unsigned long long* keys = (unsigned long long*)ws;
-    int* models = (int*)((char*)ws + key_bytes);
+    if (int rc = slam_workspace(ctx, geo_vote_bytes(0, B), &ws)) return rc;
+    unsigned long long* keys; int* models;
+    if (int rc = geo_vote_block(ctx, ws, 0, B, true, M, d_inlier, &keys, &models)) return rc;
     const double thr2 = threshold_px * threshold_px;
-    SLAM_HIP(hipMemsetAsync(ws, 0, (size_t)(key_bytes + (uint64_t)B * 4), ctx->stream));
-    if (M > 0) SLAM_HIP(hipMemsetAsync(d_inlier, 0, (size_t)M, ctx->stream));
-    hg_ransac_kernel<<<dim3((unsigned)((H + HG_THREADS - 1) / HG_THREADS), (unsigned)B), HG_THREADS, 0, ctx->stream>>>(
-        d_offsets, (int)M, d_px1, d_px2, H, thr2, seed, keys, models);
+    hg_ransac_kernel<<<geo_vote_grid(H, HG_THREADS, B), HG_THREADS, 0, ctx->stream>>>(d_offsets, (int)M, d_px1, d_px2, H, thr2, seed, keys, models);
     SLAM_HIP(hipGetLastError());
     hg_ransac_result_kernel<<<(unsigned)B, HG_LANES, 0, ctx->stream>>>(d_offsets, (int)M, d_px1, d_px2, thr2, seed, keys, models, d_H, d_inlier,
                                                                       d_stats, slam_index_error_counter(ctx));
@@ -676,13 +669,10 @@ extern "C" int slam_hg_decompose_f64(slam_ctx* ctx, int64_t B, const int32_t* d_
                                      double fx, double fy, double cx, double cy, const double* d_H, const uint8_t* d_inlier_in,
                                      double distance_thresh, double* d_pose_all, double* d_normal_all, int32_t* d_count, double* d_pose,
                                      double* d_sv, uint8_t* d_inlier_out, int32_t* d_stats) {
-    SLAM_REQUIRE(ctx, "slam_hg_decompose_f64: null ctx");
-    SLAM_REQUIRE(B >= 0 && B <= (1 << 20) && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld)", (long long)B, (long long)M);
+    GEO_CANDIDATE_SIZES(ctx, B, 1 << 20, M);
     SLAM_REQUIRE(fx > 0.0 && fy > 0.0 && distance_thresh > 0.0, "focal lengths and distance_thresh must be positive");
-    if (B == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_offsets && d_H && d_pose_all && d_normal_all && d_count && d_pose && d_sv && d_stats &&
-                     (M == 0 || (d_px1 && d_px2 && d_inlier_out)),
-                 "slam_hg_decompose_f64: null device pointer");
+    GEO_POINTERS(B, d_offsets && d_H && d_pose_all && d_normal_all && d_count && d_pose && d_sv && d_stats &&
+                        (M == 0 || (d_px1 && d_px2 && d_inlier_out)));
     SLAM_HIP(hipSetDevice(ctx->device));
     const geo_cam cam = {fx, fy, cx, cy};
     if (M > 0) SLAM_HIP(hipMemsetAsync(d_inlier_out, 0, (size_t)M, ctx->stream));
@@ -696,12 +686,10 @@ extern "C" int slam_hg_decompose_f64(slam_ctx* ctx, int64_t B, const int32_t* d_
 extern "C" int slam_hg_model_score_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_px1, const double* d_px2, int64_t M,
                                        double fx, double fy, double cx, double cy, const double* d_H, const double* d_E, double sigma,
                                        int64_t* d_score, double* d_ratio) {
-    SLAM_REQUIRE(ctx, "slam_hg_model_score_f64: null ctx");
-    SLAM_REQUIRE(B >= 0 && B <= (1 << 20) && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld)", (long long)B, (long long)M);
+    GEO_CANDIDATE_SIZES(ctx, B, 1 << 20, M);
     SLAM_REQUIRE(fx > 0.0 && fy > 0.0 && sigma > 0.0 && sigma * sigma > 0.0 && sigma * sigma < GEO_BIG,
                  "focal lengths and sigma must be positive (sigma^2 a positive finite double)");
-    if (B == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_offsets && d_H && d_E && d_score && d_ratio && (M == 0 || (d_px1 && d_px2)), "slam_hg_model_score_f64: null device pointer");
+    GEO_POINTERS(B, d_offsets && d_H && d_E && d_score && d_ratio && (M == 0 || (d_px1 && d_px2)));
     SLAM_HIP(hipSetDevice(ctx->device));
     const geo_cam cam = {fx, fy, cx, cy};
     hg_score_kernel<<<(unsigned)B, HG_THREADS, 0, ctx->stream>>>(d_offsets, (int)M, d_px1, d_px2, cam, d_H, d_E, sigma * sigma,

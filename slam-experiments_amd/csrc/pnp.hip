@@ -410,13 +410,13 @@ __global__ __launch_bounds__(PNP_LANES) void pnp_ransac_result_kernel(const int*
 }
 
 // =============================================================== entry points ================================================
+#include "geometry_host.h"           // the checks, the vote block and the launch shapes the four estimators' entry points share
+
 extern "C" int slam_pnp_p3p_f64(slam_ctx* ctx, int64_t S, const double* d_X, const double* d_x, double* d_pose, int32_t* d_nsol) {
-    SLAM_REQUIRE(ctx, "slam_pnp_p3p_f64: null ctx");
-    SLAM_REQUIRE(S >= 0 && S <= (1 << 24), "S=%lld out of range [0, 2^24]", (long long)S);
-    if (S == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_X && d_x && d_pose && d_nsol, "slam_pnp_p3p_f64: null device pointer");
+    GEO_SAMPLE_SIZES(ctx, S);
+    GEO_POINTERS(S, d_X && d_x && d_pose && d_nsol);
     SLAM_HIP(hipSetDevice(ctx->device));
-    pnp_p3p_kernel<<<(unsigned)((S + PNP_LANES - 1) / PNP_LANES), PNP_LANES, 0, ctx->stream>>>((int)S, d_X, d_x, d_pose, d_nsol);
+    pnp_p3p_kernel<<<geo_blocks(S, PNP_LANES), PNP_LANES, 0, ctx->stream>>>((int)S, d_X, d_x, d_pose, d_nsol);
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }
@@ -424,25 +424,19 @@ extern "C" int slam_pnp_p3p_f64(slam_ctx* ctx, int64_t S, const double* d_X, con
 extern "C" int slam_pnp_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_X, const double* d_px, int64_t M,
                                    double fx, double fy, double cx, double cy, int H, double threshold_px, uint64_t seed, double* d_pose,
                                    uint8_t* d_inlier, int32_t* d_stats) {
-    SLAM_REQUIRE(ctx, "slam_pnp_ransac_f64: null ctx");
-    SLAM_REQUIRE(B >= 0 && B <= 65535 && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld; B <= 65535)", (long long)B, (long long)M);
-    SLAM_REQUIRE(H >= 1 && H <= GEO_H_MAX, "H=%d out of range [1, 2^20]", H);
+    GEO_RANSAC_SIZES(ctx, B, M, H);
     SLAM_REQUIRE(threshold_px > 0.0 && fx > 0.0 && fy > 0.0, "threshold and focal lengths must be positive");
-    if (B == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_offsets && d_pose && d_stats && (M == 0 || (d_X && d_px && d_inlier)), "slam_pnp_ransac_f64: null device pointer");
+    GEO_POINTERS(B, d_offsets && d_pose && d_stats && (M == 0 || (d_X && d_px && d_inlier)));
     SLAM_HIP(hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> lk(ctx->call_mu);        // the workspace holds the keys and the model counts
-    const uint64_t key_bytes = (uint64_t)B * 8;
     void* ws = nullptr;
-    if (int rc = slam_workspace(ctx, key_bytes + (uint64_t)B * 4, &ws)) return rc;
-    unsigned long long* keys = (unsigned long long*)ws;
-    int* models = (int*)((char*)ws + key_bytes);
+    if (int rc = slam_workspace(ctx, geo_vote_bytes(0, B), &ws)) return rc;
+    unsigned long long* keys; int* models;
+    if (int rc = geo_vote_block(ctx, ws, 0, B, true, M, d_inlier, &keys, &models)) return rc;
     const geo_cam cam = {fx, fy, cx, cy};
     const double thr2 = threshold_px * threshold_px;
-    SLAM_HIP(hipMemsetAsync(ws, 0, (size_t)(key_bytes + (uint64_t)B * 4), ctx->stream));
-    if (M > 0) SLAM_HIP(hipMemsetAsync(d_inlier, 0, (size_t)M, ctx->stream));
-    pnp_ransac_kernel<<<dim3((unsigned)((H + PNP_THREADS - 1) / PNP_THREADS), (unsigned)B), PNP_THREADS, 0, ctx->stream>>>(
-        d_offsets, (int)M, d_X, d_px, cam, H, thr2, seed, keys, models);
+    pnp_ransac_kernel<<<geo_vote_grid(H, PNP_THREADS, B), PNP_THREADS, 0, ctx->stream>>>(d_offsets, (int)M, d_X, d_px, cam, H, thr2, seed, keys,
+                                                                                         models);
     SLAM_HIP(hipGetLastError());
     pnp_ransac_result_kernel<<<(unsigned)B, PNP_LANES, 0, ctx->stream>>>(d_offsets, (int)M, d_X, d_px, cam, thr2, seed, keys, models, d_pose,
                                                                        d_inlier, d_stats, slam_index_error_counter(ctx));

@@ -399,14 +399,14 @@ __global__ __launch_bounds__(S3_REFIT_THREADS) void s3_refit_kernel(const int* _
 }
 
 // =============================================================== entry points ================================================
+#include "geometry_host.h"           // the checks, the vote block and the launch shapes the four estimators' entry points share
+
 extern "C" int slam_sim3_threepoint_f64(slam_ctx* ctx, int64_t S, const double* d_X1, const double* d_X2, int fix_scale, double* d_model,
                                         int32_t* d_ok) {
-    SLAM_REQUIRE(ctx, "slam_sim3_threepoint_f64: null ctx");
-    SLAM_REQUIRE(S >= 0 && S <= (1 << 24), "S=%lld out of range [0, 2^24]", (long long)S);
-    if (S == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_X1 && d_X2 && d_model && d_ok, "slam_sim3_threepoint_f64: null device pointer");
+    GEO_SAMPLE_SIZES(ctx, S);
+    GEO_POINTERS(S, d_X1 && d_X2 && d_model && d_ok);
     SLAM_HIP(hipSetDevice(ctx->device));
-    s3_threepoint_kernel<<<(unsigned)((S + S3_LANES - 1) / S3_LANES), S3_LANES, 0, ctx->stream>>>((int)S, d_X1, d_X2, fix_scale != 0, d_model, d_ok);
+    s3_threepoint_kernel<<<geo_blocks(S, S3_LANES), S3_LANES, 0, ctx->stream>>>((int)S, d_X1, d_X2, fix_scale != 0, d_model, d_ok);
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }
@@ -414,24 +414,18 @@ extern "C" int slam_sim3_threepoint_f64(slam_ctx* ctx, int64_t S, const double* 
 extern "C" int slam_sim3_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_X1, const double* d_X2, int64_t M,
                                     const double* d_sigma2, double fx, double fy, double cx, double cy, int H, double chi2_gate, int fix_scale,
                                     uint64_t seed, double* d_model, uint8_t* d_inlier, int32_t* d_stats) {
-    SLAM_REQUIRE(ctx, "slam_sim3_ransac_f64: null ctx");
-    SLAM_REQUIRE(B >= 0 && B <= 65535 && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld; B <= 65535)", (long long)B, (long long)M);
-    SLAM_REQUIRE(H >= 1 && H <= GEO_H_MAX, "H=%d out of range [1, 2^20]", H);
+    GEO_RANSAC_SIZES(ctx, B, M, H);
     SLAM_REQUIRE(chi2_gate > 0.0 && fx > 0.0 && fy > 0.0, "chi2 gate and focal lengths must be positive");
-    if (B == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_offsets && d_model && d_stats && (M == 0 || (d_X1 && d_X2 && d_inlier)), "slam_sim3_ransac_f64: null device pointer");
+    GEO_POINTERS(B, d_offsets && d_model && d_stats && (M == 0 || (d_X1 && d_X2 && d_inlier)));
     SLAM_HIP(hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> lk(ctx->call_mu);        // the workspace holds the keys and the model counts
-    const uint64_t key_bytes = (uint64_t)B * 8;
     void* ws = nullptr;
-    if (int rc = slam_workspace(ctx, key_bytes + (uint64_t)B * 4, &ws)) return rc;
-    unsigned long long* keys = (unsigned long long*)ws;
-    int* models = (int*)((char*)ws + key_bytes);
+    if (int rc = slam_workspace(ctx, geo_vote_bytes(0, B), &ws)) return rc;
+    unsigned long long* keys; int* models;
+    if (int rc = geo_vote_block(ctx, ws, 0, B, true, M, d_inlier, &keys, &models)) return rc;
     const geo_cam cam = {fx, fy, cx, cy};
-    SLAM_HIP(hipMemsetAsync(ws, 0, (size_t)(key_bytes + (uint64_t)B * 4), ctx->stream));
-    if (M > 0) SLAM_HIP(hipMemsetAsync(d_inlier, 0, (size_t)M, ctx->stream));
-    s3_ransac_kernel<<<dim3((unsigned)((H + S3_THREADS - 1) / S3_THREADS), (unsigned)B), S3_THREADS, 0, ctx->stream>>>(
-        d_offsets, (int)M, d_X1, d_X2, d_sigma2, cam, H, chi2_gate, fix_scale != 0, seed, keys, models);
+    s3_ransac_kernel<<<geo_vote_grid(H, S3_THREADS, B), S3_THREADS, 0, ctx->stream>>>(d_offsets, (int)M, d_X1, d_X2, d_sigma2, cam, H, chi2_gate,
+                                                                                      fix_scale != 0, seed, keys, models);
     SLAM_HIP(hipGetLastError());
     s3_ransac_result_kernel<<<(unsigned)B, S3_LANES, 0, ctx->stream>>>(d_offsets, (int)M, d_X1, d_X2, d_sigma2, cam, chi2_gate, fix_scale != 0, seed,
                                                                       keys, models, d_model, d_inlier, d_stats, slam_index_error_counter(ctx));
@@ -441,10 +435,8 @@ extern "C" int slam_sim3_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_o
 
 extern "C" int slam_sim3_refit_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_X1, const double* d_X2, int64_t M,
                                    const uint8_t* d_mask, int fix_scale, double* d_model, int32_t* d_stats) {
-    SLAM_REQUIRE(ctx, "slam_sim3_refit_f64: null ctx");
-    SLAM_REQUIRE(B >= 0 && B <= (1 << 24) && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld)", (long long)B, (long long)M);
-    if (B == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_offsets && d_model && d_stats && (M == 0 || (d_X1 && d_X2)), "slam_sim3_refit_f64: null device pointer");
+    GEO_CANDIDATE_SIZES(ctx, B, 1 << 24, M);
+    GEO_POINTERS(B, d_offsets && d_model && d_stats && (M == 0 || (d_X1 && d_X2)));
     SLAM_HIP(hipSetDevice(ctx->device));
     s3_refit_kernel<<<(unsigned)B, S3_REFIT_THREADS, 0, ctx->stream>>>(d_offsets, (int)M, d_X1, d_X2, d_mask, fix_scale != 0, d_model, d_stats,
                                                                      slam_index_error_counter(ctx));

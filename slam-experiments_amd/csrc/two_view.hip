@@ -803,13 +803,13 @@ __global__ void tv_triangulate_kernel(int N, const double* __restrict__ P1, cons
 }
 
 // =============================================================== entry points ================================================
+#include "geometry_host.h"           // the checks, the vote block and the launch shapes the four estimators' entry points share
+
 extern "C" int slam_tv_fivepoint_f64(slam_ctx* ctx, int64_t S, const double* d_x1, const double* d_x2, double* d_E, int32_t* d_nroots) {
-    SLAM_REQUIRE(ctx, "slam_tv_fivepoint_f64: null ctx");
-    SLAM_REQUIRE(S >= 0 && S <= (1 << 24), "S=%lld out of range [0, 2^24]", (long long)S);
-    if (S == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_x1 && d_x2 && d_E && d_nroots, "slam_tv_fivepoint_f64: null device pointer");
+    GEO_SAMPLE_SIZES(ctx, S);
+    GEO_POINTERS(S, d_x1 && d_x2 && d_E && d_nroots);
     SLAM_HIP(hipSetDevice(ctx->device));
-    tv_fivepoint_kernel<<<(unsigned)((S + TV_LANES - 1) / TV_LANES), TV_LANES, 0, ctx->stream>>>((int)S, d_x1, d_x2, d_E, d_nroots);
+    tv_fivepoint_kernel<<<geo_blocks(S, TV_LANES), TV_LANES, 0, ctx->stream>>>((int)S, d_x1, d_x2, d_E, d_nroots);
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }
@@ -817,30 +817,24 @@ extern "C" int slam_tv_fivepoint_f64(slam_ctx* ctx, int64_t S, const double* d_x
 extern "C" int slam_tv_essential_ransac_f64(slam_ctx* ctx, int64_t B, const int32_t* d_offsets, const double* d_px1, const double* d_px2,
                                             int64_t M, double fx, double fy, double cx, double cy, int H, double threshold_px, uint64_t seed,
                                             double* d_E, uint8_t* d_inlier, int32_t* d_stats) {
-    SLAM_REQUIRE(ctx, "slam_tv_essential_ransac_f64: null ctx");
-    SLAM_REQUIRE(B >= 0 && B <= 65535 && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld; B <= 65535)", (long long)B, (long long)M);
-    SLAM_REQUIRE(H >= 1 && H <= GEO_H_MAX, "H=%d out of range [1, 2^20]", H);
+    GEO_RANSAC_SIZES(ctx, B, M, H);
     SLAM_REQUIRE(threshold_px > 0.0 && fx > 0.0 && fy > 0.0, "threshold and focal lengths must be positive");
-    if (B == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_offsets && d_E && d_stats && (M == 0 || (d_px1 && d_px2 && d_inlier)), "slam_tv_essential_ransac_f64: null device pointer");
+    GEO_POINTERS(B, d_offsets && d_E && d_stats && (M == 0 || (d_px1 && d_px2 && d_inlier)));
     SLAM_REQUIRE((((uintptr_t)d_px1 | (uintptr_t)d_px2) & 15) == 0, "d_px1 / d_px2 must be 16-byte aligned");
     SLAM_HIP(hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> lk(ctx->call_mu);        // the workspace holds the normalised points, the keys and the model counts
-    const uint64_t xn_bytes = (uint64_t)(M > 0 ? M : 1) * 32, key_bytes = (uint64_t)B * 8;
+    const uint64_t xn_bytes = (uint64_t)(M > 0 ? M : 1) * 32;
     void* ws = nullptr;
-    if (int rc = slam_workspace(ctx, xn_bytes + key_bytes + (uint64_t)B * 4, &ws)) return rc;
+    if (int rc = slam_workspace(ctx, geo_vote_bytes(xn_bytes, B), &ws)) return rc;
     double4* xn = (double4*)ws;
-    unsigned long long* keys = (unsigned long long*)((char*)ws + xn_bytes);
-    int* models = (int*)((char*)ws + xn_bytes + key_bytes);
+    unsigned long long* keys; int* models;
+    if (int rc = geo_vote_block(ctx, ws, xn_bytes, B, false, M, d_inlier, &keys, &models)) return rc;    // tv_prepare_kernel clears them
     const geo_cam cam = {fx, fy, cx, cy};
     const double thr = threshold_px / ((fx + fy) / 2.0), thr2 = thr * thr;
-    const int64_t cover = M > B ? M : B;
-    tv_prepare_kernel<<<(unsigned)((cover + 255) / 256), 256, 0, ctx->stream>>>((int)M, (int)B, (const double2*)d_px1, (const double2*)d_px2,
-                                                                                cam, xn, keys, models);
+    tv_prepare_kernel<<<geo_blocks(M > B ? M : B, 256), 256, 0, ctx->stream>>>((int)M, (int)B, (const double2*)d_px1, (const double2*)d_px2, cam,
+                                                                               xn, keys, models);
     SLAM_HIP(hipGetLastError());
-    if (M > 0) SLAM_HIP(hipMemsetAsync(d_inlier, 0, (size_t)M, ctx->stream));
-    tv_ransac_kernel<<<dim3((unsigned)((H + TV_LANES - 1) / TV_LANES), (unsigned)B), TV_LANES, 0, ctx->stream>>>(d_offsets, (int)M, xn, H, thr2, seed,
-                                                                                                               keys, models);
+    tv_ransac_kernel<<<geo_vote_grid(H, TV_LANES, B), TV_LANES, 0, ctx->stream>>>(d_offsets, (int)M, xn, H, thr2, seed, keys, models);
     SLAM_HIP(hipGetLastError());
     tv_ransac_result_kernel<<<(unsigned)B, TV_LANES, 0, ctx->stream>>>(d_offsets, (int)M, xn, thr2, seed, keys, models, d_E, d_inlier, d_stats,
                                                                       slam_index_error_counter(ctx));
@@ -852,12 +846,9 @@ extern "C" int slam_tv_recover_pose_f64(slam_ctx* ctx, int64_t B, const int32_t*
                                         int64_t M, double fx, double fy, double cx, double cy, const double* d_E,
                                         const uint8_t* d_inlier_in, double distance_thresh, double* d_pose, uint8_t* d_inlier_out,
                                         int32_t* d_stats) {
-    SLAM_REQUIRE(ctx, "slam_tv_recover_pose_f64: null ctx");
-    SLAM_REQUIRE(B >= 0 && B <= (1 << 20) && M >= 0 && M <= (1 << 28), "bad sizes (B=%lld, M=%lld)", (long long)B, (long long)M);
+    GEO_CANDIDATE_SIZES(ctx, B, 1 << 20, M);
     SLAM_REQUIRE(fx > 0.0 && fy > 0.0 && distance_thresh > 0.0, "focal lengths and distance_thresh must be positive");
-    if (B == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_offsets && d_E && d_pose && d_stats && (M == 0 || (d_px1 && d_px2 && d_inlier_out)),
-                 "slam_tv_recover_pose_f64: null device pointer");
+    GEO_POINTERS(B, d_offsets && d_E && d_pose && d_stats && (M == 0 || (d_px1 && d_px2 && d_inlier_out)));
     SLAM_REQUIRE((((uintptr_t)d_px1 | (uintptr_t)d_px2) & 15) == 0, "d_px1 / d_px2 must be 16-byte aligned");
     SLAM_HIP(hipSetDevice(ctx->device));
     const geo_cam cam = {fx, fy, cx, cy};
@@ -873,12 +864,11 @@ extern "C" int slam_tv_triangulate_f64(slam_ctx* ctx, int64_t N, const double* d
                                        const double* d_x2, double* d_X, double* d_w) {
     SLAM_REQUIRE(ctx, "slam_tv_triangulate_f64: null ctx");
     SLAM_REQUIRE(N >= 0 && N <= (1 << 28), "N=%lld out of range [0, 2^28]", (long long)N);
-    if (N == 0) return SLAM_OK;
-    SLAM_REQUIRE(d_P1 && d_P2 && d_x1 && d_x2 && d_X && d_w, "slam_tv_triangulate_f64: null device pointer");
+    GEO_POINTERS(N, d_P1 && d_P2 && d_x1 && d_x2 && d_X && d_w);
     SLAM_REQUIRE((((uintptr_t)d_x1 | (uintptr_t)d_x2) & 15) == 0, "d_x1 / d_x2 must be 16-byte aligned");
     SLAM_HIP(hipSetDevice(ctx->device));
-    tv_triangulate_kernel<<<(unsigned)((N + 255) / 256), 256, 0, ctx->stream>>>((int)N, d_P1, d_P2, (const double2*)d_x1, (const double2*)d_x2,
-                                                                                d_X, d_w);
+    tv_triangulate_kernel<<<geo_blocks(N, 256), 256, 0, ctx->stream>>>((int)N, d_P1, d_P2, (const double2*)d_x1, (const double2*)d_x2, d_X,
+                                                                       d_w);
     SLAM_HIP(hipGetLastError());
     return SLAM_OK;
 }

@@ -19,9 +19,11 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._args import _Buffers
+from ._geometry import (MAX_PAIRS, MAX_TOTAL, _cand_offsets, _check_cap, _check_ransac_args, _concat_flags, _flags, _intrinsics, _mask_down,
+                        _pair, _pair_arrays, _solve_samples, _split_mask, _Vote)
 from ._lib import check
 from .device import Context, default_context
-from .two_view import DEFAULT_DISTANCE, DEFAULT_HYPOTHESES, MAX_PAIRS, _check_ransac_args, _intrinsics, _pair_arrays, _points
+from .two_view import DEFAULT_DISTANCE, DEFAULT_HYPOTHESES
 from .two_view import DEFAULT_THRESHOLD as DEFAULT_THRESHOLD_E
 
 DEFAULT_THRESHOLD_H = 3.0       # pixels: cv2.findHomography's default, and the value in the reference's comment
@@ -32,19 +34,13 @@ ROTATION_ONLY = -2              # stats[1] of the decomposition when H is a rota
 NO_MODEL = -1
 
 
-def _offsets(offsets, px1, px2):
-    px1, px2 = _points(px1, "px1"), _points(px2, "px2")
-    if len(px1) != len(px2):
-        raise ValueError(f"{len(px1)} points in frame 1 but {len(px2)} in frame 2")
-    offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
-    B, M = len(offsets) - 1, len(px1)
-    if B < 0:
-        raise ValueError("offsets must have B + 1 entries")
-    if B > MAX_PAIRS:
-        raise ValueError(f"at most {MAX_PAIRS} pairs per call")
-    if M >= 1 << 28:
+def _matches(px1, px2, offsets):
+    """The checked matches of an offsets call: (px1 [M,2], px2 [M,2], int32 offsets [B + 1], B, M)."""
+    px1, px2 = _pair(px1, px2, "px1", "px2", 2)
+    offsets, B = _cand_offsets(offsets, MAX_PAIRS, "pairs")
+    if len(px1) >= MAX_TOTAL:
         raise ValueError("more than 2^28 matches in one call")
-    return px1, px2, offsets, B, M
+    return px1, px2, offsets, B, len(px1)
 
 
 def _matrices(A, B, name):
@@ -71,15 +67,8 @@ def fourpoint_homography_arrays(p1, p2, ctx: Optional[Context] = None):
     S = p1.shape[0]
     if S == 0:
         return np.zeros((0, 3, 3)), np.zeros(0, bool)
-    ctx = ctx or default_context()
-    m = _Buffers(ctx)
-    try:
-        d1, d2 = m.up(p1), m.up(p2)
-        dH, dk = m.new(S * 72), m.new(S * 4)
-        check(ctx.lib.slam_hg_fourpoint_f64(ctx.handle, S, d1.ptr, d2.ptr, dH.ptr, dk.ptr))
-        return dH.download(np.float64, (S, 3, 3)), dk.download(np.int32, (S,)).astype(bool)
-    finally:
-        m.free()
+    H, ok = _solve_samples(ctx, "slam_hg_fourpoint_f64", p1, p2, (3, 3))
+    return H, ok.astype(bool)
 
 
 def find_homography_offsets(px1, px2, offsets, hypotheses: int = DEFAULT_HYPOTHESES, threshold: float = DEFAULT_THRESHOLD_H,
@@ -87,18 +76,13 @@ def find_homography_offsets(px1, px2, offsets, hypotheses: int = DEFAULT_HYPOTHE
     """``slam_hg_ransac_f64`` on concatenated matches: pair b owns ``[offsets[b], offsets[b+1])``.
     Returns (H [B,9], inlier bool [M], stats int32 [B,4])."""
     H, thr, seed = _check_ransac_args(hypotheses, threshold, seed)
-    px1, px2, offsets, B, M = _offsets(offsets, px1, px2)
+    px1, px2, offsets, B, M = _matches(px1, px2, offsets)
     if B == 0:
         return np.zeros((0, 9)), np.zeros(M, bool), np.zeros((0, 4), np.int32)
     ctx = ctx or default_context()
     m = _Buffers(ctx)
     try:
-        d1, d2, do = m.up(px1), m.up(px2), m.up(offsets)
-        dH, dm, ds = m.new(B * 72), m.new(M), m.new(B * 16)
-        check(ctx.lib.slam_hg_ransac_f64(ctx.handle, B, do.ptr, d1.ptr, d2.ptr, M, H, thr, seed, dH.ptr, dm.ptr, ds.ptr))
-        Hm, st = dH.download(np.float64, (B, 9)), ds.download(np.int32, (B, 4))
-        mask = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
-        return Hm, mask, st
+        return _Vote(m, ctx.lib.slam_hg_ransac_f64, (px1, px2), offsets, (H, thr, seed), 9).download()
     finally:
         m.free()
 
@@ -109,7 +93,7 @@ def find_homography_batch(pairs: Sequence, hypotheses: int = DEFAULT_HYPOTHESES,
     (H [B,3,3], list of bool masks, stats [B,4])."""
     px1, px2, off = _pair_arrays(pairs)
     H, mask, st = find_homography_offsets(px1, px2, off, hypotheses, threshold, seed, ctx)
-    return H.reshape(-1, 3, 3), [mask[off[b]:off[b + 1]].copy() for b in range(len(off) - 1)], st
+    return H.reshape(-1, 3, 3), _split_mask(mask, off), st
 
 
 def find_homography_arrays(px1, px2, hypotheses: int = DEFAULT_HYPOTHESES, threshold: float = DEFAULT_THRESHOLD_H, seed: int = 0,
@@ -127,12 +111,9 @@ def decompose_homography_offsets(H, px1, px2, offsets, K, inlier=None, distance_
     model), second-best count, number of candidates}."""
     fx, fy, cx, cy = _intrinsics(K)
     dist = _positive(distance_thresh, "distance_thresh")
-    px1, px2, offsets, B, M = _offsets(offsets, px1, px2)
+    px1, px2, offsets, B, M = _matches(px1, px2, offsets)
     H = _matrices(H, B, "H")
-    if inlier is not None:
-        inlier = np.ascontiguousarray(inlier).astype(np.uint8).reshape(-1)
-        if len(inlier) != M:
-            raise ValueError("one inlier flag per match")
+    inlier = _flags(inlier, M)
     if B == 0:
         return dict(pose_all=np.zeros((0, 4, 3, 4)), normal_all=np.zeros((0, 4, 3)), count=np.zeros((0, 4), np.int32),
                     pose=np.zeros((0, 3, 4)), sv=np.zeros((0, 3)), good=np.zeros(M, bool), stats=np.zeros((0, 4), np.int32))
@@ -147,7 +128,7 @@ def decompose_homography_offsets(H, px1, px2, offsets, K, inlier=None, distance_
                                             ds.ptr))
         return dict(pose_all=dpa.download(np.float64, (B, 4, 3, 4)), normal_all=dna.download(np.float64, (B, 4, 3)),
                     count=dc.download(np.int32, (B, 4)), pose=dp.download(np.float64, (B, 3, 4)), sv=dsv.download(np.float64, (B, 3)),
-                    good=dg.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool), stats=ds.download(np.int32, (B, 4)))
+                    good=_mask_down(dg, M), stats=ds.download(np.int32, (B, 4)))
     finally:
         m.free()
 
@@ -157,13 +138,8 @@ def decompose_homography_batch(H, pairs: Sequence, K, inliers=None, distance_thr
     """``cv2.decomposeHomographyMat`` and the cheirality vote for a list of pairs: the dict of
     ``decompose_homography_offsets`` with ``good`` as a list of bool masks."""
     px1, px2, off = _pair_arrays(pairs)
-    inl = None
-    if inliers is not None:
-        if len(inliers) != len(off) - 1:
-            raise ValueError("one inlier mask per pair")
-        inl = np.concatenate([np.asarray(v).astype(np.uint8).reshape(-1) for v in inliers]) if len(inliers) else np.zeros(0, np.uint8)
-    out = decompose_homography_offsets(H, px1, px2, off, K, inl, distance_thresh, ctx)
-    out["good"] = [out["good"][off[b]:off[b + 1]].copy() for b in range(len(off) - 1)]
+    out = decompose_homography_offsets(H, px1, px2, off, K, _concat_flags(inliers, len(off) - 1), distance_thresh, ctx)
+    out["good"] = _split_mask(out["good"], off)
     return out
 
 
@@ -180,7 +156,7 @@ def model_scores_offsets(H, E, px1, px2, offsets, K, sigma: float = DEFAULT_SIGM
     sigma = _positive(sigma, "sigma")
     if not (0.0 < sigma * sigma < 1e200):
         raise ValueError("sigma squared must be a positive finite double")
-    px1, px2, offsets, B, M = _offsets(offsets, px1, px2)
+    px1, px2, offsets, B, M = _matches(px1, px2, offsets)
     H, E = _matrices(H, B, "H"), _matrices(E, B, "E")
     if B == 0:
         return np.zeros((0, 2), np.int64), np.zeros(0)
@@ -212,8 +188,7 @@ def verify_pairs_auto(pairs: Sequence, K, hypotheses: int = DEFAULT_HYPOTHESES, 
         raise ValueError("ambiguity must be in (0, 1]")
     px1, px2, off = _pair_arrays(pairs)
     B, M = len(off) - 1, len(px1)
-    if B > MAX_PAIRS:
-        raise ValueError(f"at most {MAX_PAIRS} pairs per call")
+    _check_cap(B, MAX_PAIRS, "pairs")
     if B == 0:
         return []
     ctx = ctx or default_context()
@@ -238,8 +213,7 @@ def verify_pairs_auto(pairs: Sequence, K, hypotheses: int = DEFAULT_HYPOTHESES, 
         score, rat = dsc.download(np.int64, (B, 2)), dr.download(np.float64, (B,))
         pa, na, cnt = dpa.download(np.float64, (B, 4, 3, 4)), dna.download(np.float64, (B, 4, 3)), dc.download(np.int32, (B, 4))
         ph, pe, sv = dph.download(np.float64, (B, 3, 4)), dpe.download(np.float64, (B, 3, 4)), dsv.download(np.float64, (B, 3))
-        me = dme.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
-        mh = dmh.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
+        me, mh = _mask_down(dme, M), _mask_down(dmh, M)
     finally:
         m.free()
     out = []

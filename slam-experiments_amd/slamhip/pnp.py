@@ -18,43 +18,21 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._args import _Buffers
+from ._geometry import (MAX_PAIRS, _cand_offsets, _check_cap, _check_edge_args, _check_ransac_args, _concat, _edge_info, _edge_pairs,
+                        _intrinsics, _points, _solve_samples, _split_mask, _Vote)
 from ._lib import check
 from .device import Context, default_context
 from .pose_opt import CHI2_THRESHOLD, HUBER_DELTA
-from .two_view import MAX_PAIRS, _check_ransac_args, _intrinsics, _points
 
 DEFAULT_HYPOTHESES = 256        # as the essential-matrix RANSAC; ln(0.001) / ln(1 - 0.5**3) = 52 would do at 50 % inliers
 DEFAULT_THRESHOLD = 8.0         # pixels, cv2.solvePnPRansac's reprojectionError default
 REFINE_ROUNDS, REFINE_ITERATIONS = 4, 10        # Frontend._correct_current_pose (frontend.py:298-393)
 
 
-def _points3(a, name: str) -> np.ndarray:
-    try:
-        a = np.asarray(a, np.float64)
-    except (TypeError, ValueError) as exc:
-        raise TypeError(f"{name} must be numeric") from exc
-    if a.size == 0:
-        return np.zeros((0, 3))
-    if a.ndim != 2 or a.shape[1] != 3:
-        raise ValueError(f"{name} must have shape [N,3], got {a.shape}")
-    return np.ascontiguousarray(a)
-
-
-def _cand_arrays(cands):
-    Xs, ps, off = [], [], [0]
-    for i, c in enumerate(cands):
-        if len(c) != 2:
-            raise ValueError(f"candidate {i}: expected (points, px)")
-        X, p = _points3(c[0], f"candidate {i} points"), _points(c[1], f"candidate {i} px")
-        if len(X) != len(p):
-            raise ValueError(f"candidate {i}: {len(X)} points but {len(p)} pixels")
-        Xs.append(X)
-        ps.append(p)
-        off.append(off[-1] + len(X))
-    if off[-1] >= 1 << 28:
-        raise ValueError("more than 2^28 correspondences in one call")
-    return (np.concatenate(Xs) if Xs else np.zeros((0, 3)), np.concatenate(ps) if ps else np.zeros((0, 2)),
-            np.asarray(off, np.int32))
+def _ransac(m: _Buffers, X, px, off, K, hypotheses, threshold, seed) -> _Vote:
+    """``slam_pnp_ransac_f64`` on checked arrays, under the caller's buffers (the refinement starts from the poses on the device)."""
+    fx, fy, cx, cy = K
+    return _Vote(m, m.ctx.lib.slam_pnp_ransac_f64, (X, px), off, (fx, fy, cx, cy, hypotheses, threshold, seed), 12)
 
 
 def p3p_arrays(X, x, ctx: Optional[Context] = None):
@@ -67,43 +45,24 @@ def p3p_arrays(X, x, ctx: Optional[Context] = None):
     S = X.shape[0]
     if S == 0:
         return np.zeros((0, 4, 3, 4)), np.zeros(0, np.int32)
-    ctx = ctx or default_context()
-    m = _Buffers(ctx)
-    try:
-        dX, dx = m.up(X), m.up(x)
-        dp, dn = m.new(S * 384), m.new(S * 4)
-        check(ctx.lib.slam_pnp_p3p_f64(ctx.handle, S, dX.ptr, dx.ptr, dp.ptr, dn.ptr))
-        return dp.download(np.float64, (S, 4, 3, 4)), dn.download(np.int32, (S,))
-    finally:
-        m.free()
+    return _solve_samples(ctx, "slam_pnp_p3p_f64", X, x, (4, 3, 4))
 
 
 def solve_pnp_ransac_offsets(points, px, offsets, K, hypotheses: int = DEFAULT_HYPOTHESES, threshold: float = DEFAULT_THRESHOLD,
                              seed: int = 0, ctx: Optional[Context] = None):
     """``slam_pnp_ransac_f64`` on concatenated correspondences: candidate b owns ``[offsets[b], offsets[b+1])``.
     Returns (pose [B,3,4], inlier bool [M], stats int32 [B,4])."""
-    fx, fy, cx, cy = _intrinsics(K)
+    K = _intrinsics(K)
     H, thr, seed = _check_ransac_args(hypotheses, threshold, seed)
-    points, px = _points3(points, "points"), _points(px, "px")
+    points, px = _points(points, "points", 3), _points(px, "px")
     if len(points) != len(px):
         raise ValueError(f"{len(points)} points but {len(px)} pixels")
-    offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
-    B, M = len(offsets) - 1, len(points)
-    if B < 0:
-        raise ValueError("offsets must have B + 1 entries")
-    if B > MAX_PAIRS:
-        raise ValueError(f"at most {MAX_PAIRS} candidates per call")
+    offsets, B = _cand_offsets(offsets, MAX_PAIRS, "candidates")
     if B == 0:
-        return np.zeros((0, 3, 4)), np.zeros(M, bool), np.zeros((0, 4), np.int32)
-    ctx = ctx or default_context()
-    m = _Buffers(ctx)
+        return np.zeros((0, 3, 4)), np.zeros(len(points), bool), np.zeros((0, 4), np.int32)
+    m = _Buffers(ctx or default_context())
     try:
-        dX, dp, do = m.up(points), m.up(px), m.up(offsets)
-        dT, dm, ds = m.new(B * 96), m.new(M), m.new(B * 16)
-        check(ctx.lib.slam_pnp_ransac_f64(ctx.handle, B, do.ptr, dX.ptr, dp.ptr, M, fx, fy, cx, cy, H, thr, seed, dT.ptr, dm.ptr, ds.ptr))
-        pose, st = dT.download(np.float64, (B, 3, 4)), ds.download(np.int32, (B, 4))
-        mask = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
-        return pose, mask, st
+        return _ransac(m, points, px, offsets, K, H, thr, seed).download(3, 4)
     finally:
         m.free()
 
@@ -121,20 +80,16 @@ def solve_pnp_ransac_batch(cands: Sequence, K, hypotheses: int = DEFAULT_HYPOTHE
     {0, -1, -1, 0} and is not refined."""
     fx, fy, cx, cy = _intrinsics(K)
     H, thr, seed = _check_ransac_args(hypotheses, threshold, seed)
-    X, px, off = _cand_arrays(cands)
-    B, M = len(off) - 1, len(X)
-    if B > MAX_PAIRS:
-        raise ValueError(f"at most {MAX_PAIRS} candidates per call")
+    X, px, off = _concat(cands, "candidate", (("points", 3), ("px", 2)), "correspondences", "{} points but {} pixels")
+    B = len(off) - 1
+    _check_cap(B, MAX_PAIRS, "candidates")
     if B == 0:
         return np.zeros((0, 3, 4)), [], np.zeros(0, np.int64), np.zeros((0, 4), np.int32), (np.zeros(0, np.int64) if refine else None)
     ctx = ctx or default_context()
     m = _Buffers(ctx)
     try:
-        dX, dp, do = m.up(X), m.up(px), m.up(off)
-        dT, dm, ds = m.new(B * 96), m.new(M), m.new(B * 16)
-        check(ctx.lib.slam_pnp_ransac_f64(ctx.handle, B, do.ptr, dX.ptr, dp.ptr, M, fx, fy, cx, cy, H, thr, seed, dT.ptr, dm.ptr, ds.ptr))
-        pose, st = dT.download(np.float64, (B, 3, 4)), ds.download(np.int32, (B, 4))
-        mask = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
+        vote = _ransac(m, X, px, off, (fx, fy, cx, cy), H, thr, seed)
+        pose, mask, st = vote.download(3, 4)
         refined = None
         if refine:
             # the optimiser takes whole slices: the inliers are packed on the host (the vote has to come down anyway) and
@@ -146,7 +101,7 @@ def solve_pnp_ransac_batch(cands: Sequence, K, hypotheses: int = DEFAULT_HYPOTHE
             if O:
                 dX2, dp2, do2 = m.up(np.ascontiguousarray(X[keep])), m.up(np.ascontiguousarray(px[keep])), m.up(off2)
                 dT2, di2, dc2, ds2 = m.new(B * 96), m.new(O), m.new(O * 8), m.new(B * 8)
-                check(ctx.lib.slam_pose_optimize_batch_f64(ctx.handle, B, dT.ptr, dX2.ptr, dp2.ptr, do2.ptr, O, fx, fy, cx, cy,
+                check(ctx.lib.slam_pose_optimize_batch_f64(ctx.handle, B, vote.model.ptr, dX2.ptr, dp2.ptr, do2.ptr, O, fx, fy, cx, cy,
                                                            REFINE_ROUNDS, REFINE_ITERATIONS, CHI2_THRESHOLD, HUBER_DELTA,
                                                            dT2.ptr, di2.ptr, dc2.ptr, ds2.ptr))
                 out, rs = dT2.download(np.float64, (B, 3, 4)), ds2.download(np.int32, (B, 2))
@@ -155,7 +110,7 @@ def solve_pnp_ransac_batch(cands: Sequence, K, hypotheses: int = DEFAULT_HYPOTHE
                 refined[has] = rs[has, 0]
     finally:
         m.free()
-    return pose, [mask[off[b]:off[b + 1]].copy() for b in range(B)], st[:, 0].astype(np.int64), st, refined
+    return pose, _split_mask(mask, off), st[:, 0].astype(np.int64), st, refined
 
 
 def solve_pnp_ransac(points, px, K, hypotheses: int = DEFAULT_HYPOTHESES, threshold: float = DEFAULT_THRESHOLD, seed: int = 0,
@@ -187,19 +142,14 @@ def loop_edges_from_pnp(pairs, poses, inlier_counts, map_poses, min_inliers: int
     The measurement is the relative pose ``T_j T_i^-1`` (``X_j = R X_i + t``), what ``optimize_pose_graph`` expects.  The
     pose is in map scale, so BOTH blocks of the information are set: ``inliers / min_inliers / sigma^2`` times the
     identity, with the rotation and the translation sigma."""
-    pairs = np.asarray(pairs)
-    if pairs.size == 0:
-        pairs = np.zeros((0, 2), np.int64)
-    if pairs.dtype.kind not in "iu" or pairs.ndim != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"pairs must be integers of shape [B,2], got {pairs.dtype} {pairs.shape}")
+    pairs = _edge_pairs(pairs)
     B = len(pairs)
     T = _pose44(poses, "poses") if B else np.zeros((0, 4, 4))
     Tm = _pose44(map_poses, "map_poses")
     n = np.asarray(inlier_counts).reshape(-1)
     if not (len(T) == len(n) == B):
         raise ValueError(f"{B} pairs but {len(T)} poses and {len(n)} inlier counts")
-    if min_inliers < 1 or rotation_sigma <= 0 or translation_sigma <= 0:
-        raise ValueError("min_inliers >= 1 and positive sigmas")
+    _check_edge_args(min_inliers, rotation_sigma, translation_sigma)
     if B and (pairs.min() < 0 or pairs.max() >= len(Tm)):
         raise ValueError(f"pair index outside the {len(Tm)} map poses")
     k = np.flatnonzero((n >= min_inliers) & (pairs[:, 0] != pairs[:, 1]))
@@ -210,9 +160,4 @@ def loop_edges_from_pnp(pairs, poses, inlier_counts, map_poses, min_inliers: int
         inv[:3, :3] = Ti[:3, :3].T
         inv[:3, 3] = -Ti[:3, :3].T @ Ti[:3, 3]
         meas[e] = (T[b] @ inv)[:3]
-    info = np.zeros((len(k), 6, 6))
-    w = n[k] / float(min_inliers)
-    for a in range(3):
-        info[:, a, a] = w / rotation_sigma ** 2
-        info[:, 3 + a, 3 + a] = w / translation_sigma ** 2
-    return np.ascontiguousarray(pairs[k], np.int32), meas, info
+    return np.ascontiguousarray(pairs[k], np.int32), meas, _edge_info(n[k] / float(min_inliers), rotation_sigma, translation_sigma)

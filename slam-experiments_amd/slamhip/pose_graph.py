@@ -25,6 +25,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from ._geometry import _check_edge_args, _edge_info, _edge_pairs
 from ._lib import addr, check
 from .device import Context, default_context
 
@@ -286,19 +287,14 @@ def loop_edges_from_two_view(pairs, R, t, inlier_counts, min_inliers: int = 20, 
     translation has unit length - its scale is unknown - so the translation block is ZERO unless ``scale`` (a number or one
     per pair: the metric length of each translation) is given; then ``t`` is multiplied by it and the block is
     ``1 / translation_sigma^2``.  With zero translation information an edge constrains the relative rotation only."""
-    pairs = np.asarray(pairs)
-    if pairs.size == 0:
-        pairs = np.zeros((0, 2), np.int64)
-    if pairs.dtype.kind not in "iu" or pairs.ndim != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"pairs must be integers of shape [B,2], got {pairs.dtype} {pairs.shape}")
+    pairs = _edge_pairs(pairs)
     B = len(pairs)
     R = np.asarray(R, np.float64).reshape(-1, 3, 3)
     t = np.asarray(t, np.float64).reshape(-1, 3)
     n = np.asarray(inlier_counts).reshape(-1)
     if not (len(R) == len(t) == len(n) == B):
         raise ValueError(f"{B} pairs but {len(R)} rotations, {len(t)} translations, {len(n)} inlier counts")
-    if min_inliers < 1 or rotation_sigma <= 0 or translation_sigma <= 0:
-        raise ValueError("min_inliers >= 1 and positive sigmas")
+    _check_edge_args(min_inliers, rotation_sigma, translation_sigma)
     s = None
     if scale is not None:
         s = np.broadcast_to(np.asarray(scale, np.float64), (B,))
@@ -309,12 +305,9 @@ def loop_edges_from_two_view(pairs, R, t, inlier_counts, min_inliers: int = 20, 
     meas = np.zeros((len(k), 3, 4))
     meas[:, :, :3] = R[k]
     meas[:, :, 3] = t[k] * (s[k, None] if s is not None else 1.0)
-    info = np.zeros((len(k), 6, 6))
-    wr = n[k] / float(min_inliers) / rotation_sigma ** 2
-    for a in range(3):
-        info[:, a, a] = wr
-        if s is not None:
-            info[:, 3 + a, 3 + a] = 1.0 / translation_sigma ** 2
+    info = _edge_info(n[k] / float(min_inliers), rotation_sigma, None)
+    if s is not None:                                   # the one block that is not weighted by the inliers
+        info[:, [3, 4, 5], [3, 4, 5]] = 1.0 / translation_sigma ** 2
     return np.ascontiguousarray(pairs[k], np.int32), meas, info
 
 

@@ -18,53 +18,19 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._args import _Buffers
+from ._geometry import (MAX_PAIRS, _cand_offsets, _check_ransac_args, _concat, _edge_info, _edge_pairs, _intrinsics, _model_srt,
+                        _pair, _rows, _solve_samples, _split_mask, _Vote)
 from ._lib import check
 from .device import Context, default_context
-from .pnp import _points3
-from .two_view import MAX_PAIRS, _check_ransac_args, _intrinsics
 
 DEFAULT_HYPOTHESES = 256        # as the other RANSAC calls; ORB-SLAM's Sim3Solver: at most 300 iterations
 DEFAULT_CHI2_GATE = 9.210       # chi-square of 2 degrees of freedom at 99 %, ORB-SLAM's Sim3Solver
 DEFAULT_MAX_LOG_SCALE = 0.05    # |log s| an SE(3) edge may hide: 5 % of scale, about the noise of a 20-inlier scale estimate
 
 
-def _split(model: np.ndarray):
-    """(s [B], R [B,3,3], t [B,3]) of models [B,13]."""
-    T = model[:, :12].reshape(-1, 3, 4)
-    return model[:, 12].copy(), np.ascontiguousarray(T[:, :, :3]), np.ascontiguousarray(T[:, :, 3])
-
-
-def _sigma2(sigma2, M: int):
-    if sigma2 is None:
-        return None
-    try:
-        a = np.asarray(sigma2, np.float64)
-    except (TypeError, ValueError) as exc:
-        raise TypeError("sigma2 must be numeric") from exc
-    if a.size == 0 and M == 0:
-        return np.zeros((0, 2))
-    if a.ndim != 2 or a.shape != (M, 2):
-        raise ValueError(f"sigma2 must have shape [{M},2], got {a.shape}")
-    return np.ascontiguousarray(a)
-
-
-def _offsets(offsets, cap: int):
-    offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
-    B = len(offsets) - 1
-    if B < 0:
-        raise ValueError("offsets must have B + 1 entries")
-    if B > cap:
-        raise ValueError(f"at most {cap} candidates per call")
-    return offsets, B
-
-
-def _pair(X1, X2):
-    X1, X2 = _points3(X1, "X1"), _points3(X2, "X2")
-    if len(X1) != len(X2):
-        raise ValueError(f"{len(X1)} points in frame 1 but {len(X2)} in frame 2")
-    if len(X1) >= 1 << 28:
-        raise ValueError("more than 2^28 correspondences in one call")
-    return X1, X2
+def _points_pair(X1, X2):
+    """The two point sets of a call, f64 [M,3] each."""
+    return _pair(X1, X2, "X1", "X2", 3, "correspondences")
 
 
 def sim3_threepoint_arrays(X1, X2, fix_scale: bool = False, ctx: Optional[Context] = None):
@@ -77,15 +43,8 @@ def sim3_threepoint_arrays(X1, X2, fix_scale: bool = False, ctx: Optional[Contex
     S = X1.shape[0]
     if S == 0:
         return np.zeros(0), np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros(0, np.int32)
-    ctx = ctx or default_context()
-    m = _Buffers(ctx)
-    try:
-        d1, d2 = m.up(X1), m.up(X2)
-        dm, do = m.new(S * 104), m.new(S * 4)
-        check(ctx.lib.slam_sim3_threepoint_f64(ctx.handle, S, d1.ptr, d2.ptr, int(bool(fix_scale)), dm.ptr, do.ptr))
-        return _split(dm.download(np.float64, (S, 13))) + (do.download(np.int32, (S,)),)
-    finally:
-        m.free()
+    model, ok = _solve_samples(ctx, "slam_sim3_threepoint_f64", X1, X2, (13,), int(bool(fix_scale)))
+    return _model_srt(model) + (ok,)
 
 
 def estimate_sim3_offsets(X1, X2, offsets, K, hypotheses: int = DEFAULT_HYPOTHESES, chi2_gate: float = DEFAULT_CHI2_GATE,
@@ -101,35 +60,31 @@ def estimate_sim3_offsets(X1, X2, offsets, K, hypotheses: int = DEFAULT_HYPOTHES
     gave a model, comes back with the identity, s = 1, an empty vote and stats {0, -1, -1, 0}."""
     fx, fy, cx, cy = _intrinsics(K)
     H, gate, seed = _check_ransac_args(hypotheses, chi2_gate, seed)
-    X1, X2 = _pair(X1, X2)
+    X1, X2 = _points_pair(X1, X2)
     M = len(X1)
-    sg = _sigma2(sigma2, M)
-    offsets, B = _offsets(offsets, MAX_PAIRS)
+    sg = None if sigma2 is None else _rows(sigma2, M, "sigma2")
+    offsets, B = _cand_offsets(offsets, MAX_PAIRS, "candidates")
     if B == 0:
         return (np.zeros(0), np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros(M, bool), np.zeros((0, 4), np.int32),
                 np.zeros((0, 2), np.int32) if refit else None)
     ctx = ctx or default_context()
     m = _Buffers(ctx)
     try:
-        d1, d2, do = m.up(X1), m.up(X2), m.up(offsets)
-        dsg = m.up(sg) if sg is not None else None
-        dT, dm, ds = m.new(B * 104), m.new(M), m.new(B * 16)
         fix = int(bool(fix_scale))
-        check(ctx.lib.slam_sim3_ransac_f64(ctx.handle, B, do.ptr, d1.ptr, d2.ptr, M, dsg.ptr if dsg is not None else None, fx, fy, cx, cy, H,
-                                           gate, fix, seed, dT.ptr, dm.ptr, ds.ptr))
+        vote = _Vote(m, ctx.lib.slam_sim3_ransac_f64, (X1, X2), offsets, (fx, fy, cx, cy, H, gate, fix, seed), 13, tail=(sg,))
         rs = None
-        if refit:
+        if refit:                                       # on the mask still on the device
             dT2, ds2 = m.new(B * 104), m.new(B * 8)
-            check(ctx.lib.slam_sim3_refit_f64(ctx.handle, B, do.ptr, d1.ptr, d2.ptr, M, dm.ptr, fix, dT2.ptr, ds2.ptr))
-        model, st = dT.download(np.float64, (B, 13)), ds.download(np.int32, (B, 4))
-        mask = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
+            check(ctx.lib.slam_sim3_refit_f64(ctx.handle, B, vote.offsets.ptr, vote.arrays[0].ptr, vote.arrays[1].ptr, M, vote.mask.ptr, fix,
+                                              dT2.ptr, ds2.ptr))
+        model, mask, st = vote.download()
         if refit:
             fit, rs = dT2.download(np.float64, (B, 13)), ds2.download(np.int32, (B, 2))
             use = (st[:, 1] >= 0) & (rs[:, 1] != 0)
             model[use] = fit[use]
     finally:
         m.free()
-    return _split(model) + (mask, st, rs)
+    return _model_srt(model) + (mask, st, rs)
 
 
 def estimate_sim3_batch(cands: Sequence, K, hypotheses: int = DEFAULT_HYPOTHESES, chi2_gate: float = DEFAULT_CHI2_GATE,
@@ -137,28 +92,16 @@ def estimate_sim3_batch(cands: Sequence, K, hypotheses: int = DEFAULT_HYPOTHESES
     """ORB-SLAM's ``Sim3Solver`` for a list of ``(X1 [N_b,3], X2 [N_b,3])`` or ``(X1, X2, sigma2 [N_b,2])`` candidates in
     one call: (s [B], R [B,3,3], t [B,3], list of bool masks, stats int32 [B,4], refit stats or None), as
     ``estimate_sim3_offsets``."""
-    A, Bs, S, off, any_sigma = [], [], [], [0], False
-    for i, c in enumerate(cands):
-        if len(c) not in (2, 3):
-            raise ValueError(f"candidate {i}: expected (X1, X2) or (X1, X2, sigma2)")
-        a, b = _points3(c[0], f"candidate {i} X1"), _points3(c[1], f"candidate {i} X2")
-        if len(a) != len(b):
-            raise ValueError(f"candidate {i}: {len(a)} points in frame 1 but {len(b)} in frame 2")
-        sg = np.ones((len(a), 2)) if len(c) == 2 or c[2] is None else _sigma2(c[2], len(a))
-        any_sigma = any_sigma or (len(c) == 3 and c[2] is not None)
-        A.append(a); Bs.append(b); S.append(sg)
-        off.append(off[-1] + len(a))
-    cat = (lambda v, w: np.concatenate(v) if v else np.zeros((0, w)))
-    s, R, t, mask, st, rs = estimate_sim3_offsets(cat(A, 3), cat(Bs, 3), np.asarray(off, np.int64), K, hypotheses, chi2_gate,
-                                                  cat(S, 2) if any_sigma else None, fix_scale, seed, refit, ctx)
-    return s, R, t, [mask[off[b]:off[b + 1]].copy() for b in range(len(off) - 1)], st, rs
+    X1, X2, sg, off = _concat(cands, "candidate", (("X1", 3), ("X2", 3)), "correspondences", sigma2=True)
+    s, R, t, mask, st, rs = estimate_sim3_offsets(X1, X2, off, K, hypotheses, chi2_gate, sg, fix_scale, seed, refit, ctx)
+    return s, R, t, _split_mask(mask, off), st, rs
 
 
 def estimate_sim3(X1, X2, K, hypotheses: int = DEFAULT_HYPOTHESES, chi2_gate: float = DEFAULT_CHI2_GATE, sigma2=None,
                   fix_scale: bool = False, seed: int = 0, refit: bool = True, ctx: Optional[Context] = None):
     """One candidate: (ok, s, R [3,3], t [3], inlier mask bool [N]); ``ok`` is False (identity, s = 1, empty vote) when
     there are fewer than 3 correspondences or no hypothesis gave a model."""
-    X1, X2 = _pair(X1, X2)
+    X1, X2 = _points_pair(X1, X2)
     s, R, t, mask, st, _ = estimate_sim3_offsets(X1, X2, [0, len(X1)], K, hypotheses, chi2_gate, sigma2, fix_scale, seed, refit, ctx)
     return bool(st[0, 1] >= 0), float(s[0]), R[0], t[0], mask
 
@@ -166,9 +109,9 @@ def estimate_sim3(X1, X2, K, hypotheses: int = DEFAULT_HYPOTHESES, chi2_gate: fl
 def fit_sim3_offsets(X1, X2, offsets, mask=None, fix_scale: bool = False, ctx: Optional[Context] = None):
     """``slam_sim3_refit_f64``: the least-squares similarity of every candidate's selected correspondences ->
     (s [B], R [B,3,3], t [B,3], stats int32 [B,2] = {points used, ok})."""
-    X1, X2 = _pair(X1, X2)
+    X1, X2 = _points_pair(X1, X2)
     M = len(X1)
-    offsets, B = _offsets(offsets, 1 << 24)
+    offsets, B = _cand_offsets(offsets, 1 << 24, "candidates")
     if mask is not None:
         mask = np.asarray(mask)
         if mask.shape != (M,):
@@ -184,7 +127,7 @@ def fit_sim3_offsets(X1, X2, offsets, mask=None, fix_scale: bool = False, ctx: O
         dT, ds = m.new(B * 104), m.new(B * 8)
         check(ctx.lib.slam_sim3_refit_f64(ctx.handle, B, do.ptr, d1.ptr, d2.ptr, M, dk.ptr if dk is not None else None, int(bool(fix_scale)),
                                           dT.ptr, ds.ptr))
-        return _split(dT.download(np.float64, (B, 13))) + (ds.download(np.int32, (B, 2)),)
+        return _model_srt(dT.download(np.float64, (B, 13))) + (ds.download(np.int32, (B, 2)),)
     finally:
         m.free()
 
@@ -193,7 +136,7 @@ def fit_sim3(X1, X2, mask=None, fix_scale: bool = False, ctx: Optional[Context] 
     """The least-squares similarity ``X2 ~ s R X1 + t`` of two point sets [N,3] (the rows with ``mask``; None: all):
     (ok, s, R [3,3], t [3]).  ``ok`` is False (identity, s = 1) with fewer than 3 selected points, collinear or repeated
     points, or non-finite data."""
-    X1, X2 = _pair(X1, X2)
+    X1, X2 = _points_pair(X1, X2)
     s, R, t, st = fit_sim3_offsets(X1, X2, [0, len(X1)], mask, fix_scale, ctx)
     return bool(st[0, 1]), float(s[0]), R[0], t[0]
 
@@ -203,7 +146,7 @@ def align_trajectory(estimated_xyz, ground_truth_xyz, fix_scale: bool = False, c
     positions [N,3] to the ground truth [N,3]: (s, R, t, aligned [N,3] = s R x + t, ate_rmse).  What ``euroc.py:63-66``
     should have done before comparing: a monocular estimate has a free gauge and a free scale.  A trajectory without a fit
     (fewer than 3 poses, all on one line) raises ``ValueError``."""
-    est, gt = _pair(estimated_xyz, ground_truth_xyz)
+    est, gt = _points_pair(estimated_xyz, ground_truth_xyz)
     ok, s, R, t = fit_sim3(est, gt, None, fix_scale, ctx)
     if not ok:
         raise ValueError("the trajectories have no unique alignment (fewer than 3 poses, collinear positions or non-finite data)")
@@ -223,11 +166,7 @@ def loop_edges_from_sim3(pairs, models, inlier_counts, min_inliers: int = 20, ma
     identity).  ``scales`` holds s for ALL candidates: an SE(3) graph cannot absorb scale drift, so a candidate beyond
     ``max_log_scale`` is reported there and gets no edge.  Edges with real scale drift go to the Sim(3) pose graph:
     ``slamhip.sim3_graph.sim3_edges_from_sim3`` and ``optimize_sim3_graph``."""
-    pairs = np.asarray(pairs)
-    if pairs.size == 0:
-        pairs = np.zeros((0, 2), np.int64)
-    if pairs.dtype.kind not in "iu" or pairs.ndim != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"pairs must be integers of shape [B,2], got {pairs.dtype} {pairs.shape}")
+    pairs = _edge_pairs(pairs)
     B = len(pairs)
     if len(models) != 3:
         raise ValueError("models must be (s [B], R [B,3,3], t [B,3])")
@@ -247,9 +186,4 @@ def loop_edges_from_sim3(pairs, models, inlier_counts, min_inliers: int = 20, ma
     meas = np.zeros((len(k), 3, 4))
     meas[:, :, :3] = R[k]
     meas[:, :, 3] = t[k] / s[k, None]
-    info = np.zeros((len(k), 6, 6))
-    w = n[k] / float(min_inliers)
-    for a in range(3):
-        info[:, a, a] = w / rotation_sigma ** 2
-        info[:, 3 + a, 3 + a] = w / translation_sigma ** 2
-    return np.ascontiguousarray(pairs[k], np.int32), meas, info, s.copy()
+    return np.ascontiguousarray(pairs[k], np.int32), meas, _edge_info(n[k] / float(min_inliers), rotation_sigma, translation_sigma), s.copy()

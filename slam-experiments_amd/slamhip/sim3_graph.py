@@ -19,6 +19,7 @@ from typing import Optional
 
 import numpy as np
 
+from ._geometry import _check_edge_args, _edge_info, _edge_pairs
 from ._lib import addr, check
 from .device import Context, default_context
 from .pose_graph import (DEFAULT_ITERATIONS, DEFAULT_PCG_MAX_ITER, DEFAULT_PCG_TOL, MAX_EDGES, MAX_VERTICES, STATS_FIELDS, _Dev,
@@ -235,11 +236,7 @@ def sim3_edges_from_sim3(pairs, models, inlier_counts, min_inliers: int = 20, ro
     An edge is emitted for EVERY pair with at least ``min_inliers`` inliers, i != j and a finite positive scale - at any
     scale, which is what ``loop_edges_from_sim3`` cannot do.  The measurement is the model unchanged; the information is
     diagonal, ``inliers / min_inliers / sigma^2`` per block."""
-    pairs = np.asarray(pairs)
-    if pairs.size == 0:
-        pairs = np.zeros((0, 2), np.int64)
-    if pairs.dtype.kind not in "iu" or pairs.ndim != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"pairs must be integers of shape [B,2], got {pairs.dtype} {pairs.shape}")
+    pairs = _edge_pairs(pairs)
     B = len(pairs)
     if len(models) != 3:
         raise ValueError("models must be (s [B], R [B,3,3], t [B,3])")
@@ -247,19 +244,13 @@ def sim3_edges_from_sim3(pairs, models, inlier_counts, min_inliers: int = 20, ro
     n = np.asarray(inlier_counts).reshape(-1)
     if not (len(Z) == len(n) == B):
         raise ValueError(f"{B} pairs but {len(Z)} models and {len(n)} inlier counts")
-    if min_inliers < 1 or rotation_sigma <= 0 or translation_sigma <= 0 or scale_sigma <= 0:
-        raise ValueError("min_inliers >= 1 and positive sigmas")
+    _check_edge_args(min_inliers, rotation_sigma, translation_sigma, scale_sigma)
     if B and pairs.min() < 0:
         raise ValueError("negative pair index")
     s = Z[:, 12]
     k = np.flatnonzero((n >= min_inliers) & (pairs[:, 0] != pairs[:, 1]) & np.isfinite(s) & (s > 0))
-    info = np.zeros((len(k), 7, 7))
-    w = n[k] / float(min_inliers)
-    for a in range(3):
-        info[:, a, a] = w / rotation_sigma ** 2
-        info[:, 3 + a, 3 + a] = w / translation_sigma ** 2
-    info[:, 6, 6] = w / scale_sigma ** 2
-    return np.ascontiguousarray(pairs[k], np.int32), Z[k].copy(), info
+    return np.ascontiguousarray(pairs[k], np.int32), Z[k].copy(), _edge_info(n[k] / float(min_inliers), rotation_sigma, translation_sigma,
+                                                                            scale_sigma)
 
 
 def lift_se3_graph(poses, edges, meas, info, scale_sigma: float = 0.05):

@@ -15,11 +15,10 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._args import _Buffers
+from ._geometry import _cand_offsets, _concat, _intrinsics, _mask_down, _model_srt, _pair, _rows, _split_mask
 from ._lib import check
 from .device import Context, default_context
-from .pnp import _points3
-from .sim3 import _offsets, _pair, _sigma2, _split, estimate_sim3_batch
-from .two_view import _intrinsics
+from .sim3 import estimate_sim3_batch
 
 DEFAULT_TH2 = 10.0                    # ORB-SLAM's ComputeSim3: OptimizeSim3(..., th2 = 10, ...)
 DEFAULT_ITERATIONS = (5, 10, 5)       # stage 1; stage 2 after outliers left; stage 2 when none left
@@ -27,18 +26,6 @@ DEFAULT_MIN_PAIRS = 10                # fewer survivors of stage 1: the candidat
 DEFAULT_MIN_INLIERS = 20              # ORB-SLAM accepts the loop on nInliers >= 20
 MAX_CANDIDATES = 65535
 REJECTED, BAD_MODEL, STALLED = 1, 2, 4   # status bits of stats[:, 3]
-
-
-def _pixels(a, M: int, name: str) -> np.ndarray:
-    try:
-        a = np.asarray(a, np.float64)
-    except (TypeError, ValueError) as exc:
-        raise TypeError(f"{name} must be numeric") from exc
-    if a.size == 0 and M == 0:
-        return np.zeros((0, 2))
-    if a.shape != (M, 2):
-        raise ValueError(f"{name} must have shape [{M},2], got {a.shape}")
-    return np.ascontiguousarray(a)
 
 
 def _is_srt(models) -> bool:
@@ -85,11 +72,11 @@ def optimize_sim3_offsets(X1, X2, px1, px2, offsets, models, K, sigma2=None, th2
     returns its input model, an empty mask and a count of 0."""
     fx, fy, cx, cy = _intrinsics(K)
     th2, it, min_pairs = _check_args(th2, iterations, min_pairs)
-    X1, X2 = _pair(X1, X2)
+    X1, X2 = _pair(X1, X2, "X1", "X2", 3, "correspondences")
     M = len(X1)
-    px1, px2 = _pixels(px1, M, "px1"), _pixels(px2, M, "px2")
-    sg = _sigma2(sigma2, M)
-    offsets, B = _offsets(offsets, MAX_CANDIDATES)
+    px1, px2 = _rows(px1, M, "px1"), _rows(px2, M, "px2")
+    sg = None if sigma2 is None else _rows(sigma2, M, "sigma2")
+    offsets, B = _cand_offsets(offsets, MAX_CANDIDATES, "candidates")
     Z = _models13(models, B)
     if B == 0:
         return np.zeros(0), np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros(M, bool), np.zeros((0, 4), np.int32), np.full((M, 2), np.nan)
@@ -103,11 +90,11 @@ def optimize_sim3_offsets(X1, X2, px1, px2, offsets, models, K, sigma2=None, th2
                                              dz.ptr, fx, fy, cx, cy, th2, it[0], it[1], it[2], min_pairs, int(bool(fix_scale)), dT.ptr,
                                              dm.ptr, dc.ptr, ds.ptr))
         model, st = dT.download(np.float64, (B, 13)), ds.download(np.int32, (B, 4))
-        mask = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
+        mask = _mask_down(dm, M)
         chi2 = dc.download(np.float64, (max(M, 1), 2))[:M]
     finally:
         m.free()
-    return _split(model) + (mask, st, chi2)
+    return _model_srt(model) + (mask, st, chi2)
 
 
 def optimize_sim3_batch(cands: Sequence, models, K, th2: float = DEFAULT_TH2, iterations: Sequence[int] = DEFAULT_ITERATIONS,
@@ -115,31 +102,16 @@ def optimize_sim3_batch(cands: Sequence, models, K, th2: float = DEFAULT_TH2, it
     """``Optimizer::OptimizeSim3`` for a list of ``(X1 [N_b,3], X2 [N_b,3], px1 [N_b,2], px2 [N_b,2])`` or ``(..., sigma2
     [N_b,2])`` candidates in one call: (s [B], R [B,3,3], t [B,3], list of bool masks, stats int32 [B,4], list of chi2
     [N_b,2]), as ``optimize_sim3_offsets``."""
-    A, Bs, P1, P2, S, off, any_sigma = [], [], [], [], [], [0], False
-    for i, c in enumerate(cands):
-        if len(c) not in (4, 5):
-            raise ValueError(f"candidate {i}: expected (X1, X2, px1, px2) or (X1, X2, px1, px2, sigma2)")
-        a, b = _points3(c[0], f"candidate {i} X1"), _points3(c[1], f"candidate {i} X2")
-        if len(a) != len(b):
-            raise ValueError(f"candidate {i}: {len(a)} points in frame 1 but {len(b)} in frame 2")
-        has = len(c) == 5 and c[4] is not None
-        any_sigma = any_sigma or has
-        A.append(a); Bs.append(b)
-        P1.append(_pixels(c[2], len(a), f"candidate {i} px1")); P2.append(_pixels(c[3], len(a), f"candidate {i} px2"))
-        S.append(_sigma2(c[4], len(a)) if has else np.ones((len(a), 2)))
-        off.append(off[-1] + len(a))
-    cat = (lambda v, w: np.concatenate(v) if v else np.zeros((0, w)))
-    s, R, t, mask, st, chi2 = optimize_sim3_offsets(cat(A, 3), cat(Bs, 3), cat(P1, 2), cat(P2, 2), np.asarray(off, np.int64), models, K,
-                                                    cat(S, 2) if any_sigma else None, th2, iterations, min_pairs, fix_scale, ctx)
-    rng = range(len(off) - 1)
-    return s, R, t, [mask[off[b]:off[b + 1]].copy() for b in rng], st, [chi2[off[b]:off[b + 1]].copy() for b in rng]
+    X1, X2, px1, px2, sg, off = _concat(cands, "candidate", (("X1", 3), ("X2", 3), ("px1", 2), ("px2", 2)), "correspondences", sigma2=True)
+    s, R, t, mask, st, chi2 = optimize_sim3_offsets(X1, X2, px1, px2, off, models, K, sg, th2, iterations, min_pairs, fix_scale, ctx)
+    return s, R, t, _split_mask(mask, off), st, _split_mask(chi2, off)
 
 
 def optimize_sim3(X1, X2, px1, px2, model, K, sigma2=None, th2: float = DEFAULT_TH2, iterations: Sequence[int] = DEFAULT_ITERATIONS,
                   min_pairs: int = DEFAULT_MIN_PAIRS, fix_scale: bool = False, ctx: Optional[Context] = None):
     """One candidate: (ok, s, R [3,3], t [3], inlier mask bool [N], stats int32 [4], chi2 [N,2]); ``ok`` is False when the
     candidate was rejected (the input model comes back, the mask is empty)."""
-    X1, X2 = _pair(X1, X2)
+    X1, X2 = _pair(X1, X2, "X1", "X2", 3, "correspondences")
     s, R, t, mask, st, chi2 = optimize_sim3_offsets(X1, X2, px1, px2, [0, len(X1)], model, K, sigma2, th2, iterations, min_pairs, fix_scale, ctx)
     return not bool(st[0, 3] & REJECTED), float(s[0]), R[0], t[0], mask, st[0], chi2
 
@@ -149,7 +121,7 @@ def sim3_to_s12(model) -> np.ndarray:
     ``X1 = (1 / s) R^T (X2 - t)``: the form ``search_by_sim3`` and ``fuse_by_sim3`` take.  ``model``: [13], [B,13] or
     (s, R, t) (-> [3,4], or [B,3,4] for batched input)."""
     batched = np.ndim(model[1]) == 3 if _is_srt(model) else np.ndim(model) == 2
-    s, R, t = _split(_models13(model))
+    s, R, t = _model_srt(_models13(model))
     if not (np.isfinite(s).all() and (s > 0).all()):
         raise ValueError("a similarity needs a finite positive scale")
     Ri = np.swapaxes(R, 1, 2) / s[:, None, None]

@@ -13,75 +13,19 @@ hypotheses from a documented counter-based generator is scored instead, so a res
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+from typing import Optional, Sequence
 
 import numpy as np
 
 from ._args import _Buffers
+from ._geometry import (MAX_HYPOTHESES, MAX_PAIRS, _cand_offsets, _check_cap, _check_ransac_args, _concat_flags, _flags,  # noqa: F401
+                        _intrinsics, _mask_down, _pair, _pair_arrays, _points, _solve_samples, _split_mask, _Vote)
 from ._lib import check
 from .device import Context, default_context
 
 DEFAULT_HYPOTHESES = 256        # the smallest power of two above ln(0.001) / ln(1 - 0.5**5) = 218: confidence 0.999 at 50 % inliers
 DEFAULT_THRESHOLD = 1.0         # pixels, cv2.findEssentialMat's default
 DEFAULT_DISTANCE = 50.0         # cv2.recoverPose's distanceThresh
-MAX_HYPOTHESES = 1 << 20
-MAX_PAIRS = 65535
-
-
-def _intrinsics(K) -> Tuple[float, float, float, float]:
-    """(fx, fy, cx, cy) from a 3x3 camera matrix or a 4-sequence."""
-    A = np.asarray(K, np.float64)
-    if A.shape == (3, 3):
-        vals = (A[0, 0], A[1, 1], A[0, 2], A[1, 2])
-    elif A.shape == (4,):
-        vals = tuple(A)
-    else:
-        raise ValueError(f"intrinsics must be a 3x3 camera matrix or (fx, fy, cx, cy), got shape {A.shape}")
-    fx, fy, cx, cy = (float(v) for v in vals)
-    if not (np.isfinite([fx, fy, cx, cy]).all() and fx > 0 and fy > 0):
-        raise ValueError("focal lengths must be positive and intrinsics finite")
-    return fx, fy, cx, cy
-
-
-def _points(a, name: str) -> np.ndarray:
-    try:
-        a = np.asarray(a, np.float64)
-    except (TypeError, ValueError) as exc:
-        raise TypeError(f"{name} must be numeric") from exc
-    if a.size == 0:
-        return np.zeros((0, 2))
-    if a.ndim != 2 or a.shape[1] != 2:
-        raise ValueError(f"{name} must have shape [N,2], got {a.shape}")
-    return np.ascontiguousarray(a)
-
-
-def _pair_arrays(pairs) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    p1, p2, off = [], [], [0]
-    for i, pair in enumerate(pairs):
-        if len(pair) != 2:
-            raise ValueError(f"pair {i}: expected (px1, px2)")
-        a, b = _points(pair[0], f"pair {i} px1"), _points(pair[1], f"pair {i} px2")
-        if len(a) != len(b):
-            raise ValueError(f"pair {i}: {len(a)} points in frame 1 but {len(b)} in frame 2")
-        p1.append(a)
-        p2.append(b)
-        off.append(off[-1] + len(a))
-    if off[-1] >= 1 << 28:
-        raise ValueError("more than 2^28 matches in one call")
-    cat = (lambda v: np.concatenate(v) if v else np.zeros((0, 2)))
-    return cat(p1), cat(p2), np.asarray(off, np.int32)
-
-
-def _check_ransac_args(hypotheses, threshold, seed):
-    if not isinstance(hypotheses, (int, np.integer)) or isinstance(hypotheses, bool):
-        raise TypeError("hypotheses must be an integer")
-    if not 1 <= int(hypotheses) <= MAX_HYPOTHESES:
-        raise ValueError(f"hypotheses must be in [1, {MAX_HYPOTHESES}]")
-    if not (np.isfinite(threshold) and threshold > 0):
-        raise ValueError("threshold must be positive")
-    if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool):
-        raise TypeError("seed must be an integer")
-    return int(hypotheses), float(threshold), int(seed) & ((1 << 64) - 1)
 
 
 def fivepoint_arrays(x1, x2, ctx: Optional[Context] = None):
@@ -94,15 +38,7 @@ def fivepoint_arrays(x1, x2, ctx: Optional[Context] = None):
     S = x1.shape[0]
     if S == 0:
         return np.zeros((0, 10, 9)), np.zeros(0, np.int32)
-    ctx = ctx or default_context()
-    m = _Buffers(ctx)
-    try:
-        d1, d2 = m.up(x1), m.up(x2)
-        dE, dn = m.new(S * 720), m.new(S * 4)
-        check(ctx.lib.slam_tv_fivepoint_f64(ctx.handle, S, d1.ptr, d2.ptr, dE.ptr, dn.ptr))
-        return dE.download(np.float64, (S, 10, 9)), dn.download(np.int32, (S,))
-    finally:
-        m.free()
+    return _solve_samples(ctx, "slam_tv_fivepoint_f64", x1, x2, (10, 9))
 
 
 def find_essential_offsets(px1, px2, offsets, K, hypotheses: int = DEFAULT_HYPOTHESES, threshold: float = DEFAULT_THRESHOLD,
@@ -111,27 +47,14 @@ def find_essential_offsets(px1, px2, offsets, K, hypotheses: int = DEFAULT_HYPOT
     Returns (E [B,9], inlier bool [M], stats int32 [B,4])."""
     fx, fy, cx, cy = _intrinsics(K)
     H, thr, seed = _check_ransac_args(hypotheses, threshold, seed)
-    px1, px2 = _points(px1, "px1"), _points(px2, "px2")
-    if len(px1) != len(px2):
-        raise ValueError(f"{len(px1)} points in frame 1 but {len(px2)} in frame 2")
-    offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
-    B, M = len(offsets) - 1, len(px1)
-    if B < 0:
-        raise ValueError("offsets must have B + 1 entries")
-    if B > MAX_PAIRS:
-        raise ValueError(f"at most {MAX_PAIRS} pairs per call")
+    px1, px2 = _pair(px1, px2, "px1", "px2", 2)
+    offsets, B = _cand_offsets(offsets, MAX_PAIRS, "pairs")
     if B == 0:
-        return np.zeros((0, 9)), np.zeros(M, bool), np.zeros((0, 4), np.int32)
+        return np.zeros((0, 9)), np.zeros(len(px1), bool), np.zeros((0, 4), np.int32)
     ctx = ctx or default_context()
     m = _Buffers(ctx)
     try:
-        d1, d2, do = m.up(px1), m.up(px2), m.up(offsets)
-        dE, dm, ds = m.new(B * 72), m.new(M), m.new(B * 16)
-        check(ctx.lib.slam_tv_essential_ransac_f64(ctx.handle, B, do.ptr, d1.ptr, d2.ptr, M, fx, fy, cx, cy, H, thr, seed,
-                                                   dE.ptr, dm.ptr, ds.ptr))
-        E, st = dE.download(np.float64, (B, 9)), ds.download(np.int32, (B, 4))
-        mask = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
-        return E, mask, st
+        return _Vote(m, ctx.lib.slam_tv_essential_ransac_f64, (px1, px2), offsets, (fx, fy, cx, cy, H, thr, seed), 9).download()
     finally:
         m.free()
 
@@ -141,7 +64,7 @@ def find_essential_batch(pairs: Sequence, K, hypotheses: int = DEFAULT_HYPOTHESE
     """``cv2.findEssentialMat`` for a list of ``(px1, px2)`` pairs in one call: (E [B,3,3], list of bool masks, stats [B,4])."""
     px1, px2, off = _pair_arrays(pairs)
     E, mask, st = find_essential_offsets(px1, px2, off, K, hypotheses, threshold, seed, ctx)
-    return E.reshape(-1, 3, 3), [mask[off[b]:off[b + 1]].copy() for b in range(len(off) - 1)], st
+    return E.reshape(-1, 3, 3), _split_mask(mask, off), st
 
 
 def find_essential_arrays(px1, px2, K, hypotheses: int = DEFAULT_HYPOTHESES, threshold: float = DEFAULT_THRESHOLD, seed: int = 0,
@@ -158,18 +81,13 @@ def recover_pose_offsets(E, px1, px2, offsets, K, inlier=None, distance_thresh: 
     fx, fy, cx, cy = _intrinsics(K)
     if not (np.isfinite(distance_thresh) and distance_thresh > 0):
         raise ValueError("distance_thresh must be positive")
-    px1, px2 = _points(px1, "px1"), _points(px2, "px2")
-    if len(px1) != len(px2):
-        raise ValueError(f"{len(px1)} points in frame 1 but {len(px2)} in frame 2")
+    px1, px2 = _pair(px1, px2, "px1", "px2", 2)
     offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
     B, M = len(offsets) - 1, len(px1)
     E = np.ascontiguousarray(E, np.float64)
     if E.size != 9 * max(B, 0):
         raise ValueError(f"E must hold one 3x3 matrix per pair ({B}), got shape {E.shape}")
-    if inlier is not None:
-        inlier = np.ascontiguousarray(inlier).astype(np.uint8).reshape(-1)
-        if len(inlier) != M:
-            raise ValueError("one inlier flag per match")
+    inlier = _flags(inlier, M)
     if B <= 0:
         return np.zeros((0, 3, 4)), np.zeros(M, bool), np.zeros((0, 2), np.int32)
     ctx = ctx or default_context()
@@ -181,8 +99,7 @@ def recover_pose_offsets(E, px1, px2, offsets, K, inlier=None, distance_thresh: 
         check(ctx.lib.slam_tv_recover_pose_f64(ctx.handle, B, do.ptr, d1.ptr, d2.ptr, M, fx, fy, cx, cy, dE.ptr,
                                                di.ptr if di is not None else None, float(distance_thresh), dp.ptr, dm.ptr, ds.ptr))
         pose, st = dp.download(np.float64, (B, 3, 4)), ds.download(np.int32, (B, 2))
-        good = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
-        return pose, good, st
+        return pose, _mask_down(dm, M), st
     finally:
         m.free()
 
@@ -190,13 +107,8 @@ def recover_pose_offsets(E, px1, px2, offsets, K, inlier=None, distance_thresh: 
 def recover_pose_batch(E, pairs: Sequence, K, inliers=None, distance_thresh: float = DEFAULT_DISTANCE, ctx: Optional[Context] = None):
     """``cv2.recoverPose`` for a list of pairs: (R [B,3,3], t [B,3], list of bool masks, stats [B,2])."""
     px1, px2, off = _pair_arrays(pairs)
-    inl = None
-    if inliers is not None:
-        if len(inliers) != len(off) - 1:
-            raise ValueError("one inlier mask per pair")
-        inl = np.concatenate([np.asarray(v).astype(np.uint8).reshape(-1) for v in inliers]) if len(inliers) else np.zeros(0, np.uint8)
-    pose, good, st = recover_pose_offsets(E, px1, px2, off, K, inl, distance_thresh, ctx)
-    return pose[:, :, :3].copy(), pose[:, :, 3].copy(), [good[off[b]:off[b + 1]].copy() for b in range(len(off) - 1)], st
+    pose, good, st = recover_pose_offsets(E, px1, px2, off, K, _concat_flags(inliers, len(off) - 1), distance_thresh, ctx)
+    return pose[:, :, :3].copy(), pose[:, :, 3].copy(), _split_mask(good, off), st
 
 
 def recover_pose_arrays(E, px1, px2, K, inlier=None, distance_thresh: float = DEFAULT_DISTANCE, ctx: Optional[Context] = None):
@@ -249,8 +161,7 @@ def verify_pairs(pairs: Sequence, K, hypotheses: int = DEFAULT_HYPOTHESES, thres
         raise ValueError("distance_thresh must be positive")
     px1, px2, off = _pair_arrays(pairs)
     B, M = len(off) - 1, len(px1)
-    if B > MAX_PAIRS:
-        raise ValueError(f"at most {MAX_PAIRS} pairs per call")
+    _check_cap(B, MAX_PAIRS, "pairs")
     if B == 0:
         return np.zeros((0, 3, 3)), np.zeros((0, 3)), [], np.zeros(0, np.int64)
     ctx = ctx or default_context()
@@ -264,12 +175,12 @@ def verify_pairs(pairs: Sequence, K, hypotheses: int = DEFAULT_HYPOTHESES, thres
         check(ctx.lib.slam_tv_recover_pose_f64(ctx.handle, B, do.ptr, d1.ptr, d2.ptr, M, fx, fy, cx, cy, dE.ptr, None,
                                                float(distance_thresh), dp.ptr, dg.ptr, dq.ptr))
         pose, st = dp.download(np.float64, (B, 3, 4)), ds.download(np.int32, (B, 4))
-        mask = dm.download(np.uint8, (M,)).astype(bool) if M else np.zeros(0, bool)
+        mask = _mask_down(dm, M)
     finally:
         m.free()
     t = pose[:, :, 3].copy()
     t[st[:, 1] < 0] = 0.0
-    return pose[:, :, :3].copy(), t, [mask[off[b]:off[b + 1]].copy() for b in range(B)], st[:, 0].astype(np.int64)
+    return pose[:, :, :3].copy(), t, _split_mask(mask, off), st[:, 0].astype(np.int64)
 
 
 def mean_reprojection_error(points, px, pose, K, ctx: Optional[Context] = None) -> float:
