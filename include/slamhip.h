@@ -450,6 +450,53 @@ SLAM_API int slam_pose_optimize_batch_f64(slam_ctx* ctx, int64_t B, const double
                                           double chi2_threshold, double huber_delta, double* d_pose_out,
                                           uint8_t* d_inlier, double* d_chi2, int32_t* d_stats);
 
+/* ---- stereo and level-weighted edges (stereo_edge.h, pose_stereo.hip, ba_stereo.hip) -------------------------
+ * The edge model of ORB-SLAM's EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ (and their OnlyPose forms) under the pose
+ * optimisation and the sparse bundle adjustment.  Observation o of point p under pose T (3x4 row-major, world -> camera),
+ * (X, Y, Z) = R p + t, measurement d_meas3 [O,3] = (mu, mv, mr), information s = d_info [O]:
+ *   prediction   u^ = (fx X + cx Z) / Z, v^ = (fy Y + cy Z) / Z, ur^ = u^ - bf / Z
+ *   residuals    e0 = mu - u^, e1 = mv - v^; mr NaN: a MONOCULAR edge (e2 = 0); otherwise a STEREO edge, e2 = mr - ur^
+ *   information  s is the inverse variance (ORB-SLAM: 1 / scale[level]^2), finite and >= 0.  s = 0 switches the edge off:
+ *                it adds nothing to any sum, its chi2 is still reported.  A negative or non-finite s is counted by
+ *                slam_index_errors and taken as 0.
+ *   chi2         s (e0^2 + e1^2 [+ e2^2]).  The Huber kernel acts on this weighted chi2 with the width delta_mono or
+ *                delta_stereo by kind: if delta > 0 and sqrt(chi2) > delta then w = delta / sqrt(chi2) and
+ *                rho = 2 delta sqrt(chi2) - delta^2, otherwise w = 1 and rho = chi2.  Normal-equation terms take the
+ *                factor (w s), formed first.
+ *   Jacobians    rows 0 and 1 are those of slam_reproj_rj_f64 / slam_bas_linearize_f64 (Zinv = 1 / (Z + 1e-18), rotation
+ *                columns first); row 2, in the update convention T <- Exp([w, v]) T:
+ *                jp2 = jp0 - bf Zinv^2 (Y, -X, 0, 0, 0, 1), jq2[c] = jq0[c] - bf Zinv^2 R[2][c]; zero for a monocular edge
+ *   inlier       s > 0 and Z > 0 and chi2 <= chi2_mono or chi2_stereo by kind (no kernel in this chi2).  Z > 0 is ORB-SLAM's
+ *                isDepthPositive; applying it in the pose optimisation too is a deviation.
+ * f64 without contraction, only + - * / sqrt: the host build of stereo_edge.h returns the device's bits.  Every buffer is the
+ * caller's; no call here takes the context's call lock or its workspace; all are asynchronous on the context's stream. */
+
+/* Per-edge linearisation over an observation table, the three-row counterpart of slam_reproj_rj_f64: d_e [O,3] (row 2 = 0
+ * for a monocular edge), d_Jpose [O,3,6], d_Jpoint [O,3,3], d_chi2 [O], d_w [O] (the Huber weight).  An index outside
+ * [0, K) / [0, L) is never dereferenced: all outputs of that observation are NaN and slam_index_errors counts it. */
+SLAM_API int slam_reproj_rj_stereo_f64(slam_ctx* ctx, const double* d_poses, int64_t K, const double* d_points, int64_t L,
+                                     const int32_t* d_obs_pose, const int32_t* d_obs_point, const double* d_meas3,
+                                     const double* d_info, int64_t O, double fx, double fy, double cx, double cy, double bf,
+                                     double delta_mono, double delta_stereo, double* d_e, double* d_Jpose, double* d_Jpoint,
+                                     double* d_chi2, double* d_w);
+
+/* ORB-SLAM's Optimizer::PoseOptimization for B frames in one launch (one workgroup of 256 threads per frame) under the
+ * offsets contract of slam_pose_optimize_batch_f64 (clamped, counted, never a wild access; B = 0 and frames without edges
+ * are legal): `rounds` rounds (ORB-SLAM: 4) of `iterations` LM iterations (10), every round restarting from d_pose_in, the
+ * active set recomputed after every round from the classification of ALL edges (an edge may come back), the Huber kernel
+ * dropped after round index 2.  ORB-SLAM's gates are 5.991 / 7.815, its widths their square roots.  Frames of up to
+ * SLAM_POSE_STEREO_STAGE edges are kept in LDS, larger ones run on the global arrays.  Fixed-order sums: two runs give equal
+ * bits, a frame gives the same bits alone or in a batch.  Outputs: d_pose_out [B,12], d_inlier u8 [O_total] = the
+ * classification at the returned pose, d_chi2 [O_total] the weighted chi2 there, d_stats int32 [B,4] = {inliers, accepted LM
+ * steps, stereo inliers, edges with s > 0}.  A frame whose edges all have s = 0 returns d_pose_in and no inlier. */
+#define SLAM_POSE_STEREO_STAGE 512
+SLAM_API int slam_pose_optimize_stereo_batch_f64(slam_ctx* ctx, int64_t B, const double* d_pose_in, const double* d_points,
+                                                 const double* d_meas3, const double* d_info, const int32_t* d_offsets,
+                                                 int64_t O_total, double fx, double fy, double cx, double cy, double bf, int rounds,
+                                                 int iterations, double chi2_mono, double chi2_stereo, double delta_mono,
+                                                 double delta_stereo, double* d_pose_out, uint8_t* d_inlier, double* d_chi2,
+                                                 int32_t* d_stats);
+
 /* ---- two-view geometry (f64): utils.py:10-28 (pose_estimation_2d2d) and utils.py:32-55 (triangulation), batched ------------
  * Conventions: points 1 are the reference's source_pts (last frame, trainIdx), points 2 its query_pts (current frame,
  * queryIdx); normalised coordinates x = ((u - cx) / fx, (v - cy) / fy, 1); x2^T E x1 = 0 with E [9] row-major; the
@@ -1359,6 +1406,29 @@ SLAM_API int slam_bas_candidate_f64(slam_ctx* ctx, int64_t K, int64_t L, const u
                                     const double* d_points, const double* d_dp, const double* d_dl, const double* d_bp,
                                     const double* d_bl, double lambda, double* d_poses_out, double* d_points_out, double* d_part,
                                     double* d_denominator);
+/* The stereo / weighted forms of the two phases that read a measurement (the edge model above; ba_stereo.hip): the argument
+ * lists of their parents with d_meas3 [O,3], d_info [O], bf, delta_mono, delta_stereo in place of d_meas, huber_delta.  Same
+ * kernels per phase, list orders, sums and index-error accounting (an information that is none counts once, with the
+ * observation's indices); slam_bas_reduce_f64, _backsub_f64, _candidate_f64 and slam_pg_pcg_f64 take the blocks as they
+ * are.  With every mr NaN, every s = 1 and delta_mono = huber_delta all outputs equal the parents' in value. */
+SLAM_API int slam_bas_linearize_stereo_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, const double* d_poses,
+                                           const double* d_points, const int32_t* d_obs_pose, const int32_t* d_obs_point,
+                                           const double* d_meas3, const double* d_info, const int32_t* d_pt_ptr,
+                                           const int32_t* d_pt_obs, const int32_t* d_ps_ptr, const int32_t* d_ps_obs,
+                                           const uint8_t* d_fixed, double fx, double fy, double cx, double cy, double bf,
+                                           double delta_mono, double delta_stereo, double* d_Hpl, double* d_Hll, double* d_bl,
+                                           double* d_Hpp, double* d_bp, double* d_cost, double* d_scal);
+SLAM_API int slam_bas_cost_stereo_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, const double* d_poses, const double* d_points,
+                                      const int32_t* d_obs_pose, const int32_t* d_obs_point, const double* d_meas3,
+                                      const double* d_info, const int32_t* d_ps_ptr, const int32_t* d_ps_obs, double fx, double fy,
+                                      double cx, double cy, double bf, double delta_mono, double delta_stereo, double* d_cost,
+                                      double* d_total);
+/* the classification at a state, one thread per observation: d_chi2 [O] the weighted chi2 (no kernel), d_inlier u8 [O] the
+ * inlier rule above.  An observation with an index outside its range has chi2 NaN and is no inlier; it is not counted here. */
+SLAM_API int slam_bas_classify_stereo_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, const double* d_poses,
+                                          const double* d_points, const int32_t* d_obs_pose, const int32_t* d_obs_point,
+                                          const double* d_meas3, const double* d_info, double fx, double fy, double cx, double cy,
+                                          double bf, double chi2_mono, double chi2_stereo, double* d_chi2, uint8_t* d_inlier);
 
 /* ---- bag-of-words place recognition (bow.hip) --------------------------------------------------------------
  * DBoW2's vocabulary tree, BoW vectors and inverted-file database for 256-bit descriptors, as ORB-SLAM's KeyFrameDatabase

@@ -36,6 +36,7 @@ from slamhip import pose_graph as _pg
 from slamhip import sim3_graph as _s3g
 from slamhip import sim3_opt as _s3o
 from slamhip import stereo as _st
+from slamhip import stereo_opt as _so
 from slamhip import pose_opt as _po
 from slamhip import reproj as _r
 from slamhip import two_view as _tv
@@ -207,6 +208,22 @@ class Backend:
         ``slamhip.StereoResult``: per pair ``u_right``, ``depth`` and a status for every left keypoint; its ``points`` and
         ``point_set`` turn the matched rows into camera-frame or world points."""
         return _st.stereo_match(left, right, pairs, bf=bf, fx=fx, **kw)
+
+    def track_stereo_pose(self, poses, points_list, edges_list, fx, fy, cx, cy, bf, rounds: int = 4, iterations: int = 10,
+                          gates=(_so.CHI2_MONO, _so.CHI2_STEREO), deltas=(_so.DELTA_MONO, _so.DELTA_STEREO)):
+        """ORB-SLAM's ``Optimizer::PoseOptimization`` with monocular and stereo edges mixed and every edge weighted by its
+        pyramid level, for several frames in one launch: ``edges_list[b]`` is a ``slamhip.StereoEdges``
+        (``slamhip.stereo_edges`` builds one from a ``stereo_frame`` result), ``points_list[b]`` the map points of its rows.
+        Returns a list of ``PoseOptResult`` (``slamhip.optimize_poses_stereo``)."""
+        return _so.optimize_poses_stereo(poses, points_list, edges_list, (fx, fy, cx, cy), bf, rounds, iterations, gates, deltas, ctx=self.ctx)
+
+    def local_bundle_adjust(self, poses, points, obs_pose_idx, obs_point_idx, stereo, fx, fy, cx, cy, fixed_poses=(0,), first: int = 5,
+                            second: int = 10, gates=(_so.CHI2_MONO, _so.CHI2_STEREO), deltas=(_so.DELTA_MONO, _so.DELTA_STEREO)):
+        """ORB-SLAM's ``Optimizer::LocalBundleAdjustment`` over a window: the sparse adjustment with stereo / level-weighted edges
+        (``stereo``: a ``slamhip.StereoEdges`` over the observations) and the two-stage outlier schedule.  Returns
+        (``slamhip.ba.BAResult``, outlier observation indices, stats dict) (``slamhip.local_bundle_adjust``)."""
+        return _so.local_bundle_adjust(poses, points, obs_pose_idx, obs_point_idx, stereo, (fx, fy, cx, cy), fixed_poses, first, second,
+                                       gates, deltas, ctx=self.ctx)
 
     def match_by_bow(self, keyframes, frame, candidates, frame_index: int = 0, keyframe_bins=None, frame_bins=None,
                      th_low: int = _bm.TH_LOW, ratio: float = _bm.RATIO):

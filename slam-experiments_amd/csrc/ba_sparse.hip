@@ -44,7 +44,8 @@
 #pragma clang fp contract(off)
 #include "ba_common.h"
 
-#define BAS_WAVES (BA_THREADS / 64)
+#include "ba_sparse_common.h"
+
 #define BAS_MAX_PART 1024          // partial sums of the candidate kernel (its grid)
 
 struct bas_obs_tab {
@@ -107,13 +108,6 @@ __global__ __launch_bounds__(BA_THREADS) void bas_point_kernel(const bas_obs_tab
     for (int i = 0; i < 6; i++) Hll[(size_t)l * 6 + i] = h[i];
 #pragma unroll
     for (int i = 0; i < 3; i++) bl[(size_t)l * 3 + i] = b[i];
-}
-
-// the slice [a0, a1) of a pose's list; a slice that does not lie in the table is taken as empty, and false comes back
-__device__ __forceinline__ bool bas_pose_range(const int* __restrict__ ps_ptr, int k, int O, int& a0, int& a1) {
-    a0 = ps_ptr[k]; a1 = ps_ptr[k + 1];
-    if (a0 < 0 || a1 < a0 || a1 > O) { a0 = a1 = 0; return false; }
-    return true;
 }
 
 __global__ __launch_bounds__(BA_THREADS) void bas_pose_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
@@ -378,12 +372,11 @@ __global__ __launch_bounds__(BA_THREADS) void bas_candidate_kernel(int K, int L,
 }
 
 // ---- the C ABI -----------------------------------------------------------------------------------------------------------------------
-static inline int bas_blocks(int64_t n) { return (int)((n + BA_THREADS - 1) / BA_THREADS); }
 static inline int bas_cand_blocks(int64_t K, int64_t L) {
     const int64_t n = (K + L + BA_THREADS - 1) / BA_THREADS;
     return (int)(n < 1 ? 1 : n > BAS_MAX_PART ? BAS_MAX_PART : n);
 }
-static int bas_sizes(const char* who, int64_t K, int64_t L, int64_t O, int64_t E, int64_t P) {
+int bas_sizes(const char* who, int64_t K, int64_t L, int64_t O, int64_t E, int64_t P) {
     SLAM_REQUIRE(K >= 1 && K <= SLAM_PG_MAX_VERTICES && L >= 1 && L <= SLAM_BAS_MAX_POINTS && O >= 0 && O <= SLAM_BAS_MAX_OBS && E >= 0 &&
                      E <= SLAM_PG_MAX_EDGES && P >= E && P <= SLAM_BAS_MAX_PAIRS,
                  "%s: bad sizes (K=%lld, L=%lld, O=%lld, E=%lld, P=%lld)", who, (long long)K, (long long)L, (long long)O, (long long)E,
@@ -422,7 +415,11 @@ extern "C" int slam_bas_plan(int64_t K, int64_t L, int64_t O, int64_t E, int64_t
     return SLAM_OK;
 }
 
-#define BAS_ALIGNED16(p) ((((uintptr_t)(p)) & 15) == 0)
+// partial sums -> one scalar behind a phase of ba_stereo.hip, on the stream of that phase (bas_finish_kernel as the phases here launch it)
+void bas_finish_launch(hipStream_t st, const double* part, int n, double* out, const double* Hpp, const uint8_t* fixed, int K, const double* Hll,
+                       int L) {
+    bas_finish_kernel<<<1, BA_THREADS, 0, st>>>(part, n, out, Hpp, fixed, K, Hll, L);
+}
 
 extern "C" int slam_bas_linearize_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O, const double* d_poses, const double* d_points,
                                       const int32_t* d_obs_pose, const int32_t* d_obs_point, const double* d_meas, const int32_t* d_pt_ptr,

@@ -163,6 +163,13 @@ from .stereo import (  # noqa: F401
     stereo_match,
     stereo_match_arrays,
 )
+from .stereo_opt import (  # noqa: F401
+    StereoEdges,
+    local_bundle_adjust,
+    optimize_poses_stereo,
+    stereo_edge_linearization,
+    stereo_edges,
+)
 from .sim3_graph import (  # noqa: F401
     correct_points,
     lift_se3_graph,

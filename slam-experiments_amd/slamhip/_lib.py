@@ -209,6 +209,13 @@ SIGNATURES = {
     "slam_bas_reduce_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64] + [c_void_p] * 12 + [c_double] + [c_void_p] * 5),
     "slam_bas_backsub_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64] + [c_void_p] * 8),
     "slam_bas_candidate_f64": (c_int, [c_void_p, c_int64, c_int64] + [c_void_p] * 7 + [c_double] + [c_void_p] * 4),
+    "slam_bas_linearize_stereo_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64] + [c_void_p] * 11 + [c_double] * 7 + [c_void_p] * 7),
+    "slam_bas_cost_stereo_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64] + [c_void_p] * 8 + [c_double] * 7 + [c_void_p] * 2),
+    "slam_bas_classify_stereo_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64] + [c_void_p] * 6 + [c_double] * 7 + [c_void_p] * 2),
+    "slam_reproj_rj_stereo_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64]
+                                + [c_double] * 7 + [c_void_p] * 5),
+    "slam_pose_optimize_stereo_batch_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64]
+                                            + [c_double] * 5 + [c_int, c_int] + [c_double] * 4 + [c_void_p] * 4),
     "slam_bow_limits": (c_int, [POINTER(c_int32)]),
     "slam_bow_transform": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
     "slam_bow_vectors": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_uint64, c_void_p,

@@ -102,6 +102,30 @@ def covisibility(obs_pose, obs_point, K: int, fixed, L: Optional[int] = None):
     return edges, np.diff(pair_ptr).astype(np.int32), pair_ptr, pa.astype(np.int32), pb.astype(np.int32)
 
 
+def _deltas(huber_delta):
+    """(delta_mono, delta_stereo) of a Huber width given as one number (both kinds) or as a pair."""
+    d = np.asarray(huber_delta, np.float64).reshape(-1)
+    if d.size not in (1, 2) or not (np.isfinite(d).all() and (d >= 0).all()):
+        raise ValueError("huber_delta must be a number >= 0, or a pair (mono, stereo) of them")
+    return float(d[0]), float(d[-1])
+
+
+def _stereo_arrays(stereo, O: int):
+    """(meas3 [O,3], info [O], bf) of a ``StereoEdges`` for O observations, checked."""
+    meas3 = np.ascontiguousarray(stereo.meas3, np.float64)
+    info = np.ascontiguousarray(stereo.info, np.float64)
+    if meas3.shape != (O, 3) or info.shape != (O,):
+        raise ValueError(f"stereo edges must hold meas3 [O,3] and info [O] for O = {O} observations, got {meas3.shape} and {info.shape}")
+    if not (np.isfinite(info).all() and (info >= 0).all()):
+        raise ValueError("info must be finite and >= 0")
+    if not np.isfinite(meas3[:, :2]).all() or np.isinf(meas3[:, 2]).any():
+        raise ValueError("meas3 must be finite (mr: finite, or NaN for a monocular edge)")
+    bf = float(stereo.bf)
+    if not (np.isfinite(bf) and bf > 0):
+        raise ValueError("bf must be positive and finite")
+    return meas3, info, bf
+
+
 def _covisibility_host(op, ol, K, fixed, L):
     """``covisibility`` for SparseBAProblem, which has an argument of the function's name (looked up at the call, as before)."""
     return covisibility(op, ol, K, fixed, L)
@@ -129,9 +153,12 @@ class SparseBAProblem:
     checked on the host (``ValueError``) before anything is allocated or launched.  With ``covisibility="device"`` the
     covisibility tables are built by ``slam_covis_*`` from the uploaded observation lists instead of by ``covisibility`` (the
     same tables, bit for bit); a (pose, point) pair observed twice is then refused after that build's count phase, with
-    everything freed."""
+    everything freed.  With ``stereo`` (a ``StereoEdges``: meas3 [O,3], info [O], bf) the phases that read a measurement take
+    their stereo / weighted forms (``slam_bas_*_stereo_f64``; ``meas`` may then be None) and ``classify`` / ``set_info`` serve
+    the outlier schedule of ``local_bundle_adjust``; with ``None`` every call is the one it was."""
 
-    def __init__(self, ctx: Context, K: int, L: int, obs_pose, obs_point, meas, intrinsics, fixed, covisibility: str = "host"):
+    def __init__(self, ctx: Context, K: int, L: int, obs_pose, obs_point, meas, intrinsics, fixed, covisibility: str = "host",
+                 stereo=None):
         self._check = check
         self.ctx = ctx
         K, L = int(K), int(L)
@@ -141,6 +168,10 @@ class SparseBAProblem:
             raise ValueError(f"covisibility must be 'host' or 'device', got {covisibility!r}")
         op, ol = _index_arrays(obs_pose, obs_point, K, L)
         O = len(op)
+        self.stereo = stereo is not None
+        if self.stereo:
+            meas3, info, self.bf = _stereo_arrays(stereo, O)
+            meas = meas3[:, :2] if meas is None else meas
         meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 2)
         if meas.shape[0] != O:
             raise ValueError("obs_pose, obs_point and meas must have one row per observation")
@@ -161,6 +192,8 @@ class SparseBAProblem:
             self.d_op, self.d_ol, self.d_fixed = up(pad(op)), up(pad(ol)), up(self.fixed.astype(np.uint8))
             self.d_edges, self.d_pair_ptr, self.d_pair_a, self.d_pair_b = up(pad(self.edges)), up(pair_ptr), up(pad(pair_a)), up(pad(pair_b))
         self.d_meas = up(meas if O else np.zeros((1, 2)))
+        if self.stereo:
+            self.d_meas3, self.d_info = up(meas3 if O else np.zeros((1, 3))), up(info if O else np.zeros(1))
         self.d_pt_ptr, self.d_pt_obs, self.d_ps_ptr, self.d_ps_obs = up(pt_ptr), up(pad(pt_obs)), up(ps_ptr), up(pad(ps_obs))
         self.d_vtx_ptr, self.d_vtx_adj = up(vtx_ptr), up(pad(vtx_adj))
         self.d_T, self.d_X = [new(K * 96), new(K * 96)], [new(L * 24), new(L * 24)]      # [0] the state, [1] the candidate
@@ -213,6 +246,14 @@ class SparseBAProblem:
     def linearize(self, huber_delta: float):
         """``slam_bas_linearize_f64`` at the state -> (cost, largest diagonal entry of the free Hpp and every Hll)."""
         c = self.ctx
+        if self.stereo:
+            self._check(c.lib.slam_bas_linearize_stereo_f64(
+                c.handle, self.K, self.L, self.O, self.d_T[0].ptr, self.d_X[0].ptr, self.d_op.ptr, self.d_ol.ptr, self.d_meas3.ptr,
+                self.d_info.ptr, self.d_pt_ptr.ptr, self.d_pt_obs.ptr, self.d_ps_ptr.ptr, self.d_ps_obs.ptr, self.d_fixed.ptr, self.fx,
+                self.fy, self.cx, self.cy, self.bf, *_deltas(huber_delta), self.d_Hpl.ptr, self.d_Hll.ptr, self.d_bl.ptr, self.d_Hpp.ptr,
+                self.d_bp.ptr, self.d_cost.ptr, self.d_scal.ptr))
+            s = self.d_scal.download(np.float64, (2,))
+            return float(s[0]), float(s[1])
         self._check(c.lib.slam_bas_linearize_f64(
             c.handle, self.K, self.L, self.O, self.d_T[0].ptr, self.d_X[0].ptr, self.d_op.ptr, self.d_ol.ptr, self.d_meas.ptr,
             self.d_pt_ptr.ptr, self.d_pt_obs.ptr, self.d_ps_ptr.ptr, self.d_ps_obs.ptr, self.d_fixed.ptr, self.fx, self.fy, self.cx,
@@ -263,17 +304,51 @@ class SparseBAProblem:
         self._check(c.lib.slam_bas_candidate_f64(c.handle, self.K, self.L, self.d_fixed.ptr, self.d_T[0].ptr, self.d_X[0].ptr, self.d_dp.ptr,
                                                  self.d_dl.ptr, self.d_bp.ptr, self.d_bl.ptr, float(lam), self.d_T[1].ptr, self.d_X[1].ptr,
                                                  self.d_part.ptr, self.d_scal.view(16, 8).ptr))
-        self._check(c.lib.slam_bas_cost_f64(c.handle, self.K, self.L, self.O, self.d_T[1].ptr, self.d_X[1].ptr, self.d_op.ptr, self.d_ol.ptr,
-                                            self.d_meas.ptr, self.d_ps_ptr.ptr, self.d_ps_obs.ptr, self.fx, self.fy, self.cx, self.cy,
-                                            float(huber_delta), self.d_cost2.ptr, self.d_scal.view(24, 8).ptr))
+        if self.stereo:
+            self._check(c.lib.slam_bas_cost_stereo_f64(c.handle, self.K, self.L, self.O, self.d_T[1].ptr, self.d_X[1].ptr, self.d_op.ptr,
+                                                       self.d_ol.ptr, self.d_meas3.ptr, self.d_info.ptr, self.d_ps_ptr.ptr, self.d_ps_obs.ptr,
+                                                       self.fx, self.fy, self.cx, self.cy, self.bf, *_deltas(huber_delta), self.d_cost2.ptr,
+                                                       self.d_scal.view(24, 8).ptr))
+        else:
+            self._check(c.lib.slam_bas_cost_f64(c.handle, self.K, self.L, self.O, self.d_T[1].ptr, self.d_X[1].ptr, self.d_op.ptr, self.d_ol.ptr,
+                                                self.d_meas.ptr, self.d_ps_ptr.ptr, self.d_ps_obs.ptr, self.fx, self.fy, self.cx, self.cy,
+                                                float(huber_delta), self.d_cost2.ptr, self.d_scal.view(24, 8).ptr))
         s = self.d_scal.download(np.float64, (4,))
         return float(s[2]), float(s[3])
+
+    # ---- the stereo / weighted problem only ---------------------------------------------------------------------------------------
+    def classify(self, chi2_mono: float, chi2_stereo: float):
+        """``slam_bas_classify_stereo_f64`` at the state -> (weighted chi2 [O], inlier bool [O])."""
+        if not self.stereo:
+            raise ValueError("classify needs a problem built with stereo edges")
+        if not (chi2_mono >= 0 and chi2_stereo >= 0):
+            raise ValueError("the gates must not be negative")
+        c, o = self.ctx, max(self.O, 1)
+        d_chi, d_in = c.malloc(o * 8), c.malloc(o)
+        try:
+            self._check(c.lib.slam_bas_classify_stereo_f64(c.handle, self.K, self.L, self.O, self.d_T[0].ptr, self.d_X[0].ptr, self.d_op.ptr,
+                                                           self.d_ol.ptr, self.d_meas3.ptr, self.d_info.ptr, self.fx, self.fy, self.cx, self.cy,
+                                                           self.bf, float(chi2_mono), float(chi2_stereo), d_chi.ptr, d_in.ptr))
+            return d_chi.download(np.float64, (o,))[:self.O], d_in.download(np.uint8, (o,))[:self.O].astype(bool)
+        finally:
+            d_chi.free()
+            d_in.free()
+
+    def set_info(self, info) -> None:
+        """Replace the informations in the device table (0 switches an edge off); tables and blocks stay as they are."""
+        if not self.stereo:
+            raise ValueError("set_info needs a problem built with stereo edges")
+        info = np.ascontiguousarray(info, np.float64)
+        if info.shape != (self.O,) or not (np.isfinite(info).all() and (info >= 0).all()):
+            raise ValueError("info must be [O], finite and >= 0")
+        if self.O:
+            self.d_info.upload(info)
 
 
 def bundle_adjust_sparse(poses, points, obs_pose_idx, obs_point_idx, meas, intrinsics, iterations: int = 10,
                          fixed_poses: Sequence[int] = (0,), huber_delta: float = 0.0, pcg_tol: float = DEFAULT_PCG_TOL,
                          pcg_max_iter: int = DEFAULT_PCG_MAX_ITER, ctx: Optional[Context] = None, on_trial=None,
-                         covisibility: str = "host"):
+                         covisibility: str = "host", stereo=None):
     """``bundle_adjust_device`` for maps instead of windows: the reduced camera system as 6x6 blocks over the covisibility
     graph (``slam_bas_*``), solved by the pose-graph PCG (``slam_pg_pcg_f64``).  Same arguments, same Levenberg-Marquardt
     schedule; the state goes to the device once and comes back once, a trial moves a few scalars.
@@ -283,12 +358,18 @@ def bundle_adjust_sparse(poses, points, obs_pose_idx, obs_point_idx, meas, intri
     trial, the damping grows), edges, pairs).  ``on_trial(dict)`` is called after every trial (timing tools).
     ``covisibility``: "host" builds the covisibility tables with numpy (``covisibility``), "device" with ``slam_covis_*``
     (``slamhip.covis``); the tables, and with them every result, are the same bit for bit.
+    ``stereo`` (a ``slamhip.StereoEdges``: meas3 [O,3] with mr NaN for a monocular edge, info [O], bf): the stereo / level-weighted
+    edge model of DESIGN.md 4v under the same schedule; ``meas`` may then be None and ``huber_delta`` a pair (mono, stereo).
+    ``None`` takes the path it took, call for call.
     Raises ``ValueError`` for an index out of range, a (pose, point) pair observed twice or no fixed pose, before any launch."""
     T12, X, K, L = state_arrays(poses, points)
-    _check_solver_args(iterations, huber_delta, pcg_tol, pcg_max_iter)
+    if stereo is None:
+        _check_solver_args(iterations, huber_delta, pcg_tol, pcg_max_iter)
+    else:
+        _check_solver_args(iterations, min(_deltas(huber_delta)), pcg_tol, pcg_max_iter)
     fixed = fixed_pose_mask(fixed_poses, K)
     ctx = ctx or default_context()
-    prob = SparseBAProblem(ctx, K, L, obs_pose_idx, obs_point_idx, meas, intrinsics, fixed, covisibility)
+    prob = SparseBAProblem(ctx, K, L, obs_pose_idx, obs_point_idx, meas, intrinsics, fixed, covisibility, stereo)
     st = dict(trials=0, cg_iterations=0, lam=0.0, status=0, unconverged=0, edges=prob.E, pairs=prob.P)
 
     def trial(lam, cost):
