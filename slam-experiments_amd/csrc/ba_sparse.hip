@@ -13,7 +13,9 @@
 //   b_k     = bp_k - sum_{o of k} Hpl_o E_l bl_l
 //   dl_l    = - E_l (bl_l + sum_{o of l} Hpl_o^T dp_pose(o))
 //
-// Kernels (f64, no contraction, no floating-point atomics; every sum in an order that depends on the index tables only):
+// Kernels (f64, no contraction, no floating-point atomics; every sum in an order that depends on the index tables only);
+// the four that read a measurement (obs, point, pose, cost) are the templates of ba_sparse_phases.h over bas_mono_edge below,
+// the one copy that ba_stereo.hip instantiates over its stereo / weighted edges.
 //   bas_obs_kernel      a thread per observation   Hpl_o; the two indices are checked here and counted (slam_index_errors)
 //   bas_point_kernel    a thread per point         Hll (6), bl (3) over its list pt_obs, in list order
 //   bas_pose_kernel     a workgroup per pose       Hpp (21), bp (6), cost: thread t takes entries t, t + 256, .. of ps_obs,
@@ -37,7 +39,8 @@
 // called by the driver between them.
 //
 // The linearisation of one observation, the block sum, the damped 3x3 inverse and the pose update are ba_schur.hip's, from
-// ba_common.h; it is included BEHIND the pragma below, so here they are compiled without contraction like everything else.
+// ba_common.h; it and ba_sparse_phases.h are included BEHIND the pragma below, so here they are compiled without contraction
+// like everything else.
 #include "internal.h"
 #include <math.h>
 
@@ -53,114 +56,30 @@ struct bas_obs_tab {
     int K, L, O;
 };
 
-// observation o of an index table linearised at (T, X); false (nothing dereferenced) when o or one of its indices is outside
-__device__ __forceinline__ bool bas_at(const bas_obs_tab& t, const double* __restrict__ T, const double* __restrict__ X, const int o,
-                                       const ba_cam& cam, const double delta, ba_lin& q, int& k, int& l) {
-    if ((unsigned)o >= (unsigned)t.O) return false;
-    k = t.obs_pose[o]; l = t.obs_point[o];
-    if ((unsigned)k >= (unsigned)t.K || (unsigned)l >= (unsigned)t.L) return false;
-    ba_linearise(T + (size_t)k * 12, X + (size_t)l * 3, t.meas[o], cam, delta, q);
-    return true;
-}
-
-__global__ __launch_bounds__(BA_THREADS) void bas_obs_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                              ba_cam cam, double delta, unsigned int* __restrict__ index_errors,
-                                                              double* __restrict__ Hpl /*[O,18]*/) {
-    const int o = (int)(blockIdx.x * BA_THREADS + threadIdx.x);
-    if (o >= t.O) return;
+// the edge model of this file under the phases of ba_sparse_phases.h: ba_linearise of ba_common.h - two rows, weight w, every
+// edge live, the Jacobians made with the residual
+struct bas_mono_edge {
+    static constexpr int ROWS = 2;
+    typedef bas_obs_tab tab;
+    typedef ba_cam cam;
+    typedef double robust;
     ba_lin q;
-    int k, l;
-    double* h = Hpl + (size_t)o * 18;
-    if (!bas_at(t, T, X, o, cam, delta, q, k, l)) {          // reported, never dereferenced; its block poisons what reads it
-        atomicAdd(index_errors, 1u);
-#pragma unroll
-        for (int i = 0; i < 18; i++) h[i] = __builtin_nan("");
-        return;
+    double r[2];
+    __device__ __forceinline__ void residual(const tab& t, int o, const double* T, const double* X, int k, int l, const cam& c, double delta) {
+        ba_linearise(T + (size_t)k * 12, X + (size_t)l * 3, t.meas[o], c, delta, q);
+        r[0] = q.e0; r[1] = q.e1;
     }
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) h[a * 3 + c] = q.w * (q.jp[0][a] * q.jq[0][c] + q.jp[1][a] * q.jq[1][c]);
-}
+    __device__ __forceinline__ static bool info_ok(const tab&, int) { return true; }
+    __device__ __forceinline__ bool live() const { return true; }
+    __device__ __forceinline__ void jacobians(const double*, const cam&) {}
+    __device__ __forceinline__ double weight() const { return q.w; }
+    __device__ __forceinline__ double rho() const { return q.rho; }
+    __device__ __forceinline__ const double* e() const { return r; }
+    __device__ __forceinline__ const double* jp() const { return &q.jp[0][0]; }
+    __device__ __forceinline__ const double* jq() const { return &q.jq[0][0]; }
+};
 
-__global__ __launch_bounds__(BA_THREADS) void bas_point_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                                const int* __restrict__ pt_ptr, const int* __restrict__ pt_obs, ba_cam cam,
-                                                                double delta, unsigned int* __restrict__ index_errors,
-                                                                double* __restrict__ Hll /*[L,6]*/, double* __restrict__ bl /*[L,3]*/) {
-    const int l = (int)(blockIdx.x * BA_THREADS + threadIdx.x);
-    if (l >= t.L) return;
-    double h[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-    int a0 = pt_ptr[l], a1 = pt_ptr[l + 1];
-    if (a0 < 0 || a1 < a0 || a1 > t.O) { atomicAdd(index_errors, 1u); a1 = a0 = 0; }
-    for (int i = a0; i < a1; i++) {
-        ba_lin q;
-        int k, l2;
-        if (!bas_at(t, T, X, pt_obs[i], cam, delta, q, k, l2)) { h[0] = __builtin_nan(""); continue; }
-        int n = 0;
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int c = a; c < 3; c++) h[n++] += q.w * (q.jq[0][a] * q.jq[0][c] + q.jq[1][a] * q.jq[1][c]);
-#pragma unroll
-        for (int a = 0; a < 3; a++) b[a] += q.w * (q.jq[0][a] * q.e0 + q.jq[1][a] * q.e1);
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) Hll[(size_t)l * 6 + i] = h[i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) bl[(size_t)l * 3 + i] = b[i];
-}
-
-__global__ __launch_bounds__(BA_THREADS) void bas_pose_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                               const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs, ba_cam cam,
-                                                               double delta, unsigned int* __restrict__ index_errors,
-                                                               double* __restrict__ Hpp /*[K,21]*/, double* __restrict__ bp /*[K,6]*/,
-                                                               double* __restrict__ cost /*[K]*/) {
-    __shared__ double sw[BAS_WAVES][28];
-    __shared__ double out[28];
-    const int k = (int)blockIdx.x;
-    double acc[28];
-#pragma unroll
-    for (int i = 0; i < 28; i++) acc[i] = 0.0;
-    int a0, a1;
-    // the first phase to read ps_ptr reports a corrupt slice, once (bas_cost_kernel and bas_diag_kernel take it as empty too)
-    if (!bas_pose_range(ps_ptr, k, t.O, a0, a1) && threadIdx.x == 0) atomicAdd(index_errors, 1u);
-    for (int i = a0 + (int)threadIdx.x; i < a1; i += BA_THREADS) {
-        ba_lin q;
-        int k2, l;
-        if (!bas_at(t, T, X, ps_obs[i], cam, delta, q, k2, l)) { acc[27] = __builtin_nan(""); continue; }
-        int n = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int c = a; c < 6; c++) acc[n++] += q.w * (q.jp[0][a] * q.jp[0][c] + q.jp[1][a] * q.jp[1][c]);
-#pragma unroll
-        for (int a = 0; a < 6; a++) acc[21 + a] += q.w * (q.jp[0][a] * q.e0 + q.jp[1][a] * q.e1);
-        acc[27] += q.rho;
-    }
-    ba_block_sum<28>(acc, sw, out);
-    if (threadIdx.x < 21) Hpp[(size_t)k * 21 + threadIdx.x] = out[threadIdx.x];
-    else if (threadIdx.x < 27) bp[(size_t)k * 6 + threadIdx.x - 21] = out[threadIdx.x];
-    else if (threadIdx.x == 27) cost[k] = out[27];
-}
-
-__global__ __launch_bounds__(BA_THREADS) void bas_cost_kernel(const bas_obs_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                               const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs, ba_cam cam,
-                                                               double delta, double* __restrict__ cost /*[K]*/) {
-    __shared__ double sw[BAS_WAVES][1];
-    __shared__ double out[1];
-    const int k = (int)blockIdx.x;
-    double acc[1] = {0.0};
-    int a0, a1;
-    bas_pose_range(ps_ptr, k, t.O, a0, a1);
-    for (int i = a0 + (int)threadIdx.x; i < a1; i += BA_THREADS) {
-        ba_lin q;
-        int k2, l;
-        if (!bas_at(t, T, X, ps_obs[i], cam, delta, q, k2, l)) { acc[0] = __builtin_nan(""); continue; }
-        acc[0] += q.rho;
-    }
-    ba_block_sum<1>(acc, sw, out);
-    if (threadIdx.x == 0) cost[k] = out[0];
-}
+#include "ba_sparse_phases.h"   // bas_obs_kernel, bas_point_kernel, bas_pose_kernel, bas_cost_kernel: behind the pragma above
 
 // out[0] = sum of part[0..n) (thread t takes t, t + 256, ..); with diagonals given, out[1] = the largest diagonal entry of the
 // Hpp of the free poses and of every Hll (the maximum does not depend on an order)
@@ -437,9 +356,9 @@ extern "C" int slam_bas_linearize_f64(slam_ctx* ctx, int64_t K, int64_t L, int64
     const ba_cam cam = {fx, fy, cx, cy};
     const bas_obs_tab t = {d_obs_pose, d_obs_point, (const double2*)d_meas, (int)K, (int)L, (int)O};
     unsigned int* ie = slam_index_error_counter(ctx);
-    if (O) bas_obs_kernel<<<bas_blocks(O), BA_THREADS, 0, st>>>(t, d_poses, d_points, cam, huber_delta, ie, d_Hpl);
-    bas_point_kernel<<<bas_blocks(L), BA_THREADS, 0, st>>>(t, d_poses, d_points, d_pt_ptr, d_pt_obs, cam, huber_delta, ie, d_Hll, d_bl);
-    bas_pose_kernel<<<(unsigned)K, BA_THREADS, 0, st>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, huber_delta, ie, d_Hpp, d_bp, d_cost);
+    if (O) bas_obs_kernel<bas_mono_edge><<<bas_blocks(O), BA_THREADS, 0, st>>>(t, d_poses, d_points, cam, huber_delta, ie, d_Hpl);
+    bas_point_kernel<bas_mono_edge><<<bas_blocks(L), BA_THREADS, 0, st>>>(t, d_poses, d_points, d_pt_ptr, d_pt_obs, cam, huber_delta, ie, d_Hll, d_bl);
+    bas_pose_kernel<bas_mono_edge><<<(unsigned)K, BA_THREADS, 0, st>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, huber_delta, ie, d_Hpp, d_bp, d_cost);
     bas_finish_kernel<<<1, BA_THREADS, 0, st>>>(d_cost, (int)K, d_scal, d_Hpp, d_fixed, (int)K, d_Hll, (int)L);
     return slam_launch_check("slam_bas_linearize_f64");
 }
@@ -456,7 +375,7 @@ extern "C" int slam_bas_cost_f64(slam_ctx* ctx, int64_t K, int64_t L, int64_t O,
     SLAM_HIP(hipSetDevice(ctx->device));
     const ba_cam cam = {fx, fy, cx, cy};
     const bas_obs_tab t = {d_obs_pose, d_obs_point, (const double2*)d_meas, (int)K, (int)L, (int)O};
-    bas_cost_kernel<<<(unsigned)K, BA_THREADS, 0, ctx->stream>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, huber_delta, d_cost);
+    bas_cost_kernel<bas_mono_edge><<<(unsigned)K, BA_THREADS, 0, ctx->stream>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, huber_delta, d_cost);
     bas_finish_kernel<<<1, BA_THREADS, 0, ctx->stream>>>(d_cost, (int)K, d_total, nullptr, nullptr, 0, nullptr, 0);
     return slam_launch_check("slam_bas_cost_f64");
 }

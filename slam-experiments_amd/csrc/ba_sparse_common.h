@@ -1,6 +1,7 @@
 // ba_sparse_common.h - what the two files of the sparse bundle adjustment share besides ba_common.h: ba_sparse.hip (every phase,
 // two residuals per observation, unit information) and ba_stereo.hip (the stereo / weighted forms of the phases that read a
-// measurement).  No arithmetic here, so the contraction state of the including file does not matter.
+// measurement; the phases themselves are the templates of ba_sparse_phases.h).  No arithmetic here, so the contraction state
+// of the including file does not matter.
 #pragma once
 #include "internal.h"
 #include "ba_common.h"

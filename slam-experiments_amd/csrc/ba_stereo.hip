@@ -7,13 +7,14 @@
 // of the blocks - slam_bas_reduce_f64, _backsub_f64, _candidate_f64, slam_pg_pcg_f64 - works on Hpl / Hll / bl / Hpp / bp and
 // is called as it is.
 //
-// Kernels: those of ba_sparse.hip's linearisation and cost, one for one, with the same lists, the same thread mapping and the
-// same ba_block_sum, so every sum has the order it has there.
-//   bast_obs_kernel      a thread per observation   Hpl_o = (w s) Jp^T Jq over two or three rows; indices and informations are
-//                                                    checked here and counted (slam_index_errors)
-//   bast_point_kernel    a thread per point         Hll (6), bl (3) over pt_obs, in list order
-//   bast_pose_kernel     a workgroup per pose       Hpp (21), bp (6), cost; a bad ps_ptr slice is counted here
-//   bast_cost_kernel     a workgroup per pose       robust cost at a state
+// Kernels: the linearisation and the cost are the four phase templates of ba_sparse_phases.h - the one copy that ba_sparse.hip
+// instantiates too: same lists, same thread mapping, same NaN poisoning, same ba_block_sum - over bast_edge below:
+//   bas_obs_kernel<bast_edge>    a thread per observation   Hpl_o = (w s) Jp^T Jq over three rows (the third 0 for a monocular
+//                                                            edge); indices and informations are checked here and counted
+//   bas_point_kernel<bast_edge>  a thread per point         Hll (6), bl (3) over pt_obs, in list order
+//   bas_pose_kernel<bast_edge>   a workgroup per pose       Hpp (21), bp (6), cost; a bad ps_ptr slice is counted here
+//   bas_cost_kernel<bast_edge>   a workgroup per pose       robust cost at a state
+// and two of this file's own:
 //   bast_classify_kernel a thread per observation   weighted chi2 and the inlier flag (se_inlier) at a state
 //   stereo_rj_kernel     a thread per observation   e, Jpose, Jpoint, chi2, w of every edge
 // Parent rule: with every mr NaN, every s = 1 and delta_mono = huber_delta the blocks, the per-pose cost and d_scal equal those
@@ -34,133 +35,30 @@ struct bast_tab {
     int K, L, O;
 };
 
-// observation o of an index table at (T, X): residuals, chi2, weight; false (nothing dereferenced) when o or one of its
-// indices is outside.  k and l come back for the Jacobians.
-__device__ __forceinline__ bool bast_at(const bast_tab& t, const double* __restrict__ T, const double* __restrict__ X, const int o,
-                                        const se_cam& cam, const se_huber& hub, se_res& r, int& k, int& l) {
-    if ((unsigned)o >= (unsigned)t.O) return false;
-    k = t.obs_pose[o]; l = t.obs_point[o];
-    if ((unsigned)k >= (unsigned)t.K || (unsigned)l >= (unsigned)t.L) return false;
-    const double* m = t.meas3 + (size_t)o * 3;
-    se_residual(T + (size_t)k * 12, X + (size_t)l * 3, m[0], m[1], m[2], t.info[o], cam, hub, r);
-    return true;
-}
-
-__global__ __launch_bounds__(BA_THREADS) void bast_obs_kernel(const bast_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                               se_cam cam, se_huber hub, unsigned int* __restrict__ index_errors,
-                                                               double* __restrict__ Hpl /*[O,18]*/) {
-    const int o = (int)(blockIdx.x * BA_THREADS + threadIdx.x);
-    if (o >= t.O) return;
+// the edge model of this file under the phases of ba_sparse_phases.h: stereo_edge.h - three rows (the third 0 for a monocular
+// edge), weight w s, an edge live iff s > 0, the Jacobians made for live edges only
+struct bast_edge {
+    static constexpr int ROWS = 3;
+    typedef bast_tab tab;
+    typedef se_cam cam;
+    typedef se_huber robust;
     se_res r;
-    int k, l;
-    double* h = Hpl + (size_t)o * 18;
-    if (!bast_at(t, T, X, o, cam, hub, r, k, l)) {           // reported, never dereferenced; its block poisons what reads it
-        atomicAdd(index_errors, 1u);
-#pragma unroll
-        for (int i = 0; i < 18; i++) h[i] = __builtin_nan("");
-        return;
-    }
-    if (!se_info_ok(t.info[o])) atomicAdd(index_errors, 1u);  // an information that is none: counted, taken as 0
-    if (!(r.s > 0.0)) {                                       // switched off: adds nothing anywhere
-#pragma unroll
-        for (int i = 0; i < 18; i++) h[i] = 0.0;
-        return;
-    }
     se_jac j;
-    se_jacobians(T + (size_t)k * 12, r, cam, j);
-    const double ws = r.w * r.s;
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) h[a * 3 + c] = ws * ((j.jp[0][a] * j.jq[0][c] + j.jp[1][a] * j.jq[1][c]) + j.jp[2][a] * j.jq[2][c]);
-}
-
-__global__ __launch_bounds__(BA_THREADS) void bast_point_kernel(const bast_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                                 const int* __restrict__ pt_ptr, const int* __restrict__ pt_obs, se_cam cam,
-                                                                 se_huber hub, unsigned int* __restrict__ index_errors,
-                                                                 double* __restrict__ Hll /*[L,6]*/, double* __restrict__ bl /*[L,3]*/) {
-    const int l = (int)(blockIdx.x * BA_THREADS + threadIdx.x);
-    if (l >= t.L) return;
-    double h[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-    int a0 = pt_ptr[l], a1 = pt_ptr[l + 1];
-    if (a0 < 0 || a1 < a0 || a1 > t.O) { atomicAdd(index_errors, 1u); a1 = a0 = 0; }
-    for (int i = a0; i < a1; i++) {
-        se_res r;
-        int k, l2;
-        if (!bast_at(t, T, X, pt_obs[i], cam, hub, r, k, l2)) { h[0] = __builtin_nan(""); continue; }
-        if (!(r.s > 0.0)) continue;
-        se_jac j;
-        se_jacobians(T + (size_t)k * 12, r, cam, j);
-        const double ws = r.w * r.s;
-        int n = 0;
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int c = a; c < 3; c++) h[n++] += ws * ((j.jq[0][a] * j.jq[0][c] + j.jq[1][a] * j.jq[1][c]) + j.jq[2][a] * j.jq[2][c]);
-#pragma unroll
-        for (int a = 0; a < 3; a++) b[a] += ws * ((j.jq[0][a] * r.e[0] + j.jq[1][a] * r.e[1]) + j.jq[2][a] * r.e[2]);
+    __device__ __forceinline__ void residual(const tab& t, int o, const double* T, const double* X, int k, int l, const cam& c, const se_huber& hub) {
+        const double* m = t.meas3 + (size_t)o * 3;
+        se_residual(T + (size_t)k * 12, X + (size_t)l * 3, m[0], m[1], m[2], t.info[o], c, hub, r);
     }
-#pragma unroll
-    for (int i = 0; i < 6; i++) Hll[(size_t)l * 6 + i] = h[i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) bl[(size_t)l * 3 + i] = b[i];
-}
+    __device__ __forceinline__ static bool info_ok(const tab& t, int o) { return se_info_ok(t.info[o]); }
+    __device__ __forceinline__ bool live() const { return r.s > 0.0; }
+    __device__ __forceinline__ void jacobians(const double* P, const cam& c) { se_jacobians(P, r, c, j); }
+    __device__ __forceinline__ double weight() const { return r.w * r.s; }
+    __device__ __forceinline__ double rho() const { return r.rho; }
+    __device__ __forceinline__ const double* e() const { return r.e; }
+    __device__ __forceinline__ const double* jp() const { return &j.jp[0][0]; }
+    __device__ __forceinline__ const double* jq() const { return &j.jq[0][0]; }
+};
 
-__global__ __launch_bounds__(BA_THREADS) void bast_pose_kernel(const bast_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                                const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs, se_cam cam,
-                                                                se_huber hub, unsigned int* __restrict__ index_errors,
-                                                                double* __restrict__ Hpp /*[K,21]*/, double* __restrict__ bp /*[K,6]*/,
-                                                                double* __restrict__ cost /*[K]*/) {
-    __shared__ double sw[BAS_WAVES][28];
-    __shared__ double out[28];
-    const int k = (int)blockIdx.x;
-    double acc[28];
-#pragma unroll
-    for (int i = 0; i < 28; i++) acc[i] = 0.0;
-    int a0, a1;
-    if (!bas_pose_range(ps_ptr, k, t.O, a0, a1) && threadIdx.x == 0) atomicAdd(index_errors, 1u);
-    for (int i = a0 + (int)threadIdx.x; i < a1; i += BA_THREADS) {
-        se_res r;
-        int k2, l;
-        if (!bast_at(t, T, X, ps_obs[i], cam, hub, r, k2, l)) { acc[27] = __builtin_nan(""); continue; }
-        if (!(r.s > 0.0)) continue;
-        se_jac j;
-        se_jacobians(T + (size_t)k2 * 12, r, cam, j);
-        const double ws = r.w * r.s;
-        int n = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int c = a; c < 6; c++) acc[n++] += ws * ((j.jp[0][a] * j.jp[0][c] + j.jp[1][a] * j.jp[1][c]) + j.jp[2][a] * j.jp[2][c]);
-#pragma unroll
-        for (int a = 0; a < 6; a++) acc[21 + a] += ws * ((j.jp[0][a] * r.e[0] + j.jp[1][a] * r.e[1]) + j.jp[2][a] * r.e[2]);
-        acc[27] += r.rho;
-    }
-    ba_block_sum<28>(acc, sw, out);
-    if (threadIdx.x < 21) Hpp[(size_t)k * 21 + threadIdx.x] = out[threadIdx.x];
-    else if (threadIdx.x < 27) bp[(size_t)k * 6 + threadIdx.x - 21] = out[threadIdx.x];
-    else if (threadIdx.x == 27) cost[k] = out[27];
-}
-
-__global__ __launch_bounds__(BA_THREADS) void bast_cost_kernel(const bast_tab t, const double* __restrict__ T, const double* __restrict__ X,
-                                                                const int* __restrict__ ps_ptr, const int* __restrict__ ps_obs, se_cam cam,
-                                                                se_huber hub, double* __restrict__ cost /*[K]*/) {
-    __shared__ double sw[BAS_WAVES][1];
-    __shared__ double out[1];
-    const int k = (int)blockIdx.x;
-    double acc[1] = {0.0};
-    int a0, a1;
-    bas_pose_range(ps_ptr, k, t.O, a0, a1);
-    for (int i = a0 + (int)threadIdx.x; i < a1; i += BA_THREADS) {
-        se_res r;
-        int k2, l;
-        if (!bast_at(t, T, X, ps_obs[i], cam, hub, r, k2, l)) { acc[0] = __builtin_nan(""); continue; }
-        if (!(r.s > 0.0)) continue;
-        acc[0] += r.rho;
-    }
-    ba_block_sum<1>(acc, sw, out);
-    if (threadIdx.x == 0) cost[k] = out[0];
-}
+#include "ba_sparse_phases.h"   // bas_obs_kernel, bas_point_kernel, bas_pose_kernel, bas_cost_kernel: behind the pragma above
 
 // chi2 and the inlier flag of every observation at a state (no kernel: the gate is on the plain weighted chi2); an observation
 // with an index outside its range has chi2 NaN and is no inlier, and is not counted here (the linearisation counts it)
@@ -169,12 +67,12 @@ __global__ __launch_bounds__(BA_THREADS) void bast_classify_kernel(const bast_ta
                                                                     uint8_t* __restrict__ inlier /*[O]*/) {
     const int o = (int)(blockIdx.x * BA_THREADS + threadIdx.x);
     if (o >= t.O) return;
-    se_res r;
+    bast_edge m;
     int k, l;
     const se_huber none = {0.0, 0.0};
-    if (!bast_at(t, T, X, o, cam, none, r, k, l)) { chi2[o] = __builtin_nan(""); inlier[o] = 0; return; }
-    chi2[o] = r.chi2;
-    inlier[o] = se_inlier(r, gate) ? 1 : 0;
+    if (!bas_at(t, T, X, o, cam, none, m, k, l)) { chi2[o] = __builtin_nan(""); inlier[o] = 0; return; }
+    chi2[o] = m.r.chi2;
+    inlier[o] = se_inlier(m.r, gate) ? 1 : 0;
 }
 
 // slam_reproj_rj_stereo_f64: a thread per observation, 35 doubles out.  Plain stores: not transposed through LDS as reproj.hip's
@@ -186,10 +84,10 @@ __global__ __launch_bounds__(BA_THREADS) void stereo_rj_kernel(const bast_tab t,
                                                                 double* __restrict__ w /*[O]*/) {
     const int o = (int)(blockIdx.x * BA_THREADS + threadIdx.x);
     if (o >= t.O) return;
-    se_res r;
+    bast_edge m;
     int k, l;
     double* eo = e + (size_t)o * 3; double* jp = Jpose + (size_t)o * 18; double* jq = Jpoint + (size_t)o * 9;
-    if (!bast_at(t, T, X, o, cam, hub, r, k, l)) {
+    if (!bas_at(t, T, X, o, cam, hub, m, k, l)) {
         atomicAdd(index_errors, 1u);
         const double nan = __builtin_nan("");
 #pragma unroll
@@ -202,8 +100,9 @@ __global__ __launch_bounds__(BA_THREADS) void stereo_rj_kernel(const bast_tab t,
         return;
     }
     if (!se_info_ok(t.info[o])) atomicAdd(index_errors, 1u);
-    se_jac j;
-    se_jacobians(T + (size_t)k * 12, r, cam, j);
+    m.jacobians(T + (size_t)k * 12, cam);
+    const se_res& r = m.r;
+    const se_jac& j = m.j;
 #pragma unroll
     for (int i = 0; i < 3; i++) eo[i] = r.e[i];
 #pragma unroll
@@ -263,9 +162,9 @@ extern "C" int slam_bas_linearize_stereo_f64(slam_ctx* ctx, int64_t K, int64_t L
     const se_huber hub = {delta_mono, delta_stereo};
     const bast_tab t = {d_obs_pose, d_obs_point, d_meas3, d_info, (int)K, (int)L, (int)O};
     unsigned int* ie = slam_index_error_counter(ctx);
-    if (O) bast_obs_kernel<<<bas_blocks(O), BA_THREADS, 0, st>>>(t, d_poses, d_points, cam, hub, ie, d_Hpl);
-    bast_point_kernel<<<bas_blocks(L), BA_THREADS, 0, st>>>(t, d_poses, d_points, d_pt_ptr, d_pt_obs, cam, hub, ie, d_Hll, d_bl);
-    bast_pose_kernel<<<(unsigned)K, BA_THREADS, 0, st>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, hub, ie, d_Hpp, d_bp, d_cost);
+    if (O) bas_obs_kernel<bast_edge><<<bas_blocks(O), BA_THREADS, 0, st>>>(t, d_poses, d_points, cam, hub, ie, d_Hpl);
+    bas_point_kernel<bast_edge><<<bas_blocks(L), BA_THREADS, 0, st>>>(t, d_poses, d_points, d_pt_ptr, d_pt_obs, cam, hub, ie, d_Hll, d_bl);
+    bas_pose_kernel<bast_edge><<<(unsigned)K, BA_THREADS, 0, st>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, hub, ie, d_Hpp, d_bp, d_cost);
     bas_finish_launch(st, d_cost, (int)K, d_scal, d_Hpp, d_fixed, (int)K, d_Hll, (int)L);
     return slam_launch_check("slam_bas_linearize_stereo_f64");
 }
@@ -283,7 +182,7 @@ extern "C" int slam_bas_cost_stereo_f64(slam_ctx* ctx, int64_t K, int64_t L, int
     const se_cam cam = {fx, fy, cx, cy, bf};
     const se_huber hub = {delta_mono, delta_stereo};
     const bast_tab t = {d_obs_pose, d_obs_point, d_meas3, d_info, (int)K, (int)L, (int)O};
-    bast_cost_kernel<<<(unsigned)K, BA_THREADS, 0, ctx->stream>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, hub, d_cost);
+    bas_cost_kernel<bast_edge><<<(unsigned)K, BA_THREADS, 0, ctx->stream>>>(t, d_poses, d_points, d_ps_ptr, d_ps_obs, cam, hub, d_cost);
     bas_finish_launch(ctx->stream, d_cost, (int)K, d_total, nullptr, nullptr, 0, nullptr, 0);
     return slam_launch_check("slam_bas_cost_stereo_f64");
 }

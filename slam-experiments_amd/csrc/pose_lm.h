@@ -1,7 +1,8 @@
 // pose_lm.h - the model-independent parts of the one-launch pose refinements: the pose update, the damped 6x6 solve and the
 // fixed-order block sums of pose_opt.hip (two residuals per edge, unit information) and pose_stereo.hip (the stereo / weighted
 // edges of stereo_edge.h).  The text is pose_opt.hip's, moved; it carries no contraction pragma and both files include it
-// under the compiler's default, before any pragma of their own.
+// under the compiler's default, before any pragma of their own.  The Levenberg-Marquardt round they both run is
+// pose_lm_round.inc, which takes the contraction state of each file instead.
 #pragma once
 #include <math.h>
 

@@ -8,8 +8,12 @@
 // iterations x 2 callbacks.  Here one 256-thread workgroup keeps the problem
 // on chip: every evaluation is a block-wide pass over the observations
 // (residual, 2x6 Jacobian, Huber weight, 28 sums by one DPP pairing + LDS in a fixed
-// order, so results are run-to-run identical), lane 0 solves the damped 6x6 system by
-// LDL^T and drives g2o's published LM schedule.
+// order, so results are run-to-run identical), lanes 0..9 of wave 0 solve the damped 6x6 systems of
+// an iteration's ten trials by LDL^T and every thread follows g2o's published LM schedule.
+// The schedule - lambda0 and the iterations of one round of speculative Levenberg-Marquardt - is pose_lm_round.inc, the one copy
+// that pose_stereo.hip includes too; pose_lm_run.h holds the shared-memory block and the offsets clamp.  This file keeps what is
+// its own: the edge arithmetic with its explicit fma()s, how edges start active, how a round ends (the threshold on the chi2 it
+// already has), rounds == 0, staging, stats and the polled `done` word.
 //
 // Measured and dropped (round 3, tools/pose_lm_probe.py, profiles/r03_pose_lm.log): the whole refinement on ONE wave
 // for frames of <= 256 edges (up to 4 edges per lane in registers, no barrier at all, every lane running the solve
@@ -32,6 +36,7 @@
 #include "internal.h"
 #include <math.h>
 #include "pose_lm.h"
+#include "pose_lm_run.h"   // no contraction pragma in this file: pose_lm_round.inc is compiled under the compiler's default
 
 static_assert(SLAM_POSE_STAGE == 512, "host_calls.hip decides by it");
 #define PO_STAGE SLAM_POSE_STAGE  // observations kept in LDS (3 + 2 + 1 doubles and a flag each: 24.5 KiB)
@@ -100,7 +105,6 @@ __device__ __forceinline__ void po_evaluate(const double* T, const double* point
 // The robust cost of the active edges at up to PO_SPEC candidate poses in ONE block-wide pass (no Jacobians, no normal
 // equations): costs[j] for every j with solved[j].  Same per-edge arithmetic as po_evaluate; the sums travel through LDS
 // in the same rotated fixed order.
-#define PO_SPEC 9     // trials 1..9 of an iteration, evaluated together after trial 0 was turned down
 __device__ __forceinline__ void po_costs(const double* Tk /*[PO_SPEC][12]*/, const int* solved, const double* points,
                                          const double2* meas, const uint8_t* active, int O, po_cam cam, double delta,
                                          double* red, double* part, double* costs) {
@@ -120,21 +124,12 @@ __device__ __forceinline__ void po_costs(const double* Tk /*[PO_SPEC][12]*/, con
     po_block_sums<PO_SPEC>(acc, red, part, costs);
 }
 
-#define PO_TRIALS (PO_SPEC + 1)   // maxTrialsAfterFailure of g2o's Levenberg-Marquardt: ten trials per iteration
-
 struct po_shared {
-    double red[PO_TERMS * PO_RED_STRIDE];
-    double part[PO_TERMS * 8];
-    double sums[2][PO_TERMS];                       // the evaluation at the current pose / at the candidate: swapped, not copied
-    double T0[12], Tcur[12];
-    double pose[2][PO_TRIALS * 12];                 // the candidates of an iteration; the buffers alternate, so an accepted
-                                                    // candidate stays where it is and becomes the current pose by pointer
-    double scale_k[PO_TRIALS], cost_k[PO_SPEC];
-    int solved_k[PO_TRIALS];
+    po_lm_shared lm;
     int nactive;
 };
 
-// The LM loop proper.  Force-inlined into both call sites of the kernel so that the staged instance addresses
+// The rounds of one refinement (lambda0 and the iterations of a round are pose_lm_round.inc).  Force-inlined into both call sites of the kernel so that the staged instance addresses
 // points / meas / active / chi2 as LDS (ds_read) and the large-problem instance as global memory, instead of
 // both going through flat loads on generic pointers.
 //
@@ -150,10 +145,11 @@ __device__ __forceinline__ int po_run(po_shared& sh, const double* points, const
                                       double* chi2_a, double* chi2_b, int O, po_cam cam, po_params prm, int* accepted_out,
                                       const double** pose_out, double** chi2_out) {
     const int tid = threadIdx.x;
-    double* red = sh.red; double* part = sh.part;
-    double* cur = sh.sums[0]; double* cand = sh.sums[1];
-    const double* T0 = sh.T0;
-    const double* T = sh.Tcur;
+    po_lm_shared& lm = sh.lm;
+    double* red = lm.red; double* part = lm.part;
+    double* cur = lm.sums[0]; double* cand = lm.sums[1];
+    const double* T0 = lm.T0;
+    const double* T = lm.Tcur;
     double* chi2 = chi2_a; double* chi2_w = chi2_b;          // current pose's / where the next evaluation writes
     const bool two_chi2 = chi2_a != chi2_b;
     int p = 0, accepted = 0;
@@ -162,82 +158,19 @@ __device__ __forceinline__ int po_run(po_shared& sh, const double* points, const
     int nactive = O;
     double delta = prm.huber_delta;
     for (int round = 0; round < prm.rounds; round++) {
-        if (tid < 12) sh.Tcur[tid] = T0[tid];           // every round restarts from the frame's pose (frontend.py:360)
-        T = sh.Tcur;
+        if (tid < 12) lm.Tcur[tid] = T0[tid];           // every round restarts from the frame's pose (frontend.py:360)
+        T = lm.Tcur;
         __syncthreads();
         po_evaluate(T, points, meas, active, O, cam, delta, chi2_w, red, part, cur);
         { double* t = chi2; chi2 = chi2_w; chi2_w = t; }
-        double lambda, ni = 2.0;
-        {
-            double dmax = 0.0;
-            const int diag[6] = {0, 6, 11, 15, 18, 20};
-#pragma unroll
-            for (int i = 0; i < 6; i++) dmax = fmax(dmax, cur[diag[i]]);
-            lambda = 1e-5 * fmax(dmax, 1e-12);          // tau * max diagonal
-        }
-        for (int it = 0; it < prm.iterations && nactive > 0; it++) {
-            // ---- the ten trials of this iteration are PROPOSED together.  A trial that is turned down changes nothing but
-            // the damping (lambda *= ni, ni *= 2), so the candidates of all ten trials are known in advance: lane j of
-            // wave 0 solves with the damping trial j would meet and builds its pose - ten solves in the instruction stream
-            // of one.  Trial 0 is then evaluated in full (cost, H, b); only when it is turned down does ONE more pass give
-            // the costs of trials 1..9, and they are walked in order: the first one the sequential loop would have accepted
-            // is accepted, with the damping that loop would have had.  g2o's schedule ends every round on ten rejected
-            // trials (maxTrialsAfterFailure): ten sequential solve + evaluation pairs (38 us of a 67 us round at 200
-            // edges) become one solve and two passes.
-            double* cands = sh.pose[p];
-            if (tid < PO_TRIALS) {
-                double lam = lambda, n2 = ni;
-                for (int k = 0; k < tid; k++) { lam *= n2; n2 *= 2.0; }
-                double dx[6];
-                const bool ok_j = po_solve(cur, cur + 21, lam, dx);
-                double sc = 1e-3;
-                for (int i = 0; i < 6; i++) sc += dx[i] * (lam * dx[i] - cur[21 + i]);
-                sh.solved_k[tid] = ok_j ? 1 : 0;
-                if (ok_j) { po_apply_update(dx, T, cands + 12 * tid); sh.scale_k[tid] = sc; }
-            }
-            __syncthreads();
-            const int solved = sh.solved_k[0];          // read now: the next iteration's proposals overwrite them
-            const double scale = sh.scale_k[0];
-            if (solved) po_evaluate(cands, points, meas, active, O, cam, delta, chi2_w, red, part, cand);
-            const double rho0 = solved ? (cur[27] - cand[27]) / scale : -1.0;
-            if (solved && rho0 > 0.0 && isfinite(cand[27])) {
-                { double* t = cur; cur = cand; cand = t; }
-                { double* t = chi2; chi2 = chi2_w; chi2_w = t; }
-                T = cands;
-                p ^= 1;
-                const double g = 2.0 * rho0 - 1.0;
-                lambda *= fmax(1.0 / 3.0, fmin(1.0 - g * g * g, 2.0 / 3.0));
-                ni = 2.0;
-                accepted++;
-                continue;
-            }
-            lambda *= ni;
-            ni *= 2.0;
-            if (solved && !isfinite(lambda)) break;     // (an unsolvable system never ends the iteration by itself)
-            // ---- trial 0 was turned down: the costs of trials 1..9 in one pass
-            po_costs(cands + 12, sh.solved_k + 1, points, meas, active, O, cam, delta, red, part, sh.cost_k);
-            int taken = -1;
-            for (int j = 0; j < PO_SPEC; j++) {
-                if (sh.solved_k[j + 1]) {
-                    const double rho = (cur[27] - sh.cost_k[j]) / sh.scale_k[j + 1];
-                    if (rho > 0.0 && isfinite(sh.cost_k[j])) {
-                        const double g = 2.0 * rho - 1.0;
-                        lambda *= fmax(1.0 / 3.0, fmin(1.0 - g * g * g, 2.0 / 3.0));
-                        ni = 2.0;
-                        taken = j + 1;
-                        break;
-                    }
-                }
-                lambda *= ni;
-                ni *= 2.0;
-                if (sh.solved_k[j + 1] && !isfinite(lambda)) break;
-            }
-            if (taken < 0) break;                       // ten trials turned down (or the damping overflowed): the round's iterations end
-            accepted++;
-            T = cands + 12 * taken;
-            p ^= 1;
-            po_evaluate(T, points, meas, active, O, cam, delta, chi2_w, red, part, cur);   // H, b, cost at the accepted pose
-            { double* t = chi2; chi2 = chi2_w; chi2_w = t; }
+        {   // lambda0 and the iterations: the one copy that pose_stereo.hip includes too, here under the compiler's default contraction
+#define PO_LM_EVALUATE(T_, out_) po_evaluate(T_, points, meas, active, O, cam, delta, chi2_w, red, part, out_)
+#define PO_LM_COSTS(Tk_, solved_, out_) po_costs(Tk_, solved_, points, meas, active, O, cam, delta, red, part, out_)
+#define PO_LM_CURRENT() do { double* t = chi2; chi2 = chi2_w; chi2_w = t; } while (0)
+#include "pose_lm_round.inc"
+#undef PO_LM_EVALUATE
+#undef PO_LM_COSTS
+#undef PO_LM_CURRENT
         }
         // chi2 at the pose this round ended on, then the outlier / level decision (frontend.py:366-379)
         if (!two_chi2) po_evaluate(T, points, meas, active, O, cam, delta, chi2, red, part, cand);
@@ -273,12 +206,11 @@ __global__ __launch_bounds__(PO_THREADS) void pose_opt_kernel(const double* __re
                                                               unsigned int* __restrict__ index_errors,
                                                               unsigned* __restrict__ done, unsigned epoch) {
     if (offsets) {
-        // O is the length of the concatenated arrays here.  A table that is not ascending or leaves [0, O] is the
-        // caller's bug; it is reported (slam_index_errors) and the frame shrinks to what lies inside, never a wild access.
-        const int b = blockIdx.x, total = O, lo = offsets[b], hi = offsets[b + 1];
-        const int first = min(max(lo, 0), total), last = min(max(hi, first), total);
-        if ((first != lo || last != hi) && threadIdx.x == 0) atomicAdd(index_errors, 1u);
-        O = last - first;
+        // O is the length of the concatenated arrays here
+        const int b = blockIdx.x;
+        const po_range r = po_frame_range(offsets, b, O, index_errors);
+        const int first = r.first;
+        O = r.count;
         pose_in += 12 * b; pose_out += 12 * b; stats += 2 * b;
         g_points += 3 * (size_t)first; g_meas += first; g_active += first; g_chi2 += first;
     }
@@ -290,10 +222,10 @@ __global__ __launch_bounds__(PO_THREADS) void pose_opt_kernel(const double* __re
     __shared__ uint8_t s_active[PO_STAGE];
     __shared__ po_shared sh;
     const int tid = threadIdx.x;
-    if (tid < 12) sh.T0[tid] = sh.Tcur[tid] = pose_in[tid];
+    if (tid < 12) sh.lm.T0[tid] = sh.lm.Tcur[tid] = pose_in[tid];
     if (tid == 0) sh.nactive = 0;
     int nactive, accepted = 0;
-    const double* pose = sh.Tcur;
+    const double* pose = sh.lm.Tcur;
     double* chi2 = nullptr;
     if (O <= PO_STAGE) {
         for (int i = tid; i < O * 3; i += PO_THREADS) s_points[i] = g_points[i];

@@ -2,16 +2,17 @@
 // (EdgeSE3ProjectXYZOnlyPose) and stereo (EdgeStereoSE3ProjectXYZOnlyPose) edges mixed, every edge weighted by its
 // information (1 / scale[level]^2), the chi2 gate and the Huber width chosen by the kind of the edge.
 //
-// The kernel is pose_opt.hip's with the edge model of stereo_edge.h under it: one workgroup of 256 threads per frame, the
-// frame's edges staged in LDS up to SLAM_POSE_STEREO_STAGE, 28 sums per evaluation through po_block_sums (a third residual row
-// adds terms to the sums, not sums), lanes 0..9 of wave 0 proposing the ten trials of an iteration together, the same
-// Levenberg-Marquardt schedule (pose_lm.h holds what the two files share: update, solve, block sums).  What differs from
-// pose_opt.hip besides the model:
-//   - the whole file is compiled without contraction (stereo_edge.h asks for it), so the evaluation and the cost-only pass
-//     round alike because they call the same text, not because every fma is written out;
+// One workgroup of 256 threads per frame, the frame's edges staged in LDS up to SLAM_POSE_STEREO_STAGE, 28 sums per evaluation
+// through po_block_sums (a third residual row adds terms to the sums, not sums).  The Levenberg-Marquardt round - lanes 0..9 of
+// wave 0 proposing the ten trials of an iteration together, trial 0 evaluated in full, trials 1..9 by one cost-only pass - is
+// pose_lm_round.inc, the one copy that pose_opt.hip includes too; pose_lm_run.h holds its shared-memory block and the offsets
+// clamp, pose_lm.h the update, the solve and the block sums.  What is this file's own:
+//   - the edge model (stereo_edge.h), and the whole file compiled without contraction (stereo_edge.h asks for it; the round is
+//     included behind the pragma), so the evaluation and the cost-only pass round alike because they call the same text, not
+//     because every fma is written out;
 //   - a round ends with a classification pass of its own over ALL edges (weighted chi2 without the kernel, information,
-//     Z > 0: se_inlier), which recomputes the active set - an edge may come back - and leaves chi2 per edge; one chi2 buffer
-//     instead of two, four cheap passes more per call;
+//     Z > 0: se_inlier), which recomputes the active set - an edge may come back - and leaves chi2 per edge; one chi2 buffer,
+//     so nothing happens when an evaluation becomes the current one;
 //   - an edge with information 0 is never active; a frame whose edges are all switched off returns pose_in.
 // Deviations from ORB-SLAM: the Z > 0 test is part of the classification here too (ORB-SLAM applies it in the bundle
 // adjustment only), there is no early exit below ten edges, and the order of the edges is the caller's.
@@ -24,9 +25,9 @@
 #pragma clang fp contract(off)
 #include "stereo_edge.h"
 
+#include "pose_lm_run.h"
+
 #define PS_STAGE SLAM_POSE_STEREO_STAGE   // edges kept in LDS: 3 + 3 + 1 + 1 doubles and a flag each (32.5 KiB at 512)
-#define PS_SPEC 9                         // trials 1..9 of an iteration, evaluated together after trial 0 was turned down
-#define PS_TRIALS (PS_SPEC + 1)           // maxTrialsAfterFailure of g2o's Levenberg-Marquardt
 
 struct ps_params {
     int rounds, iterations;
@@ -66,35 +67,29 @@ __device__ __forceinline__ void ps_evaluate(const double* T, const ps_edges& g, 
     po_block_sums<PO_TERMS>(acc, red, part, out);
 }
 
-// The robust cost of the active edges at up to PS_SPEC candidate poses in one pass: costs[j] for every j with solved[j].
-__device__ __forceinline__ void ps_costs(const double* Tk /*[PS_SPEC][12]*/, const int* solved, const ps_edges& g, const se_cam& cam,
+// The robust cost of the active edges at up to PO_SPEC candidate poses in one pass: costs[j] for every j with solved[j].
+__device__ __forceinline__ void ps_costs(const double* Tk /*[PO_SPEC][12]*/, const int* solved, const ps_edges& g, const se_cam& cam,
                                          const se_huber& hub, double* red, double* part, double* costs) {
-    double acc[PS_SPEC];
+    double acc[PO_SPEC];
 #pragma unroll
-    for (int j = 0; j < PS_SPEC; j++) acc[j] = 0.0;
+    for (int j = 0; j < PO_SPEC; j++) acc[j] = 0.0;
     for (int o = threadIdx.x; o < g.O; o += PO_THREADS) {
         if (!g.active[o]) continue;
         const double p[3] = {g.points[3 * o], g.points[3 * o + 1], g.points[3 * o + 2]};
         const double mu = g.meas3[3 * o], mv = g.meas3[3 * o + 1], mr = g.meas3[3 * o + 2], s = g.info[o];
 #pragma unroll
-        for (int j = 0; j < PS_SPEC; j++) {
+        for (int j = 0; j < PO_SPEC; j++) {
             if (!solved[j]) continue;                                   // block-uniform
             se_res r;
             se_residual(Tk + 12 * j, p, mu, mv, mr, s, cam, hub, r);
             acc[j] += r.rho;
         }
     }
-    po_block_sums<PS_SPEC>(acc, red, part, costs);
+    po_block_sums<PO_SPEC>(acc, red, part, costs);
 }
 
 struct ps_shared {
-    double red[PO_TERMS * PO_RED_STRIDE];
-    double part[PO_TERMS * 8];
-    double sums[2][PO_TERMS];                       // the evaluation at the current pose / at the candidate: swapped, not copied
-    double T0[12], Tcur[12];
-    double pose[2][PS_TRIALS * 12];                 // the candidates of an iteration; the buffers alternate
-    double scale_k[PS_TRIALS], cost_k[PS_SPEC];
-    int solved_k[PS_TRIALS];
+    po_lm_shared lm;
     int count[3];                                   // inliers, stereo inliers (a classification), edges with s > 0 (once)
 };
 
@@ -119,15 +114,16 @@ __device__ __forceinline__ void ps_classify(ps_shared& sh, const double* T, cons
     __syncthreads();
 }
 
-// The LM loop proper, pose_opt.hip's po_run on the edges above.  Force-inlined into both call sites so that the staged instance
+// The rounds of one refinement on the edges above; the LM round proper is pose_lm_round.inc.  Force-inlined into both call sites so that the staged instance
 // addresses the edges as LDS and the large-frame instance as global memory.  The Levenberg-Marquardt state lives in registers
 // of every thread: all threads read the same sums behind the same barrier and take the same decision.
 __device__ __forceinline__ const double* ps_run(ps_shared& sh, const ps_edges& g, const se_cam& cam, const ps_params& prm,
                                                 unsigned int* index_errors, int* accepted_out) {
     const int tid = threadIdx.x;
-    double* red = sh.red; double* part = sh.part;
-    double* cur = sh.sums[0]; double* cand = sh.sums[1];
-    const double* T = sh.Tcur;
+    po_lm_shared& lm = sh.lm;
+    double* red = lm.red; double* part = lm.part;
+    double* cur = lm.sums[0]; double* cand = lm.sums[1];
+    const double* T = lm.Tcur;
     int p = 0, accepted = 0;
     {   // every edge with an information starts active; an information that is none is counted and taken as 0
         int mine = 0, bad = 0;
@@ -145,73 +141,18 @@ __device__ __forceinline__ const double* ps_run(ps_shared& sh, const ps_edges& g
     int nactive = sh.count[2];
     se_huber hub = prm.hub;
     for (int round = 0; round < prm.rounds; round++) {
-        if (tid < 12) sh.Tcur[tid] = sh.T0[tid];        // every round restarts from the frame's pose
-        T = sh.Tcur;
+        if (tid < 12) lm.Tcur[tid] = lm.T0[tid];        // every round restarts from the frame's pose
+        T = lm.Tcur;
         __syncthreads();
         ps_evaluate(T, g, cam, hub, red, part, cur);
-        double lambda, ni = 2.0;
-        {
-            double dmax = 0.0;
-            const int diag[6] = {0, 6, 11, 15, 18, 20};
-#pragma unroll
-            for (int i = 0; i < 6; i++) dmax = fmax(dmax, cur[diag[i]]);
-            lambda = 1e-5 * fmax(dmax, 1e-12);          // tau * max diagonal
-        }
-        for (int it = 0; it < prm.iterations && nactive > 0; it++) {
-            // the ten trials of this iteration are proposed together: a trial that is turned down changes nothing but the
-            // damping, so lane j of wave 0 solves with the damping trial j would meet (pose_opt.hip)
-            double* cands = sh.pose[p];
-            if (tid < PS_TRIALS) {
-                double lam = lambda, n2 = ni;
-                for (int k = 0; k < tid; k++) { lam *= n2; n2 *= 2.0; }
-                double dx[6];
-                const bool ok_j = po_solve(cur, cur + 21, lam, dx);
-                double sc = 1e-3;
-                for (int i = 0; i < 6; i++) sc += dx[i] * (lam * dx[i] - cur[21 + i]);
-                sh.solved_k[tid] = ok_j ? 1 : 0;
-                if (ok_j) { po_apply_update(dx, T, cands + 12 * tid); sh.scale_k[tid] = sc; }
-            }
-            __syncthreads();
-            const int solved = sh.solved_k[0];          // read now: the next iteration's proposals overwrite them
-            const double scale = sh.scale_k[0];
-            if (solved) ps_evaluate(cands, g, cam, hub, red, part, cand);
-            const double rho0 = solved ? (cur[27] - cand[27]) / scale : -1.0;
-            if (solved && rho0 > 0.0 && isfinite(cand[27])) {
-                { double* t = cur; cur = cand; cand = t; }
-                T = cands;
-                p ^= 1;
-                const double gq = 2.0 * rho0 - 1.0;
-                lambda *= fmax(1.0 / 3.0, fmin(1.0 - gq * gq * gq, 2.0 / 3.0));
-                ni = 2.0;
-                accepted++;
-                continue;
-            }
-            lambda *= ni;
-            ni *= 2.0;
-            if (solved && !isfinite(lambda)) break;     // (an unsolvable system never ends the iteration by itself)
-            // trial 0 was turned down: the costs of trials 1..9 in one pass, walked in order
-            ps_costs(cands + 12, sh.solved_k + 1, g, cam, hub, red, part, sh.cost_k);
-            int taken = -1;
-            for (int j = 0; j < PS_SPEC; j++) {
-                if (sh.solved_k[j + 1]) {
-                    const double rho = (cur[27] - sh.cost_k[j]) / sh.scale_k[j + 1];
-                    if (rho > 0.0 && isfinite(sh.cost_k[j])) {
-                        const double gq = 2.0 * rho - 1.0;
-                        lambda *= fmax(1.0 / 3.0, fmin(1.0 - gq * gq * gq, 2.0 / 3.0));
-                        ni = 2.0;
-                        taken = j + 1;
-                        break;
-                    }
-                }
-                lambda *= ni;
-                ni *= 2.0;
-                if (sh.solved_k[j + 1] && !isfinite(lambda)) break;
-            }
-            if (taken < 0) break;                       // ten trials turned down (or the damping overflowed)
-            accepted++;
-            T = cands + 12 * taken;
-            p ^= 1;
-            ps_evaluate(T, g, cam, hub, red, part, cur);   // H, b, cost at the accepted pose
+        {   // lambda0 and the iterations: the one copy that pose_opt.hip includes too, here behind contract(off)
+#define PO_LM_EVALUATE(T_, out_) ps_evaluate(T_, g, cam, hub, red, part, out_)
+#define PO_LM_COSTS(Tk_, solved_, out_) ps_costs(Tk_, solved_, g, cam, hub, red, part, out_)
+#define PO_LM_CURRENT() ((void)0)
+#include "pose_lm_round.inc"
+#undef PO_LM_EVALUATE
+#undef PO_LM_COSTS
+#undef PO_LM_CURRENT
         }
         ps_classify(sh, T, g, cam, prm.gate);           // the active set of the next round, from ALL edges
         nactive = sh.count[0];
@@ -229,12 +170,9 @@ __global__ __launch_bounds__(PO_THREADS) void pose_stereo_kernel(const double* _
                                                                  double* __restrict__ pose_out, uint8_t* __restrict__ g_active,
                                                                  double* __restrict__ g_chi2, int* __restrict__ stats,
                                                                  unsigned int* __restrict__ index_errors) {
-    // A table that is not ascending or leaves [0, total] is the caller's bug; it is reported (slam_index_errors) and the frame
-    // shrinks to what lies inside, never a wild access.
-    const int b = blockIdx.x, lo = offsets[b], hi = offsets[b + 1];
-    const int first = min(max(lo, 0), total), last = min(max(hi, first), total);
-    if ((first != lo || last != hi) && threadIdx.x == 0) atomicAdd(index_errors, 1u);
-    const int O = last - first;
+    const int b = blockIdx.x;
+    const po_range r = po_frame_range(offsets, b, total, index_errors);
+    const int first = r.first, O = r.count;
     pose_in += 12 * (size_t)b; pose_out += 12 * (size_t)b; stats += 4 * (size_t)b;
     g_points += 3 * (size_t)first; g_meas3 += 3 * (size_t)first; g_info += first; g_active += first; g_chi2 += first;
     __shared__ double s_points[PS_STAGE * 3];
@@ -244,7 +182,7 @@ __global__ __launch_bounds__(PO_THREADS) void pose_stereo_kernel(const double* _
     __shared__ uint8_t s_active[PS_STAGE];
     __shared__ ps_shared sh;
     const int tid = threadIdx.x;
-    if (tid < 12) sh.T0[tid] = sh.Tcur[tid] = pose_in[tid];
+    if (tid < 12) sh.lm.T0[tid] = sh.lm.Tcur[tid] = pose_in[tid];
     if (tid < 3) sh.count[tid] = 0;
     int accepted = 0;
     const double* pose;

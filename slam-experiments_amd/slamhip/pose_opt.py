@@ -18,11 +18,11 @@ the residual/Jacobian arithmetic underneath is what the parity tests cover.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
 
+from ._frames import PoseOptResult, pose_rows, refine_frames
 from .device import Context, default_context
 from .reproj import PoseOnlyProblem
 
@@ -59,15 +59,6 @@ def _robust_chi2(chi2: np.ndarray, delta: float) -> float:
         return float(chi2.sum())
     e = np.sqrt(chi2)
     return float(np.where(e <= delta, chi2, 2 * delta * e - delta * delta).sum())
-
-
-@dataclass
-class PoseOptResult:
-    pose: np.ndarray          # 4x4 Tcw after the last round
-    inliers: np.ndarray       # bool [O]: chi2 <= threshold after the last round
-    chi2: np.ndarray          # [O] at the returned pose
-    n_inliers: int            # what _correct_current_pose returns (frontend.py:393)
-    iterations: int           # accepted LM steps over all rounds
 
 
 def _lm_round(prob: PoseOnlyProblem, T: np.ndarray, active: np.ndarray, delta: float, iterations: int):
@@ -184,45 +175,20 @@ def optimize_poses_batch(poses, points_list, meas_list, intrinsics, rounds: int 
     from ._lib import check
 
     ctx = ctx or default_context()
-    P = np.asarray(poses, np.float64)
-    B = P.shape[0]
+    B = np.asarray(poses).shape[0]
     if len(points_list) != B or len(meas_list) != B:
         raise ValueError("one point array and one pixel array per pose")
     if B == 0:
         return []
-    pin = np.ascontiguousarray(P.reshape(B, -1, 4)[:, :3, :4].reshape(B, 12))
     pts = [np.ascontiguousarray(p, np.float64).reshape(-1, 3) for p in points_list]
     mes = [np.ascontiguousarray(m, np.float64).reshape(-1, 2) for m in meas_list]
     if any(p.shape[0] != m.shape[0] for p, m in zip(pts, mes)):
         raise ValueError("one measurement per point in every frame")
-    off = np.zeros(B + 1, np.int32)
-    off[1:] = np.cumsum([p.shape[0] for p in pts])
-    O = int(off[-1])
     fx, fy, cx, cy = (float(v) for v in intrinsics)
-    bufs = []
-    try:
-        d_pose = ctx.upload(pin); bufs.append(d_pose)
-        d_pts = ctx.upload(np.concatenate(pts) if O else np.zeros((1, 3))); bufs.append(d_pts)
-        d_mes = ctx.upload(np.concatenate(mes) if O else np.zeros((1, 2))); bufs.append(d_mes)
-        d_off = ctx.upload(off); bufs.append(d_off)
-        d_out = ctx.malloc(B * 96); bufs.append(d_out)
-        d_inl = ctx.malloc(max(O, 1)); bufs.append(d_inl)
-        d_chi = ctx.malloc(max(O, 1) * 8); bufs.append(d_chi)
-        d_st = ctx.malloc(B * 8); bufs.append(d_st)
-        check(ctx.lib.slam_pose_optimize_batch_f64(ctx.handle, B, d_pose.ptr, d_pts.ptr, d_mes.ptr, d_off.ptr, O, fx, fy, cx, cy,
+
+    def call(d_pose, d_cols, d_off, O, d_out, d_inl, d_chi, d_st):
+        check(ctx.lib.slam_pose_optimize_batch_f64(ctx.handle, B, d_pose.ptr, d_cols[0].ptr, d_cols[1].ptr, d_off.ptr, O, fx, fy, cx, cy,
                                                    int(rounds), int(iterations), float(chi2_threshold), float(huber_delta),
                                                    d_out.ptr, d_inl.ptr, d_chi.ptr, d_st.ptr))
-        out = d_out.download(np.float64, (B, 3, 4))
-        inl = d_inl.download(np.uint8, (max(O, 1),)).astype(bool)
-        chi = d_chi.download(np.float64, (max(O, 1),))
-        st = d_st.download(np.int32, (B, 2))
-    finally:
-        for b in bufs:
-            b.free()
-    res = []
-    for b in range(B):
-        T = np.eye(4)
-        T[:3, :4] = out[b]
-        a, e = int(off[b]), int(off[b + 1])
-        res.append(PoseOptResult(pose=T, inliers=inl[a:e].copy(), chi2=chi[a:e].copy(), n_inliers=int(st[b, 0]), iterations=int(st[b, 1])))
-    return res
+
+    return refine_frames(ctx, pose_rows(poses), [p.shape[0] for p in pts], [(pts, 3), (mes, 2)], 2, call)[0]

@@ -13,12 +13,12 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from ._frames import pose_rows, refine_frames
 from ._lib import check
 from .ba import BAResult, fixed_pose_mask, lm_schedule, state_arrays
 from .ba_sparse import DEFAULT_PCG_TOL, SparseBAProblem, _deltas, _stereo_arrays
 from .device import Context, default_context
 from .pose_graph import DEFAULT_PCG_MAX_ITER, _check_solver_args
-from .pose_opt import PoseOptResult
 
 CHI2_MONO, CHI2_STEREO = 5.991, 7.815                     # the 95 % quantiles of chi-square with 2 and 3 degrees of freedom
 DELTA_MONO, DELTA_STEREO = CHI2_MONO ** 0.5, CHI2_STEREO ** 0.5
@@ -114,8 +114,7 @@ def optimize_poses_stereo(poses, points_list, edges_list, intrinsics, bf, rounds
     weighted chi2, Huber widths their square roots, dropped after round index 2.  Returns a list of ``PoseOptResult`` (chi2: the
     weighted chi2; inliers: information > 0, positive depth and the gate of the edge's kind).  ``stats_out``, when a list, receives
     the int32 [B,4] table {inliers, accepted steps, stereo inliers, edges with information > 0}."""
-    P = np.asarray(poses, np.float64)
-    B = P.shape[0]
+    B = np.asarray(poses).shape[0]
     if len(points_list) != B or len(edges_list) != B:
         raise ValueError("one point array and one set of edges per pose")
     fx, fy, cx, cy, bf, gm, gs, (dm, ds) = _model_args(intrinsics, bf, gates, deltas)
@@ -124,42 +123,21 @@ def optimize_poses_stereo(poses, points_list, edges_list, intrinsics, bf, rounds
             raise ValueError(f"{name} must be an integer in [0, {hi}]")
     if B == 0:
         return []
-    pin = np.ascontiguousarray(P.reshape(B, -1, 4)[:, :3, :4].reshape(B, 12))
     pts = [np.ascontiguousarray(p, np.float64).reshape(-1, 3) for p in points_list]
     arr = [_stereo_arrays(e, len(p)) for e, p in zip(edges_list, pts)]
     if any(a[2] != bf for a in arr):
         raise ValueError("every set of edges must carry the bf of the call")
-    off = np.zeros(B + 1, np.int32)
-    off[1:] = np.cumsum([p.shape[0] for p in pts])
-    O = int(off[-1])
     ctx = ctx or default_context()
-    bufs = []
-    try:
-        up = lambda a: bufs.append(ctx.upload(a)) or bufs[-1]          # noqa: E731
-        new = lambda n: bufs.append(ctx.malloc(n)) or bufs[-1]         # noqa: E731
-        d_pose, d_off = up(pin), up(off)
-        d_pts = up(np.concatenate(pts) if O else np.zeros((1, 3)))
-        d_mes = up(np.concatenate([a[0] for a in arr]) if O else np.zeros((1, 3)))
-        d_inf = up(np.concatenate([a[1] for a in arr]) if O else np.zeros(1))
-        d_out, d_inl, d_chi, d_st = new(B * 96), new(max(O, 1)), new(max(O, 1) * 8), new(B * 16)
-        check(ctx.lib.slam_pose_optimize_stereo_batch_f64(ctx.handle, B, d_pose.ptr, d_pts.ptr, d_mes.ptr, d_inf.ptr, d_off.ptr, O, fx, fy, cx,
-                                                          cy, bf, int(rounds), int(iterations), gm, gs, dm, ds, d_out.ptr, d_inl.ptr,
+
+    def call(d_pose, d_cols, d_off, O, d_out, d_inl, d_chi, d_st):
+        check(ctx.lib.slam_pose_optimize_stereo_batch_f64(ctx.handle, B, d_pose.ptr, d_cols[0].ptr, d_cols[1].ptr, d_cols[2].ptr, d_off.ptr, O, fx,
+                                                          fy, cx, cy, bf, int(rounds), int(iterations), gm, gs, dm, ds, d_out.ptr, d_inl.ptr,
                                                           d_chi.ptr, d_st.ptr))
-        out = d_out.download(np.float64, (B, 3, 4))
-        inl = d_inl.download(np.uint8, (max(O, 1),)).astype(bool)
-        chi = d_chi.download(np.float64, (max(O, 1),))
-        st = d_st.download(np.int32, (B, 4))
-    finally:
-        for b in bufs:
-            b.free()
+
+    res, st = refine_frames(ctx, pose_rows(poses), [p.shape[0] for p in pts], [(pts, 3), ([a[0] for a in arr], 3), ([a[1] for a in arr], 1)], 4,
+                            call)
     if stats_out is not None:
         stats_out.append(st)
-    res = []
-    for b in range(B):
-        T = np.eye(4)
-        T[:3, :4] = out[b]
-        a, e = int(off[b]), int(off[b + 1])
-        res.append(PoseOptResult(pose=T, inliers=inl[a:e].copy(), chi2=chi[a:e].copy(), n_inliers=int(st[b, 0]), iterations=int(st[b, 1])))
     return res
 
 

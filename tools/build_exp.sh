@@ -83,7 +83,7 @@ EOF
     exit 0
 fi
 # tools/build_exp.sh bas-mutants: ten copies of the library, each with ONE deliberate mistake in a temporary copy of
-# ba_sparse.hip or of the ba_common.h it includes (strides, skips, a comparison and an index that stays inside its array: no
+# ba_sparse.hip or of the ba_common.h / ba_sparse_phases.h it includes (strides, skips, a comparison and an index that stays inside its array: no
 # mutant can leave an array), to show that tests/test_ba_sparse_edges_gpu.py sees it.  Each is run on the narrowest test
 # (profiles/ba_sparse_edges_mutants.log names it):
 #     SLAMHIP_TEST_LIB=tools/exp/libslamhip_basmut1.so python -m pytest -m gpu tests/test_ba_sparse_edges_gpu.py -k long-delta5
@@ -91,7 +91,7 @@ if [ "${1:-}" = "bas-mutants" ]; then
     python3 - "$SRC" "$TMP" <<'EOF'
 import os, sys
 src, tmp = sys.argv[1], sys.argv[2]
-hip, hdr = open(f"{src}/ba_sparse.hip").read(), open(f"{src}/ba_common.h").read()
+hip, hdr, phases = open(f"{src}/ba_sparse.hip").read(), open(f"{src}/ba_common.h").read(), open(f"{src}/ba_sparse_phases.h").read()
 loop = "for (int i = a0 + (int)threadIdx.x; i < a1; i += BA_THREADS) {"
 once = "for (int i = a0 + (int)threadIdx.x; i < a1; i = a1) {"
 
@@ -103,9 +103,9 @@ def nth(text, old, new, n, times):
 
 
 mutants = {
-    1: ("hip", lambda s: nth(s, loop, once, 0, 3)),                                               # bas_pose_kernel: one trip of its loop
-    2: ("hip", lambda s: nth(s, loop, once, 1, 3)),                                               # bas_cost_kernel: one trip
-    3: ("hip", lambda s: nth(s, loop, once, 2, 3)),                                               # bas_diag_kernel: one trip
+    1: ("phases", lambda s: nth(s, loop, once, 0, 2)),                                            # bas_pose_kernel: one trip of its loop
+    2: ("phases", lambda s: nth(s, loop, once, 1, 2)),                                            # bas_cost_kernel: one trip
+    3: ("hip", lambda s: nth(s, loop, once, 0, 1)),                                               # bas_diag_kernel: one trip
     4: ("hip", lambda s: nth(s, "p < p1; p += 64)", "p < p1; p += 32)", 0, 1)),                   # edge lanes stride 32: pairs taken twice
     5: ("hdr", lambda s: nth(s, " + sw[2][threadIdx.x]) + sw[3][threadIdx.x];", " + sw[2][threadIdx.x]);", 0, 1)),   # ba_block_sum drops wave 3
     6: ("hip", lambda s: nth(s, "        if (fixed[k]) continue;\n", "", 0, 1)),                  # finish: a fixed pose's diagonal in the maximum
@@ -118,6 +118,7 @@ for k, (which, f) in mutants.items():
     os.makedirs(f"{tmp}/bas{k}")                       # ba_sparse.hip includes "ba_common.h": the copy beside it wins
     open(f"{tmp}/bas{k}/ba_sparse.hip", "w").write(f(hip) if which == "hip" else hip)
     open(f"{tmp}/bas{k}/ba_common.h", "w").write(f(hdr) if which == "hdr" else hdr)
+    open(f"{tmp}/bas{k}/ba_sparse_phases.h", "w").write(f(phases) if which == "phases" else phases)
 EOF
     BAS_OBJS=$(ls "$ROOT"/slam-experiments_amd/lib/obj/*.o | grep -v "/ba_sparse.o")
     for k in 1 2 3 4 5 6 7 8 9 10; do
