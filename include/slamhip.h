@@ -1835,6 +1835,50 @@ SLAM_API int slam_lmap_cull_count(slam_ctx* ctx, int64_t C, const int32_t* h_can
                                   const int64_t* d_frame_offsets, const int32_t* d_frame_points, const int32_t* d_level,
                                   const uint8_t* d_frame_removed, int th_obs, int max_list, void* d_ws, int32_t* d_counts, uint8_t* d_flags);
 
+/* ---- loop and relocalisation candidates (loop_detect.hip) ------------------------------------------------------
+ * The covisibility-group stage of ORB-SLAM's KeyFrameDatabase::DetectLoopCandidates and DetectRelocalizationCandidates for Q
+ * queries over E database entries (entry id = keyframe index), on tables that stay on the device.  The reference detects no
+ * loops: there is no call site to compare with, PARITY UNPINNED (as for the bag-of-words database, 4j).
+ *   d_s uint32 [Q,E] and d_common int32 [Q,E]: the dense form of slam_bow_query.
+ *   d_best int32 [E,nb], 0 <= nb <= 16: row i = GetBestCovisibilityKeyFrames(nb) of keyframe i, padded with -1.  A negative
+ *   entry is padding; an entry >= E in the row of a candidate is skipped and counted (slam_index_errors).  The table is the
+ *   caller's: a row that repeats an id or names itself is summed as written.
+ *   d_excl [h_excl_offsets[q] .. h_excl_offsets[q+1]): the excluded entries of query q - its connected keyframes and itself;
+ *   ids outside [0, E) are skipped and counted.  h_own int32 [Q]: the query's own entry, -1 for a frame not in the database.
+ *   h_limit int32 [Q], each in [0, E], or null (E for every query): entries with id >= limit are excluded as well, so that a
+ *   trajectory can be replayed in one call, each keyframe seeing only its past.
+ *   h_min_s uint32 [Q]: a threshold on s, or 0xFFFFFFFF = derive it: the least d_s[q,j] over the excluded j in [0, E) other
+ *   than h_own[q], and 2^31 (a score of 1) when there is none - ORB-SLAM's minScore.  Null: derived for every query.
+ *   mode 0 = loop; 1 = relocalisation: no excluded list, min_s = 0 (d_excl, h_excl_offsets, h_own and h_min_s are not read).
+ * Per query q:
+ *   1. shares(i): i is not excluded, i < limit and common[i] > 0.
+ *   2. cmax = the maximum of common over those entries; words_ok(i): shares(i) and 5 common[i] > 4 cmax (for
+ *      1 <= c <= cmax <= 8192 the same as ORB-SLAM's c > int(0.8f cmax)).
+ *   3. i is a candidate when words_ok(i) and s[i] >= min_s.
+ *   4. acc[i] (64 bits) = s[i] + the sum of s[j] over the j of d_best[i] with words_ok(j) - the word filter only, not min_s.
+ *   5. gbest[i] = the entry of greatest s among i and those j; on ties the candidate itself, then the earlier position.
+ *   6. acc_max = the maximum of acc over the candidates; candidate i is retained when 4 acc[i] > 3 acc_max.
+ *   7. The result is the set {gbest[i] : i retained}: no duplicates, ascending by id, each member with its own s.
+ * With cmax = 0 or no candidate the result is empty.  Integers only; atomics take a maximum, set bits or count, so two runs
+ * give the same bytes.  The workspace is the caller's.  Limits: Q <= 65535, 1 <= E <= 2^24. */
+/* h_limits [4] = {threads of a workgroup, entries of a tile over E, the largest nb, the largest Q}; needs no device */
+SLAM_API int slam_loop_limits(int32_t* h_limits);
+/* *h_bytes = the workspace of slam_loop_candidates / slam_loop_fill for Q queries over E entries (the excluded lists are the
+ * caller's d_excl); needs no device */
+SLAM_API int slam_loop_workspace(int64_t Q, int64_t E, uint64_t* h_bytes);
+/* Steps 1 - 6 and the mark of step 7: d_acc uint64 [Q,E] and d_gbest int32 [Q,E] (0 and -1 where i is no candidate), d_bitmap
+ * uint32 [Q, ceil(E / 32)] the result set.  Waits, and returns h_counts int64 [Q], the members per query, and *h_skipped (may
+ * be null), the ids this call skipped and counted. */
+SLAM_API int slam_loop_candidates(slam_ctx* ctx, int64_t Q, int64_t E, const uint32_t* d_s, const int32_t* d_common, int nb, const int32_t* d_best,
+                                  const int32_t* d_excl, const int64_t* h_excl_offsets, const int32_t* h_own, const int32_t* h_limit,
+                                  const uint32_t* h_min_s, int mode, void* d_ws, uint64_t* d_acc, int32_t* d_gbest, uint32_t* d_bitmap,
+                                  int64_t* h_counts, int64_t* h_skipped);
+/* The fill of step 7: the members of query q, ascending, to d_ids [h_out_offsets[q], ...) and their s to d_scores, never past
+ * h_out_offsets[q+1]; asynchronous on the ctx stream.  The workspace and the bitmap must live from slam_loop_candidates until
+ * the fill has run. */
+SLAM_API int slam_loop_fill(slam_ctx* ctx, int64_t Q, int64_t E, const uint32_t* d_s, const uint32_t* d_bitmap, void* d_ws,
+                            const int64_t* h_out_offsets, int32_t* d_ids, uint32_t* d_scores);
+
 /* ---- multi-GPU: RCCL all-gather of per-shard result rows ---------------- */
 #define SLAM_COMM_ID_BYTES 128
 SLAM_API int slam_comm_version(int* version); /* ncclGetVersion of the librccl that was loaded (e.g. 22703); needs no GPU */

@@ -29,6 +29,7 @@ from slamhip import bow_match as _bm
 from slamhip import camera as _cam
 from slamhip import fuse as _fz
 from slamhip import local_map as _lm
+from slamhip import loop_detect as _ld
 from slamhip import proj_match as _pm
 from slamhip import tri_match as _tm
 from slamhip import pnp as _pnp
@@ -177,6 +178,21 @@ class Backend:
         ``min_score`` are returned as (ids, scores) by (score descending, id ascending) - the candidates ``relocalize`` and
         ``estimate_sim3_batch`` take."""
         return _bow.detect_loop_candidates(db, vector, connected, min_score)
+
+    def detect_loop(self, db, vectors, graph_or_best_table, connected=None, own_ids=None, limit=None, min_score=None, nb: int = 10):
+        """ORB-SLAM's whole ``DetectLoopCandidates`` for Q BoW ``vectors`` at once (the reference detects no loops): the dense
+        query and the covisibility-group stage stay on the device - per query the entries that are not ``connected`` (nor
+        ``own_ids``), lie below ``limit``, share more than 0.8 of the largest shared-word count and score at least
+        ``min_score`` (None: the lowest score against the connected keyframes) are summed with their ``nb`` best covisibles,
+        the groups within 0.75 of the best are kept and each gives its best-scoring member ->
+        ``slamhip.LoopCandidates`` (``offsets``, ``ids`` ascending, ``scores`` as ``s_int``).  Feed the ids of consecutive
+        keyframes to a ``slamhip.LoopConsistency``, or let a ``slamhip.LoopDetector`` do both."""
+        return _ld.loop_candidates(db, vectors, graph_or_best_table, connected, own_ids, limit, min_score, nb)
+
+    def detect_relocalization_candidates(self, db, vectors, best_table, nb: int = 10):
+        """``DetectRelocalizationCandidates`` for Q lost frames at once: as ``detect_loop`` without excluded keyframes and
+        without a threshold on the score -> ``slamhip.LoopCandidates``, the keyframes ``relocalize`` tries."""
+        return _ld.relocalization_candidates(db, vectors, best_table, nb)
 
     def compute_sim3(self, cands, K, min_inliers: int = _s3o.DEFAULT_MIN_INLIERS, **kw):
         """The estimation half of ORB-SLAM's ``LoopClosing::ComputeSim3`` (the reference closes no loops): ``cands`` = list of

@@ -123,6 +123,16 @@ from .local_map import (  # noqa: F401
     remove_frames,
     votes_host,
 )
+from .loop_detect import (  # noqa: F401
+    BestTable,
+    LoopCandidates,
+    LoopConsistency,
+    LoopDetector,
+    loop_candidates,
+    loop_candidates_host,
+    loop_candidates_tables,
+    relocalization_candidates,
+)
 from .pose_graph import (  # noqa: F401
     loop_edges_from_two_view,
     optimize_pose_graph,

@@ -273,6 +273,11 @@ SIGNATURES = {
     "slam_lmap_points_fill": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "slam_lmap_cull_count": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "slam_loop_limits": (c_int, [POINTER(c_int32)]),
+    "slam_loop_workspace": (c_int, [c_int64, c_int64, POINTER(c_uint64)]),
+    "slam_loop_candidates": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
+    "slam_loop_fill": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "slam_comm_version": (c_int, [POINTER(c_int)]),
     "slam_comm_unique_id": (c_int, [c_void_p]),
     "slam_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),

@@ -443,7 +443,7 @@ class BowDatabase:
             self._index[1].free()
             self._index = None
 
-    def _run(self, vectors, max_results: int, max_id, dense: bool):
+    def _run(self, vectors, max_results: int, max_id, dense: bool, resident: bool = False):
         v = _as_vectors(vectors)
         Q = len(v)
         with self._lock:
@@ -455,7 +455,7 @@ class BowDatabase:
             if dense:
                 shape = (Q, E)
                 if Q == 0 or E == 0:
-                    return np.zeros(shape, np.uint32), np.zeros(shape, np.int32)
+                    return (None, None, Q, E) if resident else (np.zeros(shape, np.uint32), np.zeros(shape, np.int32))
             elif Q == 0:
                 return np.zeros((0, R), np.int32), np.zeros((0, R)), np.zeros((0, R), np.int32)
             off, post, _ = self._ensure_index()
@@ -468,9 +468,17 @@ class BowDatabase:
                     qo, qw, qq = m.up(np.ascontiguousarray(v.offsets, np.int64)), m.up(np.ascontiguousarray(v.words, np.int32)), \
                         m.up(np.ascontiguousarray(v.q, np.uint32))
                 if dense:
-                    ds, dc = m.new(4 * Q * E), m.new(4 * Q * E)
-                    check(ctx.lib.slam_bow_query(ctx.handle, qo.ptr, qw.ptr, qq.ptr, Q, off.ptr, post.ptr, self.vocab.n_words, E, E, 1,
-                                                 None, None, None, ds.ptr, dc.ptr))
+                    ds, dc = (ctx.malloc(4 * Q * E), ctx.malloc(4 * Q * E)) if resident else (m.new(4 * Q * E), m.new(4 * Q * E))
+                    try:
+                        check(ctx.lib.slam_bow_query(ctx.handle, qo.ptr, qw.ptr, qq.ptr, Q, off.ptr, post.ptr, self.vocab.n_words, E, E, 1,
+                                                     None, None, None, ds.ptr, dc.ptr))
+                        if resident:
+                            return ds, dc, Q, E
+                    except BaseException:
+                        if resident:
+                            ds.free()
+                            dc.free()
+                        raise
                     return ds.download(np.uint32, shape), dc.download(np.int32, shape)
                 di, ds, dc = m.new(4 * Q * R), m.new(4 * Q * R), m.new(4 * Q * R)
                 check(ctx.lib.slam_bow_query(ctx.handle, qo.ptr, qw.ptr, qq.ptr, Q, off.ptr, post.ptr, self.vocab.n_words, E, limit, R,
@@ -491,6 +499,11 @@ class BowDatabase:
     def scores_dense(self, vectors):
         """(s_int uint32 [Q,E], common int32 [Q,E]) of every query against every entry; the score is ``s_int / 2^31``."""
         return self._run(vectors, 1, None, True)
+
+    def scores_dense_device(self, vectors):
+        """``scores_dense`` without the download: (d_s, d_common, Q, E), two ``DeviceBuffer`` the caller frees, holding the
+        tables uint32 / int32 [Q,E] - what ``loop_candidates`` reads.  (None, None, Q, E) where Q or E is 0."""
+        return self._run(vectors, 1, None, True, True)
 
     def free(self) -> None:
         with self._lock:
@@ -610,7 +623,8 @@ def detect_loop_candidates(db: BowDatabase, vector, connected: Sequence[int] = (
     """The first stage of ORB-SLAM's ``DetectLoopCandidates``: the database entries that share words with ``vector`` (one
     BoW vector), without the ``connected`` ids (the keyframe's covisibility neighbours), kept when they share more than 0.8 of
     the largest shared-word count and score at least ``min_score`` -> (ids int32, scores f64) by (score descending, id
-    ascending).  The covisibility-group accumulation and the consistency check over consecutive keyframes are not done."""
+    ascending).  The covisibility-group accumulation and the consistency check over consecutive keyframes are
+    ``slamhip.loop_detect``'s (``loop_candidates``, ``LoopConsistency``); this function stays the first stage alone."""
     v = _as_vectors(vector)
     if len(v) != 1:
         raise ValueError("detect_loop_candidates takes one vector")

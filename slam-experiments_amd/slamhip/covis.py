@@ -245,6 +245,18 @@ class CovisibilityGraph:
             raise ValueError("n must not be negative")
         return self.neighbours(k, 1)[:int(n)]
 
+    def best_table(self, n: int) -> np.ndarray:
+        """int32 [K,n]: row k = ``best(k, n)``, padded with -1 - the ``d_best`` of ``loop_candidates``."""
+        if int(n) != n or n < 0:
+            raise ValueError("n must be an integer >= 0")
+        n = int(n)
+        table = np.full((self.K, n), -1, np.int32)
+        take = np.minimum(np.diff(self._ptr), n)
+        row = np.repeat(np.arange(self.K, dtype=np.int64), take)
+        col = np.arange(int(take.sum()), dtype=np.int64) - np.repeat(np.cumsum(take) - take, take)
+        table[row, col] = self._adj[self._ptr[row] + col]
+        return table
+
     def connected(self, k: int) -> np.ndarray:
         """``GetConnectedKeyFrames``: every neighbour of ``k``, ascending - the ``connected`` of ``detect_loop_candidates``."""
         return np.sort(self.neighbours(k, 1))
