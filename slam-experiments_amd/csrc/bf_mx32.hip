@@ -20,8 +20,8 @@
 //     source words are the pieces of K-quarters 2 (tid & 1) and 2 (tid & 1) + 1.
 //   * selection: the accumulators hold the bare dot D = 256 - 2 dist.  A lane keeps, per tile, the EXCLUSIVE threshold distance x
 //     (a row passes when its distance is below x) and the bit pattern of the float 258 - 2 x beside it; the 16 results of a tile
-//     fold as bit patterns with eight signed-integer maxima and one compare against that pattern.  Dots are exact integers and
-//     never -0, so for 258 - 2 x >= 0 (x <= 129) the signed comparison of patterns is the comparison of the values: negative
+//     fold as bit patterns with eight signed-integer maxima - a tree: the maxima of five row groups, then their maximum - and
+//     one compare against that pattern.  Dots are exact integers and never -0, so for 258 - 2 x >= 0 (x <= 129) the signed comparison of patterns is the comparison of the values: negative
 //     floats are negative integers, below every pattern of a value >= 0.  A signed maximum orders negative floats backwards, so
 //     for x > 129 (a worker's first groups, or rows that are all far) the pattern is INT_MIN and the tile fires unconditionally:
 //     the update path is exact whatever passes, since a key is built from D alone, key = (128 << 23 | row) - (D << 22).
@@ -36,9 +36,19 @@
 //         TESTED against c0: a tie against a key from a later row can win), and the same with the first row of the stage to come
 //         at the early exchanges (SLAM_MX_EARLY).  bound[] holds 2nd-best keys below SLAM_MX_BOUND_LIMIT, as in bf_mx.hip.
 //     A candidate is dropped only if some known 2nd-best key K has dist(K) < dist, or dist(K) == dist and row(K) < row.
-//   * row gates: a fired tile keys and merges, of a lane's 16 rows, only those at which SOME lane of the tile passes.  The 16
-//     compares are issued back to back into 16 SGPR pairs, the 16 wave-uniform branches test those on the scalar side: no
-//     branch waits on the compare in front of it.  A skipped row is below the threshold of every lane of the tile.
+//   * row gates: a fired tile tests ROW GROUPS, a partition of the accumulator indices 0 .. 15 (MX32_GATES groups, below): a
+//     group's gate is "some lane of the tile has max(acc[i], i in the group) >= its pattern".  The group maxima are the first
+//     level of the fold's tree, so the quiet fold keeps its eight maxima and one compare.  The group compares are issued back
+//     to back into SGPR pairs, the wave-uniform branches test those on the scalar side (no branch waits on the compare in front
+//     of it), and of an open group ALL rows are keyed and merged, with no inner branch.  Why this is the search it was:
+//       - a group gate is open exactly when some row of the group passes in some lane, so a row that does not enter is below
+//         the threshold of every lane of the tile, and the rows that enter are a superset of those the 16 row gates let in;
+//       - the update path is exact whatever passes (selection, above): a lane's 2nd-best can only be nearer for the extra rows,
+//         so its threshold is only tighter, and every key published to bound[] is still a real row's key;
+//       - every row that enters lies below every row the lane has still to see, so the exclusive-threshold tie rule holds;
+//       - every gate is evaluated against the threshold as it stood at the fold; the threshold moves only behind the rows;
+//       - the short last stage keeps its test against c1 on every key it builds: a row past the end never enters.
+//     The final tables are those of the full sort either way, bit for bit (tests/test_mx32_gates_cpu.py replays both).
 //   * scan loop: a whole stage is one trip of four groups in which a tile's four MFMAs run together and the folds stand between
 //     the runs: t0k0 .. t0k3 [fold of tile 1, previous group] t1k0 .. t1k3 [fold of tile 0].  A tile's fold, and its update path
 //     where it fires, stands behind four MFMAs of the OTHER tile and behind the other tile's fold, so the wave keeps the matrix
@@ -80,6 +90,12 @@ __device__ __forceinline__ mx_v16f mx32_dot(uint4 a, uint4 b, mx_v16f c) {
 
 #define MX32_GROUP 32                                  // train rows per group
 #define MX32_GROUPS (SLAM_MX_STAGE / MX32_GROUP)       // groups per whole stage
+
+// The gate groups of a fired tile: a partition of the accumulator indices 0 .. 15 whose maxima are the first level of the
+// fold's tree.  Group 0 = {0, 1, 14, 15}, group j = 1 .. 4 = {3 j - 1, 3 j, 3 j + 1}
+#define MX32_GATES 5
+constexpr int mx32_gate_rows(int j) { return j ? 3 : 4; }
+constexpr int mx32_gate_index(int j, int r) { return j ? 3 * j - 1 + r : (r < 2 ? r : 12 + r); }
 
 // One 16 KiB stage of the prepared image straight from device memory into LDS: four global_load_lds_dwordx4 per thread, piece
 // j = bytes 4096 j .. of the stage, there (scalar base src + 4096 j, plus the thread's fixed offset voff = 16 tid) and here

@@ -139,10 +139,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             // fold and update path touch that tile's accumulators and state only, so where the folds of the two tiles stand
             // relative to each other and to the other tile's MFMAs does not matter to the result
             auto fold_tile = [&](int tt, int g, const mx_v16f& acc, auto rag) {
-                int p = max(max(__float_as_int(acc[0]), __float_as_int(acc[1])), __float_as_int(acc[2]));
+                // the fold is a tree of eight maxima whose first level is the maxima of the gate groups (mx32_gate_index,
+                // bf_mx32.hip): one maximum of two accumulators, seven of three
+                auto a = [&](int i) { return __float_as_int(acc[i]); };
+                int gm[MX32_GATES];
+                gm[0] = max(a(0), a(1));
 #pragma unroll
-                for (int i = 3; i < 15; i += 2) p = max(max(p, __float_as_int(acc[i])), __float_as_int(acc[i + 1]));
-                const int m = max(p, __float_as_int(acc[15]));
+                for (int j = 1; j < MX32_GATES; j++) gm[j] = max(max(a(3 * j - 1), a(3 * j)), a(3 * j + 1));
+                gm[0] = max(max(gm[0], a(14)), a(15));
+                const int m = max(max(max(max(gm[1], gm[2]), gm[3]), gm[4]), gm[0]);
                 if (__builtin_expect(__ballot(m >= thr[tt]) == 0ull, 1)) return;
                 MX_STAMP(2);
                 // the group's first row is taken from the scalar side here: as a per-lane value it would be carried through
@@ -152,23 +157,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 const u32 rowk = (u32)row0 + (u32)(4 * hk);
                 // key = (128 - D / 2) << 23 | row: base + (-D << 22), exact modulo 2^32 (D is an even integer)
                 const u32 base = (128u << SLAM_KEY_IDX_BITS) + rowk;
-                // the 16 row gates: the compares back to back, each into an SGPR pair of its own (the threshold moves only
-                // behind the rows), then scalar tests alone, so that no branch waits on the compare in front of it
-                unsigned long long gate[16];
-#pragma unroll
-                for (int i = 0; i < 16; i++) gate[i] = __ballot(__float_as_int(acc[i]) >= thr[tt]);
-                asm volatile("" ::"s"(gate[0]), "s"(gate[1]), "s"(gate[2]), "s"(gate[3]), "s"(gate[4]), "s"(gate[5]), "s"(gate[6]),
-                             "s"(gate[7]), "s"(gate[8]), "s"(gate[9]), "s"(gate[10]), "s"(gate[11]), "s"(gate[12]), "s"(gate[13]),
-                             "s"(gate[14]), "s"(gate[15]));
-#pragma unroll
-                for (int i = 0; i < 16; i++) {
-                    if (gate[i] == 0ull) continue;
+                // a row of the lane: its key, exact whatever the row's distance, into the lane's sorted pair
+                auto enter = [&](int i) {
                     const int off = 8 * (i >> 2) + (i & 3);
                     u32 key = base + (u32)off + ((u32)(int)(-acc[i]) << (SLAM_KEY_IDX_BITS - 1));
                     if constexpr (decltype(rag)::value)   // the rows past the end of a short stage never enter
                         key = (int)rowk + off < c1 ? key : SLAM_KEY_NONE;
                     b2[tt] = umed3(b1[tt], b2[tt], key);
                     b1[tt] = min(b1[tt], key);
+                };
+                // the five group gates: the compares back to back, each into an SGPR pair of its own (the threshold moves only
+                // behind the rows), then scalar tests alone, so that no branch waits on the compare in front of it
+                unsigned long long gate[MX32_GATES];
+#pragma unroll
+                for (int j = 0; j < MX32_GATES; j++) gate[j] = __ballot(gm[j] >= thr[tt]);
+                asm volatile("" ::"s"(gate[0]), "s"(gate[1]), "s"(gate[2]), "s"(gate[3]), "s"(gate[4]));
+#pragma unroll
+                for (int j = 0; j < MX32_GATES; j++) {
+                    if (gate[j] == 0ull) continue;
+                    // an open group: all of its rows enter, no inner branch
+#pragma unroll
+                    for (int r = 0; r < mx32_gate_rows(j); r++) enter(mx32_gate_index(j, r));
                 }
                 set_threshold(tt, min(xs[tt], b2[tt] >> SLAM_KEY_IDX_BITS));
                 MX_STAMP(3);

@@ -36,6 +36,8 @@ NONE = 0xFFFFFFFF
 IDLE = 0x7F7F7F7F
 LIMIT = 0x7F000000           # bound[] holds keys below this
 NO_X = NONE >> IDX_BITS      # 511: everything passes
+# the gate groups of a fired 32x32 tile (bf_mx32.hip: MX32_GATES, mx32_gate_index): accumulator indices
+GATE_GROUPS = ((0, 1, 14, 15), (2, 3, 4), (5, 6, 7), (8, 9, 10), (11, 12, 13))
 STAGE = 128
 EARLY = 0x16                 # SLAM_MX_EARLY: exchanges after 128, 256 and 512 scanned rows
 GEOMETRY = {32: (2, 16), 16: (4, 4)}      # tile -> (lanes per query, rows per lane and group)
@@ -116,6 +118,7 @@ class Search:
         self.done = [False] * workers
         self.folds = self.fired = self.gates = self.unions = self.union_stages = self.block_stages = self.exchanges = 0
         self.tile_stages = self.carried = 0
+        self.open_groups = self.group_rows = 0      # tile 32: the gate groups of bf_mx32.hip that the open row gates lie in
         self.fired_log = []                   # (worker, stage start, group, tile) of every fire, in program order per tile
         self.x_log = {} if log else None      # (worker, stage start, group, tile parity) -> the thresholds behind that fold
 
@@ -152,6 +155,10 @@ class Search:
         if fired.any():
             self.fired += int(fired.sum())
             self.gates += int(gate[fired].sum())
+            if self.tile == 32:                                              # counted only: the dynamics stay the row gates'
+                og = np.stack([gate[:, list(grp)].any(axis=1) for grp in GATE_GROUPS], axis=1)[fired]
+                self.open_groups += int(og.sum())
+                self.group_rows += int((og * np.array([len(grp) for grp in GATE_GROUPS])).sum())
             self.fired_log += [(w, s0, g, int(t)) for t in np.flatnonzero(fired)]
             stage_fired |= fired
             keys = np.where(valid[None], (dd << IDX_BITS) | rows[None], NONE)
@@ -240,7 +247,9 @@ class Search:
     def counts(self):
         return {"tile_groups": self.folds, "fired": self.fired, "open_gates_per_fired_tile": self.gates / max(self.fired, 1),
                 "unions": self.unions, "tile_stages": self.tile_stages, "block_stages_with_a_union": self.union_stages,
-                "block_stages": self.block_stages, "exchanges": self.exchanges}
+                "block_stages": self.block_stages, "exchanges": self.exchanges,
+                "open_groups_per_fired_tile": self.open_groups / max(self.fired, 1),
+                "rows_of_open_groups_per_fired_tile": self.group_rows / max(self.fired, 1)}
 
 
 def run(d, tile, union, workers=None, plan_n=None, cus=256, carry="none"):
@@ -255,7 +264,9 @@ def line(label, s):
     c = s.counts()
     return (f"{label:<44} fired {c['fired']:5d} of {c['tile_groups']:6d} tile-groups ({100 * c['fired'] / c['tile_groups']:4.1f} %), "
             f"{c['open_gates_per_fired_tile']:5.2f} of {s.R} gates open per fired tile, unions {c['unions']:5d} of {c['tile_stages']:5d} tile-stages "
-            f"({c['block_stages_with_a_union']} of {c['block_stages']} block-stages), exchanges {c['exchanges']}")
+            f"({c['block_stages_with_a_union']} of {c['block_stages']} block-stages), exchanges {c['exchanges']}"
+            + (f", {c['open_groups_per_fired_tile']:4.2f} of {len(GATE_GROUPS)} gate groups open holding "
+               f"{c['rows_of_open_groups_per_fired_tile']:4.2f} rows" if s.tile == 32 else ""))
 
 
 def main():

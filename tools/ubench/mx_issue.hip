@@ -33,6 +33,20 @@
 //   (c) tile-major: t0k0 t0k1 [fold t1 of g - 1] t0k2 t0k3 t1k0 t1k1 [fold t0 of g] t1k2 t1k3 (four dependent MFMAs back to back)
 //   (d) tile runs:  t0k0 t0k1 t0k2 t0k3 [fold t1 of g - 1] t1k0 t1k1 t1k2 t1k3 [fold t0 of g]  (each fold behind four MFMAs of the
 //                   other tile and the other fold: the compiler owes no wait states; the order the kernel takes)
+// `mx_issue fire [spin seconds]` runs the tile-run order (d) with a FIRED tile of the kernel's listing behind one fold of tile 0
+// in every third group (one tile-group in six, 16.7 %; tools/mx_fire_model.py counts 17.7 % at the headline launch): the
+// out-of-line block of gate compares, scalar tests, five vector instructions per entering row and the threshold tail, then a
+// branch back.  Every fold ends, as in the kernel, in a compare into VCC, four moves and a branch; which fold fires, which gates
+// are open and the threshold come from a table the kernel loads, k = 1, 2, 4 or 16 open rows ({6}, {3, 9}, {1, 5, 6, 12}, all).
+// Five forms of the block, each at 1 .. 4 waves per SIMD, cycles per group and the share of the pipe fed as `group` prints:
+//   (P)  the 16 row gates: 16 compares, 16 tests whose branch is TAKEN when the gate is closed, the open rows' bodies in line;
+//   (A)  the fold as a tree whose first level is the maxima of five row groups ({0, 1, 14, 15}, {2, 3, 4}, ... {11, 12, 13}): 5
+//        group compares and tests, and inside an open group its rows' compares and tests as in (P);
+//   (B)  as (A), but all rows of an open group enter, no inner branch;
+//   (F1) the 16 row gates with a closed gate falling through and every open row's body out of line, behind a label of its own;
+//   (F2) the chain fold; the fired block computes four quad maxima (8 more vector instructions), then quad gates as in (A).
+// It first prints the cycles of one s_cbranch_scc1, not taken and taken (to the next instruction), behind an s_cmp_eq_u32 that
+// sets SCC from loaded values, less the cycles of the s_cmp alone.
 // build: hipcc --offload-arch=gfx950 -O3 mx_issue.hip -o mx_issue
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -127,6 +141,92 @@
 #define X4(a) a a a a
 #define FILL_CYCLES 1500000ull
 
+// ---- the `fire` mode ----
+// loaded per lane: the 16 row values v[112:127], the five group maxima v[82:86], the gates' threshold v87, the folds' quiet and
+// firing thresholds v108 / v109.  Scratch: v[89:93] (tree / quad maxima), v[94:95], v[97:98] (the four moves), v102 / v103 (the
+// sorted pair), v104 (key), v105 (base), v106 / v107 (threshold tail).  Gates: rows s[24:55], groups or quads s[56:65]
+#define CLOBF CLOB, "v82","v83","v84","v85","v86","v87","v89","v90","v91","v92","v93","v94","v95","v97","v98","v112","v113","v114","v115", \
+              "v116","v117","v118","v119","v120","v121","v122","v123","v124","v125","v126","v127","vcc","scc","s20","s21","s22","s23","s24", \
+              "s25","s26","s27","s28","s29","s30","s31","s32","s33","s34","s35","s36","s37","s38","s39","s40","s41","s42","s43","s44","s45", \
+              "s46","s47","s48","s49","s50","s51","s52","s53","s54","s55","s56","s57","s58","s59","s60","s61","s62","s63","s64","s65"
+#define MOV4 "v_mov_b32 v94, v87\n v_mov_b32 v95, v102\n v_mov_b32 v97, v103\n v_mov_b32 v98, v107\n"
+// the chain fold (the parent's) and the tree fold of a tile, compared against register T into VCC
+#define CHAIN0(T) "v_max_i32 v100, v50, v51\n v_max3_i32 v100, v100, v52, v53\n v_max3_i32 v100, v100, v54, v55\n v_max3_i32 v100, v100, v56, v57\n" \
+                  "v_max3_i32 v100, v100, v58, v59\n v_max3_i32 v100, v100, v60, v61\n v_max3_i32 v100, v100, v62, v63\n"                        \
+                  "v_max3_i32 v100, v100, v64, v65\n v_cmp_ge_i32_e32 vcc, v100, " T "\n" MOV4
+#define CHAIN1(T) "v_max_i32 v101, v66, v67\n v_max3_i32 v101, v101, v68, v69\n v_max3_i32 v101, v101, v70, v71\n v_max3_i32 v101, v101, v72, v73\n" \
+                  "v_max3_i32 v101, v101, v74, v75\n v_max3_i32 v101, v101, v76, v77\n v_max3_i32 v101, v101, v78, v79\n"                        \
+                  "v_max3_i32 v101, v101, v80, v81\n v_cmp_ge_i32_e32 vcc, v101, " T "\n" MOV4
+#define TREE0(T) "v_max_i32 v89, v50, v51\n v_max3_i32 v90, v52, v53, v54\n v_max3_i32 v91, v55, v56, v57\n v_max3_i32 v92, v58, v59, v60\n" \
+                 "v_max3_i32 v93, v61, v62, v63\n v_max3_i32 v89, v89, v64, v65\n v_max3_i32 v100, v90, v91, v92\n"                       \
+                 "v_max3_i32 v100, v100, v93, v89\n v_cmp_ge_i32_e32 vcc, v100, " T "\n" MOV4
+#define TREE1(T) "v_max_i32 v89, v66, v67\n v_max3_i32 v90, v68, v69, v70\n v_max3_i32 v91, v71, v72, v73\n v_max3_i32 v92, v74, v75, v76\n" \
+                 "v_max3_i32 v93, v77, v78, v79\n v_max3_i32 v89, v89, v80, v81\n v_max3_i32 v101, v90, v91, v92\n"                       \
+                 "v_max3_i32 v101, v101, v93, v89\n v_cmp_ge_i32_e32 vcc, v101, " T "\n" MOV4
+// row i of a lane: X(two-digit index, its value's register, its gate's SGPR pair, its offset 8 (i >> 2) + (i & 3))
+#define R0(X) X("00", "112", "24", "25", "0")
+#define R1(X) X("01", "113", "26", "27", "1")
+#define R2(X) X("02", "114", "28", "29", "2")
+#define R3(X) X("03", "115", "30", "31", "3")
+#define R4(X) X("04", "116", "32", "33", "8")
+#define R5(X) X("05", "117", "34", "35", "9")
+#define R6(X) X("06", "118", "36", "37", "10")
+#define R7(X) X("07", "119", "38", "39", "11")
+#define R8(X) X("08", "120", "40", "41", "16")
+#define R9(X) X("09", "121", "42", "43", "17")
+#define R10(X) X("10", "122", "44", "45", "18")
+#define R11(X) X("11", "123", "46", "47", "19")
+#define R12(X) X("12", "124", "48", "49", "24")
+#define R13(X) X("13", "125", "50", "51", "25")
+#define R14(X) X("14", "126", "52", "53", "26")
+#define R15(X) X("15", "127", "54", "55", "27")
+#define ROWS_ALL(X) R0(X) R1(X) R2(X) R3(X) R4(X) R5(X) R6(X) R7(X) R8(X) R9(X) R10(X) R11(X) R12(X) R13(X) R14(X) R15(X)
+#define ROWS_G0(X) R0(X) R1(X) R14(X) R15(X)
+#define ROWS_G1(X) R2(X) R3(X) R4(X)
+#define ROWS_G2(X) R5(X) R6(X) R7(X)
+#define ROWS_G3(X) R8(X) R9(X) R10(X)
+#define ROWS_G4(X) R11(X) R12(X) R13(X)
+#define ROWS_Q0(X) R0(X) R1(X) R2(X) R3(X)
+#define ROWS_Q1(X) R4(X) R5(X) R6(X) R7(X)
+#define ROWS_Q2(X) R8(X) R9(X) R10(X) R11(X)
+#define ROWS_Q3(X) R12(X) R13(X) R14(X) R15(X)
+// the five vector instructions of an entering row: key = base + offset - (D << 22), into the sorted pair
+#define BODY(v, off) "v_cvt_i32_f32_e64 v104, -v" v "\n v_lshlrev_b32 v104, 22, v104\n v_add3_u32 v104, v105, v104, " off "\n"  \
+                     "v_med3_u32 v103, v102, v103, v104\n v_min_u32 v102, v102, v104\n"
+#define XCMP(i, v, sl, sh, off) "v_cmp_ge_i32_e64 s[" sl ":" sh "], v" v ", v87\n"
+#define XGATED(i, v, sl, sh, off) "s_cmp_eq_u64 s[" sl ":" sh "], 0\n s_cbranch_scc1 1" i "f\n" BODY(v, off) "1" i ":\n"
+#define XBODY(i, v, sl, sh, off) BODY(v, off)
+#define XTEST_OUT(i, v, sl, sh, off) "s_cmp_lg_u64 s[" sl ":" sh "], 0\n s_cbranch_scc1 2" i "f\n 3" i ":\n"
+#define XBODY_OUT(i, v, sl, sh, off) "2" i ":\n" BODY(v, off) "s_branch 3" i "b\n"
+// gate j of the groups (value in register g) or quads: compare, and the test that skips to label 40j
+#define GCMP(j, g) "v_cmp_ge_i32_e64 s[" j "], " g ", v87\n"
+#define GCMPS GCMP("56:57", "v82") GCMP("58:59", "v83") GCMP("60:61", "v84") GCMP("62:63", "v85") GCMP("64:65", "v86")
+#define GTEST(j, n) "s_cmp_eq_u64 s[" j "], 0\n s_cbranch_scc1 40" n "f\n"
+#define OPEN_A(j, n, ROWS) GTEST(j, n) ROWS(XCMP) ROWS(XGATED) "40" n ":\n"
+#define OPEN_B(j, n, ROWS) GTEST(j, n) ROWS(XBODY) "40" n ":\n"
+#define QUADS "v_max3_i32 v89, v112, v113, v114\n v_max3_i32 v90, v116, v117, v118\n v_max3_i32 v91, v120, v121, v122\n"                    \
+              "v_max3_i32 v92, v124, v125, v126\n v_max_i32 v89, v89, v115\n v_max_i32 v90, v90, v119\n v_max_i32 v91, v91, v123\n"          \
+              "v_max_i32 v92, v92, v127\n" GCMP("56:57", "v89") GCMP("58:59", "v90") GCMP("60:61", "v91") GCMP("62:63", "v92")
+#define BLOCK_P ROWS_ALL(XCMP) ROWS_ALL(XGATED)
+#define BLOCK_A GCMPS OPEN_A("56:57", "0", ROWS_G0) OPEN_A("58:59", "1", ROWS_G1) OPEN_A("60:61", "2", ROWS_G2) OPEN_A("62:63", "3", ROWS_G3) \
+                OPEN_A("64:65", "4", ROWS_G4)
+#define BLOCK_B GCMPS OPEN_B("56:57", "0", ROWS_G0) OPEN_B("58:59", "1", ROWS_G1) OPEN_B("60:61", "2", ROWS_G2) OPEN_B("62:63", "3", ROWS_G3) \
+                OPEN_B("64:65", "4", ROWS_G4)
+#define BLOCK_F1 ROWS_ALL(XCMP) ROWS_ALL(XTEST_OUT)
+#define BLOCK_F2 QUADS OPEN_A("56:57", "0", ROWS_Q0) OPEN_A("58:59", "1", ROWS_Q1) OPEN_A("60:61", "2", ROWS_Q2) OPEN_A("62:63", "3", ROWS_Q3)
+// the threshold tail: seven dependent vector instructions and an s_nop
+#define TAIL "v_lshrrev_b32 v106, 23, v103\n v_min_u32 v107, v107, v106\n v_lshlrev_b32 v106, 1, v107\n v_sub_u32 v106, 0x102, v106\n" \
+             "v_cvt_f32_u32 v106, v106\n v_cmp_gt_u32_e32 vcc, 0x82, v107\n s_nop 0\n v_cndmask_b32 v106, v105, v106, vcc\n"
+// three groups in the order (d); the fold of tile 0 of the second fires.  The fired block (label 2) and the out-of-line row
+// bodies stand in front of the groups; a quiet fold's branch is never taken
+#define BRQ "s_cbranch_vccnz 2b\n"
+#define FIRE_LOOP(F0, F1, BLOCK, OUTLINE)                                                                      \
+    "s_branch 1f\n 2:\n" BLOCK TAIL "s_branch 3f\n" OUTLINE "1:\n"                                             \
+    D0 D2 D4 D6 F1("v108") BRQ D1 D3 D5 D7 F0("v108") BRQ                                                      \
+    D0 D2 D4 D6 F1("v108") BRQ D1 D3 D5 D7 F0("v109") "s_cbranch_vccnz 2b\n 3:\n"                              \
+    D0 D2 D4 D6 F1("v108") BRQ D1 D3 D5 D7 F0("v108") BRQ
+#define FIRE_ROWS 24                                   // ints per lane of the table
+
 struct stamp { unsigned long long c0, r0, c1, r1; unsigned role, hwid, xcc, count; };
 
 // FORM 0 16x16x128 scaled (shipped) | 1 16x16x128 unscaled | 2 32x32x64 scaled | 3 32x32x64 unscaled | 4, 5, 6, 7 the real group
@@ -145,7 +245,7 @@ struct stamp { unsigned long long c0, r0, c1, r1; unsigned role, hwid, xcc, coun
         if (K == 8) asm volatile(X4(BODY(F8)) ::: CLOB);      \
     }
 template <int FORM, int PLACE, int K>
-__global__ __launch_bounds__(256) void k(uint32_t* out, stamp* st, int iters) {
+__global__ __launch_bounds__(256) void k(uint32_t* out, stamp* st, int iters, const int* gd) {
     static_assert(PLACE < 2 || (FORM == 0 && K <= 4), "the cross-wave rows exist for the shipped form only");
     uint32_t seed = threadIdx.x * 2654435761u + blockIdx.x * 40503u + 1u;
     // FP4 +-1 operands: every nibble 0x2 or 0xA
@@ -167,14 +267,27 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, stamp* st, int iters) {
                      "v_mov_b32 v46, v34\n v_mov_b32 v47, v34\n v_mov_b32 v48, v34\n v_mov_b32 v49, v34\n" A0 A1 A2 A3 "s_nop 15\n" ::: CLOB);
     else
         asm volatile(C0 C1 "s_nop 15\n s_nop 15\n" ::: CLOB);
+    if (FORM >= 8) {                                    // the fire mode's table, lane by lane
+        const uint32_t off = (threadIdx.x & 63) * FIRE_ROWS * 4;
+        asm volatile("global_load_dwordx4 v[112:115], %0, %1\n global_load_dwordx4 v[116:119], %0, %1 offset:16\n"
+                     "global_load_dwordx4 v[120:123], %0, %1 offset:32\n global_load_dwordx4 v[124:127], %0, %1 offset:48\n"
+                     "global_load_dwordx4 v[82:85], %0, %1 offset:64\n global_load_dwordx2 v[86:87], %0, %1 offset:80\n"
+                     "global_load_dwordx2 v[108:109], %0, %1 offset:88\n s_waitcnt vmcnt(0)\n"
+                     "v_mov_b32 v105, 0x40000000\n v_mov_b32 v102, -1\n v_mov_b32 v103, -1\n v_mov_b32 v107, 0x1ff" ::"v"(off), "s"(gd) : CLOBF);
+    }
     unsigned hwid, xcc, count = 0;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n s_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hwid), "=s"(xcc));
     const bool filler_wave = PLACE == 2 && (hwid & 1);             // HW_ID[3:0] = wave slot of the SIMD
     unsigned long long c0, r0, c1, r1;
     asm volatile("s_memtime %0\n s_memrealtime %1\n s_waitcnt lgkmcnt(0)" : "=s"(c0), "=s"(r0)::"memory");
     if (!filler_wave) {
-        for (int it = 0; it < iters; it += 4) {
-            if (PLACE == 2) asm volatile(X4(INTER_A(F0)) ::: CLOB);
+        for (int it = 0; it < iters; it += FORM >= 8 ? 3 : 4) {
+            if (FORM == 8) asm volatile(FIRE_LOOP(CHAIN0, CHAIN1, BLOCK_P, "") ::: CLOBF);
+            else if (FORM == 9) asm volatile(FIRE_LOOP(TREE0, TREE1, BLOCK_A, "") ::: CLOBF);
+            else if (FORM == 10) asm volatile(FIRE_LOOP(TREE0, TREE1, BLOCK_B, "") ::: CLOBF);
+            else if (FORM == 11) asm volatile(FIRE_LOOP(CHAIN0, CHAIN1, BLOCK_F1, ROWS_ALL(XBODY_OUT)) ::: CLOBF);
+            else if (FORM == 12) asm volatile(FIRE_LOOP(CHAIN0, CHAIN1, BLOCK_F2, "") ::: CLOBF);
+            else if (PLACE == 2) asm volatile(X4(INTER_A(F0)) ::: CLOB);
             else if (FORM == 0 && PLACE == 0) PICK(INTER_A)
             else if (FORM == 0 && PLACE == 1) PICK(BUNCH_A)
             else if (FORM == 1 && PLACE == 0) PICK(INTER_B)
@@ -218,20 +331,22 @@ static double median(std::vector<double>& v) { std::sort(v.begin(), v.end()); re
 
 static const int MAXW = 4, NCU = 256;
 static const char* const FORM_NAME[] = {"16x16x128 scaled", "16x16x128 plain ", "32x32x64 scaled ", "32x32x64 plain  ",
-                                        "group (a) bunched", "group (b) pipelined", "group (c) tile-major", "group (d) tile runs"};
+                                        "group (a) bunched", "group (b) pipelined", "group (c) tile-major", "group (d) tile runs",
+                                        "fire (P) 16 row gates", "fire (A) 5 groups, row gates", "fire (B) 5 groups, rows enter",
+                                        "fire (F1) open rows out of line", "fire (F2) quads in the block"};
 
 // one row; *cyc = the SIMD's cycles per MFMA (median over SIMDs)
-template <int FORM, int PLACE, int K> int run(int waves, uint32_t* out, stamp* d_st, double spin_s, double* cyc) {
-    const int iters = 20000, blocks = NCU * waves;
+template <int FORM, int PLACE, int K> int run(int waves, uint32_t* out, stamp* d_st, double spin_s, double* cyc, const int* gd = nullptr) {
+    const int iters = FORM >= 8 ? 19998 : 20000, blocks = NCU * waves;   // the fire mode's loop is three groups
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     CK(hipEventRecord(e0));
     float spun = 0;
     while (spun < spin_s * 1e3f) {                      // spin-up: back-to-back launches of the same body
-        for (int i = 0; i < 8; i++) k<FORM, PLACE, K><<<blocks, 256>>>(out, d_st, iters);
+        for (int i = 0; i < 8; i++) k<FORM, PLACE, K><<<blocks, 256>>>(out, d_st, iters, gd);
         CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
         CK(hipEventElapsedTime(&spun, e0, e1));
     }
-    k<FORM, PLACE, K><<<blocks, 256>>>(out, d_st, iters);
+    k<FORM, PLACE, K><<<blocks, 256>>>(out, d_st, iters, gd);
     CK(hipDeviceSynchronize());
     CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1));
     std::vector<stamp> st(blocks * 4);
@@ -338,11 +453,91 @@ template <int FORM> int group_rows(uint32_t* out, stamp* d_st, double spin_s) {
     return 0;
 }
 
+// the fire mode's table for k open rows: the open rows hold 200 in lane 5 and 0 elsewhere, the threshold is 100 in every lane
+static void fire_table(int k, std::vector<int>& t) {
+    static const int one[] = {6}, two[] = {3, 9}, four[] = {1, 5, 6, 12};
+    static const int groups[5][4] = {{0, 1, 14, 15}, {2, 3, 4, -1}, {5, 6, 7, -1}, {8, 9, 10, -1}, {11, 12, 13, -1}};
+    t.assign(64 * FIRE_ROWS, 0);
+    for (int lane = 0; lane < 64; lane++) {
+        int* r = t.data() + lane * FIRE_ROWS;
+        if (lane == 5)
+            for (int i = 0; i < k; i++) r[k == 16 ? i : k == 4 ? four[i] : k == 2 ? two[i] : one[i]] = 200;
+        for (int j = 0; j < 5; j++)
+            for (int i : groups[j])
+                if (i >= 0) r[16 + j] = std::max(r[16 + j], r[i]);
+        r[21] = 100;
+        r[22] = 0x7fffffff;                             // a quiet fold's threshold: above every pattern
+        r[23] = (int)0x80000000u;                       // the firing fold's: below every pattern
+    }
+}
+
+template <int FORM> int fire_rows(uint32_t* out, stamp* d_st, double spin_s, int* gd) {
+    for (int k : {1, 2, 4, 16}) {
+        std::vector<int> t;
+        fire_table(k, t);
+        CK(hipMemcpy(gd, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
+        for (int w : {1, 2, 3, 4}) {
+            double c = 0;
+            if (run<FORM, 0, 0>(w, out, d_st, spin_s, &c, gd)) return 1;
+            printf("  %s, k = %2d open rows, %d waves per SIMD: %6.1f cycles per group and SIMD, pipe fed %5.1f %%\n", FORM_NAME[FORM], k, w, 8 * c,
+                   100.0 * 32.0 / c);
+            fflush(stdout);
+        }
+    }
+    return 0;
+}
+
+// 256 x (s_cmp_eq_u32 of two loaded values [+ s_cbranch_scc1 to the next instruction]) per trip: a dependent chain through SCC
+#define X16(a) X4(X4(a))
+#define X256(a) X16(X16(a))
+template <bool BRANCH> __global__ void kb(unsigned long long* cyc, const int* v, int trips) {
+    const int a = v[0], b = v[1];
+    unsigned long long c0, c1;
+    asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(c0)::"memory");
+    for (int i = 0; i < trips; i++) {
+        if (BRANCH) asm volatile(X256("s_cmp_eq_u32 %0, %1\n s_cbranch_scc1 1f\n 1:\n") ::"s"(a), "s"(b) : "scc");
+        else asm volatile(X256("s_cmp_eq_u32 %0, %1\n") ::"s"(a), "s"(b) : "scc");
+    }
+    asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(c1)::"memory");
+    if (threadIdx.x == 0) cyc[blockIdx.x] = c1 - c0;
+}
+
+static int branch_rows(int* gd) {
+    const int trips = 1000;
+    unsigned long long* d; CK(hipMalloc(&d, NCU * sizeof(*d)));
+    double res[3];
+    for (int mode = 0; mode < 3; mode++) {                // 0 the compare alone | 1 branch not taken | 2 branch taken
+        const int v[2] = {1, mode == 2 ? 1 : 2};
+        CK(hipMemcpy(gd, v, sizeof(v), hipMemcpyHostToDevice));
+        for (int rep = 0; rep < 3; rep++) {
+            if (mode) kb<true><<<NCU, 64>>>(d, gd, trips);
+            else kb<false><<<NCU, 64>>>(d, gd, trips);
+        }
+        CK(hipDeviceSynchronize());
+        std::vector<unsigned long long> h(NCU);
+        CK(hipMemcpy(h.data(), d, NCU * sizeof(*d), hipMemcpyDeviceToHost));
+        std::vector<double> c;
+        for (auto x : h) c.push_back((double)x / (256.0 * trips));
+        res[mode] = median(c);
+    }
+    printf("  one wave per CU, a chain of 256000: s_cmp_eq_u32 alone %5.2f cycles | + s_cbranch_scc1 not taken %5.2f (branch %5.2f) | + "
+           "s_cbranch_scc1 taken to the next instruction %5.2f (branch %5.2f)\n", res[0], res[1], res[1] - res[0], res[2], res[2] - res[0]);
+    fflush(stdout);
+    CK(hipFree(d));
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const bool group = argc > 1 && !strcmp(argv[1], "group");
-    const double spin_s = argc > 1 + group ? atof(argv[1 + group]) : 0.5;
+    const bool fire = argc > 1 && !strcmp(argv[1], "fire");
+    const double spin_s = argc > 1 + (group || fire) ? atof(argv[1 + (group || fire)]) : 0.5;
     uint32_t* out; CK(hipMalloc(&out, (size_t)NCU * MAXW * 256 * 4));
     stamp* d_st; CK(hipMalloc(&d_st, (size_t)NCU * MAXW * 4 * sizeof(stamp)));
+    if (fire) {
+        int* gd; CK(hipMalloc(&gd, 64 * FIRE_ROWS * sizeof(int)));
+        return branch_rows(gd) || fire_rows<8>(out, d_st, spin_s, gd) || fire_rows<9>(out, d_st, spin_s, gd) ||
+               fire_rows<10>(out, d_st, spin_s, gd) || fire_rows<11>(out, d_st, spin_s, gd) || fire_rows<12>(out, d_st, spin_s, gd);
+    }
     if (group) return group_rows<4>(out, d_st, spin_s) || group_rows<5>(out, d_st, spin_s) || group_rows<6>(out, d_st, spin_s) ||
                       group_rows<7>(out, d_st, spin_s);
     if (form<0>(out, d_st, spin_s) || form<1>(out, d_st, spin_s) || form<2>(out, d_st, spin_s) || form<3>(out, d_st, spin_s)) return 1;
